@@ -12,10 +12,14 @@ Primary parameter set: the reference accuracy-test setting iterations=10 with ep
 (fixed work: cudaoptflow/test/test_optflow.cpp:450; CPU equivalent median=1, inner=1, outer=10)
 unless --defaults is given (class defaults: 300 iterations, epsilon 0.01, data-dependent exit).
 The JSON line carries N and the per-pair algorithmic bytes so the number can be read against
-BASELINE.md section 2.  Extra parameter sets are reported under "variants".
+BASELINE.md section 2.  Extra parameter sets are reported under "variants" (--full).
 
-Rank 0 prints ONE compact JSON line (<= 4 KB, strict JSON: `compact_line`) as the only line on stdout; the long form
-(variants, secondary workloads, per-level tables, notes) goes to bench_full.json and to stderr.
+A plain run sets up, warms up, times `--steps` steps, writes the flows of the last step with --dump-outputs DIR, and prints
+the headline line.  --full adds everything else: the roofline (per-launch event profile of the timed run), EPE vs the
+analytic flow, the power leg, the scatter / gather leg of --gpus N, variants, CPU baseline and secondary workloads.
+
+Rank 0 prints ONE compact JSON line (<= 4 KB, strict JSON: `compact_line`) as the only line on stdout; with --full the long
+form (variants, secondary workloads, per-level tables, notes) goes to bench_full.json and to stderr.
 """
 from __future__ import annotations
 
@@ -347,6 +351,25 @@ def time_steps(alg, I0, I1, flows, steps, warmup, dist):
     if dist is not None:
         dist.barrier()
     return time.perf_counter() - t0
+
+
+DUMP_SAMPLE = 1 << 20             # flow vectors of the seeded sample --dump-outputs takes over the whole batch (8 MB)
+DUMP_WHOLE_PAIR_MAX = 32 << 20    # bytes: pair 0 is written whole up to this size (16.6 MB at 1080p), so the files stay under 64 MB
+
+
+def dump_flows(d, flows):
+    """--dump-outputs: what calc_batch returned in the last timed step, as float32 .npy files under `d` -- flow_sample.npy, the flow at
+    DUMP_SAMPLE (pair, row, column) positions drawn with a fixed seed over the whole batch (n x 2; the same positions for the same
+    --batch / --width / --height), and flow_pair0.npy, pair 0 whole (H x W x 2) where it fits in DUMP_WHOLE_PAIR_MAX."""
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+    H, W = int(flows.shape[1]), int(flows.shape[2])
+    flat = flows.reshape(-1, 2)
+    idx = np.random.default_rng(1234).integers(0, flat.shape[0], min(DUMP_SAMPLE, flat.shape[0]))
+    np.save(os.path.join(d, "flow_sample.npy"), flat[torch.from_numpy(idx).to(flows.device)].cpu().numpy().astype(np.float32))
+    if H * W * 2 * 4 <= DUMP_WHOLE_PAIR_MAX:
+        np.save(os.path.join(d, "flow_pair0.npy"), flows[0].cpu().numpy().astype(np.float32))
 
 
 def bench_exchange(args, parallel, dist, rank, world, dev, I0, I1, flows_ref):
@@ -1147,6 +1170,13 @@ def main():
     ap.add_argument("--time-block", type=int, default=0, help="iterations fused per HBM pass (fast math; 0 = auto, 1 = off)")
     ap.add_argument("--lanes", type=int, default=0, help="internal streams a batch is split over (0 = library default: 2 from 4 pairs on)")
     ap.add_argument("--semantics", type=int, default=None, help="0 = CPU class arithmetic (library default), 1 = cv::cuda's kernels")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline (TV-L1 workload): roofline from the timed run's event profile, EPE vs the analytic flow, "
+                         "power leg, scatter / gather leg (--gpus N > 1), variants, CPU baseline, secondary workloads; the --no-* "
+                         "switches below thin this out.  Without it a run times the steps and prints the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the flows of the last timed step to DIR/*.npy (float32): pair 0 whole and a fixed, seeded sample "
+                         "over the whole batch (TV-L1 workload)")
     ap.add_argument("--no-variants", action="store_true")
     ap.add_argument("--no-secondary", action="store_true")
     ap.add_argument("--no-cpu", action="store_true")
@@ -1177,6 +1207,8 @@ def main():
                  f"refusing to report a line whose n_gpus is not what was asked for")
     if args.workload != "tvl1" and args.gpus != 1:
         sys.exit("bench.py: the secondary workloads are single-GPU lines (--gpus 1); the sharded metric is --workload tvl1")
+    if args.workload != "tvl1" and args.dump_outputs:
+        sys.exit("bench.py: --dump-outputs writes the flows of the headline workload (--workload tvl1)")
     if args.workload == "stereobm":
         return emit(bench_stereobm(args), "bench_full_stereobm.json")
     if args.workload == "surf":
@@ -1243,18 +1275,44 @@ def main():
         its = alg.lastIterations(0)
         return float(el), prof, its, alg
 
+    # the headline: per-launch event profile on in every run, so that `value` stays comparable with the earlier records; --full reads
+    # the profile back for the roofline
     el, prof, its, alg = run(args.iterations, args.epsilon, args.steps, args.warmup, profile=True)
     local_s = parallel.all_over_ranks(dist, getattr(time_steps, "local_s", el), dev if backend == "nccl" else None)
     P = alg._p
     pairs = B * world * args.steps
     fps = pairs / el
+    if args.dump_outputs and rank == 0:
+        dump_flows(args.dump_outputs, flows)   # before any leg below writes `flows` again
+    mean_it = float(np.mean(its))
+    ab_pair = algo_bytes_per_pair(W, H, warps, mean_it)
+    out = {"metric": "frame-pairs/sec dense TV-L1 flow @1080p", "value": fps, "unit": "pairs/s", "n_gpus": world,
+           "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * el / args.steps,
+           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+           "config": {"workload": f"DualTVL1 dense flow, {W}x{H} CV_32FC1, {B} pairs/GPU/step (BASELINE configs[1]; 64 pairs/GPU = the per-GPU share of configs[4])",
+                      "object": "default-constructed OpticalFlowDual_TVL1 + setNumIterations(N) + setEpsilon(eps); miflow extensions at "
+                                "the library defaults unless listed.  NOTE: the reference's accuracy test (cudaoptflow/test/"
+                                "test_optflow.cpp:448-451) calls setNumIterations(10) ONLY, i.e. epsilon stays 0.01 and its loop is "
+                                "convergence-checked: that literal setting is variants.iterations10_eps0.01_reference_test_setting; the "
+                                "headline's epsilon = 0 makes N = 10 fixed work (BASELINE.md section 2 accounting)",
+                      "iterations": args.iterations, "epsilon": args.epsilon, "warps": warps, "nscales": 5,
+                      "executed_iterations_per_warp_mean": mean_it,
+                      "semantics": "CPU_REF" if P.semantics == capi.MI_SEM_CPU_REF else "CUDA_COMPAT",
+                      "math": "exact" if P.exact_math else "fast", "time_block": P.time_block,
+                      "lanes": alg.calc_lanes() if hasattr(alg, "calc_lanes") else (2 if (P.lanes == 0 and B >= 4) or P.lanes == 2 else 1),
+                      "algorithmic_GB_per_pair": ab_pair / 1e9},
+           # every rank's own rate (its batch over its own time, before the closing barrier): a slow GPU or link shows here, the
+           # aggregate `value` is all pairs over the SLOWEST rank's time
+           "per_rank_pairs_per_s": [B * args.steps / t_ for t_ in local_s],
+           "rccl_ranks": ranks_info}
+    if not args.full:
+        return finish(out, dist, rank, full=False)
+
     # accuracy of what was just computed: EPE vs the analytic flow of pair 0
     gt = base[0][2]
     f0 = flows[0].cpu().numpy()
     epe_gt = float(np.sqrt(((f0 - gt) ** 2).sum(-1))[40:-40, 40:-40].mean())
 
-    mean_it = float(np.mean(its))
-    ab_pair = algo_bytes_per_pair(W, H, warps, mean_it)
     blocked = (not P.exact_math) and P.time_block != 1
     (ms_it, n_it, bytes_it), (ms_w, n_w, bytes_w) = prof
     px_levels = float(sum(level_pixels(W, H)))
@@ -1378,29 +1436,10 @@ def main():
             "note": "iteration kernel (static mix x pixel-iterations x halo factors) + warp kernel (static count x pixels) over the wall "
                     "time of a step; resize / convert / pack (4 % of the kernel time) not counted"}
 
-    out = {"metric": "frame-pairs/sec dense TV-L1 flow @1080p", "value": fps, "unit": "pairs/s", "n_gpus": world,
-           "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * el / args.steps,
-           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-           "config": {"workload": f"DualTVL1 dense flow, {W}x{H} CV_32FC1, {B} pairs/GPU/step (BASELINE configs[1]; 64 pairs/GPU = the per-GPU share of configs[4])",
-                      "object": "default-constructed OpticalFlowDual_TVL1 + setNumIterations(N) + setEpsilon(eps); miflow extensions at "
-                                "the library defaults unless listed.  NOTE: the reference's accuracy test (cudaoptflow/test/"
-                                "test_optflow.cpp:448-451) calls setNumIterations(10) ONLY, i.e. epsilon stays 0.01 and its loop is "
-                                "convergence-checked: that literal setting is variants.iterations10_eps0.01_reference_test_setting; the "
-                                "headline's epsilon = 0 makes N = 10 fixed work (BASELINE.md section 2 accounting)",
-                      "iterations": args.iterations, "epsilon": args.epsilon, "warps": warps, "nscales": 5,
-                      "executed_iterations_per_warp_mean": mean_it,
-                      "semantics": "CPU_REF" if P.semantics == capi.MI_SEM_CPU_REF else "CUDA_COMPAT",
-                      "math": "exact" if P.exact_math else "fast", "time_block": P.time_block,
-                      "lanes": alg.calc_lanes() if hasattr(alg, "calc_lanes") else (2 if (P.lanes == 0 and B >= 4) or P.lanes == 2 else 1),
-                      "algorithmic_GB_per_pair": ab_pair / 1e9},
-           # every rank's own rate (its batch over its own time, before the closing barrier): a slow GPU or link shows here, the
-           # aggregate `value` is all pairs over the SLOWEST rank's time
-           "per_rank_pairs_per_s": [B * args.steps / t_ for t_ in local_s],
-           "rccl_ranks": ranks_info,
-           "whole_job_algorithmic_GBps": ab_pair * fps / 1e9,
-           "whole_job_frac_of_hbm_peak": ab_pair * fps / 1e9 / HBM_PEAK_GBS,
-           "epe_vs_analytic_flow_px": epe_gt,
-           "roofline": roof}
+    out.update({"whole_job_algorithmic_GBps": ab_pair * fps / 1e9,
+                "whole_job_frac_of_hbm_peak": ab_pair * fps / 1e9 / HBM_PEAK_GBS,
+                "epe_vs_analytic_flow_px": epe_gt,
+                "roofline": roof})
 
     if world == 1 and not args.no_power:
         # the same step held on the chip for a few seconds with rocm-smi polled beside it (untimed leg: the headline above is not touched)
@@ -1495,7 +1534,7 @@ def main():
             var["class_defaults_300_eps0.01_history_from_other_pairs"] = {"error": repr(e)[:200]}
         try:
             import subprocess
-            r_ = subprocess.run([sys.executable, os.path.abspath(__file__), "--no-variants", "--no-cpu", "--no-secondary", "--no-power", "--iterations", "300",
+            r_ = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--no-variants", "--no-cpu", "--no-secondary", "--no-power", "--iterations", "300",
                                  "--epsilon", "0.01", "--steps", str(max(2, hs)), "--warmup", "1", "--batch", str(B)], capture_output=True, text=True,
                                 env=dict(os.environ, MIFLOW_TB_HIST="0"), timeout=300)
             d_ = json.loads([l for l in r_.stdout.splitlines() if l.startswith("{")][-1])
@@ -1785,13 +1824,21 @@ def main():
         del I0, I1, flows
         torch.cuda.empty_cache()
         out["secondary"] = secondary(args)
-    # The JSON line must be the LAST thing on stdout: RCCL writes a version banner to the C-level stdout, which stays in the C
-    # buffer until the process exits when stdout is a pipe.  Tear the group down first, push the C buffer out, then print.
+    finish(out, dist, rank, full=True, exchange_hung=exchange_hung)
+
+
+def finish(out, dist, rank, full, exchange_hung=False):
+    """The JSON line must be the LAST thing on stdout: RCCL writes a version banner to the C-level stdout, which stays in the C
+    buffer until the process exits when stdout is a pipe.  Tear the group down first, push the C buffer out, then print.  A run
+    without --full prints the compact line only (no long form to write)."""
     if dist is not None and not exchange_hung:
         dist.destroy_process_group()
     _flush_c_stdio()
     if rank == 0:
-        emit(out)
+        if full:
+            emit(out)
+        else:
+            print(compact_line(out), flush=True)
     if exchange_hung:
         os._exit(0)
 

@@ -99,3 +99,35 @@ def test_bench_refuses_work_skipping_switches():
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run"], env=dict(os.environ, **{var: "1"}),
                            capture_output=True, text=True, timeout=120)
         assert r.returncode != 0 and var in r.stderr and r.stdout.strip() == ""
+
+
+def test_dump_flows_writes_a_fixed_float32_sample_within_64_mb(tmp_path):
+    """--dump-outputs: the flows of the last timed step as float32 .npy files -- pair 0 whole where it fits, and the same seeded sample
+    of the whole batch from run to run -- at most 64 MB in all, also for 4K frames."""
+    import numpy as np
+    import torch
+    flows = torch.from_numpy(np.random.default_rng(5).standard_normal((4, 1080, 1920, 2), dtype=np.float32))
+    for d in ("a", "b"):
+        bench.dump_flows(str(tmp_path / d), flows)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["flow_pair0.npy", "flow_sample.npy"]
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype == np.float32 and np.array_equal(x, y)
+    assert np.array_equal(np.load(tmp_path / "a" / "flow_pair0.npy"), flows[0].numpy())
+    s = np.load(tmp_path / "a" / "flow_sample.npy")
+    assert s.shape == (bench.DUMP_SAMPLE, 2) and np.isin(s[:, 0], flows[..., 0].numpy()).all()
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 << 20
+    bench.dump_flows(str(tmp_path / "k4"), torch.zeros((1, 2160, 3840, 2)))
+    assert os.listdir(tmp_path / "k4") == ["flow_sample.npy"]
+
+
+def test_full_and_dump_outputs_options():
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--full", "--dump-outputs", "unused"],
+                       capture_output=True, text=True, timeout=120, env=env)
+    assert r.returncode == 0 and json.loads(r.stdout.splitlines()[-1])["dry_run"], r.stderr[-2000:]
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "stereobm", "--dump-outputs", "unused"],
+                       capture_output=True, text=True, timeout=120, env=env)
+    assert r.returncode != 0 and "--dump-outputs" in r.stderr and r.stdout.strip() == ""

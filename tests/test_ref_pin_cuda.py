@@ -229,28 +229,37 @@ def test_farneback_oracle_equals_the_reference_cuda_host_class(oracle, h, w, see
 
 # ------------------------------------------------------------------- SURF: the reference's HOST class over surf.cu, end to end
 def _surf_tables_of_the_reference():
-    """c_aptX / c_aptY / c_aptW / c_DW parsed out of modules/xfeatures2d/src/cuda/surf.cu (None when /root/reference is absent)."""
-    import os
-    import re
-    path = "/root/reference/modules/xfeatures2d/src/cuda/surf.cu"
-    if not os.path.exists(path):
-        return None
-    src = open(path).read()
-    out = []
-    for name in ("c_aptX", "c_aptY", "c_aptW", "c_DW"):
-        body = re.search(name + r"\s*\[[^\]]*\]\s*=\s*\{(.*?)\};", src, re.S).group(1)
-        out.append(np.array([np.float32(float(v.rstrip("f"))) for v in re.findall(r"[-+]?\d+\.?\d*(?:[eE][-+]?\d+)?f?", body)], np.float32))
-    return out
+    """c_aptX / c_aptY / c_aptW / c_DW of modules/xfeatures2d/src/cuda/surf.cu as compiled into oracle/_ref/libref_cu.so.  They are
+    local read-only symbols there (no dlsym): found through the library's ELF64 symbol table and read from the file."""
+    import struct
+    refcu.lib()                                        # builds oracle/_ref where it is missing
+    data = open(refcu.LIB, "rb").read()
+    shoff, = struct.unpack_from("<Q", data, 0x28)
+    shentsize, shnum = struct.unpack_from("<HH", data, 0x3A)
+    sh = [struct.unpack_from("<IIQQQQIIQQ", data, shoff + k * shentsize) for k in range(shnum)]   # name type flags addr offset size link ...
+    symtab = next(s for s in sh if s[1] == 2)          # SHT_SYMTAB
+    strtab = sh[symtab[6]]
+    names = ("c_aptX", "c_aptY", "c_aptW", "c_DW")
+    found = {}
+    for off in range(symtab[4], symtab[4] + symtab[5], 24):
+        st_name, _, _, shndx, value, size = struct.unpack_from("<IBBHQQ", data, off)
+        start = strtab[4] + st_name
+        sym = data[start:data.index(b"\0", start)]
+        for t in names:
+            if b"4surf" in sym and sym.endswith(b"%d%sE" % (len(t), t.encode())):   # cv::cuda::device::surf::<t>
+                sec = sh[shndx]
+                found[t] = np.frombuffer(data, np.float32, size // 4, sec[4] + value - sec[3]).copy()
+    assert sorted(found) == sorted(names), sorted(found)
+    return [found[t] for t in names]
 
 
 def test_surf_weight_tables_equal_the_literals_of_surf_cu(oracle):
     """surf.cu:520-522,685-707 hold the orientation sample offsets / weights and the 20 x 20 descriptor weights as LITERALS.  The
     oracle (and csrc/surf_api.cpp, same code) GENERATES them -- outer products in float of the Gaussian kernel as OpenCV 2.4 rounded it
     (exp -> float, sum in double, float * (1 / sum) -> float) for sigma = 2.5f / 3.3f -- and must reproduce every literal bit for bit.
-    (Today's single-rounding getGaussianKernel, which the CPU class calls at run time, differs in 60 / 113 and 188 / 400 entries.)"""
+    (Today's single-rounding getGaussianKernel, which the CPU class calls at run time, differs in 60 / 113 and 188 / 400 entries.)
+    The literals are read as the compiler stored them in the reference library, so the test needs oracle/_ref, not the source tree."""
     ref = _surf_tables_of_the_reference()
-    if ref is None:
-        pytest.skip("/root/reference absent")
     for r, mine, n in zip(ref, oracle.surf_tables(), (113, 113, 113, 400)):
         assert r.shape == (n,)
         np.testing.assert_array_equal(mine, r)

@@ -11,7 +11,7 @@ for r in $(seq 1 "$R"); do
     lib=libmiflow.so; [ "$name" != "rel" ] && lib=libmiflow_$name.so
     envs=""; args=""
     for tok in $extra; do case "$tok" in *=*) envs="$envs $tok";; *) args="$args $tok";; esac; done
-    line=$(env MIFLOW_LIB=$lib $envs timeout 600 python bench.py --no-variants --no-cpu --no-secondary --no-power --steps 10 --warmup 3 $args 2>>"$OUT/ab_err.log" | grep '^{' | tail -1)
+    line=$(env MIFLOW_LIB=$lib $envs timeout 600 python bench.py --full --no-variants --no-cpu --no-secondary --no-power --steps 10 --warmup 3 $args 2>>"$OUT/ab_err.log" | grep '^{' | tail -1)
     val=$(python -c "import json,sys; d=json.loads(sys.argv[1]); print('%.1f pairs/s  %.2f ms/step  iterate %.0f us' % (d['value'], d['ms_per_step'], (d.get('roofline') or {}).get('avg_launch_us') or 0))" "$line" 2>/dev/null)
     echo "round $r  $v: $val" | tee -a "$OUT/ab.log"
   done

@@ -16,7 +16,7 @@ ab_tile)
   CFGS="${AB_TILE_CFGS:-0,0 300000,0 1200000,0 2300000,0 2300000,2 9000000,0 9000000,2 40000000,2}"
   for cfg in $CFGS; do
     mx=${cfg%,*}; v=${cfg#*,}
-    (MIFLOW_TILE_MAXPX=$mx MIFLOW_TILE_VARIANT=$v timeout 300 python bench.py --no-variants --no-cpu --no-secondary --steps 12 --warmup 3 2>$O/ab_tile_${mx}_$v.err | tail -1) > $O/ab_tile_${mx}_$v.json
+    (MIFLOW_TILE_MAXPX=$mx MIFLOW_TILE_VARIANT=$v timeout 300 python bench.py --full --no-variants --no-cpu --no-secondary --steps 12 --warmup 3 2>$O/ab_tile_${mx}_$v.err | tail -1) > $O/ab_tile_${mx}_$v.json
     python - <<PY
 import json
 try:
@@ -27,7 +27,7 @@ PY
   done ;;
 timeline)
   cd /tmp
-  timeout 400 rocprofv3 --kernel-trace -f csv -d $R/$O/tl -- python $R/bench.py --no-variants --no-cpu --no-secondary --steps 3 --warmup 2 > $R/$O/tl_bench.log 2>&1
+  timeout 400 rocprofv3 --kernel-trace -f csv -d $R/$O/tl -- python $R/bench.py --full --no-variants --no-cpu --no-secondary --steps 3 --warmup 2 > $R/$O/tl_bench.log 2>&1
   cd $R
   python tools/timeline.py $O/tl > $O/timeline.txt 2>&1; tail -5 $O/timeline.txt
   find $O -type f -size +4M -delete ;;
@@ -37,7 +37,7 @@ ab_env)
   for cfg in ${AB_ENVS:--}; do
     i=$((i+1))
     envs=""; [ "$cfg" != "-" ] && envs=$(echo $cfg | tr '+' ' ')
-    (env $envs timeout 300 python bench.py --no-variants --no-cpu --no-secondary --steps ${AB_STEPS:-12} --warmup 3 ${AB_ARGS:-} 2>$O/ab_env_$i.err | tail -1) > $O/ab_env_$i.json
+    (env $envs timeout 300 python bench.py --full --no-variants --no-cpu --no-secondary --steps ${AB_STEPS:-12} --warmup 3 ${AB_ARGS:-} 2>$O/ab_env_$i.err | tail -1) > $O/ab_env_$i.json
     python - <<PY
 import json
 try:
@@ -52,7 +52,7 @@ ab_args)
   IFS=';' read -ra LISTS <<< "${AB_ARGLIST:-}"
   for a in "${LISTS[@]}"; do
     i=$((i+1))
-    (env ${AB_ENV:-} timeout 300 python bench.py --no-variants --no-cpu --no-secondary --warmup 3 $a 2>$O/ab_args_$i.err | tail -1) > $O/ab_args_$i.json
+    (env ${AB_ENV:-} timeout 300 python bench.py --full --no-variants --no-cpu --no-secondary --warmup 3 $a 2>$O/ab_args_$i.err | tail -1) > $O/ab_args_$i.json
     python - <<PY
 import json
 try:
@@ -70,7 +70,7 @@ smoke)
 ab_warp)
   for cfg in "1 2" "2 2" "4 2" "4 1"; do
     set -- $cfg
-    (MIFLOW_WARP_NP=$1 timeout 300 python bench.py --no-variants --no-cpu --no-secondary --lanes $2 --steps 12 --warmup 3 2>$O/ab_np$1_l$2.err | tail -1) > $O/ab_np$1_l$2.json
+    (MIFLOW_WARP_NP=$1 timeout 300 python bench.py --full --no-variants --no-cpu --no-secondary --lanes $2 --steps 12 --warmup 3 2>$O/ab_np$1_l$2.err | tail -1) > $O/ab_np$1_l$2.json
     python - <<PY
 import json
 try:
@@ -81,12 +81,12 @@ PY
   done ;;
 bench)
   # stdout = the compact line the driver parses (bench_line.json); the long form is bench_full.json (copied as bench.json)
-  (timeout 900 python bench.py ${BENCH_ARGS:-} 2>$O/bench.err) > $O/bench_stdout.txt; tail -1 $O/bench_stdout.txt > $O/bench_line.json
+  (timeout 900 python bench.py --full ${BENCH_ARGS:-} 2>$O/bench.err) > $O/bench_stdout.txt; tail -1 $O/bench_stdout.txt > $O/bench_line.json
   echo "stdout lines: $(wc -l < $O/bench_stdout.txt), last line bytes: $(tail -1 $O/bench_stdout.txt | wc -c)"
   cp bench_full.json $O/bench.json 2>/dev/null; cat $O/bench_line.json; grep -v "full record" $O/bench.err | tail -5 ;;
 trace)
   cd /tmp
-  timeout 400 rocprofv3 --kernel-trace --stats -f csv -d $R/$O/trace -- python $R/bench.py --no-variants --no-cpu --no-secondary --steps 5 --warmup 2 > $R/$O/trace_bench.log 2>&1
+  timeout 400 rocprofv3 --kernel-trace --stats -f csv -d $R/$O/trace -- python $R/bench.py --full --no-variants --no-cpu --no-secondary --steps 5 --warmup 2 > $R/$O/trace_bench.log 2>&1
   cd $R
   find $O/trace -name "*kernel_stats.csv" | head -3
   for f in $(find $O/trace -name "*kernel_stats.csv" | head -1); do cp $f $O/kernel_stats.csv; head -12 $f; done
@@ -94,7 +94,7 @@ trace)
 pmc)
   cd /tmp
   for c in FETCH_SIZE WRITE_SIZE; do
-    timeout 400 rocprofv3 --kernel-trace --pmc $c -f csv -d $R/$O/pmc_$c -- python $R/bench.py --no-variants --no-cpu --no-secondary --steps 2 --warmup 1 > $R/$O/pmc_$c.log 2>&1
+    timeout 400 rocprofv3 --kernel-trace --pmc $c -f csv -d $R/$O/pmc_$c -- python $R/bench.py --full --no-variants --no-cpu --no-secondary --steps 2 --warmup 1 > $R/$O/pmc_$c.log 2>&1
   done
   cd $R
   python tools/pmc_summary.py $O > $O/pmc_summary.md 2>&1; head -30 $O/pmc_summary.md
@@ -102,7 +102,7 @@ pmc)
   find $O -type f -size +4M -delete ;;
 trace_defaults)
   cd /tmp
-  timeout 400 rocprofv3 --kernel-trace --stats -f csv -d $R/$O/trace_defaults -- python $R/bench.py --defaults --no-variants --no-cpu --no-secondary --steps 2 --warmup 1 > $R/$O/trace_defaults_bench.log 2>&1
+  timeout 400 rocprofv3 --kernel-trace --stats -f csv -d $R/$O/trace_defaults -- python $R/bench.py --full --defaults --no-variants --no-cpu --no-secondary --steps 2 --warmup 1 > $R/$O/trace_defaults_bench.log 2>&1
   cd $R
   tail -1 $O/trace_defaults_bench.log | cut -c1-600
   for f in $(find $O/trace_defaults -name "*kernel_stats.csv" | head -1); do cp $f $O/kernel_stats_defaults.csv; head -12 $f; done
@@ -119,7 +119,7 @@ trace_fb)
   find $O -type f -size +4M -delete ;;
 spec_quick)
   for sl in 0 1; do
-    (timeout 300 python bench.py --defaults --stop-slack $sl --no-variants --no-cpu --no-secondary --steps 4 --warmup 2 2>$O/spec_sl$sl.err | tail -1) > $O/spec_sl$sl.json
+    (timeout 300 python bench.py --full --defaults --stop-slack $sl --no-variants --no-cpu --no-secondary --steps 4 --warmup 2 2>$O/spec_sl$sl.err | tail -1) > $O/spec_sl$sl.json
     python - <<PY
 import json
 try:
@@ -142,7 +142,7 @@ ab_planwps)
   for wps in 0 2 1; do
     for mode in fixed defaults; do
       extra=""; [ $mode = defaults ] && extra="--defaults"
-      (MIFLOW_TB_WPS=$wps timeout 300 python bench.py $extra --no-variants --no-cpu --no-secondary --steps 6 --warmup 2 2>$O/ab_wps${wps}_$mode.err | tail -1) > $O/ab_wps${wps}_$mode.json
+      (MIFLOW_TB_WPS=$wps timeout 300 python bench.py --full $extra --no-variants --no-cpu --no-secondary --steps 6 --warmup 2 2>$O/ab_wps${wps}_$mode.err | tail -1) > $O/ab_wps${wps}_$mode.json
       python - <<PY
 import json
 try:
@@ -153,7 +153,7 @@ PY
   done ;;
 trace_tb5)
   cd /tmp
-  timeout 400 rocprofv3 --kernel-trace --stats -f csv -d $R/$O/trace_tb5 -- python $R/bench.py --time-block 5 --no-variants --no-cpu --no-secondary --steps 3 --warmup 1 > $R/$O/trace_tb5_bench.log 2>&1
+  timeout 400 rocprofv3 --kernel-trace --stats -f csv -d $R/$O/trace_tb5 -- python $R/bench.py --full --time-block 5 --no-variants --no-cpu --no-secondary --steps 3 --warmup 1 > $R/$O/trace_tb5_bench.log 2>&1
   cd $R
   python - <<PY
 import csv, glob, collections
@@ -170,7 +170,7 @@ PY
 pmc_sq)
   cd /tmp
   rm -rf $R/$O/pmc_sq
-  env ${PMC_ENV:-} timeout 400 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_INSTS_VALU -f csv -d $R/$O/pmc_sq -- python $R/bench.py --lanes 1 --no-variants --no-cpu --no-secondary --steps 2 --warmup 1 > $R/$O/pmc_sq.log 2>&1
+  env ${PMC_ENV:-} timeout 400 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_INSTS_VALU -f csv -d $R/$O/pmc_sq -- python $R/bench.py --full --lanes 1 --no-variants --no-cpu --no-secondary --steps 2 --warmup 1 > $R/$O/pmc_sq.log 2>&1
   cd $R
   python - <<PY
 import csv, glob, collections

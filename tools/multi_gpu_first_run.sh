@@ -69,10 +69,10 @@ step multi_entry_peer_copies 900 env MIFLOW_MULTI_RCCL=0 python "$OUT/multi_entr
 # 3. the bench at 1 / 2 / 4 / 8 ranks, with and without the exchange leg
 for N in 1 2 4 8; do
   [ "$N" -le "$NGPU" ] || continue
-  step "bench_gpus${N}" 1500 python bench.py --gpus "$N" --steps 10 --warmup 2 --no-variants --no-secondary --no-cpu
+  step "bench_gpus${N}" 1500 python bench.py --full --gpus "$N" --steps 10 --warmup 2 --no-variants --no-secondary --no-cpu
   cp -f bench_full.json "$OUT/bench_full_gpus${N}.json" 2>/dev/null
   if [ "$N" -gt 1 ]; then
-    step "bench_gpus${N}_no_exchange" 1500 env MIFLOW_BENCH_EXCHANGE=0 python bench.py --gpus "$N" --steps 10 --warmup 2 --no-variants --no-secondary --no-cpu
+    step "bench_gpus${N}_no_exchange" 1500 env MIFLOW_BENCH_EXCHANGE=0 python bench.py --full --gpus "$N" --steps 10 --warmup 2 --no-variants --no-secondary --no-cpu
   fi
 done
 
