@@ -55,8 +55,6 @@ const Tuning &tuning()
 #ifndef MIFLOW_EXPERIMENTS
         warn_unread_switches();
 #endif
-        const char *w = EXP_ENV("MIFLOW_WARP");
-        t.warp_legacy = (w && w[0] == 'p') ? 1 : 0;
         t.x_skip = EXP_INT("MIFLOW_X_SKIP", 0);
         t.warp_tile = EXP_INT("MIFLOW_WARP_TILE", 32);
         if (t.warp_tile != 64 && t.warp_tile != 32 && t.warp_tile != 16) t.warp_tile = 32;
@@ -67,7 +65,6 @@ const Tuning &tuning()
         t.tb_swz = EXP_INT("MIFLOW_TB_SWZ", 1);
         // joined-wave form of the T = 10 blocked iteration kernel (tvl1_tbr_kernels.hip): 2 (default since r03w) = hand-over with one
         // workgroup barrier per stage, 1 = with tags and bounded waits, 0 = independent 64-column waves; all three bit-identical
-        t.warp_zoom = EXP_INT("MIFLOW_WARP_ZOOM", 0);   // r08k: bit-identical, 1 388 against 1 406 pairs/s: the per-pixel (double precision) coordinates of cv::resize cost more than the resize launch and its 8 B/px
         t.tb_p16 = EXP_INT("MIFLOW_TB_P16", 0);
         t.tb_nograd = EXP_INT("MIFLOW_TB_NOGRAD", 1);
         t.tb_skip_p = EXP_INT("MIFLOW_TB_SKIP_P", 1);

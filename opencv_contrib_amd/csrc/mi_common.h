@@ -29,16 +29,14 @@ void set_error(const char *fmt, ...);
     } while (0)
 
 // Tuning switches (environment, read ONCE for the process under std::call_once; DESIGN.md lists them).  None is needed
-// in production: every default is the measured best.
+// in production: every default is the measured best.  The TV-L1 calc plan reads its switches through tv_knobs() (tvl1_plan.h).
 struct Tuning {
     int x_skip;              // MIFLOW_X_SKIP (EXPERIMENTS BUILD ONLY; wrong results): 1 = no warp launches after a level's first, 2 = no iteration launches; always 0 in the release library
-    int warp_legacy;         // MIFLOW_WARP=pk: packed-float4 gather warp (the round-1 kernel) instead of the fused-gradient one
     int warp_tile;           // MIFLOW_WARP_TILE: pixels of a wave along x in the warp kernels (64 | 32 | 16)
     int warp_lds;            // MIFLOW_WARP_LDS: windows of the fused-gradient warp read from an LDS-staged region of I1 (1) or gathered from global memory (0)
     int warp_fast;           // MIFLOW_WARP_FAST: fast-math calcs form the warp's bicubic sums separably (1: +4.7 % pairs/s, 2-3 x the EPE against the oracle) or tap by tap in the reference's order (0); -1 (default): separably under MI_SEM_CUDA_COMPAT, whose map is not quantised (EPE 1.2e-5 either way), tap by tap under MI_SEM_CPU_REF
     int warp_np;             // MIFLOW_WARP_NP: patches a wave of the fused-gradient warp kernel walks (1 | 2 | 4)
     int tb_swz;             // MIFLOW_TB_SWZ: XCD-aware workgroup remap of the blocked iteration kernels
-    int warp_zoom;          // MIFLOW_WARP_ZOOM: the first warp of a scale zooms the coarser flow itself instead of a resize launch (1; default 0: measured slower)
     int tb_p16;             // MIFLOW_TB_P16=1 (opt-in, CHANGES RESULTS within the fast path's tolerance): p between the passes of a scale as signed 16-bit fixed point
     int tb_nograd;          // MIFLOW_TB_NOGRAD: the blocked pass forms |grad|^2 itself and the warp does not store the plane (1, default) / stored plane (0)
     int tb_hist;            // MIFLOW_TB_HIST: block lengths of the convergence-checked path from the handle's previous calc (1, default)

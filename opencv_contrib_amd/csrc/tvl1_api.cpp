@@ -27,6 +27,31 @@ struct LevelBuf {
 
 struct SlotInfo { int scale, warp; };
 
+// A lane's device (Host = false) or pinned host buffer of n elements: grown on demand, never shrunk, freed with the handle.
+template <class T, bool Host = false, unsigned HostFlags = 0>
+struct GrowBuf {
+    T *p = nullptr;
+    size_t n = 0;
+    GrowBuf() = default;
+    GrowBuf(const GrowBuf &) = delete;
+    ~GrowBuf() { release(); }
+    int ensure(size_t want)
+    {
+        if (n >= want) return MI_OK;
+        release();
+        void *q = nullptr;
+        if (Host) MI_HIP_TRY(hipHostMalloc(&q, sizeof(T) * want, HostFlags));
+        else MI_HIP_TRY(hipMalloc(&q, sizeof(T) * want));
+        p = (T *)q; n = want;
+        return MI_OK;
+    }
+    void release()
+    {
+        if (p) (void)(Host ? hipHostFree(p) : hipFree(p));
+        p = nullptr; n = 0;
+    }
+};
+
 }  // namespace
 
 // Everything one sub-batch needs: its own arena, pointer table, control slots and profiling events, so that two lanes can
@@ -36,40 +61,34 @@ struct Lane {
     // capacity the arena was built for
     int capW = 0, capH = 0, capB = 0, capScales = 0;
     double capStep = 0;
-    bool capGamma = false, capMedian = false, capPack = false;
+    bool capGamma = false, capMedian = false;
     float *arena = nullptr;
-    size_t arena_floats = 0, arena_bytes = 0;
+    size_t arena_bytes = 0;
     std::vector<LevelBuf> L;
     // full-resolution-capacity scratch planes (re-laid-out densely per level)
     float *scr[6] = {};    // scr[0..1]: median-filter temporaries; I1wx, I1wy, grad, rho_c
-    float *pack = nullptr; // MIFLOW_WARP=pk only: float4 {I1, I1x, I1y, 0} per pixel of the current level
     float *pbuf[2][6] = {};   // [set][p11,p12,p21,p22,p31,p32]
-    PtrTab *tab_dev = nullptr;
-    int tab_cap = 0;
+    GrowBuf<PtrTab> tab;
     std::vector<PtrTab> tab_host;   // source of the asynchronous upload: must outlive the call
     // device loop control
-    int2 *S = nullptr;
-    unsigned long long *E = nullptr;
-    double *Pd = nullptr;   // per slot prevError (cv::cuda check schedule)
-    int4 *X = nullptr;      // per slot state of the speculative steps (SpecK::X)
+    GrowBuf<int2> S;
+    GrowBuf<unsigned long long> E;
+    GrowBuf<double> Pd;   // per slot prevError (cv::cuda check schedule)
+    GrowBuf<int4> X;      // per slot state of the speculative steps (SpecK::X)
     long long Q = 0;
     int ctlB = 0;
     // iteration counts per (scale, warp, pair slot) of the previous calc, two parities (SpecK::h_in / h_out)
-    int *H = nullptr;
-    size_t H_cap = 0;             // ints per parity
+    GrowBuf<int> H;
     unsigned long long H_sig = 0; // geometry / batch / loop shape the counts belong to (0: none)
     int H_par = 0;                // parity the NEXT calc writes
     std::vector<SlotInfo> slots;
-    int batch = 0;          // pairs of the last calc
     // host feedback (mi_tvl1_params.host_feedback): pinned landing area of the control slots read back between launches
-    int2 *fb_host = nullptr;
-    int fb_cap = 0;
+    GrowBuf<int2, true, hipHostMallocDefault> fb_host;
     hipEvent_t fb_ev = nullptr;
-    int *fb_flag = nullptr;   // polled form (SpecK::fb_flag): {decision word, count} per pair, pinned
+    GrowBuf<int, true, hipHostMallocCoherent | hipHostMallocMapped> fb_flag;   // polled form (SpecK::fb_flag): {decision word, count} per pair
     int fb_seq = 0;
     std::vector<int> fb_hist;        // polled form: most iterations a (scale, warp) of the previous calc needed over its pairs (0: unknown)
     unsigned long long fb_hist_sig = 0;
-    long long fb_waits = 0, fb_skipped = 0;   // of the last calc: host waits, launches not enqueued
     // profiling (mi_tvl1_set_profiling)
     std::vector<hipEvent_t> ev_pool;
     struct Region { int e0, e1; long long launches; double bytes; int kind; int level; };   // kind 0: iteration launches, 1: warp launch; level = pyramid scale
@@ -94,8 +113,6 @@ struct mi_tvl1 {
     bool last_check = false;
     bool profiling = false;
 };
-
-static int round_half_even(double v) { return (int)std::lrint(v); }
 
 void mi_tvl1_default_params(mi_tvl1_params *p)
 {
@@ -204,8 +221,7 @@ int mi_tvl1_query_plan(int width, int height, int pairs_per_lane, int iterations
     MI_REQUIRE(width > 0 && height > 0 && pairs_per_lane > 0 && iterations_per_launch > 0, MI_ERR_BAD_ARG, "bad plan query");
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) { set_error("no HIP device"); return MI_ERR_NO_DEVICE; }
-    Geo g;
-    g.w = width; g.h = height; g.ld = (width + 63) / 64 * 64; g.ps = (long long)g.ld * height; g.batch = pairs_per_lane;
+    const Geo g{width, height, (width + 63) / 64 * 64, (long long)((width + 63) / 64 * 64) * height, pairs_per_lane};
     return tb_query_plan(iterations_per_launch, g, kernel, rows_per_band);
 }
 
@@ -251,16 +267,8 @@ void mi_tvl1_destroy(mi_tvl1 *h)
         for (hipEvent_t e : ln.ev_pool) (void)hipEventDestroy(e);
         free_arena(ln);
         if (ln.idle_ev) { (void)hipEventDestroy(ln.idle_ev); ln.idle_ev = nullptr; }
-        if (ln.tab_dev) (void)hipFree(ln.tab_dev);
-        if (ln.S) (void)hipFree(ln.S);
-        if (ln.E) (void)hipFree(ln.E);
-        if (ln.Pd) (void)hipFree(ln.Pd);
-        if (ln.X) (void)hipFree(ln.X);
-        if (ln.H) (void)hipFree(ln.H);
         if (ln.done) (void)hipEventDestroy(ln.done);
         if (ln.fb_ev) (void)hipEventDestroy(ln.fb_ev);
-        if (ln.fb_host) (void)hipHostFree(ln.fb_host);
-        if (ln.fb_flag) (void)hipHostFree(ln.fb_flag);
         if (ln.stream) (void)hipStreamDestroy(ln.stream);
     }
     if (h->fork) (void)hipEventDestroy(h->fork);
@@ -268,69 +276,27 @@ void mi_tvl1_destroy(mi_tvl1 *h)
     delete h;
 }
 
-// Level sizes: dsize = saturate_cast<int>(ssize * scaleStep) (cudawarping/src/resize.cpp:78),
-// stop below 16 px (cudaoptflow/src/tvl1flow.cpp:243-247).
-static int plan_levels(const mi_tvl1_params &P, int W, int H, int B, std::vector<Geo> &geo)
+// The lane's arena in the plan's layout (kept while the frame, the pyramid and the optional planes stay and the batch does not grow)
+static int ensure_arena(const mi_tvl1_params &P, Lane &ln, const TvPlan &pl, int W, int H, int B)
 {
-    geo.clear();
-    int w = W, h = H;
-    for (int s = 0; s < P.nscales; ++s) {
-        if (s > 0) {
-            w = round_half_even(w * P.scale_step);
-            h = round_half_even(h * P.scale_step);
-            if (w < 1 || h < 1) break;
-        }
-        Geo g;
-        g.w = w; g.h = h; g.ld = align_up(w, 64); g.ps = (long long)g.ld * h; g.batch = B;
-        geo.push_back(g);
-        if (s > 0 && (w < 16 || h < 16)) break;  // level s is built but not used
-    }
-    return (int)geo.size();
-}
-
-static int ensure_arena(const mi_tvl1_params &P, Lane &ln, int W, int H, int B)
-{
-    const bool gam = P.gamma != 0.0;
-    const bool med = P.median_filtering > 1;
-    const bool pk = tuning().warp_legacy != 0;
-    if (ln.arena && ln.capW == W && ln.capH == H && ln.capB >= B && ln.capScales == P.nscales && ln.capStep == P.scale_step &&
-        ln.capGamma == gam && ln.capMedian == med && ln.capPack == pk)
-        return MI_OK;
-    free_arena(ln);
-    std::vector<Geo> geo;
-    const int nl = plan_levels(P, W, H, B, geo);
-    size_t total = 0;
-    auto take = [&](size_t nfloats) { size_t o = total; total += (nfloats + 63) / 64 * 64; return o; };
-    std::vector<size_t> offI0(nl), offI1(nl), offU(nl * 6);
-    for (int l = 0; l < nl; ++l) {
-        const size_t n = (size_t)geo[l].ps * B;
-        offI0[l] = take(n); offI1[l] = take(n);
-        for (int k = 0; k < 6; ++k) offU[l * 6 + k] = (k % 3 == 2 && !gam) ? 0 : take(n);   // u3 planes only when gamma != 0
-    }
-    const size_t nfull = (size_t)geo[0].ps * B;
-    size_t offScr[6], offP[12];
-    for (int k = 0; k < 6; ++k) offScr[k] = (k < 2 && !med) ? 0 : take(nfull);   // scr[0..1]: median-filter temporaries
-    const size_t offPack = pk ? take(nfull * 4) : 0;
-    for (int k = 0; k < 12; ++k) offP[k] = (k % 6 >= 4 && !gam) ? 0 : take(nfull);
-    {
+    const bool gam = P.gamma != 0.0, med = pl.median != 0;
+    if (!(ln.arena && ln.capW == W && ln.capH == H && ln.capB >= B && ln.capScales == P.nscales && ln.capStep == P.scale_step &&
+          ln.capGamma == gam && ln.capMedian == med)) {
+        free_arena(ln);
         void *blk = nullptr;
-        const int brc = big_alloc(&blk, total * sizeof(float), &ln.arena_bytes);
-        if (brc) return brc;
+        if (const int rc = big_alloc(&blk, pl.arena.total * sizeof(float), &ln.arena_bytes)) return rc;
         ln.arena = (float *)blk;
+        const auto at = [&](size_t o) { return o == kNoPlane ? nullptr : ln.arena + o; };
+        ln.L.resize(pl.geo.size());
+        for (size_t l = 0; l < pl.geo.size(); ++l) {
+            ln.L[l].I0 = at(pl.arena.lv[l][0]); ln.L[l].I1 = at(pl.arena.lv[l][1]);
+            for (int k = 0; k < 6; ++k) ln.L[l].u[k / 3][k % 3] = at(pl.arena.lv[l][2 + k]);
+        }
+        for (int k = 0; k < 6; ++k) ln.scr[k] = at(pl.arena.scr[k]);
+        for (int k = 0; k < 12; ++k) ln.pbuf[k / 6][k % 6] = at(pl.arena.p[k]);
+        ln.capGamma = gam; ln.capMedian = med; ln.capW = W; ln.capH = H; ln.capB = B; ln.capScales = P.nscales; ln.capStep = P.scale_step;
     }
-    ln.arena_floats = total;
-    ln.L.resize(nl);
-    for (int l = 0; l < nl; ++l) {
-        ln.L[l].g = geo[l];
-        ln.L[l].I0 = ln.arena + offI0[l];
-        ln.L[l].I1 = ln.arena + offI1[l];
-        for (int k = 0; k < 6; ++k) ln.L[l].u[k / 3][k % 3] = (k % 3 == 2 && !gam) ? nullptr : ln.arena + offU[l * 6 + k];
-    }
-    for (int k = 0; k < 6; ++k) ln.scr[k] = ln.arena + offScr[k];
-    ln.pack = pk ? ln.arena + offPack : nullptr;
-    for (int k = 0; k < 12; ++k) ln.pbuf[k / 6][k % 6] = (k % 6 >= 4 && !gam) ? nullptr : ln.arena + offP[k];
-    ln.capGamma = gam; ln.capMedian = med; ln.capPack = pk;
-    ln.capW = W; ln.capH = H; ln.capB = B; ln.capScales = P.nscales; ln.capStep = P.scale_step;
+    for (size_t l = 0; l < pl.geo.size(); ++l) ln.L[l].g = pl.geo[l];   // (this calc's batch)
     return MI_OK;
 }
 
@@ -359,7 +325,410 @@ static int check_pair(const mi_mat *I0, const mi_mat *I1, const mi_mat *flow, co
     return MI_OK;
 }
 
-// The whole coarse-to-fine computation of n pairs on one stream (OpticalFlowDual_TVL1_Impl::calcImpl + procOneScale).
+const TvKnobs &mi::tvl1::tv_knobs()
+{
+    static const TvKnobs k = [] {
+        const Tuning &t = tuning();
+        TvKnobs v{};
+        v.tile_maxpx = t.tile_maxpx; v.tile_spec = t.tile_spec; v.tile_variant = t.tile_variant; v.tile_small_wgs = t.tile_small_wgs;
+        v.tile_variants = std::min(tile_variants(), (int)(sizeof(v.tile_rows) / sizeof(v.tile_rows[0])));
+        for (int i = 0; i < v.tile_variants; ++i) v.tile_rows[i] = tile_shape_rows(i);
+        v.tile_fb_block = t.tile_fb_block; v.tile_fb_model = t.tile_fb_model;
+        v.tb_force = t.tb_force != 0; v.tb_nograd = t.tb_nograd; v.tb_jw = t.tb_jw; v.tb_ppl = t.tb_ppl; v.tb_jw_spec = t.tb_jw_spec;
+        v.tb_fw = t.tb_fw; v.tb_skip_p = t.tb_skip_p; v.tb_hist = t.tb_hist; v.spec = t.spec; v.exact_tb = t.exact_tb;
+        v.fb_poll = t.fb_poll; v.fb_ahead = t.fb_ahead; v.warp_fast = t.warp_fast; v.warp_lds = t.warp_lds; v.x_skip = t.x_skip;
+        return v;
+    }();
+    return k;
+}
+
+// The lane's pointer table, control slots, history and host-feedback buffers for plan pl (stream-ordered uploads and clears).
+static int ensure_buffers(const TvPlan &pl, Lane &ln, int B, const mi_mat *I0s, const mi_mat *I1s, mi_mat *flows, hipStream_t st)
+{
+    int rc;
+    if ((rc = ln.tab.ensure(B))) return rc;
+    ln.tab_host.resize(B);
+    for (int i = 0; i < B; ++i)
+        ln.tab_host[i] = PtrTab{I0s[i].data, I1s[i].data, flows[i].data, (long long)I0s[i].step, (long long)I1s[i].step, (long long)flows[i].step};
+    // pageable source: a few KB, staged by the runtime before the call returns; kept in the lane anyway
+    MI_HIP_TRY(hipMemcpyAsync(ln.tab.p, ln.tab_host.data(), sizeof(PtrTab) * B, hipMemcpyHostToDevice, st));
+    if (pl.check) {
+        MI_REQUIRE(pl.Q <= kMaxSlots, MI_ERR_BAD_ARG, "scales x warps x iterations = %lld control slots exceed the limit of %lld", pl.Q, kMaxSlots);
+        if (ln.Q < pl.Q || ln.ctlB < B) {
+            const size_t n = (size_t)pl.Q * B;
+            if ((rc = ln.S.ensure(n)) || (rc = ln.E.ensure(n)) || (rc = ln.Pd.ensure(n)) || (rc = ln.X.ensure(n))) return rc;
+            ln.Q = pl.Q; ln.ctlB = B;
+        }
+        MI_HIP_TRY(hipMemsetAsync(ln.E.p, 0, sizeof(unsigned long long) * (size_t)ln.Q * B, st));
+        MI_HIP_TRY(hipMemsetAsync(ln.S.p, 0, sizeof(int2) * (size_t)ln.Q * B, st));
+    }
+    if (pl.hist) {   // counts of the previous calc of this lane
+        const int nw = (int)pl.warp[0].size();
+        const size_t h_n = (size_t)pl.used * nw * B;
+        if (ln.H.n < 2 * h_n) ln.H_sig = 0;
+        if ((rc = ln.H.ensure(2 * h_n))) return rc;
+        if (ln.H_sig != pl.hist_sig) {   // counts of another geometry say nothing: start from none (0 = no estimate)
+            MI_HIP_TRY(hipMemsetAsync(ln.H.p, 0, sizeof(int) * ln.H.n, st));
+            ln.H_sig = pl.hist_sig;
+        }
+        if (ln.fb_hist_sig != pl.hist_sig || ln.fb_hist.size() != (size_t)pl.used * nw) {
+            ln.fb_hist.assign((size_t)pl.used * nw, 0);
+            ln.fb_hist_sig = pl.hist_sig;
+        }
+        ln.H_par ^= 1;
+    }
+    if (pl.fb) {
+        const bool fresh = ln.fb_flag.n < 2 * (size_t)B;
+        if ((rc = ln.fb_host.ensure(2 * (size_t)B)) || (rc = ln.fb_flag.ensure(2 * (size_t)B))) return rc;
+        if (fresh) memset(ln.fb_flag.p, 0, sizeof(int) * ln.fb_flag.n);
+        if (!ln.fb_ev) MI_HIP_TRY(hipEventCreateWithFlags(&ln.fb_ev, hipEventDisableTiming));
+    }
+    return MI_OK;
+}
+
+namespace {
+
+// What one lane's calc carries from launch to launch; the executors below advance it.
+struct Run {
+    mi_tvl1 *h;
+    Lane &ln;
+    const TvPlan &pl;
+    const TvKnobs &K;
+    hipStream_t st;
+    int B;
+    size_t ev_used = 0;
+    Ctl ctl;                 // the device loop control every launch starts from (thr: the current scale's)
+    IterPlanes planes;       // the current scale's (planes.g = grad)
+    float *grad = nullptr;   // the current warp's |grad|^2 plane (nullptr: the warp does not store it)
+    float l_t, theta, taut;
+    int q = 0, q_last = -1, e_next = 0;   // device-control slot counters; next per-iteration error-sum index (speculative steps)
+    int q_settle_prev = -1, q_settle_scale = -1;   // settling launches of the previous warp / of the coarser scale's first warp
+    int fb_prev_warp = 2, fb_prev_scale = 2;       // launch index at which the previous warp / the coarser scale's first warp was found stopped
+    int cur = 0;             // host-known buffer set (fixed work)
+    bool first_of_scale = true;
+    bool pre_warped = false; // this warp's kernel was enqueued ahead, behind the previous warp's last launch (host feedback)
+};
+
+// records a profiling event on the lane's stream
+int record(Run &r, int *idx)
+{
+    if (r.ev_used == r.ln.ev_pool.size()) {
+        hipEvent_t e;
+        MI_HIP_TRY(hipEventCreate(&e));
+        r.ln.ev_pool.push_back(e);
+    }
+    *idx = (int)r.ev_used++;
+    MI_HIP_TRY(hipEventRecord(r.ln.ev_pool[*idx], r.st));
+    return MI_OK;
+}
+
+// level 0: convertTo(CV_32F, 8U ? 1 : 255) (tvl1flow.cpp:200-201); the scales (:238-266); the coarsest flow's start
+int enqueue_pyramid(Run &r, int type)
+{
+    const mi_tvl1_params &P = r.h->P;
+    Lane &ln = r.ln;
+    const int ns = r.pl.used, B = r.B;
+    int rc = convert(ln.tab.p, type, ln.L[0].I0, ln.L[0].I1, ln.L[0].g, r.st);
+    if (rc) return rc;
+    // CPU behaviour (optflow/src/tvl1flow.cpp:435-439); the CUDA calc() never splits the caller's flow (latent reference bug,
+    // SURVEY Appendix B Q8)
+    if (P.use_initial_flow && (rc = unpack_flow(ln.tab.p, ln.L[0].u[0][0], ln.L[0].u[0][1], ln.L[0].g, r.st))) return rc;
+    const float one3[3] = {1.f, 1.f, 1.f};
+    for (size_t s = 1; s < ln.L.size(); ++s) {
+        const LevelBuf &c = ln.L[s - 1];
+        const float *src[3][2] = {{c.I0, nullptr}, {c.I1, nullptr}, {nullptr, nullptr}};
+        float *dst[3] = {ln.L[s].I0, ln.L[s].I1, nullptr};
+        rc = resize(P.semantics, 2, src, 1, dst, c.g, ln.L[s].g, P.scale_step, P.scale_step, one3, nullptr, 0, r.st);
+        if (rc) return rc;
+        if ((int)s >= ns) break;
+        if (P.use_initial_flow) {
+            const float *us[3][2] = {{c.u[0][0], nullptr}, {c.u[0][1], nullptr}, {nullptr, nullptr}};
+            float *ud[3] = {ln.L[s].u[0][0], ln.L[s].u[0][1], nullptr};
+            const float post[3] = {(float)P.scale_step, (float)P.scale_step, 1.f};
+            rc = resize(P.semantics, 2, us, 1, ud, c.g, ln.L[s].g, P.scale_step, P.scale_step, post, nullptr, 0, r.st);
+            if (rc) return rc;
+        }
+    }
+    const LevelBuf &Lc = ln.L[ns - 1];
+    const size_t bytes = sizeof(float) * (size_t)Lc.g.ps * B;
+    if (!P.use_initial_flow) {
+        MI_HIP_TRY(hipMemsetAsync(Lc.u[0][0], 0, bytes, r.st));
+        MI_HIP_TRY(hipMemsetAsync(Lc.u[0][1], 0, bytes, r.st));
+    }
+    if (P.gamma != 0.0) MI_HIP_TRY(hipMemsetAsync(Lc.u[0][2], 0, bytes, r.st));   // u3 starts at 0 on the coarsest scale (tvl1flow.cpp:273-275)
+    return MI_OK;
+}
+
+// the warp of the current scale (warpBackward + centeredGradient, tvl1flow.cpp:325-340); ahead: enqueued before the host knows whether
+// the previous warp has stopped, it runs only for pairs whose slot q_last says so (Ctl::need_done)
+int launch_warp(Run &r, const LevelBuf &Lv, bool ahead)
+{
+    const float *u1v[2] = {Lv.u[0][0], Lv.u[1][0]}, *u2v[2] = {Lv.u[0][1], Lv.u[1][1]};
+    Ctl c = r.ctl;
+    c.q_prev = r.q_last;
+    c.need_done = ahead ? 1 : 0;
+    const bool dev_cur = ahead || (r.pl.check && !r.first_of_scale);   // at the first warp of a scale u lives in set 0 (host-known)
+    return warp_fused(r.h->P.semantics, r.pl.fast_warp, -1, Lv.I0, Lv.I1, u1v, u2v, nullptr, r.ln.scr[2], r.ln.scr[3],
+                      r.grad, r.ln.scr[5], r.h->cubic_tab, Lv.g, dev_cur ? &c : nullptr, r.cur, r.st);
+}
+
+// Fixed work: T iterations per HBM pass (tvl1_tbr_kernels.hip), the optional median filter between outer iterations; in exact math
+// blocks of up to 5 fused iterations (k_iterate_tbr MODE 2), bit-identical to one launch per iteration
+int run_blocked(Run &r, LevelBuf &Lv, const TvWarp &w, long long *nlaunch)
+{
+    const int sem = r.h->P.semantics;
+    float *const mu1[2] = {Lv.u[0][0], Lv.u[1][0]}, *const mu2[2] = {Lv.u[0][1], Lv.u[1][1]};
+    const int nb = (int)w.blocks.size();
+    int rc;
+    for (int no = 0; no < w.outer; ++no) {
+        if (r.pl.median && (rc = median_flow(r.pl.median, mu1, mu2, r.ln.scr[0], r.ln.scr[1], Lv.g, nullptr, r.cur, r.st))) return rc;
+        for (int k = 0; k < nb; ++k) {
+            ++*nlaunch;
+            if (w.skip_iterations) { r.first_of_scale = false; continue; }
+            const bool last_pass = w.skip_p_last && no == w.outer - 1 && k == nb - 1;
+            rc = w.form == TvForm::ExactBlocked ? iterate_tb_exact(w.blocks[k], r.planes, Lv.g, r.l_t, r.theta, r.taut, r.first_of_scale, r.cur, r.st)
+               : w.fused ? iterate_tb_fused(sem, Lv.I0, Lv.I1, r.h->cubic_tab, w.blocks[k], r.planes, Lv.g, r.l_t, r.theta, r.taut,
+                                            r.first_of_scale, r.cur, r.st, last_pass)
+                         : iterate_tb(w.blocks[k], r.planes, Lv.g, r.l_t, r.theta, r.taut, r.first_of_scale, r.cur, 0, r.st, last_pass);
+            if (rc) return rc;
+            r.cur ^= 1;
+            r.first_of_scale = false;
+        }
+    }
+    return MI_OK;
+}
+
+// One launch per iteration, with the convergence check on the device where epsilon > 0
+int run_per_iteration(Run &r, LevelBuf &Lv, int s, int wp, long long *nlaunch)
+{
+    const mi_tvl1_params &P = r.h->P;
+    const int mf = r.pl.median;
+    float *const mu1[2] = {Lv.u[0][0], Lv.u[1][0]}, *const mu2[2] = {Lv.u[0][1], Lv.u[1][1]};
+    int rc;
+    for (int it = 0; it < r.pl.iters; ++it) {
+        ++*nlaunch;
+        if (mf && it % P.inner_iterations == 0) {   // cv::medianBlur before each outer iteration (optflow tvl1flow.cpp:1381-1384)
+            Ctl mc = r.ctl;
+            mc.q_prev = r.q_last; mc.first_of_warp = (it == 0); mc.reset_cur = r.first_of_scale;
+            if ((rc = median_flow(mf, mu1, mu2, r.ln.scr[0], r.ln.scr[1], Lv.g, r.pl.check ? &mc : nullptr, r.cur, r.st))) return rc;
+        }
+        if (r.pl.check) {
+            Ctl ic = r.ctl;
+            ic.q = r.q; ic.q_prev = r.q_last; ic.first_of_warp = (it == 0); ic.reset_cur = r.first_of_scale; ic.n = it;
+            rc = iterate(P.exact_math != 0, r.planes, Lv.g, r.l_t, r.theta, r.taut, r.first_of_scale, &ic, 0, r.st);
+            r.ln.slots.push_back({s, wp});
+            r.q_last = r.q++;
+        } else {
+            rc = iterate(P.exact_math != 0, r.planes, Lv.g, r.l_t, r.theta, r.taut, r.first_of_scale, nullptr, r.cur, r.st);
+            r.cur ^= 1;
+        }
+        if (rc) return rc;
+        r.first_of_scale = false;
+    }
+    return MI_OK;
+}
+
+struct Feedback { bool all = true, all_before = true; int n_most = 0; };
+
+// Polled host feedback: the launch just enqueued publishes its decision word (sequence seq) when it starts -- wait for that word, not
+// for the launch.  Bare spin (pause) for the first ~20 us -- the flag normally lands within a few microseconds of the launch starting --
+// then the core is handed back between looks (sched_yield; a sleep of 50 us once 2 ms have passed: earlier work queued on the caller's
+// stream, or many handles waiting in many threads), so a waiting calc() does not hold a core.  The stream is queried on the slow path
+// only; a wall-clock bound ends a wait no launch will ever answer.
+int poll_feedback(Run &r, int seq, Feedback *f)
+{
+    const int *flag = r.ln.fb_flag.p;
+    for (int b = 0; b < r.B; ++b) {
+        int v = 0;
+        const auto t_wait0 = std::chrono::steady_clock::now();
+        for (long long spin = 0;; ++spin) {
+            v = __atomic_load_n(flag + 2 * b, __ATOMIC_ACQUIRE);
+            if ((v >> 2) == seq) break;
+            if ((spin & 63) != 63) {
+#if defined(__x86_64__) || defined(__i386__)
+                __builtin_ia32_pause();
+#endif
+                continue;
+            }
+            const double waited_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_wait0).count();
+            if (waited_us < 20.0) continue;
+            // a failed launch never writes: the stream is idle (or in error) and the word is not there
+            const hipError_t qe = hipStreamQuery(r.st);
+            if (qe != hipErrorNotReady) {
+                v = __atomic_load_n(flag + 2 * b, __ATOMIC_ACQUIRE);
+                if ((v >> 2) == seq) break;
+                MI_HIP_TRY(qe);
+                MI_REQUIRE(false, MI_ERR_HIP, "host feedback: launch finished without publishing its decision");
+            }
+            MI_REQUIRE(waited_us < kFeedbackWaitLimitUs, MI_ERR_HIP, "host feedback: no decision from the device within %.0f s", kFeedbackWaitLimitUs * 1e-6);
+            if (waited_us < 2000.0) sched_yield();
+            else { struct timespec ts_ = {0, 50000}; nanosleep(&ts_, nullptr); }
+        }
+        f->all_before = f->all_before && (v & 2);
+        f->all = f->all && (v & 1);
+        f->n_most = std::max(f->n_most, flag[2 * b + 1]);
+    }
+    return MI_OK;
+}
+
+// Copied host feedback: the slots of the last launch and of the one before it, per pair
+int copy_feedback(Run &r, Feedback *f)
+{
+    Lane &ln = r.ln;
+    MI_HIP_TRY(hipMemcpy2DAsync(ln.fb_host.p, 2 * sizeof(int2), ln.S.p + (r.q_last - 1), sizeof(int2) * (size_t)ln.Q, 2 * sizeof(int2),
+                                (size_t)r.B, hipMemcpyDeviceToHost, r.st));
+    MI_HIP_TRY(hipEventRecord(ln.fb_ev, r.st));
+    MI_HIP_TRY(hipEventSynchronize(ln.fb_ev));
+    for (int b = 0; b < r.B; ++b) {
+        f->all_before = f->all_before && (ln.fb_host.p[2 * b].y & MI_SLOT_DONE);
+        f->all = f->all && (ln.fb_host.p[2 * b + 1].y & MI_SLOT_DONE);
+    }
+    return MI_OK;
+}
+
+// Speculative steps (k_iterate_tbr MODE 1): a launch runs a block of iterations recording their error sums; the next launch applies the
+// reference's stopping rule to them and either builds on the block or replays the exact count from its input.  One settling launch
+// ends the warp.  After convergence the remaining launches end at once.
+// Host feedback (mi_tvl1_params.host_feedback): a call of one or two pairs reads the pairs' control slots back between launches and
+// stops enqueuing for this warp once every pair's slot says DONE -- the state is then settled (a replay, if one was due, ran inside the
+// launch that wrote the flag) and the slot is the one the following kernels look at.  First read-back at spec_first_poll, then after
+// every second launch.  The host waits like the reference's class does at each of its checks (cudaoptflow/src/tvl1flow.cpp:362-368);
+// the flows do not depend on any of it.
+int run_spec(Run &r, LevelBuf &Lv, const TvWarp &w, int s, int wp, long long *nlaunch)
+{
+    const TvPlan &pl = r.pl;
+    Lane &ln = r.ln;
+    const int nw = (int)pl.warp[s].size();
+    int rc, hprev = 0;   // the previous calc's count for this warp, where the host has seen it (polled host feedback)
+    if (pl.fb_poll && pl.hist) {
+        int &hc = ln.fb_hist[(size_t)s * nw + wp];
+        hprev = hc;
+        hc = 0;   // known again once this warp's stop has been seen
+    }
+    const std::vector<int> plan = spec_blocks(w, Lv.g, hprev, r.K);
+    int t_after = 0;
+    for (int v : plan) t_after += v;
+    SpecK sk;
+    memset(&sk, 0, sizeof(sk));
+    sk.X = ln.X.p; sk.iters = pl.iters;
+    sk.q_hist = wp > 0 ? r.q_settle_prev : r.q_settle_scale;
+    spec_hist_fraction(wp, &sk.hist_num, &sk.hist_den);
+    sk.slack = r.h->P.stop_slack;
+    if (pl.hist) {
+        const size_t o = ((size_t)s * nw + wp) * r.B, half = ln.H.n / 2;
+        sk.h_in = ln.H.p + (size_t)(ln.H_par ^ 1) * half + o;
+        sk.h_out = ln.H.p + (size_t)ln.H_par * half + o;
+    }
+    if (r.first_of_scale) {   // a replay of the scale's first block must see p = 0 in the input set as well
+        const size_t n = (size_t)Lv.g.ps * r.B;
+        if ((rc = zero_planes4(ln.pbuf[0], n, r.st))) return rc;
+        float *const p3[4] = {ln.pbuf[0][4], ln.pbuf[0][5], ln.pbuf[0][4], ln.pbuf[0][5]};
+        if (r.h->P.gamma != 0.0 && (rc = zero_planes4(p3, n, r.st))) return rc;
+    }
+    int e_prev = 0;
+    int fb_next = pl.fb ? spec_first_poll(plan, hprev, wp > 0 ? r.fb_prev_warp : r.fb_prev_scale) : -1;
+    int fb_done_at = (int)plan.size();
+    for (size_t k = 0; k <= plan.size(); ++k) {
+        const bool last = k == plan.size();
+        const int T = last ? plan.back() : plan[k];
+        if (!last) t_after -= T;
+        Ctl a = r.ctl;
+        a.q = r.q; a.q_prev = r.q_last; a.first_of_warp = (k == 0); a.reset_cur = (k == 0 && r.first_of_scale); a.n = 0;
+        sk.e0_prev = e_prev; sk.final_launch = last ? 1 : 0; sk.t_after = t_after;
+        if (pl.fb_poll) {
+            ln.fb_seq = (ln.fb_seq + 1) & 0x0fffffff;
+            sk.fb_flag = ln.fb_flag.p; sk.fb_seq = ln.fb_seq;
+        }
+        MI_REQUIRE((long long)r.e_next + T <= ln.Q && r.q < ln.Q, MI_ERR_BAD_ARG,
+                   "speculative steps: error-sum slot %d + %d or launch slot %d beyond the %lld slots sized for this calc", r.e_next, T, r.q, ln.Q);
+        if ((rc = iterate_tb_spec(T, r.planes, Lv.g, r.l_t, r.theta, r.taut, false, a, sk, r.e_next, r.st))) return rc;
+        ln.slots.push_back({s, wp});
+        r.q_last = r.q++;
+        ++*nlaunch;
+        e_prev = r.e_next;
+        if (!last) r.e_next += T;
+        if (!pl.fb || last || (int)k != fb_next) continue;
+        // The next warp's kernel goes in BEHIND this launch before the host knows whether the warp has stopped (Ctl::need_done) and is
+        // enqueued again, unconditionally, where one did not.  With the estimate right the device never waits for the host between
+        // two warps of a scale.
+        const bool ahead = pl.fb_poll && r.K.fb_ahead != 0 && r.K.x_skip == 0 && !r.h->profiling && wp + 1 < nw;
+        if (ahead && (rc = launch_warp(r, Lv, true))) return rc;
+        Feedback f;
+        if ((rc = pl.fb_poll ? poll_feedback(r, ln.fb_seq, &f) : copy_feedback(r, &f))) return rc;
+        if (f.all) {
+            r.pre_warped = ahead;
+            if (pl.fb_poll && pl.hist) ln.fb_hist[(size_t)s * nw + wp] = f.n_most;
+            fb_done_at = f.all_before ? (int)k - 1 : (int)k;   // where the next warp's first read-back goes
+            break;
+        }
+        fb_next = (int)k + 2;
+    }
+    if (pl.fb) {
+        r.fb_prev_warp = fb_done_at;
+        if (wp == 0) r.fb_prev_scale = fb_done_at;
+    }
+    r.q_settle_prev = r.q_last;
+    if (wp == 0) r.q_settle_scale = r.q_last;
+    r.first_of_scale = false;
+    return MI_OK;
+}
+
+// The warp wp of scale s and its iterations, in the plan's form (with their profiling regions)
+int run_warp(Run &r, LevelBuf &Lv, int s, int wp)
+{
+    const TvWarp &w = r.pl.warp[s][wp];
+    const Geo &g = Lv.g;
+    const bool prof = r.h->profiling;
+    int rc, w0 = -1, w1 = -1, e0 = -1, e1 = -1;
+    r.planes.g = r.grad = w.nograd ? nullptr : r.ln.scr[4];
+    if (prof && (rc = record(r, &w0))) return rc;
+    if (r.pre_warped) r.pre_warped = false;
+    else if (w.warp_launch && (rc = launch_warp(r, Lv, false))) return rc;
+    if (prof && !w.fused) {
+        if ((rc = record(r, &w1))) return rc;
+        r.ln.regions.push_back({w0, w1, 1, 44.0 * g.w * g.h * r.B, 1, s});   // 44 B/px per warp
+    }
+    if (prof && r.pl.iters > 0 && (rc = record(r, &e0))) return rc;
+    long long nlaunch = 0;
+    switch (w.form) {
+    case TvForm::Blocked:
+    case TvForm::ExactBlocked: rc = run_blocked(r, Lv, w, &nlaunch); break;
+    case TvForm::Spec: rc = run_spec(r, Lv, w, s, wp, &nlaunch); break;
+    case TvForm::PerIter: rc = run_per_iteration(r, Lv, s, wp, &nlaunch); break;
+    }
+    if (rc) return rc;
+    if (e0 >= 0) {
+        if ((rc = record(r, &e1))) return rc;
+        r.ln.regions.push_back({e0, e1, nlaunch, 64.0 * g.w * g.h * r.B * r.pl.iters, 0, s});
+    }
+    return MI_OK;
+}
+
+// scale s done: the flow to the caller (s = 0) or zoomed to the next finer scale and rescaled (tvl1flow.cpp:291-300; u3 is zoomed too
+// but NOT rescaled, optflow tvl1flow.cpp:524-528)
+int zoom_or_pack(Run &r, int s)
+{
+    const mi_tvl1_params &P = r.h->P;
+    const LevelBuf &Lv = r.ln.L[s];
+    Ctl ec = r.ctl;
+    ec.q_prev = r.q_last;
+    const Ctl *dev = r.pl.check && !r.first_of_scale ? &ec : nullptr;
+    if (s == 0) {
+        const float *u1v[2] = {Lv.u[0][0], Lv.u[1][0]}, *u2v[2] = {Lv.u[0][1], Lv.u[1][1]};
+        return pack_flow(r.ln.tab.p, u1v, u2v, Lv.g, dev, r.cur, r.st);
+    }
+    const LevelBuf &Lf = r.ln.L[s - 1];
+    const bool gam = P.gamma != 0.0;
+    const float *us[3][2] = {{Lv.u[0][0], Lv.u[1][0]}, {Lv.u[0][1], Lv.u[1][1]}, {gam ? Lv.u[0][2] : nullptr, gam ? Lv.u[1][2] : nullptr}};
+    float *ud[3] = {Lf.u[0][0], Lf.u[0][1], gam ? Lf.u[0][2] : nullptr};
+    const float post[3] = {(float)(1.0 / P.scale_step), (float)(1.0 / P.scale_step), 1.f};
+    return resize(P.semantics, gam ? 3 : 2, us, 2, ud, Lv.g, Lf.g, (double)Lf.g.w / Lv.g.w, (double)Lf.g.h / Lv.g.h, post, dev, r.cur, r.st);
+}
+
+}  // namespace
+
+// The whole coarse-to-fine computation of n pairs on one stream (OpticalFlowDual_TVL1_Impl::calcImpl + procOneScale): the plan of the
+// calc (tvl1_plan.h), executed.
 static int lane_calc(mi_tvl1 *h, Lane &ln, int n, const mi_mat *I0s, const mi_mat *I1s, mi_mat *flows, hipStream_t st, int *ns_out)
 {
     // behind everything this call enqueues for the lane (also on an error return: part of the calc may be in flight): the event the
@@ -377,547 +746,34 @@ static int lane_calc(mi_tvl1 *h, Lane &ln, int n, const mi_mat *I0s, const mi_ma
         }
     } mark{ln, st};
     const mi_tvl1_params &P = h->P;
-    const int W = I0s[0].cols, H = I0s[0].rows, B = n;
-    int rc = ensure_arena(P, ln, W, H, B);
-    if (rc) return rc;
-    ln.batch = B;
-    const int nl_built = (int)ln.L.size();
-    // number of usable scales (tvl1flow.cpp:243-247)
-    int ns = nl_built;
-    if (ns > 1 && (ln.L[ns - 1].g.w < 16 || ln.L[ns - 1].g.h < 16)) ns -= 1;
-    *ns_out = ns;
-    for (int l = 0; l < nl_built; ++l) ln.L[l].g.batch = B;
-
-    // external pointer table
-    if (ln.tab_cap < B) {
-        if (ln.tab_dev) (void)hipFree(ln.tab_dev);
-        ln.tab_dev = nullptr; ln.tab_cap = 0;
-        MI_HIP_TRY(hipMalloc((void **)&ln.tab_dev, sizeof(PtrTab) * B));
-        ln.tab_cap = B;
-    }
-    {
-        std::vector<PtrTab> &tab = ln.tab_host;
-        tab.resize(B);
-        for (int i = 0; i < B; ++i) {
-            tab[i].a = I0s[i].data; tab[i].b = I1s[i].data; tab[i].out = flows[i].data;
-            tab[i].step_a = (long long)I0s[i].step; tab[i].step_b = (long long)I1s[i].step;
-            tab[i].step_out = (long long)flows[i].step;
-        }
-        // pageable source: a few KB, staged by the runtime before the call returns; kept in the lane anyway
-        MI_HIP_TRY(hipMemcpyAsync(ln.tab_dev, tab.data(), sizeof(PtrTab) * B, hipMemcpyHostToDevice, st));
-    }
-
-    const int iters_per_warp = P.iterations * P.inner_iterations;
-    const bool check = P.epsilon > 0.0 && iters_per_warp > 0;
-    // convergence-checked path in fast math: speculative blocks (k_iterate_tbr MODE 1 / 2) instead of one launch per iteration
-    // (gamma != 0 -- round 6: the illumination channel runs the same speculative steps on its own kernels, tvl1_tbr_kernels.hip GAM)
-    const bool spec = check && !P.exact_math && P.time_block != 1 && P.median_filtering <= 1 && tuning().spec != 0;
-    // control slots per pair: one per launch (S, P, X) and one error sum per iteration (E); both index spaces fit max(.,.)
-    long long Q = (long long)ns * P.warps * iters_per_warp;
-    std::vector<int> spec_plan[4];   // kernel block sizes of the speculative steps: first warp of a large level / of a small one / later warps / levels on the register-tile kernel
-    const double kLargeLevel = 12e6;   // px x pairs from which the T = 10 kernel pays for a long first block
-    if (spec) {
-        long long e_max = 0, l_max = 0;
-        for (int k = 0; k < 4; ++k) {
-            spec_plan[k].resize(iters_per_warp + 40);
-            if (k == 3) {
-                // register-tile kernel: a launch costs its iterations, not its block size, and a converged warp pays ~3 us per
-                // remaining (empty) launch -- the fewest launches: blocks of the kernel's margin
-                int kk = 0, sum = 0;
-                const int want = iters_per_warp + (iters_per_warp > 10 ? 30 : iters_per_warp > 1 ? 10 : 0);
-                // one or two pairs (host feedback: launches behind the stop are never enqueued): shorter blocks on tiles of a
-                // smaller margin own more of their 64 columns x rows (MIFLOW_TILE_FB_BLOCK)
-                const int tb = (B <= 2 && tuning().tile_fb_block > 0) ? std::min(tuning().tile_fb_block, tile_max_block()) : tile_max_block();
-                while (sum < want && kk < (int)spec_plan[k].size()) { spec_plan[k][kk++] = tb; sum += tb; }
-                spec_plan[k].resize(kk);
-            } else
-            spec_plan[k].resize(tb_spec_plan(iters_per_warp, k == 2 ? 1 : 0, k == 0, spec_plan[k].data(), (int)spec_plan[k].size()));
-            long long t = 0;
-            for (int v : spec_plan[k]) t += v;
-            e_max = std::max(e_max, t);
-            l_max = std::max(l_max, (long long)spec_plan[k].size() + 1);
-        }
-        // the cost-model plan of a one-or-two-pair calc (below) rounds a warp's total UP to a multiple of its block length, and the
-        // settling launch of a warp indexes one more block: a block of slack per warp (the launch loop checks the bound as well)
-        e_max += 2 * (long long)std::max(tile_max_block(), tb_max_block());
-        Q = std::max((long long)ns * P.warps * e_max, (long long)ns * P.warps * l_max);
-    }
-    if (check) {
-        MI_REQUIRE(Q <= kMaxSlots, MI_ERR_BAD_ARG, "scales x warps x iterations = %lld control slots exceed the limit of %lld", Q, kMaxSlots);
-        if (ln.Q < Q || ln.ctlB < B) {
-            if (ln.S) (void)hipFree(ln.S);
-            if (ln.E) (void)hipFree(ln.E);
-            if (ln.Pd) (void)hipFree(ln.Pd);
-            if (ln.X) (void)hipFree(ln.X);
-            ln.S = nullptr; ln.E = nullptr; ln.Pd = nullptr; ln.X = nullptr; ln.Q = 0; ln.ctlB = 0;
-            MI_HIP_TRY(hipMalloc((void **)&ln.S, sizeof(int2) * (size_t)Q * B));
-            MI_HIP_TRY(hipMalloc((void **)&ln.E, sizeof(unsigned long long) * (size_t)Q * B));
-            MI_HIP_TRY(hipMalloc((void **)&ln.Pd, sizeof(double) * (size_t)Q * B));
-            MI_HIP_TRY(hipMalloc((void **)&ln.X, sizeof(int4) * (size_t)Q * B));
-            ln.Q = Q; ln.ctlB = B;
-        }
-        MI_HIP_TRY(hipMemsetAsync(ln.E, 0, sizeof(unsigned long long) * (size_t)ln.Q * B, st));
-        MI_HIP_TRY(hipMemsetAsync(ln.S, 0, sizeof(int2) * (size_t)ln.Q * B, st));
-    }
-    // history of the previous calc of this lane (speculative steps only)
-    const size_t h_n = (size_t)ns * P.warps * B;
-    bool hist = spec && tuning().tb_hist != 0;
-    if (hist) {
-        unsigned long long sig = 1469598103934665603ull;
-        for (long long v : {(long long)W, (long long)H, (long long)B, (long long)ns, (long long)P.warps, (long long)iters_per_warp, (long long)I0s[0].type}) sig = (sig ^ (unsigned long long)v) * 1099511628211ull;
-        if (ln.H_cap < h_n) {
-            if (ln.H) (void)hipFree(ln.H);
-            ln.H = nullptr; ln.H_cap = 0; ln.H_sig = 0;
-            MI_HIP_TRY(hipMalloc((void **)&ln.H, sizeof(int) * 2 * h_n));
-            ln.H_cap = h_n;
-        }
-        if (ln.H_sig != sig) {   // counts of another geometry say nothing: start from none (0 = no estimate)
-            MI_HIP_TRY(hipMemsetAsync(ln.H, 0, sizeof(int) * 2 * ln.H_cap, st));
-            ln.H_sig = sig;
-        }
-        if (ln.fb_hist_sig != sig || ln.fb_hist.size() != (size_t)ns * P.warps) {
-            ln.fb_hist.assign((size_t)ns * P.warps, 0);
-            ln.fb_hist_sig = sig;
-        }
-        ln.H_par ^= 1;
-    }
-    ln.slots.clear();
-    ln.regions.clear();
-    size_t ev_used = 0;
-    auto next_event = [&](int *idx) -> int {
-        if (ev_used == ln.ev_pool.size()) {
-            hipEvent_t e;
-            MI_HIP_TRY(hipEventCreate(&e));
-            ln.ev_pool.push_back(e);
-        }
-        *idx = (int)ev_used++;
-        return MI_OK;
-    };
-
-    const int sem = P.semantics;
-    const bool legacy_warp = tuning().warp_legacy != 0;
-    // level 0: convertTo(CV_32F, 8U ? 1 : 255)  tvl1flow.cpp:200-201
-    rc = convert(ln.tab_dev, I0s[0].type, ln.L[0].I0, ln.L[0].I1, ln.L[0].g, st);
-    if (rc) return rc;
-    if (P.use_initial_flow) {
-        // CPU behaviour (optflow/src/tvl1flow.cpp:435-439); the CUDA calc() never splits the
-        // caller's flow (latent reference bug).
-        rc = unpack_flow(ln.tab_dev, ln.L[0].u[0][0], ln.L[0].u[0][1], ln.L[0].g, st);
-        if (rc) return rc;
-    }
-    const float one3[3] = {1.f, 1.f, 1.f};
-    // create the scales (tvl1flow.cpp:238-266)
-    for (int s = 1; s < nl_built; ++s) {
-        const float *src[3][2] = {{ln.L[s - 1].I0, nullptr}, {ln.L[s - 1].I1, nullptr}, {nullptr, nullptr}};
-        float *dst[3] = {ln.L[s].I0, ln.L[s].I1, nullptr};
-        rc = resize(sem, 2, src, 1, dst, ln.L[s - 1].g, ln.L[s].g, P.scale_step, P.scale_step, one3, nullptr, 0, st);
-        if (rc) return rc;
-        if (s >= ns) break;
-        if (P.use_initial_flow) {
-            const float *us[3][2] = {{ln.L[s - 1].u[0][0], nullptr}, {ln.L[s - 1].u[0][1], nullptr}, {nullptr, nullptr}};
-            float *ud[3] = {ln.L[s].u[0][0], ln.L[s].u[0][1], nullptr};
-            const float sc = (float)P.scale_step;
-            const float post[3] = {sc, sc, 1.f};
-            rc = resize(sem, 2, us, 1, ud, ln.L[s - 1].g, ln.L[s].g, P.scale_step, P.scale_step, post, nullptr, 0, st);
-            if (rc) return rc;
-        }
-    }
-    if (!P.use_initial_flow) {
-        const Geo &g = ln.L[ns - 1].g;
-        MI_HIP_TRY(hipMemsetAsync(ln.L[ns - 1].u[0][0], 0, sizeof(float) * (size_t)g.ps * B, st));
-        MI_HIP_TRY(hipMemsetAsync(ln.L[ns - 1].u[0][1], 0, sizeof(float) * (size_t)g.ps * B, st));
-    }
-    const bool gam = P.gamma != 0.0;
-    if (gam) {   // u3 starts at 0 on the coarsest scale (tvl1flow.cpp:273-275; optflow tvl1flow.cpp:498-500)
-        const Geo &g = ln.L[ns - 1].g;
-        MI_HIP_TRY(hipMemsetAsync(ln.L[ns - 1].u[0][2], 0, sizeof(float) * (size_t)g.ps * B, st));
-    }
-
-    const float l_t = (float)(P.lambda * P.theta);
-    const float taut = (float)(P.tau / P.theta);
-    const float theta = (float)P.theta;
-
-    int q = 0, q_last = -1;   // device-control slot counters
-    int e_next = 0;           // next per-iteration error-sum index (speculative path)
-    int q_settle_prev = -1, q_settle_scale = -1;   // settling launches of the previous warp / of the coarser scale's first warp
-    // host feedback: only where the calc is one lane on the caller's stream (a wait inside lane k would hold up the enqueue of lane k+1)
-    // ... and never while the stream is being captured into a graph: an event synchronise on a capturing stream fails and
-    // invalidates the capture (hipGraph users get the fully stream-ordered enqueue, host_feedback = -1 behaviour)
     hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;
     const bool capturing = hipStreamIsCapturing(st, &cap_st) == hipSuccess && cap_st != hipStreamCaptureStatusNone;
-    const bool fb = spec && h->last_lanes == 1 && P.host_feedback >= 0 && (P.host_feedback == 1 || B <= 2) && !capturing;
-    const bool fb_poll = fb && tuning().fb_poll != 0;
-    int fb_prev_warp = 2, fb_prev_scale = 2;   // launch index at which the previous warp / the coarser scale's first warp was found stopped
-    ln.fb_waits = ln.fb_skipped = 0;
-    if (fb) {
-        if (ln.fb_cap < B) {
-            if (ln.fb_host) (void)hipHostFree(ln.fb_host);
-            if (ln.fb_flag) (void)hipHostFree(ln.fb_flag);
-            ln.fb_host = nullptr; ln.fb_flag = nullptr; ln.fb_cap = 0;
-            MI_HIP_TRY(hipHostMalloc((void **)&ln.fb_host, 2 * sizeof(int2) * (size_t)B, hipHostMallocDefault));
-            MI_HIP_TRY(hipHostMalloc((void **)&ln.fb_flag, 2 * sizeof(int) * (size_t)B, hipHostMallocCoherent | hipHostMallocMapped));
-            memset(ln.fb_flag, 0, 2 * sizeof(int) * (size_t)B);
-            ln.fb_cap = B;
-        }
-        if (!ln.fb_ev) MI_HIP_TRY(hipEventCreateWithFlags(&ln.fb_ev, hipEventDisableTiming));
-    }
-    int cur = 0;              // host-known buffer set (fixed-work mode)
-    Ctl ctl;
-    memset(&ctl, 0, sizeof(ctl));
-    ctl.S = ln.S; ctl.E = ln.E; ctl.Q = (int)ln.Q;
-    ctl.P = ln.Pd; ctl.sched = (P.semantics == MI_SEM_CUDA_COMPAT) ? 1 : 0;   // cv::cuda's check schedule vs the CPU class's every-iteration check
+    const TvPlan pl = tv_make_plan(TvShape{I0s[0].cols, I0s[0].rows, n, I0s[0].type, P, h->last_lanes, capturing}, tv_knobs());
+    int rc = ensure_arena(P, ln, pl, I0s[0].cols, I0s[0].rows, n);
+    if (rc || (rc = ensure_buffers(pl, ln, n, I0s, I1s, flows, st))) return rc;
+    *ns_out = pl.used;
+    ln.slots.clear();
+    ln.regions.clear();
 
-    WarpZoom zoom;
-    memset(&zoom, 0, sizeof(zoom));
-    bool have_zoom = false;
-    const bool zoom_path = !check && !P.exact_math && P.time_block != 1 && P.gamma == 0.0 && !legacy_warp && warp_zoom_ok() && tuning().x_skip == 0;
-    for (int s = ns - 1; s >= 0; --s) {
+    Run r{h, ln, pl, tv_knobs(), st, n};
+    memset(&r.ctl, 0, sizeof(r.ctl));
+    r.ctl.S = ln.S.p; r.ctl.E = ln.E.p; r.ctl.Q = (int)ln.Q; r.ctl.P = ln.Pd.p;
+    r.ctl.sched = P.semantics == MI_SEM_CUDA_COMPAT ? 1 : 0;   // cv::cuda's check schedule vs the CPU class's every-iteration check
+    r.l_t = (float)(P.lambda * P.theta); r.taut = (float)(P.tau / P.theta); r.theta = (float)P.theta;
+    if ((rc = enqueue_pyramid(r, I0s[0].type))) return rc;
+    for (int s = pl.used - 1; s >= 0; --s) {
         LevelBuf &Lv = ln.L[s];
-        Geo g = Lv.g;
-        // dense per-level re-layout of the full-resolution scratch planes
-        float *I1wx = ln.scr[2], *I1wy = ln.scr[3], *grad = ln.scr[4], *rho = ln.scr[5];
-        if (legacy_warp) {   // pair stride of the packed plane is g.ps float4 = 4*g.ps floats: same element index as the planes
-            rc = gradient_pack(Lv.I1, ln.pack, g, st);
-            if (rc) return rc;
-        }
-        const float *u1v[2] = {Lv.u[0][0], Lv.u[1][0]}, *u2v[2] = {Lv.u[0][1], Lv.u[1][1]};
-        IterPlanes pl;
-        pl.ix = I1wx; pl.iy = I1wy; pl.g = grad; pl.rc = rho;
-        for (int k = 0; k < 2; ++k) { for (int j = 0; j < 3; ++j) pl.u[k][j] = Lv.u[k][j]; for (int j = 0; j < 6; ++j) pl.p[k][j] = ln.pbuf[k][j]; }
-        pl.gamma = (float)P.gamma;
-        pl.err_u3 = sem == MI_SEM_CPU_REF ? 1 : 0;   // optflow tvl1flow.cpp:1110 vs cuda tvl1flow.cu:276-283
-        cur = 0;
-        bool first_of_scale = true;
+        IterPlanes &ip = r.planes;
+        ip.ix = ln.scr[2]; ip.iy = ln.scr[3]; ip.rc = ln.scr[5]; ip.gamma = (float)P.gamma;
+        for (int k = 0; k < 2; ++k) { for (int j = 0; j < 3; ++j) ip.u[k][j] = Lv.u[k][j]; for (int j = 0; j < 6; ++j) ip.p[k][j] = ln.pbuf[k][j]; }
+        ip.err_u3 = P.semantics == MI_SEM_CPU_REF ? 1 : 0;   // optflow tvl1flow.cpp:1110 vs cuda tvl1flow.cu:276-283
+        r.cur = 0; r.first_of_scale = true; r.pre_warped = false;
         // scaledEpsilon: float in the CPU class (optflow tvl1flow.cpp:1315), double in cv::cuda (:310)
-        const double se = P.epsilon * P.epsilon * (double)(g.w * g.h);
-        ctl.thr = sem == MI_SEM_CPU_REF ? (double)(float)se : se;
-
-        bool pre_warped = false;   // this warp's kernel was enqueued ahead, behind the previous warp's last launch (host feedback)
-        for (int wp = 0; wp < P.warps; ++wp) {
-            Ctl wc = ctl;
-            wc.q_prev = q_last;
-            // at the first warp of a scale u lives in set 0 (host-known)
-            const bool dev_cur = check && !first_of_scale;
-            int w0 = -1, w1 = -1;
-            if (h->profiling) {
-                rc = next_event(&w0); if (rc) return rc;
-                MI_HIP_TRY(hipEventRecord(ln.ev_pool[w0], st));
-            }
-            // Round 4 byte cuts of the fixed-work blocked path: (1) where every pass of this warp is the default T = 10 kernel, the
-            // warp does not store |grad|^2 and the pass forms it from I1wx, I1wy (8 B/px per warp less through HBM, the same bits);
-            // (2) the last pass of a scale does not store p (the next scale starts from p = 0; 16 B/px per scale).
-            const bool blocked_w = !check && !P.exact_math && P.time_block != 1;
-            std::vector<int> plan_w;
-            bool nograd = false;
-            if (blocked_w && !legacy_warp) {
-                const int mfw = P.median_filtering > 1 ? P.median_filtering : 0;
-                const int per = mfw ? P.inner_iterations : iters_per_warp;
-                plan_w.resize(per + 1);
-                plan_w.resize(tb_plan_level(g, per, P.time_block > 0 ? P.time_block : tb_max_block(), plan_w.data(), per, gam));
-                nograd = !plan_w.empty();
-                for (int v : plan_w) nograd = nograd && (gam || tb_nograd_ok(v, g));   // the illumination channel's kernels never read the plane
-            }
-            if (spec && !legacy_warp && P.median_filtering <= 1 && (gam || tb_spec_nograd_ok(g))) nograd = true;   // speculative steps: every block is a tbr launch
-            float *grad_w = nograd ? nullptr : grad;
-            pl.g = grad_w;
-            // Round 5: a warp whose iterations are ONE pass of the default kernel runs inside that pass (producer waves, k_iterate_tbr
-            // FW) -- no warp launch, no static planes through HBM
-            const bool fast_w0 = !P.exact_math && (tuning().warp_fast > 0 || (tuning().warp_fast < 0 && sem == MI_SEM_CUDA_COMPAT));
-            const bool fuse_w = blocked_w && !gam && !legacy_warp && nograd && plan_w.size() == 1 && P.median_filtering <= 1 && tuning().x_skip == 0 &&
-                                tuning().warp_lds == 0 && !(wp == 0 && have_zoom) && tb_fused_ok(plan_w[0], g, sem, fast_w0);
-            const bool warp_is_fused = !legacy_warp && tuning().x_skip == 0;
-            const bool fast_w = !P.exact_math && (tuning().warp_fast > 0 || (tuning().warp_fast < 0 && sem == MI_SEM_CUDA_COMPAT));
-            if (pre_warped) { rc = MI_OK; pre_warped = false; }
-            else if (fuse_w) rc = MI_OK;
-            else if (tuning().x_skip == 1 && wp > 0) rc = MI_OK;   // timing experiment: what a step costs without the warps' work and bytes
-            else if (legacy_warp)
-                rc = warp(sem, Lv.I0, ln.pack, u1v, u2v, nullptr, I1wx, I1wy, grad, rho, h->cubic_tab, g, dev_cur ? &wc : nullptr, cur, st);
-            else
-                rc = warp_fused(sem, !P.exact_math && (tuning().warp_fast > 0 || (tuning().warp_fast < 0 && sem == MI_SEM_CUDA_COMPAT)), -1, Lv.I0, Lv.I1, u1v, u2v, nullptr, I1wx, I1wy, grad_w, rho, h->cubic_tab, g, dev_cur ? &wc : nullptr, cur, st,
-                                (wp == 0 && have_zoom) ? &zoom : nullptr);
-            if (rc) return rc;
-            if (w0 >= 0 && !fuse_w) {
-                rc = next_event(&w1); if (rc) return rc;
-                MI_HIP_TRY(hipEventRecord(ln.ev_pool[w1], st));
-                ln.regions.push_back({w0, w1, 1, 44.0 * g.w * g.h * B, 1, s});   // 44 B/px per warp
-            }
-            int e0 = -1, e1 = -1;
-            if (h->profiling && iters_per_warp > 0) {
-                rc = next_event(&e0); if (rc) return rc;
-                MI_HIP_TRY(hipEventRecord(ln.ev_pool[e0], st));
-            }
-            const bool blocked = !check && !P.exact_math && P.time_block != 1;
-            const bool exact_blocked = !check && P.exact_math && P.time_block != 1 && !gam && P.median_filtering <= 1 && tuning().exact_tb != 0;
-            long long nlaunch = 0;
-            const int mf = P.median_filtering > 1 ? P.median_filtering : 0;
-            float *const mu1[2] = {Lv.u[0][0], Lv.u[1][0]}, *const mu2[2] = {Lv.u[0][1], Lv.u[1][1]};
-            if (blocked) {
-                // T iterations per HBM pass (tvl1_tbr_kernels.hip), decomposition by measured cost; the optional median
-                // filter sits between outer iterations, so blocks never span more than inner_iterations
-                const int per = mf ? P.inner_iterations : iters_per_warp, nouter = mf ? P.iterations : 1;
-                std::vector<int> plan(per + 1);
-                const int nb = tb_plan_level(g, per, P.time_block > 0 ? P.time_block : tb_max_block(), plan.data(), per, gam);
-                for (int no = 0; no < nouter; ++no) {
-                    if (mf && (rc = median_flow(mf, mu1, mu2, ln.scr[0], ln.scr[1], g, nullptr, cur, st))) return rc;
-                    for (int k = 0; k < nb; ++k) {
-                        ++nlaunch;
-                        if (tuning().x_skip == 2) { first_of_scale = false; continue; }   // timing experiment: the warps alone
-                        const bool last_pass = tuning().tb_skip_p && wp == P.warps - 1 && no == nouter - 1 && k == nb - 1 && !mf;
-                        if (fuse_w) rc = iterate_tb_fused(sem, Lv.I0, Lv.I1, h->cubic_tab, plan[k], pl, g, l_t, theta, taut, first_of_scale, cur, st, last_pass);
-                        else rc = iterate_tb(plan[k], pl, g, l_t, theta, taut, first_of_scale, cur, 0, st, last_pass);
-                        if (rc) return rc;
-                        cur ^= 1;
-                        first_of_scale = false;
-                    }
-                }
-            } else if (exact_blocked) {
-                // exact math, fixed work: blocks of up to 5 fused iterations (k_iterate_tbr MODE 2), bit-identical to the
-                // one-iteration launches below
-                for (int left = iters_per_warp; left > 0;) {
-                    const int cap = P.time_block > 0 ? std::min(P.time_block, tb_exact_max_block()) : tb_exact_max_block();
-                    const int T = std::min(left, cap);
-                    ++nlaunch;
-                    rc = iterate_tb_exact(T, pl, g, l_t, theta, taut, first_of_scale, cur, st);
-                    if (rc) return rc;
-                    cur ^= 1;
-                    left -= T;
-                    first_of_scale = false;
-                }
-            } else if (spec) {
-                // Speculative steps (k_iterate_tbr MODE 1): a launch runs a block of iterations recording their error sums; the next
-                // launch applies the reference's stopping rule to them and either builds on the block or replays the exact
-                // count from its input.  One settling launch ends the warp.  After convergence the remaining launches end at once.
-                const bool on_tiles = tile_eligible(g) && tuning().tile_spec != 0;
-                std::vector<int> plan = spec_plan[on_tiles ? 3 : wp > 0 ? 2 : ((double)g.w * g.h * B >= kLargeLevel ? 0 : 1)];
-                // the previous calc's count for this warp, where the host has seen it (polled host feedback): a first block of at most
-                // 4 / 7 iterations runs on tiles of that margin (k_iterate_tile M), and the first poll goes where that many iterations
-                // end.  A count that turns out different costs one more block or one more poll, as any estimate does.
-                int hprev = 0;
-                if (fb_poll && hist) {
-                    int &hc = ln.fb_hist[(size_t)s * P.warps + wp];
-                    hprev = hc;
-                    hc = 0;   // known again once this warp's stop has been seen
-                }
-                if (on_tiles && hprev >= 1 && !plan.empty() && tuning().tile_fb_model != 0) {
-                    // Block length = tile margin for the whole warp, from a cost model fitted to the traces of profiles/r10:
-                    // a pass costs ~7 us (MIFLOW_TILE_FB_MODEL) of launch and hand-over plus (tile lanes) x (10.8 ps of loads and stores + 2.4 ps per
-                    // iteration); tile lanes = pixels x 64 / (64 - 2M) x TR / (TR - 2M) with TR = 48 or 64 rows (tile_rows_for).
-                    // Few iterations or a small level: one block of the margin that just holds them; many iterations on a
-                    // level that fills the device: more, shorter blocks whose tiles own more of their pixels.
-                    const double px = (double)g.w * g.h * B, TR = (double)tile_rows_for(g);
-                    int best = 10;
-                    double best_cost = 1e30;
-                    for (int bl : {4, 7, 10}) {
-                        const double passes = (double)((hprev + bl - 1) / bl);
-                        const double lanes = px * 64.0 / (64.0 - 2.0 * bl) * TR / (TR - 2.0 * bl);
-                        const double cost = passes * (double)tuning().tile_fb_model + lanes * (passes * 10.8e-6 + (double)hprev * 2.4e-6);
-                        if (cost < best_cost) { best_cost = cost; best = bl; }
-                    }
-                    int total = 0;
-                    for (int v : plan) total += v;
-                    plan.assign((size_t)((total + best - 1) / best), best);
-                } else if (on_tiles && hprev >= 1 && hprev <= 7 && !plan.empty()) plan[0] = hprev <= 4 ? 4 : 7;
-                int t_after = 0;
-                for (int v : plan) t_after += v;
-                SpecK sk;
-                memset(&sk, 0, sizeof(sk));
-                sk.X = ln.X; sk.iters = iters_per_warp;
-                // the first block's length: a fraction of what an earlier warp needed (measured on textured pairs: the second
-                // warp of a scale needs about half of the first, later warps slightly fewer than their predecessor, the first
-                // warp of a scale about 0.7 of the first warp one scale coarser)
-                sk.q_hist = wp > 0 ? q_settle_prev : q_settle_scale;
-                sk.hist_num = wp == 0 ? 7 : wp == 1 ? 9 : 4;
-                sk.hist_den = wp == 0 ? 10 : wp == 1 ? 20 : 5;
-                sk.slack = P.stop_slack;
-                if (hist) {
-                    const size_t o = ((size_t)s * P.warps + wp) * B;
-                    sk.h_in = ln.H + (size_t)(ln.H_par ^ 1) * ln.H_cap + o;
-                    sk.h_out = ln.H + (size_t)ln.H_par * ln.H_cap + o;
-                }
-                if (first_of_scale) {   // a replay of the scale's first block must see p = 0 in the input set as well
-                    rc = zero_planes4(ln.pbuf[0], (size_t)g.ps * B, st);
-                    if (rc) return rc;
-                    if (gam) {
-                        float *const p3[4] = {ln.pbuf[0][4], ln.pbuf[0][5], ln.pbuf[0][4], ln.pbuf[0][5]};
-                        rc = zero_planes4(p3, (size_t)g.ps * B, st);
-                        if (rc) return rc;
-                    }
-                }
-                int e_prev = 0;
-                // Host feedback (mi_tvl1_params.host_feedback): a call of one or two pairs reads the pairs' control slots back
-                // between launches and stops enqueuing for this warp once every pair's slot says DONE -- the state is then settled
-                // (a replay, if one was due, ran inside the launch that wrote the flag) and the slot is the one the following kernels
-                // look at.  First read-back where the previous warp of this scale stopped (the first warp: where the coarser scale's
-                // first warp did), then after every second launch.  The host waits like the reference's class does at each of its
-                // checks (cudaoptflow/src/tvl1flow.cpp:362-368); the flows do not depend on any of it.
-                int fb_next = fb ? std::max(1, wp > 0 ? fb_prev_warp : fb_prev_scale) : -1;
-                if (fb && hprev > 0) {   // the launch behind the block in which iteration hprev falls
-                    int kq = 0, sum = 0;
-                    while (kq < (int)plan.size() && (sum += plan[kq]) < hprev) ++kq;
-                    fb_next = std::max(1, std::min(kq + 1, (int)plan.size() - 1));
-                }
-                int fb_done_at = (int)plan.size();
-                for (size_t k = 0; k <= plan.size(); ++k) {
-                    const bool last = k == plan.size();
-                    const int T = last ? plan.back() : plan[k];
-                    if (!last) t_after -= T;
-                    Ctl a = ctl;
-                    a.q = q; a.q_prev = q_last; a.first_of_warp = (k == 0); a.reset_cur = (k == 0 && first_of_scale); a.n = 0;
-                    sk.e0_prev = e_prev; sk.final_launch = last ? 1 : 0; sk.t_after = t_after;
-                    int fb_seq_k = 0;
-                    if (fb_poll) {
-                        fb_seq_k = ln.fb_seq = (ln.fb_seq + 1) & 0x0fffffff;
-                        sk.fb_flag = ln.fb_flag; sk.fb_seq = fb_seq_k;
-                    }
-                    MI_REQUIRE((long long)e_next + T <= (long long)ln.Q && q < (int)ln.Q, MI_ERR_BAD_ARG,
-                               "speculative steps: error-sum slot %d + %d or launch slot %d beyond the %lld slots sized for this calc", e_next, T, q, (long long)ln.Q);
-                    rc = iterate_tb_spec(T, pl, g, l_t, theta, taut, false, a, sk, e_next, st);
-                    if (rc) return rc;
-                    ln.slots.push_back({s, wp});
-                    q_last = q++;
-                    ++nlaunch;
-                    e_prev = e_next;
-                    if (!last) e_next += T;
-                    if (fb && !last && (int)k == fb_next) {
-                        bool all = true, all_before = true;
-                        int n_most = 0;
-                        // The next warp's kernel goes in BEHIND this launch before the host knows whether the warp has stopped: it
-                        // runs only for pairs whose slot says so (Ctl::need_done) and is enqueued again, unconditionally, where one
-                        // did not.  With the estimate right the device never waits for the host between two warps of a scale.
-                        bool ahead = false;
-                        if (fb_poll && tuning().fb_ahead != 0 && warp_is_fused && !h->profiling && wp + 1 < P.warps) {
-                            Ctl nc = ctl;
-                            nc.q_prev = q_last; nc.need_done = 1;
-                            rc = warp_fused(sem, fast_w, -1, Lv.I0, Lv.I1, u1v, u2v, nullptr, I1wx, I1wy, grad_w, rho, h->cubic_tab, g, &nc, cur, st, nullptr);
-                            if (rc) return rc;
-                            ahead = true;
-                        }
-                        if (fb_poll) {
-                            // the launch just enqueued publishes its decision when it starts: wait for that word, not for the launch
-                            ++ln.fb_waits;
-                            for (int b = 0; b < B; ++b) {
-                                int v = 0;
-                                // Bare spin (pause) for the first ~20 us -- the flag normally lands within a few microseconds of the launch
-                                // starting -- then the core is handed back between looks (sched_yield; a sleep of 50 us once 2 ms have
-                                // passed: earlier work queued on the caller's stream, or many handles waiting in many threads), so a
-                                // waiting calc() does not hold a core.  The stream is queried on the slow path only; a wall-clock bound ends
-                                // a wait no launch will ever answer.
-                                const auto t_wait0 = std::chrono::steady_clock::now();
-                                for (long long spin = 0;; ++spin) {
-                                    v = __atomic_load_n(ln.fb_flag + 2 * b, __ATOMIC_ACQUIRE);
-                                    if ((v >> 2) == fb_seq_k) break;
-                                    if ((spin & 63) != 63) {
-#if defined(__x86_64__) || defined(__i386__)
-                                        __builtin_ia32_pause();
-#endif
-                                        continue;
-                                    }
-                                    const double waited_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_wait0).count();
-                                    if (waited_us < 20.0) continue;
-                                    // a failed launch never writes: the stream is idle (or in error) and the word is not there
-                                    const hipError_t qe = hipStreamQuery(st);
-                                    if (qe != hipErrorNotReady) {
-                                        v = __atomic_load_n(ln.fb_flag + 2 * b, __ATOMIC_ACQUIRE);
-                                        if ((v >> 2) == fb_seq_k) break;
-                                        MI_HIP_TRY(qe);
-                                        MI_REQUIRE(false, MI_ERR_HIP, "host feedback: launch finished without publishing its decision");
-                                    }
-                                    MI_REQUIRE(waited_us < kFeedbackWaitLimitUs, MI_ERR_HIP, "host feedback: no decision from the device within %.0f s", kFeedbackWaitLimitUs * 1e-6);
-                                    if (waited_us < 2000.0) sched_yield();
-                                    else { struct timespec ts_ = {0, 50000}; nanosleep(&ts_, nullptr); }
-                                }
-                                all_before = all_before && (v & 2);
-                                all = all && (v & 1);
-                                n_most = std::max(n_most, ln.fb_flag[2 * b + 1]);
-                            }
-                        } else {
-                            // the slots of this launch and of the one before it (k >= 1), per pair
-                            MI_HIP_TRY(hipMemcpy2DAsync(ln.fb_host, 2 * sizeof(int2), ln.S + (q_last - 1), sizeof(int2) * (size_t)ln.Q, 2 * sizeof(int2),
-                                                        (size_t)B, hipMemcpyDeviceToHost, st));
-                            MI_HIP_TRY(hipEventRecord(ln.fb_ev, st));
-                            MI_HIP_TRY(hipEventSynchronize(ln.fb_ev));
-                            ++ln.fb_waits;
-                            for (int b = 0; b < B; ++b) {
-                                all_before = all_before && (ln.fb_host[2 * b].y & MI_SLOT_DONE);
-                                all = all && (ln.fb_host[2 * b + 1].y & MI_SLOT_DONE);
-                            }
-                        }
-                        if (all) {
-                            pre_warped = ahead;
-                            if (fb_poll && hist) ln.fb_hist[(size_t)s * P.warps + wp] = n_most;
-                            ln.fb_skipped += (long long)plan.size() - (long long)k;
-                            fb_done_at = all_before ? (int)k - 1 : (int)k;   // where the next warp's first read-back goes
-                            break;
-                        }
-                        fb_next = (int)k + 2;
-                    }
-                }
-                if (fb) {
-                    fb_prev_warp = fb_done_at;
-                    if (wp == 0) fb_prev_scale = fb_done_at;
-                }
-                q_settle_prev = q_last;
-                if (wp == 0) q_settle_scale = q_last;
-                first_of_scale = false;
-            } else for (int it = 0; it < iters_per_warp; ++it) {
-                ++nlaunch;
-                if (mf && it % P.inner_iterations == 0) {   // cv::medianBlur before each outer iteration (optflow tvl1flow.cpp:1381-1384)
-                    Ctl mc = ctl;
-                    mc.q_prev = q_last; mc.first_of_warp = (it == 0); mc.reset_cur = first_of_scale;
-                    if ((rc = median_flow(mf, mu1, mu2, ln.scr[0], ln.scr[1], g, check ? &mc : nullptr, cur, st))) return rc;
-                }
-                if (check) {
-                    Ctl ic = ctl;
-                    ic.q = q; ic.q_prev = q_last;
-                    ic.first_of_warp = (it == 0);
-                    ic.reset_cur = first_of_scale;
-                    ic.n = it;
-                    rc = iterate(P.exact_math != 0, pl, g, l_t, theta, taut, first_of_scale, &ic, 0, st);
-                    ln.slots.push_back({s, wp});
-                    q_last = q++;
-                } else {
-                    rc = iterate(P.exact_math != 0, pl, g, l_t, theta, taut, first_of_scale, nullptr, cur, st);
-                    cur ^= 1;
-                }
-                if (rc) return rc;
-                first_of_scale = false;
-            }
-            if (e0 >= 0) {
-                rc = next_event(&e1); if (rc) return rc;
-                MI_HIP_TRY(hipEventRecord(ln.ev_pool[e1], st));
-                ln.regions.push_back({e0, e1, nlaunch, 64.0 * g.w * g.h * B * iters_per_warp, 0, s});
-            }
-        }
-        Ctl ec = ctl;
-        ec.q_prev = q_last;
-        const bool dev_cur = check && !first_of_scale;
-        if (s == 0) {
-            rc = pack_flow(ln.tab_dev, u1v, u2v, g, dev_cur ? &ec : nullptr, cur, st);
-            if (rc) return rc;
-            break;
-        }
-        // zoom the flow to the next finer scale and rescale it (tvl1flow.cpp:291-300)
-        const Geo &gf = ln.L[s - 1].g;
-        have_zoom = false;
-        if (zoom_path && !dev_cur) {
-            // fixed-work blocked path: the finer scale's FIRST WARP samples this scale's flow itself (k_warp6 UP) -- no resize launch,
-            // no 8 B/px round trip of the zoomed flow
-            zoom.u1c = Lv.u[cur][0]; zoom.u2c = Lv.u[cur][1];
-            zoom.u1o = ln.L[s - 1].u[0][0]; zoom.u2o = ln.L[s - 1].u[0][1];
-            zoom.gc = g;
-            zoom.inv_scale_x = (double)gf.w / g.w; zoom.inv_scale_y = (double)gf.h / g.h;
-            zoom.post = (float)(1.0 / P.scale_step);
-            have_zoom = true;
-            continue;
-        }
-        // u3 is zoomed too but NOT rescaled (tvl1flow.cpp:293-300; optflow tvl1flow.cpp:524-528)
-        const float *us[3][2] = {{Lv.u[0][0], Lv.u[1][0]}, {Lv.u[0][1], Lv.u[1][1]}, {gam ? Lv.u[0][2] : nullptr, gam ? Lv.u[1][2] : nullptr}};
-        float *ud[3] = {ln.L[s - 1].u[0][0], ln.L[s - 1].u[0][1], gam ? ln.L[s - 1].u[0][2] : nullptr};
-        const float inv = (float)(1.0 / P.scale_step);
-        const float post[3] = {inv, inv, 1.f};
-        rc = resize(sem, gam ? 3 : 2, us, 2, ud, g, gf, (double)gf.w / g.w, (double)gf.h / g.h, post,
-                    dev_cur ? &ec : nullptr, cur, st);
-        if (rc) return rc;
+        const double se = P.epsilon * P.epsilon * (double)(Lv.g.w * Lv.g.h);
+        r.ctl.thr = P.semantics == MI_SEM_CPU_REF ? (double)(float)se : se;
+        for (int wp = 0; wp < P.warps; ++wp)
+            if ((rc = run_warp(r, Lv, s, wp))) return rc;
+        if ((rc = zoom_or_pack(r, s))) return rc;
     }
     return MI_OK;
 }
@@ -992,6 +848,27 @@ int mi_tvl1_calc(mi_tvl1 *h, const mi_mat *I0, const mi_mat *I1, mi_mat *flow, v
     return mi_tvl1_calc_batch(h, 1, I0, I1, flow, stream);
 }
 
+// the control slots (and the speculative steps' state) of the last calc's launches for one pair, after the stream has drained
+static int read_slots(mi_tvl1 *h, int pair, hipStream_t stream, const Lane **lane, std::vector<int2> *S, std::vector<int4> *X,
+                      int cap_launches = -1)
+{
+    int li = 0;
+    while (li + 1 < h->last_lanes && pair >= h->last_first[li + 1]) ++li;
+    const Lane &ln = h->lane[li];
+    const size_t off = (size_t)(pair - h->last_first[li]) * ln.Q;
+    const int nq = (int)ln.slots.size();
+    MI_REQUIRE(cap_launches < 0 || nq <= cap_launches, MI_ERR_BAD_ARG, "capacity too small");
+    *lane = &ln;
+    S->resize(nq);
+    MI_HIP_TRY(hipStreamSynchronize(stream));
+    MI_HIP_TRY(hipMemcpy(S->data(), ln.S.p + off, sizeof(int2) * nq, hipMemcpyDeviceToHost));
+    if (X) {
+        X->resize(nq);
+        if (ln.X.p) MI_HIP_TRY(hipMemcpy(X->data(), ln.X.p + off, sizeof(int4) * nq, hipMemcpyDeviceToHost));
+    }
+    return MI_OK;
+}
+
 int mi_tvl1_last_iterations(mi_tvl1 *h, int pair, int *nscales_used, int *iters, int cap, void *stream)
 {
     MI_REQUIRE(h && iters && nscales_used, MI_ERR_BAD_ARG, "null argument");
@@ -1004,18 +881,13 @@ int mi_tvl1_last_iterations(mi_tvl1 *h, int pair, int *nscales_used, int *iters,
         for (int i = 0; i < ns * nw; ++i) iters[i] = h->P.iterations * h->P.inner_iterations;
         return MI_OK;
     }
-    int li = 0;
-    while (li + 1 < h->last_lanes && pair >= h->last_first[li + 1]) ++li;
-    Lane &ln = h->lane[li];
-    const int lp = pair - h->last_first[li];
-    const int nq = (int)ln.slots.size();
-    std::vector<int2> S(nq);
-    MI_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    MI_HIP_TRY(hipMemcpy(S.data(), ln.S + (size_t)lp * ln.Q, sizeof(int2) * nq, hipMemcpyDeviceToHost));
-    for (int i = 0; i < nq; ++i) {
+    const Lane *ln = nullptr;
+    std::vector<int2> S;
+    if (const int rc = read_slots(h, pair, (hipStream_t)stream, &ln, &S, nullptr)) return rc;
+    for (size_t i = 0; i < S.size(); ++i) {
         // one-iteration launches: bit 0 = the iteration was executed; speculative launches: bits 8..15 = iterations kept
         const int k = (S[i].y >> 8) & 0xff;
-        iters[ln.slots[i].scale * nw + ln.slots[i].warp] += k ? k : (S[i].y & 1);
+        iters[ln->slots[i].scale * nw + ln->slots[i].warp] += k ? k : (S[i].y & 1);
     }
     return MI_OK;
 }
@@ -1025,20 +897,14 @@ int miflow_selftest_tvl1_slots(mi_tvl1 *h, int pair, int *out_host, int cap_laun
     MI_REQUIRE(h && out_host, MI_ERR_BAD_ARG, "null argument");
     MI_REQUIRE(pair >= 0 && pair < h->last_batch, MI_ERR_BAD_ARG, "pair out of range");
     if (!h->last_check) return 0;
-    int li = 0;
-    while (li + 1 < h->last_lanes && pair >= h->last_first[li + 1]) ++li;
-    Lane &ln = h->lane[li];
-    const int lp = pair - h->last_first[li];
-    const int nq = (int)ln.slots.size();
-    MI_REQUIRE(nq <= cap_launches, MI_ERR_BAD_ARG, "capacity too small");
-    std::vector<int2> S(nq);
-    std::vector<int4> X(nq);
-    MI_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    MI_HIP_TRY(hipMemcpy(S.data(), ln.S + (size_t)lp * ln.Q, sizeof(int2) * nq, hipMemcpyDeviceToHost));
-    if (ln.X) MI_HIP_TRY(hipMemcpy(X.data(), ln.X + (size_t)lp * ln.Q, sizeof(int4) * nq, hipMemcpyDeviceToHost));
+    const Lane *ln = nullptr;
+    std::vector<int2> S;
+    std::vector<int4> X;
+    if (const int rc = read_slots(h, pair, (hipStream_t)stream, &ln, &S, &X, cap_launches)) return rc;
+    const int nq = (int)S.size();
     for (int i = 0; i < nq; ++i) {
         int *o = out_host + 8 * i;
-        o[0] = ln.slots[i].scale; o[1] = ln.slots[i].warp; o[2] = S[i].x; o[3] = S[i].y;
+        o[0] = ln->slots[i].scale; o[1] = ln->slots[i].warp; o[2] = S[i].x; o[3] = S[i].y;
         o[4] = X[i].x; o[5] = X[i].y; o[6] = X[i].z; o[7] = X[i].w;
     }
     return nq;

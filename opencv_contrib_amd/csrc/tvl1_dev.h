@@ -1,17 +1,13 @@
 // Internal launch API of the TV-L1 HIP kernels (tvl1_kernels.hip).  Not part of the C-ABI.
 #pragma once
 #include "mi_common.h"
+#include "tvl1_plan.h"
 
 namespace mi {
 namespace tvl1 {
 
-// All scratch planes of one pyramid level are dense float planes, `ld` floats per row
-// (multiple of 64), `ps` floats between consecutive pairs of the batch.
-struct Geo {
-    int w, h, ld;
-    long long ps;  // pair stride (floats)
-    int batch;
-};
+// the knobs of the plans (tvl1_plan.h), filled once from tuning() and the kernel tables
+const TvKnobs &tv_knobs();
 
 // Device-side loop control (epsilon > 0).  One slot per iteration launch q and pair b:
 //   S[b*Q + q] = {cur_in, active};  E[b*Q + q] = sum(du^2) of launch q, 2^-24 fixed point.
@@ -72,7 +68,6 @@ int gradient(const float *src, float *dx, float *dy, const Geo &g, hipStream_t s
 int median_flow(int ksize, float *const u1[2], float *const u2[2], float *tmp1, float *tmp2, const Geo &g, const Ctl *ctl, int cur_host,
                 hipStream_t s);
 // pk = one float4 {I1, I1x, I1y, 0} per pixel (4 * g.ps floats per pair, 16-B aligned)
-int gradient_pack(const float *src, float *pk, const Geo &g, hipStream_t s);
 int pack3(const float *a, const float *b, const float *c, float *pk, const Geo &g, hipStream_t s);
 int warp(int semantics, const float *I0, const float *pk, const float *u1[2], const float *u2[2], float *I1w,
          float *I1wx, float *I1wy, float *grad, float *rho, const float *cubic_tab_dev, const Geo &g, const Ctl *ctl,
@@ -81,12 +76,9 @@ int warp(int semantics, const float *I0, const float *pk, const float *u1[2], co
 // plane, half the gathered bytes, bit-identical results
 // fast: the three bicubic sums in separable form (rounding differs from the reference's tap-by-tap order; fast-math paths only)
 // lds: windows read from an LDS-staged region of I1 (1) or gathered from global memory (0); -1 = the tuning default
-// zoom: the first warp of a scale samples the coarser scale's flow itself (k_resize's arithmetic), writes it to (u1o, u2o) and uses it
-struct WarpZoom { const float *u1c, *u2c; float *u1o, *u2o; Geo gc; double inv_scale_x, inv_scale_y; float post; };
-bool warp_zoom_ok();
 int warp_fused(int semantics, bool fast, int lds, const float *I0, const float *I1, const float *u1[2], const float *u2[2], float *I1w, float *I1wx,
                float *I1wy, float *grad, float *rho, const float *cubic_tab_dev, const Geo &g, const Ctl *ctl, int cur_host,
-               hipStream_t s, const WarpZoom *zoom = nullptr);
+               hipStream_t s);
 // one fused iteration (estimateU + estimateDualVariables), set cur -> set cur^1.
 // p_zero: p_in is known to be all-zero (first iteration of a scale) and is not read.
 int iterate(bool exact, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut,
@@ -95,31 +87,24 @@ int iterate(bool exact, const IterPlanes &pl, const Geo &g, float l_t, float the
 // Temporally blocked fast-math iteration (tvl1_tbr_kernels.hip): T fused iterations in one HBM pass,
 // set cur -> cur^1.  Supported T: 1,2,3,4,5,6,8,10.  rows_per_band <= 0: auto.
 // skip_p_out: the launch stores u only (the last pass of a scale: nobody reads its p).  pl.g == nullptr: no |grad|^2 plane, the kernel
-// forms it from I1wx, I1wy (only where tb_nograd_ok says so)
+// forms it from I1wx, I1wy (only where tb_nograd_ok, tvl1_plan.h, says so)
 // independent_waves (test hook of the stage-level entry): the kernel whose waves each own a 64-column strip, never the joined form
 int iterate_tb(int T, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut, bool p_zero,
                int cur, int rows_per_band, hipStream_t s, bool skip_p_out = false, bool independent_waves = false);
-bool tb_nograd_ok(int T, const Geo &g);
-// the warp of a one-pass warp INSIDE that pass (k_iterate_tbr FW): no warp launch, no I1wx / I1wy / rho_c planes in HBM; bit-identical
-bool tb_fused_ok(int T, const Geo &g, int semantics, bool fast_warp);
+// the warp of a one-pass warp INSIDE that pass (k_iterate_tbr FW, where tb_fused_ok says so): no warp launch, no I1wx / I1wy / rho_c
+// planes in HBM; bit-identical
 int iterate_tb_fused(int semantics, const float *I0, const float *I1, const float *cubic_tab_dev, int T, const IterPlanes &pl, const Geo &g,
                      float l_t, float theta, float taut, bool p_zero, int cur, hipStream_t s, bool skip_p_out);
-bool tb_spec_nograd_ok(const Geo &g);   // the same for the speculative steps of the convergence-checked path
-int tb_max_block();
 // Register-tile formulation of the same fused iterations for the small pyramid levels (tvl1_tile_kernels.hip): nit in
-// 1..tile_max_block() iterations per launch, bit-identical to iterate_tb.  variant < 0: default of the table.
+// 1..kTileMaxBlock iterations per launch, bit-identical to iterate_tb.  variant < 0: default of the table.
 int iterate_tile(int variant, int nit, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut, bool p_zero, int cur,
                  hipStream_t s);
-int tile_max_block();
 int tile_owned_rows();   // rows a tile of the default variant owns
-int tile_rows_for(const Geo &g);   // rows (owned + margins) of the tiles level g runs on
+int tile_shape_rows(int variant);   // rows (owned + margins) of the tiles of a variant
 int tb_query_plan(int T, const Geo &g, int *kernel, int *rows);   // kernel 0 = streaming (band height), 1 = register tile
 int tile_variants();
-bool tile_eligible(const Geo &g);   // this level (pixels x pairs) runs on the register-tile kernel
-// the same in exact math (bit-identical to T one-iteration launches of iterate(exact = true)); T in 1..tb_exact_max_block()
+// the same in exact math (bit-identical to T one-iteration launches of iterate(exact = true)); T in 1..kTbExactMaxBlock
 int iterate_tb_exact(int T, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut, bool p_zero, int cur, hipStream_t s);
-int tb_exact_max_block();
-// speculative steps of the convergence-checked path (epsilon > 0, fast math): see k_iterate_tbr MODE 1
 // Speculative step of the convergence-checked path (k_iterate_tbr MODE 1), host-side constants of one launch.
 struct SpecK {
     int4 *X;            // per slot: {iterations accepted in this warp, iterations this launch ran speculatively (0: none),
@@ -143,23 +128,11 @@ struct SpecK {
     int fb_seq;
 };
 
-int tb_spec_plan(int n, int warp_index, bool large_level, int *blocks, int max_blocks);
-// the same step on register tiles (tvl1_tile_kernels.hip); iterate_tb_spec dispatches to it where tile_eligible(g)
+// the same step on register tiles (tvl1_tile_kernels.hip); iterate_tb_spec dispatches to it where runs_on_tiles(.., spec = true)
 int iterate_tile_spec(int T, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut, const Ctl &ctl, const SpecK &sk, int e0,
                       hipStream_t s);
 int iterate_tb_spec(int T, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut, bool p_zero, const Ctl &ctl,
                     const SpecK &sk, int e0, hipStream_t s);
-// cost-model decomposition of n iterations into supported blocks (largest first); returns the count
-int tb_plan(int n, int cap, int *blocks, int max_blocks);
-// the same for level g: greedy blocks of tile_max_block() where the level runs on the register-tile kernel
-int tb_plan_level(const Geo &g, int n, int cap, int *blocks, int max_blocks, bool gam = false);   // gam: the illumination channel's block set on streaming levels (10, 5, 2, 1)
-// largest supported block <= n (n >= 1)
-inline int tb_pick_block(int n, int cap)
-{
-    static const int sup[] = {10, 8, 6, 5, 4, 3, 2, 1};
-    for (int t : sup) if (t <= n && t <= cap) return t;
-    return 1;
-}
 int dbg_lane_shift(int *out_dev, hipStream_t s);
 int tb_jw_fault(int *fault_host);   // sticky fault flag of the joined-wave blocked kernels (synchronises the device)
 

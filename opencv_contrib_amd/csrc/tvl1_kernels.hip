@@ -212,23 +212,8 @@ __global__ __launch_bounds__(256) void k_gradient(const float *src, float *dxp, 
     dyp[o] = 0.5f * (d - u);
 }
 
-// Same differences, written together with the image as one float4 per pixel {I1, I1x, I1y, 0}: the warp
-// kernel then gathers ONE 16-B element per bicubic tap instead of three dwords (the gather is bound by the
-// texture-addresser rate of ~4 lanes/clk per wave-load, rocprofv3 r01a: 48 dword gathers/px = 308 us/launch).
-__global__ __launch_bounds__(256) void k_gradient_pack(const float *src, float4 *pk, Geo g)
-{
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    const int b = blockIdx.z;
-    if (x >= g.w || y >= g.h) return;
-    const float *S = src + (long long)b * g.ps;
-    const long long r = (long long)y * g.ld;
-    const float c = S[r + x];
-    const float l = S[r + max(x - 1, 0)], rr = S[r + min(x + 1, g.w - 1)];
-    const float u = S[(long long)max(y - 1, 0) * g.ld + x], d = S[(long long)min(y + 1, g.h - 1) * g.ld + x];
-    pk[(long long)b * g.ps + r + x] = make_float4(c, 0.5f * (rr - l), 0.5f * (d - u), 0.f);
-}
-
+// The image and its differences as one float4 per pixel {I1, I1x, I1y, 0}: the packed-plane warp kernel gathers ONE 16-B element per
+// bicubic tap instead of three dwords (the gather is bound by the texture-addresser rate of ~4 lanes/clk per wave-load, rocprofv3 r01a).
 __global__ __launch_bounds__(256) void k_pack3(const float *a, const float *b_, const float *c, float4 *pk, Geo g)
 {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
@@ -770,13 +755,6 @@ int gradient(const float *src, float *dx, float *dy, const Geo &g, hipStream_t s
     return MI_OK;
 }
 
-int gradient_pack(const float *src, float *pk, const Geo &g, hipStream_t s)
-{
-    hipLaunchKernelGGL(k_gradient_pack, grid2d(g, g.batch), dim3(256), 0, s, src, reinterpret_cast<float4 *>(pk), g);
-    MI_HIP_TRY(hipGetLastError());
-    return MI_OK;
-}
-
 int pack3(const float *a, const float *b, const float *c, float *pk, const Geo &g, hipStream_t s)
 {
     hipLaunchKernelGGL(k_pack3, grid2d(g, g.batch), dim3(256), 0, s, a, b, c, reinterpret_cast<float4 *>(pk), g);
@@ -788,9 +766,9 @@ int warp(int semantics, const float *I0, const float *pk, const float *u1[2], co
          float *I1wx, float *I1wy, float *grad, float *rho, const float *cubic_tab_dev, const Geo &g, const Ctl *ctl,
          int cur_host, hipStream_t s)
 {
-    // Packed-plane gather: one float4 {I1, I1x, I1y, 0} per bicubic tap.  Used by the stage-level entry point when the caller
-    // supplies its own derivative planes, and by calc() under MIFLOW_WARP=pk (the round-1 kernel, kept for A/B runs); calc()
-    // otherwise runs warp_fused (tvl1_warp_kernels.hip), which needs half the gathered bytes.
+    // Packed-plane gather: one float4 {I1, I1x, I1y, 0} per bicubic tap (the round-1 kernel).  Used by the stage-level entry point,
+    // where the caller supplies its own derivative planes; calc() runs warp_fused (tvl1_warp_kernels.hip), which needs half the
+    // gathered bytes.
     WarpArgs A;
     A.I0 = I0; A.pk = reinterpret_cast<const float4 *>(pk);
     A.u1[0] = u1[0]; A.u1[1] = u1[1]; A.u2[0] = u2[0]; A.u2[1] = u2[1];

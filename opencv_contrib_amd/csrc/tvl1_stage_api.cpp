@@ -164,14 +164,14 @@ int mi_tvl1_iterate(int exact_math, int time_block, int niter, const mi_mat *I1w
     int cur = 0;
     for (int it = 0; it < niter;) {
         if (tiled) {
-            const int T = std::min(niter - it, tile_max_block());
+            const int T = std::min(niter - it, kTileMaxBlock);
             TRY(iterate_tile(-time_block - 1, T, pl, g, l_t, theta, taut, false, cur, st));
             it += T;
             cur ^= 1;
             continue;
         }
         if (blocked) {
-            const int T = tb_pick_block(niter - it, time_block);
+            const int T = greedy_blocks(std::min(niter - it, 10), time_block, {1, 2, 3, 4, 5, 6, 8, 10})[0];   // the largest supported block
             // rows_per_band = -1: always the streaming kernel (the tile kernel is compared against it)
             TRY(iterate_tb(T, pl, g, l_t, theta, taut, false, cur, -1, st, false, indep));
             it += T;

@@ -1150,7 +1150,7 @@ static const TbrEntry g_tbr_fw[] = {{10, 1, 4, 2, 2, launch_tbr<10, 1, 4, 2, 0, 
 #endif
 // gamma != 0 (round 6): the blocked kernel with the illumination channel -- nine dynamic registers per set (T = 10:
 // three waves/SIMD), always without a |grad|^2 plane.  Blocks of 10 and 5 as joined waves, 2 and 1 as independent waves (any iteration
-// count decomposes greedily: tb_plan_gam)
+// count decomposes greedily: tb_plan_gam, tvl1_plan.h)
 // (T = 10 with ONE prefetched row: 163 VGPRs = three waves/SIMD without scratch; with two it is 168 + 12 spilled dwords)
 static const TbrEntry g_tbr_gam[] = {{10, 1, 3, 1, 3, launch_tbr<10, 1, 3, 1, 0, 2, true, false, 0, true>, nullptr, 2, true},
                                      {5, 1, 4, 2, 3, launch_tbr<5, 1, 4, 2, 0, 2, true, false, 0, true>, nullptr, 2, true},
@@ -1184,11 +1184,6 @@ static const TbrEntry g_spec_jw[] = {TBRSJ(10, 1, 3, 2, 2), TBRSJ(5, 1, 4, 2, 2)
 #endif
 // ... and the same two without a |grad|^2 plane (round 4: the convergence-checked path re-reads the statics once per block)
 static const TbrEntry g_spec_jw_ng[] = {{10, 1, 3, 2, 2, nullptr, launch_tbr<10, 1, 3, 2, 1, 2, true>, 2}, {5, 1, 4, 2, 2, nullptr, launch_tbr<5, 1, 4, 2, 1, 2, true>, 2}};
-bool tb_spec_nograd_ok(const Geo &g)
-{
-    if (!tuning().tb_nograd || tuning().tb_jw < 2 || !tuning().tb_jw_spec) return false;
-    return !(tile_eligible(g) && tuning().tile_spec != 0);   // the register-tile kernel reads the stored plane
-}
 
 // Exact-math blocks (MODE 2; 1 px per lane).  The stage costs about four times the fast one (three IEEE divisions, two double
 // square roots), so short blocks already move the kernel from the HBM bound of the one-iteration kernel to the issue bound.
@@ -1210,68 +1205,6 @@ static const TbrEntry *tbr_pick(int T)
         if (e.PPL == tn.tb_ppl && e.WPS == tn.tb_wps && e.PF == tn.tb_pf) { def = &e; break; }
     }
     return def;
-}
-
-int tb_max_block() { return 10; }
-
-// Decompose n iterations into supported time blocks minimising the modelled cost.  cost[T] = measured
-// ps per pixel-iteration of k_iterate_tbr<T> at 1080p x 16 pairs (tools/sweep_tb.py, profiles/r01s):
-// deeper blocks save HBM passes but cost registers (occupancy) and halo recomputation.
-int tb_plan(int n, int cap, int *blocks, int max_blocks)
-{
-    static const int sup[] = {1, 2, 3, 4, 5, 6, 8, 10};
-    static const double cost[11] = {0, 15.6, 9.4, 6.6, 4.65, 3.9, 3.7, 0, 2.83, 0, 2.54};
-    if (n <= 0) return 0;
-    if (tuning().tb_force) {   // tuning sweeps: greedy blocks of exactly `cap` (then the largest that fit)
-        int k = 0;
-        for (int left = n; left > 0 && k < max_blocks;) {
-            int t = 1;
-            for (int c : sup) if (c <= left && c <= cap) t = c;
-            blocks[k++] = t;
-            left -= t;
-        }
-        return k;
-    }
-    std::vector<double> best(n + 1, 1e300);
-    std::vector<int> pick(n + 1, 1);
-    best[0] = 0;
-    for (int i = 1; i <= n; ++i)
-        for (int t : sup) {
-            if (t > i || t > cap) continue;
-            const double c = best[i - t] + t * cost[t];
-            if (c < best[i]) { best[i] = c; pick[i] = t; }
-        }
-    int k = 0;
-    for (int i = n; i > 0 && k < max_blocks; i -= pick[i]) blocks[k++] = pick[i];
-    return k;
-}
-
-// gamma != 0: greedy blocks of the four lengths the channel's kernels exist in (g_tbr_gam)
-int tb_plan_gam(int n, int cap, int *blocks, int max_blocks)
-{
-    int k = 0;
-    for (int left = n; left > 0 && k < max_blocks;) {
-        int t = 1;
-        for (const TbrEntry &e : g_tbr_gam) if (e.T <= left && e.T <= cap && e.T > t) t = e.T;
-        blocks[k++] = t;
-        left -= t;
-    }
-    return k;
-}
-
-int tb_plan_level(const Geo &g, int n, int cap, int *blocks, int max_blocks, bool gam)
-{
-    if (gam && (!tile_eligible(g) || tuning().tb_force)) return tb_plan_gam(n, cap, blocks, max_blocks);   // the channel's streaming kernels: blocks of 10 / 5 / 2 / 1
-    if (!tile_eligible(g) || tuning().tb_force) return tb_plan(n, cap, blocks, max_blocks);
-    // register-tile kernel: any block length up to its margin costs one launch; fewest launches win
-    int k = 0;
-    const int top = cap < tile_max_block() ? cap : tile_max_block();
-    for (int left = n; left > 0 && k < max_blocks;) {
-        const int t = left < top ? left : top;
-        blocks[k++] = t;
-        left -= t;
-    }
-    return k;
 }
 
 // Band height: every wave streams rows_per_band + 2T rows, in whole blocks of P = T + 1 + PF steps.  Pick the band count
@@ -1315,7 +1248,7 @@ static int plan_band_rows(const TbrEntry &e, const Geo &g)
 // height), 1 = register tile (rows = owned rows of a tile).
 int tb_query_plan(int T, const Geo &g, int *kernel, int *rows)
 {
-    if (tile_eligible(g) && T <= tile_max_block() && !tuning().tb_force) {
+    if (runs_on_tiles(g, T, tv_knobs())) {
         *kernel = 1;
         *rows = tile_owned_rows();
         return MI_OK;
@@ -1327,29 +1260,7 @@ int tb_query_plan(int T, const Geo &g, int *kernel, int *rows)
     return MI_OK;
 }
 
-// T fused iterations, set cur -> cur^1.  Returns MI_ERR_BAD_ARG for unsupported T.
-// The launch iterate_tb(T) would make can run without a |grad|^2 plane (pl.g == nullptr): the default joined-wave T = 10 kernel on a
-// level that does not take the register-tile kernel.  The caller (lane_calc) asks BEFORE the warp, which then does not store the plane.
-bool tb_nograd_ok(int T, const Geo &g)
-{
-    if (!tuning().tb_nograd || T != 10 || tuning().tb_jw != 2 || tuning().tb_ppl >= 0) return false;
-    if (tile_eligible(g) && T <= tile_max_block() && !tuning().tb_force) return false;
-    return true;
-}
-
-// A warp whose iterations are ONE pass of the default T = 10 kernel can run with the warp inside that pass (k_iterate_tbr FW): no warp
-// launch, no I1wx / I1wy / rho_c planes.  Which warp arithmetic: the two defaults (CPU class + tap-by-tap sums, cv::cuda + separable sums).
-bool tb_fused_ok(int T, const Geo &g, int semantics, bool fast_warp)
-{
-#ifndef MIFLOW_EXPERIMENTS
-    (void)T; (void)g; (void)semantics; (void)fast_warp;
-    return false;   // measured slower (profiles/r14): the fused form is built into the experiments library only
-#else
-    if (!tuning().tb_fw || !tb_nograd_ok(T, g) || g.w < 6 || g.h < 6) return false;   // (the producers' unconditional window gather needs an interior)
-    return (semantics == MI_SEM_CPU_REF && !fast_warp) || (semantics == MI_SEM_CUDA_COMPAT && fast_warp);
-#endif
-}
-
+// The warp inside a single T = 10 pass (k_iterate_tbr FW): the plan (tvl1_plan.h tb_fused_ok) decides it before the warp.
 int iterate_tb_fused(int semantics, const float *I0, const float *I1, const float *cubic_tab_dev, int T, const IterPlanes &pl, const Geo &g,
                      float l_t, float theta, float taut, bool p_zero, int cur, hipStream_t s, bool skip_p_out)
 {
@@ -1358,7 +1269,7 @@ int iterate_tb_fused(int semantics, const float *I0, const float *I1, const floa
     set_error("the warp fused into the pass kernel exists in the experiments build only (-DMIFLOW_EXPERIMENTS)");
     return MI_ERR_NOT_IMPL;
 #else
-    MI_REQUIRE(T == 10 && tb_nograd_ok(T, g), MI_ERR_BAD_ARG, "fused warp: one pass of the default T = 10 kernel only");
+    MI_REQUIRE(T == 10 && tb_nograd_ok(T, g, tv_knobs()), MI_ERR_BAD_ARG, "fused warp: one pass of the default T = 10 kernel only");
     const TbrEntry &e = g_tbr_fw[semantics == MI_SEM_CPU_REF ? 0 : 1];
     TbArgs A;
     memset(&A, 0, sizeof(A));
@@ -1375,10 +1286,12 @@ int iterate_tb_fused(int semantics, const float *I0, const float *I1, const floa
 #endif
 }
 
+// T fused iterations, set cur -> cur^1.  Returns MI_ERR_BAD_ARG for unsupported T.  pl.g == nullptr (the plan's tb_nograd_ok, decided
+// before the warp, which then does not store the plane): the pass forms |grad|^2 itself.
 int iterate_tb(int T, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut, bool p_zero,
                int cur, int rows_per_band, hipStream_t s, bool skip_p_out, bool independent_waves)
 {
-    if (pl.gamma != 0.f && rows_per_band == 0 && tile_eligible(g) && T <= tile_max_block() && !tuning().tb_force)
+    if (pl.gamma != 0.f && rows_per_band == 0 && runs_on_tiles(g, T, tv_knobs()))
         return iterate_tile(-1, T, pl, g, l_t, theta, taut, p_zero, cur, s);   // small levels: the register tile with the channel (bit-identical)
     if (pl.gamma != 0.f) {   // the illumination channel: its own kernels (no |grad|^2 plane read, whether or not the warp stored one)
         const TbrEntry *e = nullptr;
@@ -1392,7 +1305,7 @@ int iterate_tb(int T, const IterPlanes &pl, const Geo &g, float l_t, float theta
         A.rows_per_band = rows_per_band > 0 ? rows_per_band : plan_band_rows(*e, g);
         return e->launch(A, p_zero, s);
     }
-    if (rows_per_band == 0 && tile_eligible(g) && T <= tile_max_block() && !tuning().tb_force) {
+    if (rows_per_band == 0 && runs_on_tiles(g, T, tv_knobs())) {
         MI_REQUIRE(pl.g, MI_ERR_BAD_ARG, "the register-tile kernel needs the |grad|^2 plane");
         return iterate_tile(-1, T, pl, g, l_t, theta, taut, p_zero, cur, s);
     }
@@ -1403,7 +1316,7 @@ int iterate_tb(int T, const IterPlanes &pl, const Geo &g, float l_t, float theta
     }
     if (!e) { set_error("unsupported time block %d", T); return MI_ERR_BAD_ARG; }
     if (!pl.g) {
-        MI_REQUIRE(tb_nograd_ok(T, g), MI_ERR_BAD_ARG, "no |grad|^2 plane, but the kernel of this launch needs one");
+        MI_REQUIRE(tb_nograd_ok(T, g, tv_knobs()), MI_ERR_BAD_ARG, "no |grad|^2 plane, but the kernel of this launch needs one");
 #ifdef MIFLOW_EXPERIMENTS
         e = tuning().tb_p16 ? &g_tbr_ng16 : &g_tbr_ng;
 #else
@@ -1424,7 +1337,6 @@ int iterate_tb(int T, const IterPlanes &pl, const Geo &g, float l_t, float theta
 }
 
 // T fused EXACT iterations, set cur -> cur^1 (bit-identical to T launches of the one-iteration exact kernel).  T in 1..5.
-int tb_exact_max_block() { return 5; }
 int iterate_tb_exact(int T, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut, bool p_zero, int cur, hipStream_t s)
 {
     const TbrEntry *e = nullptr;
@@ -1437,24 +1349,6 @@ int iterate_tb_exact(int T, const IterPlanes &pl, const Geo &g, float l_t, float
     return e->launch(A, p_zero, s);
 }
 
-// Kernel block sizes of a warp's speculative steps (MODE 1 instantiations: 10 and 5).  A pass of the T = 5 kernel costs half
-// of a T = 10 pass on the small pyramid levels and two thirds on a large one (profiles/r02k), and most warps settle within a few
-// iterations: only the first warp of a LARGE level (px x pairs >= 12M) starts with the long kernel; after twelve short blocks
-// the plan continues with long ones to bound the launch count.  It covers n + 30 iterations so that blocks cut short by the
-// device's estimate cannot make the iteration limit unreachable.
-int tb_spec_plan(int n, int warp_index, bool large_level, int *blocks, int max_blocks)
-{
-    int k = 0, sum = 0;
-    if (n <= 0) return 0;
-    const int want = n + (n > 10 ? 30 : n > 1 ? 10 : 0);
-    while (sum < want && k < max_blocks) {
-        const int t = n <= 5 ? 5 : (large_level && warp_index == 0) ? 10 : k < 12 ? 5 : 10;
-        blocks[k++] = t;
-        sum += t;
-    }
-    return k;
-}
-
 // One speculative step with kernel block size T (see k_iterate_tbr MODE 1); ctl carries the slot protocol, sk the step's
 // constants, e0 the index of the first per-iteration error sum this launch may write.
 int iterate_tb_spec(int T, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut, bool p_zero, const Ctl &ctl,
@@ -1462,13 +1356,13 @@ int iterate_tb_spec(int T, const IterPlanes &pl, const Geo &g, float l_t, float 
 {
     // small levels: the same step on register tiles (serial depth of a launch = its iterations, not the image height); integer
     // error sums and identical per-pixel arithmetic => the same decisions and the same flows as the streaming kernel
-    if (tile_eligible(g) && T <= tile_max_block() && !p_zero && tuning().tile_spec != 0)
+    if (runs_on_tiles(g, T, tv_knobs(), true) && !p_zero)
         return iterate_tile_spec(T, pl, g, l_t, theta, taut, ctl, sk, e0, s);
     const TbrEntry *e = nullptr;
     if (pl.gamma != 0.f) {
         for (const TbrEntry &c : g_spec_gam) if (c.T == T) e = &c;
     } else if (!pl.g) {
-        MI_REQUIRE(tb_spec_nograd_ok(g), MI_ERR_BAD_ARG, "no |grad|^2 plane, but the speculative kernel of this launch needs one");
+        MI_REQUIRE(tb_spec_nograd_ok(g, tv_knobs()), MI_ERR_BAD_ARG, "no |grad|^2 plane, but the speculative kernel of this launch needs one");
         for (const TbrEntry &c : g_spec_jw_ng) if (c.T == T) e = &c;
     }
 #ifdef MIFLOW_EXPERIMENTS

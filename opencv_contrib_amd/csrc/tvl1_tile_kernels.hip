@@ -282,7 +282,7 @@ struct TileEntry {
 #define TILEG(RW, NW) {RW, NW, launch_tile<RW, NW, false>, launch_tile<RW, NW, true>, launch_tile<RW, NW, true, 4>, launch_tile<RW, NW, true, 7>, \
                        launch_tile<RW, NW, false, TILE_M, true>, launch_tile<RW, NW, true, TILE_M, true>}
 // [0] = the large-grid shape (64-row tiles of 16 waves), [1] = the small-grid shape (48-row tiles of 8 waves x 6 rows): what a release
-// build runs (auto_variant).  The other shapes of the r02 / r10 sweeps exist in the experiments build only.
+// build runs (tile_auto_variant, tvl1_plan.h).  The other shapes of the r02 / r10 sweeps exist in the experiments build only.
 static const TileEntry g_tile[] = {TILEG(4, 16), TILEG(6, 8),
 #ifdef MIFLOW_EXPERIMENTS
                                    TILE(6, 16), TILE(8, 16), TILE(8, 8), TILE(3, 16),
@@ -291,27 +291,8 @@ static const TileEntry g_tile[] = {TILEG(4, 16), TILEG(6, 8),
 constexpr int kTileVariants = (int)(sizeof(g_tile) / sizeof(g_tile[0]));
 
 int tile_variants() { return kTileVariants; }
-// MIFLOW_TILE_VARIANT < 0 (default): by the size of the grid -- where 64-row tiles of 16 waves give the device fewer than four
-// workgroups per CU (the levels of a single pair, the coarse levels of a small batch) 48-row tiles of 8 waves x 6 rows run the same
-// iterations faster (r10c: one pair per calc 640 x 480 552 -> 606 calcs/s, 1080p 362 -> 375)
-// spec: the speculative steps of the convergence-checked path take the small-grid shape up to twice the grid size (round 6, r19k: their
-// blocks are mostly shorter than the margin, and the 48-row tiles' shorter dependent chain per iteration pays for longer -- one 1080p pair
-// per calc() with the class defaults 423 -> 439 calcs/s -- while fixed-work launches lose 2-4 % there)
-static int auto_variant(const Geo &g, bool spec = false)
-{
-    const int v = tuning().tile_variant;
-    if (v >= 0) return v < kTileVariants ? v : 0;
-    constexpr int M = TILE_M, LW = 64, STRIDE = LW - 2 * M;
-    const long long nstrips = g.w <= LW - M ? 1 : 1 + div_up(g.w - (LW - M), STRIDE);
-    const long long wgs = nstrips * div_up(g.h, 64 - 2 * M) * g.batch;
-    return wgs < (long long)tuning().tile_small_wgs * (spec ? 2 : 1) ? 1 : 0;
-}
-int tile_max_block() { return TILE_M; }
-int tile_rows_for(const Geo &g)
-{
-    const TileEntry &e = g_tile[auto_variant(g, true)];   // (asked by the cost model of the speculative steps)
-    return e.RW * e.NW;
-}
+static_assert(TILE_M == kTileMaxBlock, "the plan's tile margin");
+int tile_shape_rows(int variant) { return g_tile[variant].RW * g_tile[variant].NW; }
 int tile_owned_rows()
 {
     int v = tuning().tile_variant;
@@ -319,19 +300,12 @@ int tile_owned_rows()
     return g_tile[v].RW * g_tile[v].NW - 2 * TILE_M;
 }
 
-// Levels of at most this many pixels x pairs run on the register-tile kernel (0: never).  MIFLOW_TILE_MAXPX.
-bool tile_eligible(const Geo &g)
-{
-    const long long lim = tuning().tile_maxpx;
-    return lim > 0 && (long long)g.w * g.h * g.batch <= lim;
-}
-
 // nit (1..10) fused iterations, set cur -> cur^1, on register tiles.  variant < 0: the table default (MIFLOW_TILE_VARIANT).
 int iterate_tile(int variant, int nit, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut, bool p_zero, int cur,
                  hipStream_t s)
 {
     if (nit < 1 || nit > TILE_M) { set_error("register-tile kernel: %d iterations per launch (1..%d)", nit, TILE_M); return MI_ERR_BAD_ARG; }
-    if (variant < 0) variant = auto_variant(g);
+    if (variant < 0) variant = tile_auto_variant(g, false, tv_knobs());   // MIFLOW_TILE_VARIANT < 0 (default): by the size of the grid
     if (variant < 0 || variant >= kTileVariants) { set_error("register-tile kernel: no variant %d", variant); return MI_ERR_BAD_ARG; }
     TileArgs A;
     memset(&A, 0, sizeof(A));
@@ -342,7 +316,7 @@ int iterate_tile(int variant, int nit, const IterPlanes &pl, const Geo &g, float
             fprintf(stderr, "[tile] rw=%d nw=%d nit=%d %dx%d batch=%d\n", g_tile[variant].RW, g_tile[variant].NW, nit, g.w, g.h, g.batch);
     }
     if (pl.gamma != 0.f) {
-        if (!g_tile[variant].launch_gam) variant = auto_variant(g) < 2 ? auto_variant(g) : 0;   // the channel exists on the two release shapes
+        if (!g_tile[variant].launch_gam) variant = tile_auto_variant(g, false, tv_knobs()) < 2 ? tile_auto_variant(g, false, tv_knobs()) : 0;   // the channel exists on the two release shapes
         MI_REQUIRE(pl.u[0][2] && pl.u[1][2] && pl.p[0][4] && pl.p[0][5] && pl.p[1][4] && pl.p[1][5], MI_ERR_BAD_ARG, "gamma != 0 needs the u3 / p31 / p32 planes");
         return g_tile[variant].launch_gam(A, p_zero, s);
     }
@@ -355,7 +329,7 @@ int iterate_tile_spec(int T, const IterPlanes &pl, const Geo &g, float l_t, floa
                       hipStream_t s)
 {
     if (T < 1 || T > TILE_M) { set_error("register-tile kernel: block of %d iterations (1..%d)", T, TILE_M); return MI_ERR_BAD_ARG; }
-    const int variant = auto_variant(g, true);
+    const int variant = tile_auto_variant(g, true, tv_knobs());
     TileArgs A;
     memset(&A, 0, sizeof(A));
     A.pl = pl; A.g = g; A.l_t = l_t; A.theta = theta; A.taut = taut; A.cur = 0; A.nit = T; A.swz = tuning().tile_swz;
