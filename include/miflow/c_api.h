@@ -214,6 +214,44 @@ MI_API int mi_tvl1_iterate(int exact_math, int time_block, int niter, const mi_m
                            const mi_mat *grad, const mi_mat *rho_c, const mi_mat *u_in /*[2]*/,
                            const mi_mat *p_in /*[4]*/, mi_mat *u_out /*[2]*/, mi_mat *p_out /*[4]*/,
                            float l_t, float theta, float taut, double *err_host, void *stream);
+/* Test hook of the same iterations in every form calc() runs them (mi_tvl1_iterate_stage): the form, its grid and loop, the
+ * illumination channel, a batch and the raw error sums.  Every plane is MI_32FC1 with batch * h rows of w columns (the pairs
+ * stacked) and goes through one launch per step.  Unsupported combinations are refused before anything is enqueued; the call
+ * synchronises `stream` before returning. */
+enum {
+    MI_TVL1_STAGE_ONE = 0,           /* one launch per iteration (exact_math: exact / fast); with err_fix: the error-checked launch */
+    MI_TVL1_STAGE_BLOCKED = 1,       /* streaming blocks of fast iterations, the kernel calc() picks for the block length (joined waves) */
+    MI_TVL1_STAGE_INDEP = 2,         /* the same on the independent-wave kernel of the block length (gamma != 0: blocks of 2 and 1) */
+    MI_TVL1_STAGE_TILE = 3,          /* register tiles of shape `variant`, blocks of 1..10 */
+    MI_TVL1_STAGE_EXACT_BLOCKED = 4, /* exact-math blocks of 1..5 (gamma = 0) */
+    MI_TVL1_STAGE_SPEC = 5,          /* speculative steps of the convergence-checked path, streaming kernel of block time_block (10, 5) */
+    MI_TVL1_STAGE_SPEC_TILE = 6      /* the same on register tiles of shape `variant` (margin 4 / 7 / 10 for blocks <= 4 / <= 7 / 10) */
+};
+typedef struct mi_tvl1_stage_desc {
+    int form;                 /* MI_TVL1_STAGE_* */
+    int exact_math;           /* STAGE_ONE only */
+    int niter;                /* >= 1 */
+    int time_block;           /* blocked forms: longest block (0: the form's longest), greedy over the form's lengths; SPEC*: the block */
+    const int *blocks;        /* blocked forms, optional (host): nblocks block lengths in launch order, summing to niter */
+    int nblocks;
+    int rows_per_band;        /* streaming forms: 0 = the planner's band height, >= 8 = forced */
+    int variant;              /* TILE / SPEC_TILE: register-tile shape */
+    int p_zero;               /* the first step takes p = 0 (the first pass of a scale) and does not read p_in */
+    int batch;                /* pairs, >= 1 */
+    float l_t, theta, taut;
+    float gamma;              /* != 0: the illumination channel (u3, p31, p32) */
+    int err_u3;               /* gamma != 0: the error sum includes (du3)^2 (the CPU class) */
+    const mi_mat *I1wx, *I1wy;
+    const mi_mat *grad;       /* |grad|^2; NULL: the pass forms it from I1wx, I1wy (BLOCKED with blocks of 10, SPEC) */
+    const mi_mat *rho_c;
+    const mi_mat *u_in;       /* [3] u1, u2, u3 (u3 with gamma != 0 only) */
+    const mi_mat *p_in;       /* [6] p11, p12, p21, p22, p31, p32 (p31, p32 with gamma != 0 only; not read with p_zero, may be NULL then) */
+    mi_mat *u_out;            /* [3] */
+    mi_mat *p_out;            /* [6] */
+    unsigned long long *err_fix;   /* host [batch][niter] or NULL (STAGE_ONE, SPEC, SPEC_TILE): the per-iteration error sums as the
+                                    * device's 2^-24 fixed-point integers */
+} mi_tvl1_stage_desc;
+MI_API int mi_tvl1_iterate_stage(const mi_tvl1_stage_desc *d, void *stream);
 /* Replaces: cv::cuda::resize(INTER_LINEAR) on CV_32FC1, cudawarping/src/resize.cpp:57-108
  * (semantics CUDA_COMPAT) / cv::resize (semantics CPU_REF); inv_scale = fx given by the
  * caller when `explicit_dsize` is 0, else dst/src.  dst *= post_scale afterwards. */

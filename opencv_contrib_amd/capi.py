@@ -39,6 +39,20 @@ class TVL1Params(C.Structure):
                 ("time_block", C.c_int), ("lanes", C.c_int), ("stop_slack", C.c_int), ("host_feedback", C.c_int)]
 
 
+class TVL1StageDesc(C.Structure):
+    """mi_tvl1_stage_desc (c_api.h): the TV-L1 iterations in one of the forms calc() runs them (test hook)."""
+    _fields_ = [("form", C.c_int), ("exact_math", C.c_int), ("niter", C.c_int), ("time_block", C.c_int),
+                ("blocks", C.POINTER(C.c_int)), ("nblocks", C.c_int), ("rows_per_band", C.c_int), ("variant", C.c_int),
+                ("p_zero", C.c_int), ("batch", C.c_int), ("l_t", C.c_float), ("theta", C.c_float), ("taut", C.c_float),
+                ("gamma", C.c_float), ("err_u3", C.c_int), ("I1wx", C.POINTER(Mat)), ("I1wy", C.POINTER(Mat)),
+                ("grad", C.POINTER(Mat)), ("rho_c", C.POINTER(Mat)), ("u_in", C.POINTER(Mat)), ("p_in", C.POINTER(Mat)),
+                ("u_out", C.POINTER(Mat)), ("p_out", C.POINTER(Mat)), ("err_fix", C.POINTER(C.c_ulonglong))]
+
+
+MI_TVL1_STAGE_ONE, MI_TVL1_STAGE_BLOCKED, MI_TVL1_STAGE_INDEP, MI_TVL1_STAGE_TILE = 0, 1, 2, 3
+MI_TVL1_STAGE_EXACT_BLOCKED, MI_TVL1_STAGE_SPEC, MI_TVL1_STAGE_SPEC_TILE = 4, 5, 6
+
+
 class SURFParams(C.Structure):
     _fields_ = [("hessian_threshold", C.c_double), ("n_octaves", C.c_int), ("n_octave_layers", C.c_int), ("extended", C.c_int),
                 ("keypoints_ratio", C.c_float), ("upright", C.c_int)]
@@ -131,6 +145,7 @@ def lib():
         "mi_tvl1_centered_gradient": (i, [PM, PM, PM, vp]),
         "mi_tvl1_warp_backward": (i, [i] + [PM] * 11),
         "mi_tvl1_iterate": (i, [i, i, i, PM, PM, PM, PM, PM, PM, PM, PM, f, f, f, C.POINTER(d), vp]),
+        "mi_tvl1_iterate_stage": (i, [C.POINTER(TVL1StageDesc), vp]),
         "mi_resize_linear": (i, [i, PM, PM, d, d, i, f, vp]),
         "miflow_selftest_lane_shift": (i, [C.POINTER(i)]),
         "miflow_selftest_rccl_self_copy": (i, [C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(i)]),

@@ -85,9 +85,10 @@ int iterate(bool exact, const IterPlanes &pl, const Geo &g, float l_t, float the
             bool p_zero, const Ctl *ctl, int cur_host, hipStream_t s);
 
 // Temporally blocked fast-math iteration (tvl1_tbr_kernels.hip): T fused iterations in one HBM pass,
-// set cur -> cur^1.  Supported T: 1,2,3,4,5,6,8,10.  rows_per_band <= 0: auto.
+// set cur -> cur^1.  Supported T: 1,2,3,4,5,6,8,10.  rows_per_band = 0: the plan decides (register tiles on small levels), -1: the
+// streaming kernel with the planner's band height, > 0: the streaming kernel with that band height.
 // skip_p_out: the launch stores u only (the last pass of a scale: nobody reads its p).  pl.g == nullptr: no |grad|^2 plane, the kernel
-// forms it from I1wx, I1wy (only where tb_nograd_ok, tvl1_plan.h, says so)
+// forms it from I1wx, I1wy (only where tb_nograd_ok, tvl1_plan.h, says so -- or anywhere with a streaming kernel forced, rows_per_band != 0)
 // independent_waves (test hook of the stage-level entry): the kernel whose waves each own a 64-column strip, never the joined form
 int iterate_tb(int T, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut, bool p_zero,
                int cur, int rows_per_band, hipStream_t s, bool skip_p_out = false, bool independent_waves = false);
@@ -103,8 +104,13 @@ int tile_owned_rows();   // rows a tile of the default variant owns
 int tile_shape_rows(int variant);   // rows (owned + margins) of the tiles of a variant
 int tb_query_plan(int T, const Geo &g, int *kernel, int *rows);   // kernel 0 = streaming (band height), 1 = register tile
 int tile_variants();
-// the same in exact math (bit-identical to T one-iteration launches of iterate(exact = true)); T in 1..kTbExactMaxBlock
-int iterate_tb_exact(int T, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut, bool p_zero, int cur, hipStream_t s);
+// the same in exact math (bit-identical to T one-iteration launches of iterate(exact = true)); T in 1..kTbExactMaxBlock.
+// rows_per_band <= 0: the planner's band height
+int iterate_tb_exact(int T, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut, bool p_zero, int cur, hipStream_t s,
+                     int rows_per_band = 0);
+// which kernels of block length T exist (the stage-level entry refuses what no table holds before it enqueues anything): kind 0 = the
+// streaming kernel iterate_tb picks, 1 = its independent-wave kernel, 2 = the exact-math blocks, 3 = the speculative steps
+bool tb_kernel_exists(int kind, int T, bool gam, bool nograd);
 // Speculative step of the convergence-checked path (k_iterate_tbr MODE 1), host-side constants of one launch.
 struct SpecK {
     int4 *X;            // per slot: {iterations accepted in this warp, iterations this launch ran speculatively (0: none),
@@ -129,10 +135,13 @@ struct SpecK {
 };
 
 // the same step on register tiles (tvl1_tile_kernels.hip); iterate_tb_spec dispatches to it where runs_on_tiles(.., spec = true)
+// (variant < 0: by the size of the grid, tile_auto_variant)
 int iterate_tile_spec(int T, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut, const Ctl &ctl, const SpecK &sk, int e0,
-                      hipStream_t s);
+                      hipStream_t s, int variant = -1);
+// rows_per_band as in iterate_tb: 0 = the plan decides (register tiles on small levels), -1 = the streaming kernel with the planner's
+// band height, > 0 = the streaming kernel with that band height
 int iterate_tb_spec(int T, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut, bool p_zero, const Ctl &ctl,
-                    const SpecK &sk, int e0, hipStream_t s);
+                    const SpecK &sk, int e0, hipStream_t s, int rows_per_band = 0);
 int dbg_lane_shift(int *out_dev, hipStream_t s);
 int tb_jw_fault(int *fault_host);   // sticky fault flag of the joined-wave blocked kernels (synchronises the device)
 

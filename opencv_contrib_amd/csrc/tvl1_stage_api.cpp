@@ -3,6 +3,7 @@
 // modules/cudaoptflow/src/tvl1flow.cpp:58-76, and cuda::resize).  Caller planes may be
 // arbitrarily pitched; they are staged through dense 256-B-aligned scratch planes.
 #include <algorithm>
+#include <cstring>
 #include "tvl1_dev.h"
 #include "mi_selftest.h"
 #include <vector>
@@ -15,11 +16,12 @@ namespace {
 struct Stage {
     std::vector<float *> bufs;
     ~Stage() { for (float *p : bufs) (void)hipFree(p); }
-    float *alloc(const Geo &g)
+    float *alloc(const Geo &g) { return (float *)alloc_bytes(sizeof(float) * (size_t)g.ps * g.batch); }
+    void *alloc_bytes(size_t n)
     {
-        float *p = nullptr;
-        if (hipMalloc((void **)&p, sizeof(float) * (size_t)g.ps) != hipSuccess) return nullptr;
-        bufs.push_back(p);
+        void *p = nullptr;
+        if (hipMalloc(&p, n) != hipSuccess) return nullptr;
+        bufs.push_back((float *)p);
         return p;
     }
 };
@@ -40,18 +42,20 @@ int check_f32(const mi_mat *m, const char *name)
     return MI_OK;
 }
 
+// (the g.batch pairs of a plane are its g.batch * g.h rows: pair b's row y is row b * h + y of the caller's plane and of the scratch
+// plane, whose pair stride g.ps is g.h rows of g.ld floats)
 int stage_in(Stage &S, const mi_mat *m, const Geo &g, float **out, hipStream_t st)
 {
     float *p = S.alloc(g);
     MI_REQUIRE(p, MI_ERR_OOM, "stage allocation failed");
-    MI_HIP_TRY(hipMemcpy2DAsync(p, (size_t)g.ld * 4, m->data, m->step, (size_t)g.w * 4, (size_t)g.h, hipMemcpyDeviceToDevice, st));
+    MI_HIP_TRY(hipMemcpy2DAsync(p, (size_t)g.ld * 4, m->data, m->step, (size_t)g.w * 4, (size_t)g.h * g.batch, hipMemcpyDeviceToDevice, st));
     *out = p;
     return MI_OK;
 }
 
 int stage_out(const float *p, const Geo &g, mi_mat *m, hipStream_t st)
 {
-    MI_HIP_TRY(hipMemcpy2DAsync(m->data, m->step, p, (size_t)g.ld * 4, (size_t)g.w * 4, (size_t)g.h, hipMemcpyDeviceToDevice, st));
+    MI_HIP_TRY(hipMemcpy2DAsync(m->data, m->step, p, (size_t)g.ld * 4, (size_t)g.w * 4, (size_t)g.h * g.batch, hipMemcpyDeviceToDevice, st));
     return MI_OK;
 }
 
@@ -196,6 +200,216 @@ int mi_tvl1_iterate(int exact_math, int time_block, int niter, const mi_mat *I1w
         std::vector<unsigned long long> e(niter);
         MI_HIP_TRY(hipMemcpy(e.data(), ctl.E, sizeof(unsigned long long) * niter, hipMemcpyDeviceToHost));
         for (int i = 0; i < niter; ++i) err_host[i] = (double)e[i] / 16777216.0;
+    }
+    return MI_OK;
+}
+
+// The iterations in the forms calc() runs them (c_api.h, mi_tvl1_stage_desc).  Everything the descriptor asks for is checked before
+// the first byte is staged; the launches are those of lane_calc's executors (tvl1_api.cpp run_blocked, run_per_iteration, run_spec) with
+// the streaming kernels forced where a form names them (rows_per_band != 0 in iterate_tb / iterate_tb_spec).
+int mi_tvl1_iterate_stage(const mi_tvl1_stage_desc *d, void *stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    MI_REQUIRE(d, MI_ERR_BAD_ARG, "null descriptor");
+    const int form = d->form, niter = d->niter, B = d->batch;
+    MI_REQUIRE(form >= MI_TVL1_STAGE_ONE && form <= MI_TVL1_STAGE_SPEC_TILE, MI_ERR_BAD_ARG, "unknown form %d", form);
+    MI_REQUIRE(niter >= 1 && niter <= 100000, MI_ERR_BAD_ARG, "niter must be in 1..100000");
+    MI_REQUIRE(B >= 1, MI_ERR_BAD_ARG, "batch must be >= 1");
+    const bool gam = d->gamma != 0.f, ng = d->grad == nullptr, pz = d->p_zero != 0;
+    const bool spec = form == MI_TVL1_STAGE_SPEC || form == MI_TVL1_STAGE_SPEC_TILE;
+    const bool tiles = form == MI_TVL1_STAGE_TILE || form == MI_TVL1_STAGE_SPEC_TILE;
+    const bool streaming = form == MI_TVL1_STAGE_BLOCKED || form == MI_TVL1_STAGE_INDEP || form == MI_TVL1_STAGE_EXACT_BLOCKED ||
+                           form == MI_TVL1_STAGE_SPEC;
+    MI_REQUIRE(d->rows_per_band == 0 || (streaming && d->rows_per_band >= 8), MI_ERR_BAD_ARG,
+               "rows_per_band: 0 (the planner) or >= 8, streaming forms only");
+    MI_REQUIRE(!tiles || (d->variant >= 0 && d->variant < tile_variants() && (!gam || d->variant < 2)), MI_ERR_BAD_ARG,
+               "no register-tile variant %d%s", d->variant, gam ? " with the illumination channel" : "");
+    MI_REQUIRE(!ng || form == MI_TVL1_STAGE_BLOCKED || form == MI_TVL1_STAGE_SPEC || gam, MI_ERR_BAD_ARG,
+               "no |grad|^2 plane: only the blocked and speculative streaming forms form it themselves");
+    MI_REQUIRE(!d->err_fix || form == MI_TVL1_STAGE_ONE || spec, MI_ERR_BAD_ARG, "error sums: one-iteration and speculative forms only");
+    MI_REQUIRE(!(spec && pz), MI_ERR_BAD_ARG, "the speculative steps never take p = 0 (a replay re-reads the input set)");
+    MI_REQUIRE(!(form == MI_TVL1_STAGE_ONE && ng), MI_ERR_BAD_ARG, "the one-iteration kernel needs the |grad|^2 plane");
+    MI_REQUIRE(!(form == MI_TVL1_STAGE_ONE && d->blocks), MI_ERR_BAD_ARG, "blocks: blocked forms only");
+    MI_REQUIRE(!(spec && d->blocks), MI_ERR_BAD_ARG, "the speculative steps run blocks of time_block");
+
+    // the passes: the caller's block list, or greedy blocks of at most time_block over the lengths the form's table holds
+    const int kind = form == MI_TVL1_STAGE_INDEP ? 1 : form == MI_TVL1_STAGE_EXACT_BLOCKED ? 2 : spec ? 3 : 0;
+    auto exists = [&](int T) {
+        if (form == MI_TVL1_STAGE_ONE) return T == 1;
+        if (tiles) return T >= 1 && T <= kTileMaxBlock;
+        return tb_kernel_exists(kind, T, gam, ng);
+    };
+    std::vector<int> blocks;
+    if (form == MI_TVL1_STAGE_ONE) {
+        blocks.assign(niter, 1);
+    } else if (spec) {
+        MI_REQUIRE(exists(d->time_block) && (form != MI_TVL1_STAGE_SPEC || d->time_block <= kTbMaxBlock), MI_ERR_BAD_ARG,
+                   "no speculative kernel for block %d", d->time_block);
+        blocks.assign((size_t)((niter + d->time_block - 1) / d->time_block), d->time_block);
+    } else if (d->blocks) {
+        MI_REQUIRE(d->nblocks >= 1 && d->nblocks <= niter, MI_ERR_BAD_ARG, "nblocks must be in 1..niter");
+        long long sum = 0;
+        for (int k = 0; k < d->nblocks; ++k) {
+            MI_REQUIRE(exists(d->blocks[k]), MI_ERR_BAD_ARG, "no kernel of this form for a block of %d", d->blocks[k]);
+            sum += d->blocks[k];
+            blocks.push_back(d->blocks[k]);
+        }
+        MI_REQUIRE(sum == niter, MI_ERR_BAD_ARG, "the blocks sum to %lld, not niter = %d", sum, niter);
+    } else {
+        const int cap = d->time_block > 0 ? d->time_block : tiles ? kTileMaxBlock : form == MI_TVL1_STAGE_EXACT_BLOCKED ? kTbExactMaxBlock
+                                                                                                                          : kTbMaxBlock;
+        for (int left = niter; left > 0; left -= blocks.back()) {
+            int t = 0;
+            for (int c = std::min(cap, left); c >= 1 && !t; --c) if (exists(c)) t = c;
+            MI_REQUIRE(t, MI_ERR_BAD_ARG, "no kernel of this form for blocks of at most %d", cap);
+            blocks.push_back(t);
+        }
+    }
+
+    // the planes: h rows per pair
+    MI_REQUIRE(d->I1wx && d->I1wy && d->rho_c && d->u_in && d->u_out && d->p_out && (d->p_in || pz), MI_ERR_BAD_ARG, "null plane");
+    TRY(check_f32(d->I1wx, "I1wx"));
+    MI_REQUIRE(d->I1wx->rows % B == 0, MI_ERR_BAD_SIZE, "rows (%d) must be batch (%d) x the pair height", d->I1wx->rows, B);
+    const int nu = gam ? 3 : 2, np = gam ? 6 : 4;
+    std::vector<const mi_mat *> ins = {d->I1wx, d->I1wy, d->rho_c};
+    if (!ng) ins.push_back(d->grad);
+    for (int i = 0; i < nu; ++i) ins.push_back(&d->u_in[i]);
+    if (!pz) for (int i = 0; i < np; ++i) ins.push_back(&d->p_in[i]);
+    std::vector<const mi_mat *> all = ins;
+    for (int i = 0; i < nu; ++i) all.push_back(&d->u_out[i]);
+    for (int i = 0; i < np; ++i) all.push_back(&d->p_out[i]);
+    for (const mi_mat *m : all) {
+        TRY(check_f32(m, "plane"));
+        MI_REQUIRE(m->rows == d->I1wx->rows && m->cols == d->I1wx->cols, MI_ERR_BAD_SIZE, "plane size mismatch");
+    }
+    Geo g = geo_of(d->I1wx->cols, d->I1wx->rows / B);
+    g.batch = B;
+
+    Stage S;
+    IterPlanes pl;
+    memset(&pl, 0, sizeof(pl));
+    float *stat[4] = {nullptr, nullptr, nullptr, nullptr};
+    const mi_mat *statm[4] = {d->I1wx, d->I1wy, d->grad, d->rho_c};
+    for (int i = 0; i < 4; ++i) if (statm[i]) TRY(stage_in(S, statm[i], g, &stat[i], st));
+    pl.ix = stat[0]; pl.iy = stat[1]; pl.g = stat[2]; pl.rc = stat[3];
+    pl.gamma = d->gamma;
+    pl.err_u3 = d->err_u3 ? 1 : 0;
+    for (int i = 0; i < nu; ++i) {
+        TRY(stage_in(S, &d->u_in[i], g, &pl.u[0][i], st));
+        pl.u[1][i] = S.alloc(g);
+        MI_REQUIRE(pl.u[1][i], MI_ERR_OOM, "stage allocation failed");
+    }
+    for (int i = 0; i < np; ++i) {
+        if (pz) {   // never read: NaN, so that a kernel reading them shows
+            pl.p[0][i] = S.alloc(g);
+            MI_REQUIRE(pl.p[0][i], MI_ERR_OOM, "stage allocation failed");
+            MI_HIP_TRY(hipMemsetAsync(pl.p[0][i], 0xff, sizeof(float) * (size_t)g.ps * B, st));
+        } else {
+            TRY(stage_in(S, &d->p_in[i], g, &pl.p[0][i], st));
+        }
+        pl.p[1][i] = S.alloc(g);
+        MI_REQUIRE(pl.p[1][i], MI_ERR_OOM, "stage allocation failed");
+    }
+
+    // control slots: the checked one-iteration launches use slot `it` and error sum `it`; the speculative steps slot k and the error
+    // sums of the blocks from e0 = k * T on (a block runs all its T iterations but the last, which runs what is left)
+    const int nb = (int)blocks.size();
+    const bool check = form == MI_TVL1_STAGE_ONE && d->err_fix;
+    Ctl ctl;
+    memset(&ctl, 0, sizeof(ctl));
+    if (check || spec) {
+        const long long Q = spec ? (long long)(nb + 1) * d->time_block + nb + 2 : niter;
+        const size_t n = (size_t)Q * B;
+        ctl.S = (int2 *)S.alloc_bytes(sizeof(int2) * n);
+        ctl.E = (unsigned long long *)S.alloc_bytes(sizeof(unsigned long long) * n);
+        ctl.P = (double *)S.alloc_bytes(sizeof(double) * n);
+        MI_REQUIRE(ctl.S && ctl.E && ctl.P, MI_ERR_OOM, "stage allocation failed");
+        MI_HIP_TRY(hipMemsetAsync(ctl.S, 0, sizeof(int2) * n, st));
+        MI_HIP_TRY(hipMemsetAsync(ctl.E, 0, sizeof(unsigned long long) * n, st));
+        MI_HIP_TRY(hipMemsetAsync(ctl.P, 0, sizeof(double) * n, st));
+        ctl.Q = (int)Q;
+        ctl.thr = -1.0;   // the CPU class's rule, a threshold no iteration passes: every launch active, no block cut short
+    }
+    std::vector<int> cur_b(B, 0);   // per pair: the set the result is in
+    if (spec) {
+        // run_spec (tvl1_api.cpp) without history and host feedback: blocks of T, then the launch that settles the last of them
+        int4 *X = (int4 *)S.alloc_bytes(sizeof(int4) * (size_t)ctl.Q * B);
+        MI_REQUIRE(X, MI_ERR_OOM, "stage allocation failed");
+        MI_HIP_TRY(hipMemsetAsync(X, 0, sizeof(int4) * (size_t)ctl.Q * B, st));
+        SpecK sk;
+        memset(&sk, 0, sizeof(sk));
+        sk.X = X; sk.iters = niter; sk.q_hist = -1; sk.hist_num = 1; sk.hist_den = 1;
+        const int T = d->time_block;
+        int t_after = nb * T, e_next = 0, e_prev = 0;
+        for (int k = 0; k <= nb; ++k) {
+            const bool last = k == nb;
+            if (!last) t_after -= T;
+            Ctl a = ctl;
+            a.q = k; a.q_prev = k - 1; a.first_of_warp = (k == 0); a.reset_cur = (k == 0); a.n = 0;
+            sk.e0_prev = e_prev; sk.final_launch = last ? 1 : 0; sk.t_after = t_after;
+            TRY(tiles ? iterate_tile_spec(T, pl, g, d->l_t, d->theta, d->taut, a, sk, e_next, st, d->variant)
+                      : iterate_tb_spec(T, pl, g, d->l_t, d->theta, d->taut, false, a, sk, e_next, st, d->rows_per_band > 0 ? d->rows_per_band : -1));
+            e_prev = e_next;
+            if (!last) e_next += T;
+        }
+        std::vector<int2> sl(B);
+        MI_HIP_TRY(hipMemcpy2DAsync(sl.data(), sizeof(int2), ctl.S + nb, sizeof(int2) * (size_t)ctl.Q, sizeof(int2), (size_t)B,
+                                    hipMemcpyDeviceToHost, st));
+        MI_HIP_TRY(hipStreamSynchronize(st));
+        for (int b = 0; b < B; ++b) {
+            cur_b[b] = sl[b].x ^ (sl[b].y & MI_SLOT_FLIP);
+            MI_REQUIRE((sl[b].y & MI_SLOT_DONE) && MI_SLOT_ITERS(sl[b].y) == niter - (nb - 1) * T, MI_ERR_HIP,
+                       "speculative steps: pair %d settled as {%d, %#x}, not done after %d iterations", b, sl[b].x, sl[b].y, niter);
+        }
+    } else {
+        int cur = 0;
+        for (int k = 0; k < nb; ++k) {
+            const int T = blocks[k];
+            const bool pzk = pz && k == 0;
+            const int rows = d->rows_per_band > 0 ? d->rows_per_band : -1;
+            switch (form) {
+            case MI_TVL1_STAGE_ONE:
+                if (check) {
+                    Ctl c = ctl;
+                    c.q = k; c.q_prev = k - 1; c.first_of_warp = (k == 0); c.reset_cur = (k == 0);
+                    TRY(iterate(d->exact_math != 0, pl, g, d->l_t, d->theta, d->taut, pzk, &c, 0, st));
+                } else {
+                    TRY(iterate(d->exact_math != 0, pl, g, d->l_t, d->theta, d->taut, pzk, nullptr, cur, st));
+                }
+                break;
+            case MI_TVL1_STAGE_BLOCKED:
+            case MI_TVL1_STAGE_INDEP:
+                TRY(iterate_tb(T, pl, g, d->l_t, d->theta, d->taut, pzk, cur, rows, st, false, form == MI_TVL1_STAGE_INDEP));
+                break;
+            case MI_TVL1_STAGE_TILE:
+                TRY(iterate_tile(d->variant, T, pl, g, d->l_t, d->theta, d->taut, pzk, cur, st));
+                break;
+            case MI_TVL1_STAGE_EXACT_BLOCKED:
+                TRY(iterate_tb_exact(T, pl, g, d->l_t, d->theta, d->taut, pzk, cur, st, d->rows_per_band));
+                break;
+            }
+            cur ^= 1;
+        }
+        std::fill(cur_b.begin(), cur_b.end(), cur);
+    }
+
+    // the result planes, per pair from the set it ended in
+    for (int b = 0; b < B; ++b) {
+        Geo g1 = g;
+        g1.batch = 1;
+        const long long o = (long long)b * g.ps;
+        for (int i = 0; i < nu + np; ++i) {
+            const float *src = (i < nu ? pl.u[cur_b[b]][i] : pl.p[cur_b[b]][i - nu]) + o;
+            mi_mat m = i < nu ? d->u_out[i] : d->p_out[i - nu];
+            m.data = (char *)m.data + (size_t)b * g.h * m.step;
+            m.rows = g.h;
+            TRY(stage_out(src, g1, &m, st));
+        }
+    }
+    MI_HIP_TRY(hipStreamSynchronize(st));
+    if (d->err_fix) {
+        MI_HIP_TRY(hipMemcpy2D(d->err_fix, sizeof(unsigned long long) * niter, ctl.E, sizeof(unsigned long long) * (size_t)ctl.Q,
+                               sizeof(unsigned long long) * niter, (size_t)B, hipMemcpyDeviceToHost));
     }
     return MI_OK;
 }

@@ -1316,7 +1316,10 @@ int iterate_tb(int T, const IterPlanes &pl, const Geo &g, float l_t, float theta
     }
     if (!e) { set_error("unsupported time block %d", T); return MI_ERR_BAD_ARG; }
     if (!pl.g) {
-        MI_REQUIRE(tb_nograd_ok(T, g, tv_knobs()), MI_ERR_BAD_ARG, "no |grad|^2 plane, but the kernel of this launch needs one");
+        // (tb_nograd_ok's other conditions are the plan's choice of kernel; where the caller forces the streaming kernel, the stage-level
+        // entry, the NG kernel runs at any geometry)
+        MI_REQUIRE(!independent_waves && (rows_per_band != 0 ? T == 10 : tb_nograd_ok(T, g, tv_knobs())), MI_ERR_BAD_ARG,
+                   "no |grad|^2 plane, but the kernel of this launch needs one");
 #ifdef MIFLOW_EXPERIMENTS
         e = tuning().tb_p16 ? &g_tbr_ng16 : &g_tbr_ng;
 #else
@@ -1337,7 +1340,8 @@ int iterate_tb(int T, const IterPlanes &pl, const Geo &g, float l_t, float theta
 }
 
 // T fused EXACT iterations, set cur -> cur^1 (bit-identical to T launches of the one-iteration exact kernel).  T in 1..5.
-int iterate_tb_exact(int T, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut, bool p_zero, int cur, hipStream_t s)
+int iterate_tb_exact(int T, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut, bool p_zero, int cur, hipStream_t s,
+                     int rows_per_band)
 {
     const TbrEntry *e = nullptr;
     for (const TbrEntry &c : g_exact) if (c.T == T) e = &c;
@@ -1345,24 +1349,47 @@ int iterate_tb_exact(int T, const IterPlanes &pl, const Geo &g, float l_t, float
     TbArgs A;
     memset(&A, 0, sizeof(A));
     A.pl = pl; A.g = g; A.l_t = l_t; A.theta = theta; A.taut = taut; A.cur = cur;
-    A.rows_per_band = plan_band_rows(*e, g);
+    A.rows_per_band = rows_per_band > 0 ? rows_per_band : plan_band_rows(*e, g);
     return e->launch(A, p_zero, s);
+}
+
+bool tb_kernel_exists(int kind, int T, bool gam, bool nograd)
+{
+    auto in = [T](const TbrEntry *t, size_t n, bool spec) {
+        for (size_t i = 0; i < n; ++i) if (t[i].T == T && (spec ? t[i].spec : t[i].launch)) return true;
+        return false;
+    };
+#define TB_IN(tab, spec) in(tab, sizeof(tab) / sizeof(tab[0]), spec)
+    switch (kind) {
+    case 0: return gam ? TB_IN(g_tbr_gam, false) : nograd ? T == g_tbr_ng.T : tbr_pick(T) != nullptr;
+    case 1: {
+        if (nograd) return false;
+        if (!gam) return TB_IN(g_tbr, false);
+        for (const TbrEntry &c : g_tbr_gam) if (c.T == T && c.JW == 0) return true;
+        return false;
+    }
+    case 2: return !gam && !nograd && TB_IN(g_exact, false);
+    case 3: return gam ? TB_IN(g_spec_gam, true) : TB_IN(g_spec_jw_ng, true);
+    }
+#undef TB_IN
+    return false;
 }
 
 // One speculative step with kernel block size T (see k_iterate_tbr MODE 1); ctl carries the slot protocol, sk the step's
 // constants, e0 the index of the first per-iteration error sum this launch may write.
 int iterate_tb_spec(int T, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut, bool p_zero, const Ctl &ctl,
-                    const SpecK &sk, int e0, hipStream_t s)
+                    const SpecK &sk, int e0, hipStream_t s, int rows_per_band)
 {
     // small levels: the same step on register tiles (serial depth of a launch = its iterations, not the image height); integer
     // error sums and identical per-pixel arithmetic => the same decisions and the same flows as the streaming kernel
-    if (runs_on_tiles(g, T, tv_knobs(), true) && !p_zero)
+    if (rows_per_band == 0 && runs_on_tiles(g, T, tv_knobs(), true) && !p_zero)
         return iterate_tile_spec(T, pl, g, l_t, theta, taut, ctl, sk, e0, s);
     const TbrEntry *e = nullptr;
     if (pl.gamma != 0.f) {
         for (const TbrEntry &c : g_spec_gam) if (c.T == T) e = &c;
     } else if (!pl.g) {
-        MI_REQUIRE(tb_spec_nograd_ok(g, tv_knobs()), MI_ERR_BAD_ARG, "no |grad|^2 plane, but the speculative kernel of this launch needs one");
+        MI_REQUIRE(rows_per_band != 0 || tb_spec_nograd_ok(g, tv_knobs()), MI_ERR_BAD_ARG,
+                   "no |grad|^2 plane, but the speculative kernel of this launch needs one");
         for (const TbrEntry &c : g_spec_jw_ng) if (c.T == T) e = &c;
     }
 #ifdef MIFLOW_EXPERIMENTS
@@ -1374,7 +1401,7 @@ int iterate_tb_spec(int T, const IterPlanes &pl, const Geo &g, float l_t, float 
     if (!e) { set_error("no speculative kernel for time block %d", T); return MI_ERR_BAD_ARG; }
     TbArgs A;
     A.pl = pl; A.g = g; A.l_t = l_t; A.theta = theta; A.taut = taut; A.cur = 0; A.swz = 0; A.nstrips = 0; A.skip_p_out = 0;
-    A.rows_per_band = plan_band_rows(*e, g);
+    A.rows_per_band = rows_per_band > 0 ? rows_per_band : plan_band_rows(*e, g);
     A.ctl = make_ctlk(&ctl);
     A.e0 = e0;
     A.sk = sk;

@@ -326,10 +326,11 @@ int iterate_tile(int variant, int nit, const IterPlanes &pl, const Geo &g, float
 
 // One speculative step on register tiles (see iterate_tb_spec): T = the most iterations the launch may run (1..10).
 int iterate_tile_spec(int T, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut, const Ctl &ctl, const SpecK &sk, int e0,
-                      hipStream_t s)
+                      hipStream_t s, int variant)
 {
     if (T < 1 || T > TILE_M) { set_error("register-tile kernel: block of %d iterations (1..%d)", T, TILE_M); return MI_ERR_BAD_ARG; }
-    const int variant = tile_auto_variant(g, true, tv_knobs());
+    if (variant < 0) variant = tile_auto_variant(g, true, tv_knobs());
+    if (variant >= kTileVariants) { set_error("register-tile kernel: no variant %d", variant); return MI_ERR_BAD_ARG; }
     TileArgs A;
     memset(&A, 0, sizeof(A));
     A.pl = pl; A.g = g; A.l_t = l_t; A.theta = theta; A.taut = taut; A.cur = 0; A.nit = T; A.swz = tuning().tile_swz;

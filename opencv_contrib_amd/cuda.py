@@ -241,6 +241,48 @@ def tvl1_iterate(I1wx, I1wy, grad, rho_c, u, p, l_t, theta, taut, niter=1, exact
     return u_out, p_out, list(err)
 
 
+_STAGE_FORMS = {"one": capi.MI_TVL1_STAGE_ONE, "blocked": capi.MI_TVL1_STAGE_BLOCKED, "indep": capi.MI_TVL1_STAGE_INDEP,
+                "tile": capi.MI_TVL1_STAGE_TILE, "exact_blocked": capi.MI_TVL1_STAGE_EXACT_BLOCKED, "spec": capi.MI_TVL1_STAGE_SPEC,
+                "spec_tile": capi.MI_TVL1_STAGE_SPEC_TILE}
+
+
+def tvl1_iterate_stage(form, I1wx, I1wy, grad, rho_c, u, p, l_t, theta, taut, niter=1, *, exact=False, time_block=0, blocks=None,
+                       rows_per_band=0, variant=0, p_zero=False, gamma=0.0, err_u3=0, want_err=False):
+    """The iterations in one of the forms calc() runs them (mi_tvl1_iterate_stage).  form: 'one' | 'blocked' | 'indep' | 'tile' |
+    'exact_blocked' | 'spec' | 'spec_tile'.  Planes are (h, w) or (B, h, w) float32 CUDA tensors (B pairs in one launch); grad may
+    be None (the pass forms |grad|^2); u = [u1, u2(, u3)], p = [p11, p12, p21, p22(, p31, p32)] (p may be None with p_zero).
+    Returns (u_out, p_out, err) -- err: per pair the per-iteration error sums as 2^-24 fixed-point ints (want_err), else None."""
+    import torch
+    B = I1wx.shape[0] if I1wx.dim() == 3 else 1
+    flat = lambda t: t.reshape(-1, t.shape[-1]) if t is not None else None   # (B, h, w) -> (B*h, w): the pairs stacked
+    gam = gamma != 0.0
+    nu, np_ = (3, 6) if gam else (2, 4)
+    u_out = [torch.empty_like(t) for t in u[:nu]]
+    p_out = [torch.empty_like(u[0]) for _ in range(np_)]
+    ms = lambda ts, n: (capi.Mat * 6)(*[_m(flat(t)) for t in ts[:n]])
+    U, UO, PO = ms(u, nu), ms(u_out, nu), ms(p_out, np_)
+    P = ms(p, np_) if p is not None else None
+    stat = [_m(flat(t)) if t is not None else None for t in (I1wx, I1wy, grad, rho_c)]
+    d = capi.TVL1StageDesc()
+    d.form, d.exact_math, d.niter, d.time_block = _STAGE_FORMS[form], int(exact), niter, time_block
+    blk = (C.c_int * len(blocks))(*blocks) if blocks else None
+    if blk is not None:
+        d.blocks, d.nblocks = C.cast(blk, C.POINTER(C.c_int)), len(blocks)
+    d.rows_per_band, d.variant, d.p_zero, d.batch = rows_per_band, variant, int(bool(p_zero)), B
+    d.l_t, d.theta, d.taut, d.gamma, d.err_u3 = l_t, theta, taut, gamma, int(err_u3)
+    ref = lambda m: C.pointer(m) if m is not None else None
+    d.I1wx, d.I1wy, d.grad, d.rho_c = (ref(m) for m in stat)
+    d.u_in, d.u_out, d.p_out = C.cast(U, C.POINTER(capi.Mat)), C.cast(UO, C.POINTER(capi.Mat)), C.cast(PO, C.POINTER(capi.Mat))
+    d.p_in = C.cast(P, C.POINTER(capi.Mat)) if P is not None else None
+    err = (C.c_ulonglong * (niter * B))() if want_err else None
+    if err is not None:
+        d.err_fix = C.cast(err, C.POINTER(C.c_ulonglong))
+    capi.check(capi.lib().mi_tvl1_iterate_stage(C.byref(d), capi.current_stream_ptr()))
+    torch.cuda.synchronize()
+    errs = [[int(v) for v in err[b * niter:(b + 1) * niter]] for b in range(B)] if want_err else None
+    return u_out, p_out, errs
+
+
 def resize_linear(src, dsize=None, fx=0.0, fy=0.0, semantics=capi.MI_SEM_CPU_REF, post_scale=1.0):
     """cv::resize / cv::cuda::resize (INTER_LINEAR, CV_32FC1).  dsize = (width, height)."""
     import torch

@@ -84,6 +84,8 @@ def lib():
         L.orc_tvl1_warp.argtypes = [C.c_int] + [_f32p] * 6 + [C.c_int, C.c_int] + [_f32p] * 5
         L.orc_tvl1_proc_one_scale.argtypes = [C.POINTER(TVL1Params), _f32p, _f32p, _f32p, _f32p, C.c_void_p, C.c_int, C.c_int,
                                               C.c_void_p]
+        L.orc_tvl1_err_fix.restype = C.c_ulonglong
+        L.orc_tvl1_err_fix.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]
         L.orc_tvl1_iteration.restype = C.c_float
         L.orc_tvl1_iteration.argtypes = [C.c_int] + [_f32p] * 4 + [C.c_void_p] * 9 + [C.c_int, C.c_int] + [C.c_float] * 4
         _bind_stereobm(L)
@@ -284,6 +286,20 @@ def tvl1_iteration(semantics, I1wx, I1wy, grad, rho_c, u1, u2, p11, p12, p21, p2
     if u3 is not None:
         out = out + (u3c, p3[0], p3[1])
     return out
+
+
+def tvl1_err_fix(u_prev, u_next, eu3=0):
+    """The device's convergence error of one iteration, u_prev -> u_next ([u1, u2] or [u1, u2, u3]), as the exact sum of the per-pixel
+    terms round-half-even(et * 2^24), each saturated to 2^32 - 1 (int).  et = fmaf(e1, e1, e2*e2) (+ e3*e3 where eu3)."""
+    if eu3 and (len(u_prev) < 3 or len(u_next) < 3):
+        raise ValueError("eu3 needs u3 in both lists")
+    pv = [_c(a) for a in u_prev]
+    nx = [_c(a) for a in u_next]
+    h, w = pv[0].shape
+    if any(a.shape != (h, w) for a in pv + nx):
+        raise ValueError("plane shapes differ")
+    arr = lambda planes: (C.c_void_p * 3)(*([a.ctypes.data for a in planes[:3]] + [None] * (3 - len(planes[:3]))))
+    return int(lib().orc_tvl1_err_fix(arr(pv), arr(nx), w, h, int(bool(eu3))))
 
 
 def tvl1_proc_one_scale(I0, I1, u1, u2, params: TVL1Params):

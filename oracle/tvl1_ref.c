@@ -305,6 +305,34 @@ static void proc_one_scale(const orc_tvl1_params *P, const level_t *L, int *iter
     free(p11); free(p12); free(p21); free(p22); free(p31); free(p32); free(tmp);
 }
 
+/* v_cvt_u32_f32 of et * 2^24 (tvl1_tbr_kernels.hip stage_r, tvl1_tile_kernels.hip): the product is exact (a power of two; inf past
+ * the float range), the conversion rounds to nearest even and saturates */
+static unsigned long long err_term_fix(float et)
+{
+    const float v = et * 16777216.0f;
+    if (!(v > 0.f)) return 0ull;                  /* 0, negative zero, NaN */
+    if (v >= 4294967296.0f) return 4294967295ull;  /* saturated: a term >= 256 px^2 */
+    return (unsigned long long)rintf(v);           /* default rounding mode: to nearest, ties to even */
+}
+
+unsigned long long orc_tvl1_err_fix(const float *const *u_prev, const float *const *u_next, int w, int h, int eu3)
+{
+    const size_t n = (size_t)w * h;
+    unsigned long long sum = 0;
+#pragma omp parallel for schedule(static) reduction(+ : sum)
+    for (long long i = 0; i < (long long)n; ++i) {
+        const float e1 = u_next[0][i] - u_prev[0][i], e2 = u_next[1][i] - u_prev[1][i];
+        float et = fmaf(e1, e1, e2 * e2);     /* libm's fmaf: one rounding */
+        if (eu3) {
+            const float e3 = u_next[2][i] - u_prev[2][i];
+            const float e3sq = e3 * e3;
+            et = et + e3sq;
+        }
+        sum += err_term_fix(et);
+    }
+    return sum;
+}
+
 void orc_tvl1_proc_one_scale(const orc_tvl1_params *P, const float *I0, const float *I1, float *u1, float *u2,
                              float *u3, int w, int h, int *iters_out)
 {

@@ -55,6 +55,12 @@ float orc_tvl1_iteration(int semantics, const float *I1wx, const float *I1wy, co
                          float *p12, float *p21, float *p22, float *p31, float *p32, int w, int h,
                          float l_t, float theta, float taut, float gamma);
 
+/* The device's convergence error of one iteration as a 2^-24 fixed-point integer sum (the speculative steps' accounting): per pixel
+ * et = fmaf(e1, e1, e2 * e2), plus (e3 * e3) * 1 as a separately rounded float where eu3 != 0, e_k = u_next[k] - u_prev[k];
+ * quantised as round-half-even(et * 2^24) saturated to 2^32 - 1 (and NaN to 0), summed exactly.  u_prev[2] / u_next[2] (u3) may be
+ * NULL when eu3 == 0. */
+unsigned long long orc_tvl1_err_fix(const float *const *u_prev, const float *const *u_next, int w, int h, int eu3);
+
 /* one pyramid level: gradient, `warps` x (warp + iteration loop with the class's convergence rule), in place on
  * u1, u2 (u3 when gamma != 0).  iters_out[warp] = executed inner iterations (may be NULL). */
 void orc_tvl1_proc_one_scale(const orc_tvl1_params *p, const float *I0, const float *I1, float *u1, float *u2,

@@ -168,3 +168,68 @@ def test_bench_cpu_baseline_protocol_and_distinct_inputs(oracle):
     assert cb["one_core"] and cb["one_core"]["cores"] == 1
     assert len(calls) >= 1 + 1 + nrep + 1               # sweep, warm-up, repetitions, one core
     np.testing.assert_array_equal(cb["ref0"], oracle.tvl1_calc(base[0][0], base[0][1], p))   # the thread count never changes a flow
+
+
+# ---------------------------------------------------------------- the device's fixed-point convergence error (tvl1_err_fix)
+def _err_planes(e1, e2, e3=None, base=0.0):
+    """u_prev = base, u_next = base + e per pixel (the differences are exact for the values used below)."""
+    f = lambda v: np.asarray(v, np.float32).reshape(1, -1)
+    prev = [np.full_like(f(e1), base) for _ in range(3 if e3 is not None else 2)]
+    nxt = [prev[0] + f(e1), prev[1] + f(e2)] + ([prev[2] + f(e3)] if e3 is not None else [])
+    for p, n, e in zip(prev, nxt, (e1, e2, e3)):
+        assert np.array_equal(n - p, f(e)), "inexact difference"
+    return prev, nxt
+
+
+def test_err_fix_rounds_ties_to_even(oracle):
+    # e1 = a 2^-13, e2 = b 2^-13 (a, b odd): et 2^24 = (a^2 + b^2) / 4 = k + 0.5 exactly -> the even neighbour
+    for a, b, want in ((1, 1, 0), (1, 3, 2), (3, 3, 4), (1, 5, 6), (3, 5, 8), (1, 7, 12)):
+        prev, nxt = _err_planes([a * 2.0 ** -13], [b * 2.0 ** -13], base=1.0)
+        assert oracle.tvl1_err_fix(prev, nxt) == want, (a, b)
+    # ... and upwards: 0.5 + c^2 from e3 = c 2^-12 (eu3 = 1): 1.5 -> 2, 4.5 -> 4, 9.5 -> 10
+    for c, want in ((1, 2), (2, 4), (3, 10)):
+        prev, nxt = _err_planes([2.0 ** -13], [2.0 ** -13], [c * 2.0 ** -12])
+        assert oracle.tvl1_err_fix(prev, nxt, eu3=1) == want, c
+    # a sum is the sum of the rounded terms, not the rounded sum: four ties of 0.5 -> 0, not 2
+    prev, nxt = _err_planes([2.0 ** -13] * 4, [2.0 ** -13] * 4)
+    assert oracle.tvl1_err_fix(prev, nxt) == 0
+
+
+def test_err_fix_saturates_each_term_and_sums_in_64_bits(oracle):
+    sat = 2 ** 32 - 1
+    # et = 256 px^2 is 2^32 in fixed point: saturated; 15.5^2 = 240.25 is not; an overflowing square (inf) saturates
+    prev, nxt = _err_planes([16.0, 15.5, 1e20, 0.0], [0.0, 0.0, 0.0, 300.0])
+    terms = [sat, int(240.25 * 2 ** 24), sat, sat]
+    assert oracle.tvl1_err_fix(prev, nxt) == sum(terms) and sum(terms) > 2 ** 32
+    # one pixel at a time: every saturated term counts 2^32 - 1, never more
+    for k in range(4):
+        p1, n1 = _err_planes([[16.0, 15.5, 1e20, 0.0][k]], [[0.0, 0.0, 0.0, 300.0][k]])
+        assert oracle.tvl1_err_fix(p1, n1) == terms[k]
+
+
+def test_err_fix_u3_term_only_with_eu3(oracle):
+    prev, nxt = _err_planes([0.0, 2.0 ** -12], [0.0, 0.0], [2.0 ** -12, 3 * 2.0 ** -12])
+    assert oracle.tvl1_err_fix(prev, nxt, eu3=0) == 1
+    assert oracle.tvl1_err_fix(prev, nxt, eu3=1) == 1 + (1 + 9)
+    assert oracle.tvl1_err_fix(prev[:2], nxt[:2]) == 1
+    with pytest.raises(ValueError):
+        oracle.tvl1_err_fix(prev[:2], nxt[:2], eu3=1)
+    # (e1^2 + e2^2) is rounded once (fmaf), then e3^2 added as a separately rounded float: 1 + 2^-24 ties to 1 both times, where the
+    # three squares rounded once would give 1 + 2^-23 (2^24 + 2 in fixed point) -- the order decides
+    prev, nxt = _err_planes([1.0], [2.0 ** -12], [2.0 ** -12])
+    assert oracle.tvl1_err_fix(prev, nxt, eu3=1) == 2 ** 24
+    assert int(np.rint((1.0 + 2.0 ** -24 + 2.0 ** -24) * 2 ** 24)) == 2 ** 24 + 2
+    assert oracle.tvl1_err_fix(prev[:2], nxt[:2]) == 2 ** 24
+
+
+def test_err_fix_uses_a_correctly_rounded_fma(oracle):
+    """e1 = 4097 2^-12: e1^2 2^24 = 16785409 = 2^24 + 2^13 + 1, the midpoint between two floats; e2 = 2^-30 adds 2^-36 to it.  fmaf
+    rounds the exact sum once (upwards, 16785410); a float64 shortcut either keeps the midpoint (16785409) or, rounding it to float
+    afterwards, breaks the tie to even (16785408).  Only the first is what the device computes."""
+    e1, e2 = np.float32(4097 * 2.0 ** -12), np.float32(2.0 ** -30)
+    prev, nxt = _err_planes([e1], [e2])
+    assert oracle.tvl1_err_fix(prev, nxt) == 16785410
+    et64 = float(e1) * float(e1) + float(e2) * float(e2)
+    assert int(np.rint(et64 * 2 ** 24)) == 16785409                       # float64 throughout
+    assert int(np.rint(np.float32(et64) * np.float32(2 ** 24))) == 16785408   # float64 fma, rounded to float (double rounding)
+    assert int(np.rint((e1 * e1 + e2 * e2) * np.float32(2 ** 24))) == 16785408   # two float roundings, no fma
