@@ -563,6 +563,54 @@ MI_API int mi_superres_to_gray8(const mi_mat *src, mi_mat *dst, void *stream);
  * flow: MI_32FC2; u, v: MI_32FC1 of the same size. */
 MI_API int mi_split_flow(const mi_mat *flow, mi_mat *u, mi_mat *v, void *stream);
 
+/* ================================================= BTV-L1 super-resolution ===== */
+
+/* The numeric parameters of cv::superres::SuperResolution as BTVL1_CUDA_Base holds them (superres/src/btv_l1_cuda.cpp:241-249;
+ * temporalAreaRadius belongs to the frame ring around process(), i.e. to the caller). */
+typedef struct mi_btvl1_params {
+    int scale;             /* 4 */
+    int iterations;        /* 180 */
+    double tau;            /* 1.3 */
+    double lambda;         /* 0.03 */
+    double alpha;          /* 0.7 */
+    int btv_kernel_size;   /* 7 */
+    int blur_kernel_size;  /* 5 */
+    double blur_sigma;     /* 0.0 */
+} mi_btvl1_params;
+
+typedef struct mi_btvl1 mi_btvl1;
+
+/* Replaces: BTVL1_CUDA_Base::BTVL1_CUDA_Base (the defaults), btv_l1_cuda.cpp:280-289 */
+MI_API void mi_btvl1_default_params(mi_btvl1_params *p);
+/* Replaces: cv::superres::createSuperResolution_BTVL1_CUDA (the process() half of the object), btv_l1_cuda.cpp:585-588 */
+MI_API int mi_btvl1_create(const mi_btvl1_params *p, mi_btvl1 **out);
+MI_API int mi_btvl1_set_params(mi_btvl1 *h, const mi_btvl1_params *p);
+MI_API int mi_btvl1_get_params(const mi_btvl1 *h, mi_btvl1_params *p);
+/* Replaces: BTVL1_CUDA_Base::process, btv_l1_cuda.cpp:306-400 (with calcRelativeMotions, upscaleMotions, buildMotionMaps, upscale,
+ * diffSign, calcBtvWeights, calcBtvRegularization :80-207 and the kernels of cuda/btv_l1_gpu.cu).
+ * frames[n]: MI_32FC1 / MI_32FC3 / MI_32FC4 of one size; fwd_x / fwd_y / bwd_x / bwd_y[n]: MI_32FC1 planes of that size with the
+ * reference's convention: fwd[i] (the motion from frame i to frame i + 1) is read for i < n - 1 and bwd[i] (from frame i to frame
+ * i - 1) for i > 0; the other entries are ignored and the four arrays may be NULL when n == 1.  dst: the type of the frames,
+ * (rows scale - 2 btv_kernel_size) x (cols scale - 2 btv_kernel_size).  Parameters are checked as the reference asserts them
+ * (scale > 1, iterations > 0, tau > 0, alpha > 0, btv_kernel_size 1 .. 16, blur_kernel_size odd 1 .. 31, blur_sigma >= 0).
+ * Stream-ordered: three set-up launches, then two launches per iteration whatever n is, no host wait in between. */
+MI_API int mi_btvl1_process(mi_btvl1 *h, int n, const mi_mat *frames, const mi_mat *fwd_x, const mi_mat *fwd_y, const mi_mat *bwd_x,
+                            const mi_mat *bwd_y, int base_idx, mi_mat *dst, void *stream);
+/* Device time (events around the launches) and number of kernel launches of the handle's last process; waits for that process. */
+MI_API int mi_btvl1_get_profile(mi_btvl1 *h, double *ms, long long *launches);
+/* Stage hook (tests): everything process() does before its first iteration.  maps[4 n]: MI_32FC1 high-res planes forwardMap x,
+ * forwardMap y, backwardMap x, backwardMap y of frame 0, then of frame 1, ... (btv_l1_cuda.cpp:339-347); initial: the initial
+ * estimate (:354), high-res, the type of the frames; taps_host[32] / weights_host[256]: the blur taps and the BTV weights the
+ * handle passes to its kernels (host memory, unused entries 0).  Synchronises `stream`. */
+MI_API int mi_btvl1_stage(mi_btvl1 *h, int n, const mi_mat *frames, const mi_mat *fwd_x, const mi_mat *fwd_y, const mi_mat *bwd_x,
+                          const mi_mat *bwd_y, int base_idx, mi_mat *maps, mi_mat *initial, float *taps_host, float *weights_host,
+                          void *stream);
+MI_API void mi_btvl1_destroy(mi_btvl1 *h);
+/* Replaces: GpuMat::convertTo(CV_32F) of an incoming frame / convertTo(CV_8U) of a stored output in BTVL1_CUDA, btv_l1_cuda.cpp:524,540,
+ * and curFrame_.copyTo(prevFrame_) (:551) where both depths are equal.  src, dst: CV_8U or CV_32F, 1 / 3 / 4 channels, the same
+ * channels and size; 32F -> 8U is saturate_cast (round to nearest even, clamp). */
+MI_API int mi_btvl1_convert(const mi_mat *src, mi_mat *dst, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -87,6 +87,11 @@ class StereoBMParams(C.Structure):
                 ("uniqueness_ratio", C.c_int), ("emulate_cuda_edge", C.c_int)]
 
 
+class BTVL1Params(C.Structure):
+    _fields_ = [("scale", C.c_int), ("iterations", C.c_int), ("tau", C.c_double), ("lambda_", C.c_double), ("alpha", C.c_double),
+                ("btv_kernel_size", C.c_int), ("blur_kernel_size", C.c_int), ("blur_sigma", C.c_double)]
+
+
 _lib = None
 
 
@@ -232,6 +237,16 @@ def lib():
         "mi_bf_radius_match": (i, [vp, PM, PM, PM, i, C.c_float, PM, PM, PM, PM, vp]),
         "mi_superres_to_gray8": (i, [PM, PM, vp]),
         "mi_split_flow": (i, [PM, PM, PM, vp]),
+        "mi_btvl1_default_params": (None, [C.POINTER(BTVL1Params)]),
+        "mi_btvl1_create": (i, [C.POINTER(BTVL1Params), C.POINTER(vp)]),
+        "mi_btvl1_set_params": (i, [vp, C.POINTER(BTVL1Params)]),
+        "mi_btvl1_get_params": (i, [vp, C.POINTER(BTVL1Params)]),
+        "mi_btvl1_process": (i, [vp, i, PM, PM, PM, PM, PM, i, PM, vp]),
+        "mi_btvl1_get_profile": (i, [vp, C.POINTER(d), C.POINTER(C.c_longlong)]),
+        "mi_btvl1_stage": (i, [vp, i, PM, PM, PM, PM, PM, i, PM, PM, C.POINTER(f), C.POINTER(f), vp]),
+        "mi_btvl1_destroy": (None, [vp]),
+        "mi_btvl1_convert": (i, [PM, PM, vp]),
+        "miflow_selftest_btvl1_poison": (i, [vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

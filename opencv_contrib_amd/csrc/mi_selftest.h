@@ -31,6 +31,9 @@ MI_API int miflow_selftest_rccl_self_copy(const unsigned char *in_host, unsigned
  * MI_ERR_BAD_ARG before the handle's first calc (no arena yet). */
 struct mi_farneback;
 MI_API int miflow_selftest_farneback_poison(struct mi_farneback *h, void *stream);
+/* the same for a BTV-L1 handle: every scratch plane of its arena (frames, motions, maps, both estimates, the sign field) */
+struct mi_btvl1;
+MI_API int miflow_selftest_btvl1_poison(struct mi_btvl1 *h, void *stream);
 struct mi_tvl1;
 MI_API int miflow_selftest_tvl1_slots(struct mi_tvl1 *h, int pair, int *out_host, int cap_launches, void *stream);
 #ifdef __cplusplus

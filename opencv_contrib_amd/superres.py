@@ -1,4 +1,5 @@
-"""Mirror of the reference's superres GPU optical-flow adapters: the one in-tree CALLER of the hot path.
+"""Mirror of the reference's superres GPU classes: the optical-flow adapters, the one in-tree CALLER of the hot
+path, and BTV-L1 super-resolution (`createSuperResolution_BTVL1_CUDA`, superres/src/btv_l1_cuda.cpp), their one in-tree consumer.
 
 `cv::superres::createOptFlow_DualTVL1_CUDA()` / `createOptFlow_Farneback_CUDA()` (superres/src/optical_flow.cpp:665-845) wrap
 the `cv::cuda` flow classes behind `DenseOpticalFlowExt::calc(frame0, frame1, flow1, flow2)`: frames of any supported
@@ -111,3 +112,221 @@ def createOptFlow_DualTVL1_CUDA():
 
 def createOptFlow_Farneback_CUDA():
     return Farneback_CUDA()
+
+
+# ------------------------------------------------------------------------------------------------ BTV-L1 super-resolution
+class _EmptyFrameSource:
+    """cv::superres::createFrameSource_Empty() (superres/src/frame_source.cpp): nextFrame yields an empty frame."""
+
+    def nextFrame(self):
+        return None
+
+    def reset(self):
+        pass
+
+
+class ListFrameSource:
+    """A frame source over a sequence of CUDA tensors (the tree has no videoio: video / camera sources are out of scope)."""
+
+    def __init__(self, frames):
+        self._frames, self._pos = list(frames), 0
+
+    def nextFrame(self):
+        if self._pos >= len(self._frames):
+            return None
+        self._pos += 1
+        return self._frames[self._pos - 1]
+
+    def reset(self):
+        self._pos = 0
+
+
+def createFrameSource_Empty():
+    return _EmptyFrameSource()
+
+
+def createFrameSource_List(frames):
+    return ListFrameSource(frames)
+
+
+def _mats(tensors):
+    """list of tensors (None where the reference does not read the entry) -> ctypes array of mi_mat"""
+    arr = (capi.Mat * max(len(tensors), 1))()
+    for i, t in enumerate(tensors):
+        if t is not None:
+            arr[i] = _m(t)
+    return arr
+
+
+class BTVL1_CUDA:
+    """cv::superres::createSuperResolution_BTVL1_CUDA() (btv_l1_cuda.cpp:209-588): BTVL1_CUDA_Base::process behind the C-ABI
+    (mi_btvl1_process), the frame ring of BTVL1_CUDA and SuperResolution::nextFrame (super_resolution.cpp) in Python."""
+
+    def __init__(self):
+        p = capi.BTVL1Params()
+        capi.lib().mi_btvl1_default_params(C.byref(p))
+        self._h = C.c_void_p()
+        capi.check(capi.lib().mi_btvl1_create(C.byref(p), C.byref(self._h)))
+        self._p = dict(Scale=p.scale, Iterations=p.iterations, Tau=p.tau, Lambda=p.lambda_, Alpha=p.alpha, KernelSize=p.btv_kernel_size,
+                       BlurKernelSize=p.blur_kernel_size, BlurSigma=p.blur_sigma, TemporalAreaRadius=4,   # btv_l1_cuda.cpp:461
+                       OpticalFlow=createOptFlow_Farneback_CUDA())                                           # btv_l1_cuda.cpp:292
+        self._source = createFrameSource_Empty()
+        self._first = True
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            try:
+                capi.lib().mi_btvl1_destroy(h)
+            except Exception:
+                pass
+
+    # ---- BTVL1_CUDA_Base
+    def _push_params(self):
+        q = self._p
+        p = capi.BTVL1Params(q["Scale"], q["Iterations"], q["Tau"], q["Lambda"], q["Alpha"], q["KernelSize"], q["BlurKernelSize"], q["BlurSigma"])
+        capi.check(capi.lib().mi_btvl1_set_params(self._h, C.byref(p)))
+
+    @staticmethod
+    def _planes(motions, k):
+        return [None if m is None else m[k] for m in motions]
+
+    def _args(self, frames, forward, backward):
+        n = len(frames)
+        forward = list(forward) if forward is not None else [None] * n
+        backward = list(backward) if backward is not None else [None] * n
+        if n < 1 or len(forward) != n or len(backward) != n:
+            raise capi.MiError(-1, "frames, forward and backward motions must have one entry per frame")
+        keep = [frames, forward, backward]   # the tensors behind the mi_mat views
+        return keep, (_mats(frames), _mats(self._planes(forward, 0)), _mats(self._planes(forward, 1)),
+                      _mats(self._planes(backward, 0)), _mats(self._planes(backward, 1)))
+
+    def process(self, frames, forward, backward, baseIdx):
+        """BTVL1_CUDA_Base::process (btv_l1_cuda.cpp:306-400).  frames: n float32 CUDA tensors (H, W) or (H, W, 3 | 4); forward /
+        backward: n entries (x, y) of float32 (H, W) planes, forward[i] read for i < n - 1 and backward[i] for i > 0 (None elsewhere).
+        Returns the high-res frame without its border of KernelSize pixels."""
+        import torch
+        self._push_params()
+        keep, (fr, fx, fy, bx, by) = self._args(frames, forward, backward)
+        s, b = self._p["Scale"], self._p["KernelSize"]
+        f0 = frames[0]
+        shape = (f0.shape[0] * s - 2 * b, f0.shape[1] * s - 2 * b) + tuple(f0.shape[2:])
+        if shape[0] <= 0 or shape[1] <= 0:
+            raise capi.MiError(-3, "high-res frame not larger than the cropped border of KernelSize pixels")
+        dst = torch.empty(shape, dtype=torch.float32, device=f0.device)
+        md = _m(dst)
+        capi.check(capi.lib().mi_btvl1_process(self._h, len(frames), fr, fx, fy, bx, by, baseIdx, C.byref(md), capi.current_stream_ptr()))
+        del keep
+        return dst
+
+    def stage(self, frames, forward, backward, baseIdx):
+        """mi_btvl1_stage (test hook): ([(forwardMap x, y, backwardMap x, y) per frame], initial estimate, blur taps, BTV weights)."""
+        import torch
+        self._push_params()
+        keep, (fr, fx, fy, bx, by) = self._args(frames, forward, backward)
+        s, n, f0 = self._p["Scale"], len(frames), frames[0]
+        hh, hw = f0.shape[0] * s, f0.shape[1] * s
+        maps = [torch.empty((hh, hw), dtype=torch.float32, device=f0.device) for _ in range(4 * n)]
+        init = torch.empty((hh, hw) + tuple(f0.shape[2:]), dtype=torch.float32, device=f0.device)
+        taps, weights = (C.c_float * 32)(), (C.c_float * 256)()
+        mi = _m(init)
+        capi.check(capi.lib().mi_btvl1_stage(self._h, n, fr, fx, fy, bx, by, baseIdx, _mats(maps), C.byref(mi), taps, weights,
+                                             capi.current_stream_ptr()))
+        del keep
+        return [tuple(maps[4 * k:4 * k + 4]) for k in range(n)], init, list(taps), list(weights)
+
+    def getProfile(self):
+        """(device milliseconds, kernel launches) of the last process (mi_btvl1_get_profile); waits for it."""
+        ms, n = C.c_double(), C.c_longlong()
+        capi.check(capi.lib().mi_btvl1_get_profile(self._h, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    # ---- SuperResolution (superres/src/super_resolution.cpp)
+    def setInput(self, source):
+        self._source = source
+        self._first = True
+
+    def nextFrame(self):
+        """uint8 CUDA tensor, or None at the end of the source (the reference's empty frame)."""
+        if self._first:
+            self._init_impl()
+            self._first = False
+        return self._process_impl()
+
+    def reset(self):
+        self._source.reset()
+        self._first = True
+
+    def collectGarbage(self):
+        # BTVL1_CUDA::collectGarbage (btv_l1_cuda.cpp:464-481): the ring and the scratch memory go, the parameters stay
+        self._frames = self._fwd = self._bwd = self._outputs = None
+        self._cur = self._prev = None
+        self._p["OpticalFlow"].collectGarbage()
+        capi.lib().mi_btvl1_destroy(self._h)
+        self._h = C.c_void_p()
+        capi.check(capi.lib().mi_btvl1_create(None, C.byref(self._h)))
+
+    # ---- BTVL1_CUDA (btv_l1_cuda.cpp:483-582)
+    @staticmethod
+    def _at(index, items):
+        n = len(items)
+        return ((index % n) + n) % n
+
+    def _init_impl(self):
+        r = self._p["TemporalAreaRadius"]
+        n = 2 * r + 1
+        self._frames, self._fwd, self._bwd, self._outputs = [None] * n, [None] * n, [None] * n, [None] * n
+        self._store, self._prev = -1, None
+        for _ in range(-r, r + 1):
+            self._read_next_frame()
+        # the reference runs processFrame(0 .. r) whatever the source held and indexes an empty window where it held fewer than
+        # r + 1 frames; here only the frames that exist are processed (an empty source then yields no frame at all)
+        for i in range(min(r, self._store) + 1):
+            self._process_frame(i)
+        self._proc, self._out = r, -1
+
+    def _process_impl(self):
+        import torch
+        if self._out >= self._store:
+            return None
+        self._read_next_frame()
+        if self._proc < self._store:
+            self._proc += 1
+            self._process_frame(self._proc)
+        self._out += 1
+        cur = self._outputs[self._at(self._out, self._outputs)]
+        return torch.round(cur).clamp_(0, 255).to(torch.uint8)   # convertTo(CV_8U): round to nearest even, saturate
+
+    def _read_next_frame(self):
+        import torch
+        cur = self._source.nextFrame()
+        if cur is None:
+            return
+        self._store += 1
+        self._frames[self._at(self._store, self._frames)] = cur.to(torch.float32).contiguous()   # convertTo(CV_32F)
+        if self._store > 0:
+            flow = self._p["OpticalFlow"]
+            self._fwd[self._at(self._store - 1, self._fwd)] = flow.calc(self._prev, cur)
+            self._bwd[self._at(self._store, self._bwd)] = flow.calc(cur, self._prev)
+        self._prev = cur.clone()
+
+    def _process_frame(self, idx):
+        r = self._p["TemporalAreaRadius"]
+        start = max(idx - r, 0)
+        end = min(start + 2 * r, self._store)
+        frames, fwd, bwd, base = [], [], [], -1
+        for i in range(start, end + 1):
+            if i == idx:
+                base = len(frames)
+            frames.append(self._frames[self._at(i, self._frames)])
+            fwd.append(self._fwd[self._at(i, self._fwd)] if i < end else None)
+            bwd.append(self._bwd[self._at(i, self._bwd)] if i > start else None)
+        self._outputs[self._at(idx, self._outputs)] = self.process(frames, fwd, bwd, base)
+
+
+_add_accessors(BTVL1_CUDA, ["Scale", "Iterations", "Tau", "Lambda", "Alpha", "KernelSize", "BlurKernelSize", "BlurSigma",
+                            "TemporalAreaRadius", "OpticalFlow"])
+
+
+def createSuperResolution_BTVL1_CUDA():
+    return BTVL1_CUDA()
