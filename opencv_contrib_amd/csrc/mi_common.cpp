@@ -82,6 +82,8 @@ const Tuning &tuning()
         t.tb_force = EXP_ENV("MIFLOW_TB_FORCE") != nullptr;
         t.tb_plan_wps = EXP_INT("MIFLOW_TB_WPS", 0);
         t.tb_rows = EXP_INT("MIFLOW_TB_ROWS", 0);
+        t.tb_rows_equal = EXP_INT("MIFLOW_TB_ROWS_EQUAL", 0);
+        t.tb_il = EXP_INT("MIFLOW_TB_IL", 1);
         t.tb_verbose = getenv("MIFLOW_TB_VERBOSE") != nullptr;
         {
             const char *e = getenv("MIFLOW_TILE_MAXPX");

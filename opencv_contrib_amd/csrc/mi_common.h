@@ -50,6 +50,8 @@ struct Tuning {
     int tb_force;            // MIFLOW_TB_FORCE: greedy blocks of exactly the cap (tuning sweeps)
     int tb_plan_wps;         // MIFLOW_TB_WPS: waves/SIMD the band planner assumes (0: table)
     int tb_rows;             // MIFLOW_TB_ROWS: band height (0: planner)
+    int tb_rows_equal;       // MIFLOW_TB_ROWS_EQUAL (experiments build): 1 = the planner cuts equal bands of ceil(H / bands) rows (the round-3 rule); 0 (default, and always in the release library) = the height that wastes the fewest steps of the bands' last blocks
+    int tb_il;               // MIFLOW_TB_IL (experiments build): 0 = the calc's final pass stores u planes and k_pack_flow interleaves them (as before round 20); 1 (default, and always in the release library) = the pass writes the callers' flow matrices itself
     int tb_verbose;          // MIFLOW_TB_VERBOSE
     long long tile_maxpx;    // MIFLOW_TILE_MAXPX: levels of at most this many pixels x pairs iterate on the register-tile kernel (0: never)
     int tile_spec;           // MIFLOW_TILE_SPEC: speculative steps of the convergence-checked path on the register-tile kernel where it is eligible (1) or always on the streaming kernel (0)

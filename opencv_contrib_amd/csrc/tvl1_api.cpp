@@ -336,6 +336,7 @@ const TvKnobs &mi::tvl1::tv_knobs()
         v.tile_fb_block = t.tile_fb_block; v.tile_fb_model = t.tile_fb_model;
         v.tb_force = t.tb_force != 0; v.tb_nograd = t.tb_nograd; v.tb_jw = t.tb_jw; v.tb_ppl = t.tb_ppl; v.tb_jw_spec = t.tb_jw_spec;
         v.tb_fw = t.tb_fw; v.tb_skip_p = t.tb_skip_p; v.tb_hist = t.tb_hist; v.spec = t.spec; v.exact_tb = t.exact_tb;
+        v.tb_il_mask = t.tb_il ? tb_interleave_mask() : 0u;
         v.fb_poll = t.fb_poll; v.fb_ahead = t.fb_ahead; v.warp_fast = t.warp_fast; v.warp_lds = t.warp_lds; v.x_skip = t.x_skip;
         return v;
     }();
@@ -489,7 +490,8 @@ int run_blocked(Run &r, LevelBuf &Lv, const TvWarp &w, long long *nlaunch)
             rc = w.form == TvForm::ExactBlocked ? iterate_tb_exact(w.blocks[k], r.planes, Lv.g, r.l_t, r.theta, r.taut, r.first_of_scale, r.cur, r.st)
                : w.fused ? iterate_tb_fused(sem, Lv.I0, Lv.I1, r.h->cubic_tab, w.blocks[k], r.planes, Lv.g, r.l_t, r.theta, r.taut,
                                             r.first_of_scale, r.cur, r.st, last_pass)
-                         : iterate_tb(w.blocks[k], r.planes, Lv.g, r.l_t, r.theta, r.taut, r.first_of_scale, r.cur, 0, r.st, last_pass);
+                         : iterate_tb(w.blocks[k], r.planes, Lv.g, r.l_t, r.theta, r.taut, r.first_of_scale, r.cur, 0, r.st, last_pass, false,
+                                      last_pass && w.pack_in_pass ? r.ln.tab.p : nullptr);
             if (rc) return rc;
             r.cur ^= 1;
             r.first_of_scale = false;
@@ -714,6 +716,7 @@ int zoom_or_pack(Run &r, int s)
     ec.q_prev = r.q_last;
     const Ctl *dev = r.pl.check && !r.first_of_scale ? &ec : nullptr;
     if (s == 0) {
+        if (!r.pl.warp[0].empty() && r.pl.warp[0].back().pack_in_pass) return MI_OK;   // the last pass wrote the callers' matrices itself
         const float *u1v[2] = {Lv.u[0][0], Lv.u[1][0]}, *u2v[2] = {Lv.u[0][1], Lv.u[1][1]};
         return pack_flow(r.ln.tab.p, u1v, u2v, Lv.g, dev, r.cur, r.st);
     }
@@ -751,6 +754,8 @@ static int lane_calc(mi_tvl1 *h, Lane &ln, int n, const mi_mat *I0s, const mi_ma
     const TvPlan pl = tv_make_plan(TvShape{I0s[0].cols, I0s[0].rows, n, I0s[0].type, P, h->last_lanes, capturing}, tv_knobs());
     int rc = ensure_arena(P, ln, pl, I0s[0].cols, I0s[0].rows, n);
     if (rc || (rc = ensure_buffers(pl, ln, n, I0s, I1s, flows, st))) return rc;
+    if (!pl.warp.empty() && !pl.warp[0].empty() && pl.warp[0].back().pack_in_pass)   // the pass keeps the matrices' pitch in 32 bits
+        for (int i = 0; i < n; ++i) MI_REQUIRE(flows[i].step < (1ll << 31), MI_ERR_BAD_ARG, "flow matrix pitch of %lld bytes", (long long)flows[i].step);
     *ns_out = pl.used;
     ln.slots.clear();
     ln.regions.clear();

@@ -90,8 +90,11 @@ int iterate(bool exact, const IterPlanes &pl, const Geo &g, float l_t, float the
 // skip_p_out: the launch stores u only (the last pass of a scale: nobody reads its p).  pl.g == nullptr: no |grad|^2 plane, the kernel
 // forms it from I1wx, I1wy (only where tb_nograd_ok, tvl1_plan.h, says so -- or anywhere with a streaming kernel forced, rows_per_band != 0)
 // independent_waves (test hook of the stage-level entry): the kernel whose waves each own a 64-column strip, never the joined form
+// out_tab (with skip_p_out, two-channel streaming kernels only): the pass writes the flow interleaved into the callers' MI_32FC2
+// matrices (tab.out / tab.step_out of each pair) instead of the u planes of set cur^1 -- the calc's final pass, no pack_flow behind it
 int iterate_tb(int T, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut, bool p_zero,
-               int cur, int rows_per_band, hipStream_t s, bool skip_p_out = false, bool independent_waves = false);
+               int cur, int rows_per_band, hipStream_t s, bool skip_p_out = false, bool independent_waves = false,
+               const PtrTab *out_tab = nullptr);
 // the warp of a one-pass warp INSIDE that pass (k_iterate_tbr FW, where tb_fused_ok says so): no warp launch, no I1wx / I1wy / rho_c
 // planes in HBM; bit-identical
 int iterate_tb_fused(int semantics, const float *I0, const float *I1, const float *cubic_tab_dev, int T, const IterPlanes &pl, const Geo &g,
@@ -104,6 +107,9 @@ int tile_owned_rows();   // rows a tile of the default variant owns
 int tile_shape_rows(int variant);   // rows (owned + margins) of the tiles of a variant
 int tb_query_plan(int T, const Geo &g, int *kernel, int *rows);   // kernel 0 = streaming (band height), 1 = register tile
 int tile_variants();
+// block lengths T (bit T) whose streaming kernel can store the flow interleaved into the callers' matrices (iterate_tb out_tab); bit 31:
+// the T = 10 kernel without a |grad|^2 plane can
+unsigned tb_interleave_mask();
 // the same in exact math (bit-identical to T one-iteration launches of iterate(exact = true)); T in 1..kTbExactMaxBlock.
 // rows_per_band <= 0: the planner's band height
 int iterate_tb_exact(int T, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut, bool p_zero, int cur, hipStream_t s,

@@ -39,6 +39,8 @@ struct TvKnobs {
     int tb_nograd, tb_jw, tb_ppl, tb_jw_spec;   // which blocked kernels exist without a |grad|^2 plane
     int tb_fw;                       // warp fused into the pass (experiments build; 0 in the release library)
     int tb_skip_p, tb_hist, spec, exact_tb;
+    unsigned tb_il_mask;             // block lengths T (bit T; bit 31: T = 10 without a |grad|^2 plane) whose streaming kernel can write the
+                                     // flow into the callers' matrices itself (0: never -- k_pack_flow behind every calc)
     int fb_poll, fb_ahead;
     int warp_fast, warp_lds, x_skip;
 };
@@ -145,6 +147,64 @@ inline std::vector<int> tb_spec_plan(int n, int list, int B, const TvKnobs &K)
     return blocks;
 }
 
+// ---- band height of the streaming kernels (k_iterate_tbr) --------------------------------------------------------------------------
+// Every band wave streams its R rows + 2T rows of halo in whole blocks of P = T + 1 + PF steps.
+struct TbBandShape {
+    int T, PF, H;
+    long long per_band;   // waves per band row: strips x pairs (x the waves of a joined group)
+    long long cap;        // resident waves the plan fills: SIMDs x waves per SIMD
+    long long simds;      // independent waves only (0 for the joined forms): a workgroup is four consecutive bands of a strip, so with
+    int wps;              // nb < 4 bands it has only nb live waves -- at most nb per SIMD where nb < wps (r02z4)
+};
+inline long long tb_band_wave_steps(int T, int PF, int rows)
+{
+    const int P = T + 1 + PF;
+    return (long long)((rows + 2 * T + P - 1) / P) * P;
+}
+// executed steps of all bands of one strip: (nb - 1) bands of R rows and the remainder
+inline long long tb_band_sum_steps(int T, int PF, int H, int R)
+{
+    const int nb = (H + R - 1) / R;
+    return (nb - 1) * tb_band_wave_steps(T, PF, R) + tb_band_wave_steps(T, PF, H - (nb - 1) * R);
+}
+// The band COUNT (the round-3 rule, unchanged): the one that minimises rounds x steps of equal bands of ceil(H / nb) rows, rounds =
+// ceil(waves / capacity), so that the grid fills the SIMDs in whole rounds while the 2T-row overlap stays small; bands of at least 8 rows.
+inline int tb_band_count(const TbBandShape &b)
+{
+    long long best_cost = -1;
+    int best_nb = 1;
+    for (int nb = 1; nb <= b.H; ++nb) {
+        const int R = (b.H + nb - 1) / nb;
+        if (R < 8 && nb > 1) break;
+        const long long cap_nb = b.simds > 0 && nb < 4 && nb < b.wps ? b.simds * nb : b.cap;
+        const long long rounds = (b.per_band * nb + cap_nb - 1) / cap_nb;
+        const long long cost = rounds * tb_band_wave_steps(b.T, b.PF, R);
+        if (best_cost < 0 || cost < best_cost) { best_cost = cost; best_nb = nb; }
+    }
+    return best_nb;
+}
+inline int tb_band_rows_equal(const TbBandShape &b) { const int nb = tb_band_count(b); return (b.H + nb - 1) / nb; }   // the round-3 height
+// The band HEIGHT for that count: equal bands of R0 = ceil(H / nb) rows usually end in the middle of their last block (up to P - 1 steps
+// whose rows are never stored).  Any R with ceil(H / R) = nb cuts the same number of bands, the last one taking the remainder: pick the
+// R >= R0 that minimises the SUM of the bands' executed steps, among those whose full bands run no more blocks than a band of R0 rows
+// does (so the longest wave of the launch is never longer than before: a launch alone on the device cannot get slower); ties -> the
+// smallest R.  R0 itself is admissible, so the sum never grows.
+inline int tb_band_rows(const TbBandShape &b)
+{
+    const int nb = tb_band_count(b);
+    const int R0 = (b.H + nb - 1) / nb;
+    if (nb == 1) return R0;
+    const long long tallest = tb_band_wave_steps(b.T, b.PF, R0);
+    int best = R0;
+    long long best_sum = tb_band_sum_steps(b.T, b.PF, b.H, R0);
+    for (int R = R0 + 1; (long long)(nb - 1) * R < b.H; ++R) {   // ceil(H / R) == nb  <=>  (nb - 1) R < H <= nb R
+        if (tb_band_wave_steps(b.T, b.PF, R) > tallest) break;
+        const long long sum = tb_band_sum_steps(b.T, b.PF, b.H, R);
+        if (sum < best_sum) { best_sum = sum; best = R; }
+    }
+    return best;
+}
+
 // ---- the plan ----------------------------------------------------------------------------------------------------------------------
 
 struct TvShape {
@@ -171,6 +231,8 @@ struct TvWarp {
     bool warp_launch;          // the warp is enqueued (not fused, not dropped by the MIFLOW_X_SKIP=1 timing experiment)
     bool skip_iterations;      // MIFLOW_X_SKIP=2 timing experiment: the blocked passes are counted, not enqueued
     bool skip_p_last;          // the last pass does not store p (the last pass of a scale: the next scale starts from p = 0)
+    bool pack_in_pass;         // the last pass IS the calc's last launch: it stores the flow interleaved into the callers' matrices (no
+                               // pack_flow launch).  The last warp of scale 0 only
 };
 
 constexpr size_t kNoPlane = (size_t)-1;
@@ -358,6 +420,14 @@ inline TvPlan tv_make_plan(const TvShape &S, const TvKnobs &K)
                 x.blocks = spec_list[x.on_tiles ? 3 : wp > 0 ? 2 : ((double)g.w * g.h * B >= kLargeLevel ? 0 : 1)];
             x.warp_launch = !x.fused && !(K.x_skip == 1 && wp > 0);
             x.skip_p_last = x.form == TvForm::Blocked && K.tb_skip_p && wp == P.warps - 1 && !p.median;
+            // the flow straight into the callers' matrices: the fixed-work blocked form whose last pass runs on a streaming kernel that
+            // has the interleaved store (two channels, one pixel per lane); register tiles, the speculative steps, the fused warp and
+            // calcs that read the callers' matrices first (use_initial_flow) keep pack_flow
+            if (s == 0 && x.skip_p_last && !gam && !x.fused && !x.skip_iterations && !P.use_initial_flow && !x.blocks.empty()) {
+                const int tl = x.blocks.back();
+                x.pack_in_pass = !runs_on_tiles(g, tl, K) && tl < 31 &&
+                                 ((x.nograd ? K.tb_il_mask >> 31 : K.tb_il_mask >> tl) & 1u) != 0;
+            }
         }
     }
     return p;

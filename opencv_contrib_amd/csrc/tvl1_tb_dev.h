@@ -53,6 +53,9 @@ struct TbArgs {
     int cur;  // input set
     int swz, nstrips;
     int skip_p_out;   // MODE 0: the launch does not store p (last pass of a scale)
+    // MODE 0, wave-uniform like skip_p_out: the launch is the calc's FINAL pass and stores the leaving rows interleaved (float2 {u1, u2})
+    // into the callers' CV_32FC2 matrices, one row of the table per pair, instead of the two u planes (nullptr: the planes)
+    const PtrTab *otab;
     CtlK ctl;   // speculative convergence path only (MODE 1): slot protocol of Ctl, e0 = first error-sum index of this launch's block
     int e0;
     SpecK sk;

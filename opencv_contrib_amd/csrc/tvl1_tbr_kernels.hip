@@ -26,6 +26,7 @@
 // kernel is tested with a stated tolerance (tests/test_tvl1_gpu.py).
 #include "tvl1_tb_dev.h"
 #include "tvl1_warp_px.h"
+#include <type_traits>
 #include <utility>
 #include <cstdlib>
 #include <cstdio>
@@ -274,6 +275,8 @@ struct CtxR {
     float *ring;
     float *inbox;   // FW: this wave's inbox (FW_RING slots of {I1wx | I1wy | rho_c} x 64 columns), written by its producer wave
     int lane, H, ld, y0, y1, ystart, nsteps;
+    int ostep;         // pitch in bytes of the rows u1, u2 are stored to, and the shift of the byte offset of a column: 4 ld and 0
+    int osh;           // (the planes), or the caller's pitch and 1 (TbArgs::otab: interleaved into the caller's flow matrix)
     unsigned xc;
     bool st_ok, x0;   // x0: this lane holds column 0 (MODE 2)
     bool right_ok[PPL];
@@ -645,10 +648,37 @@ __device__ __forceinline__ void fw_produce_staged(const TbArgs &A, float *inbox,
     for (int i = 0; i < NW - 1; ++i) xbarrier();   // the consumers' skew
 }
 
+// The kernels that can store the flow interleaved into the callers' matrices (TbArgs::otab): one pixel per lane, and not the joined waves
+// that read a |grad|^2 plane -- that kernel sits at exactly 128 VGPRs and no calc's final pass runs on it (tb_nograd_ok picks the NG form)
+__host__ __device__ constexpr bool tb_il_form(int PPL, int JW, bool NG) { return PPL == 1 && (NG || JW == 0); }
+
+// The kernels whose first block is the fill form (step_r FILLB).  Two kernels at their register limit keep their single block: the T = 10
+// joined waves that read p AND a |grad|^2 plane (the stage entry and MIFLOW_TB_NOGRAD=0 reach it; no default calc does) sit at exactly
+// 128 VGPRs and would spill four of them, the T = 5 kernel of two pixels per lane that reads p spills eleven already and would spill 29.
+__host__ __device__ constexpr bool tb_fill_form(int T, int PPL, bool PZ, int MODE, int JW, bool NG, bool GAM)
+{
+    return MODE != 1 && JW != 1 && !(T == 10 && JW == 2 && !NG && !PZ && !GAM) && !(T == 5 && PPL == 2 && !PZ);
+}
+
 // Pipeline step with phase k (= step index mod P): every register-set index below is a compile-time constant.
 // No early exit inside the unrolled block (an exit per step keeps every register set alive across P merge points): the last
 // block may run up to P-1 steps past the band end; those rows are clamped loads whose results are never stored.
-template <int T, int PPL, bool PZ, int PF, int MODE, int JW, bool MK, bool NG, bool P16, int FW, bool GAM, int k>
+//
+// FILLB: the instantiation for the FIRST block of a band (n0 == 0, so the step index is the phase k), without the stages of the pipeline
+// fill.  Stage t of step n works on row a = y0 - T + n - t: its U half writes u_(t+1)(a), its P half p_(t+1)(a-1).  The stored rows
+// [y0, y1) of level T depend on u_i only from row y0 - (T - i) on and on p_i only from row y0 - (T - i) on as well (one row per
+// iteration: u_(i+1)(r) reads u_i(r), p_i(r), p_i(r-1), and p_(i+1)(r) reads u_(i+1)(r), u_(i+1)(r+1), p_i(r)), so the U half is needed
+// from n >= 2t + 1 and the P half from n >= 2t + 2 on: while n <= 2t the stage writes nothing a stored value depends on, and every
+// needed value is computed by a live stage from needed values only (induction over the cone; at n = 2t + 1 the inputs u_t(a), p_t(a),
+// p_t(a-1) come from stage t-1 at steps 2t, 2t + 1, both live with a needed P half).  The dead stages -- always the stages t >= TL =
+// ceil(n / 2), a suffix -- are compiled out: sum(2t + 1) = T^2 stage executions per band wave, those of the first block here.  What a
+// dead stage still does: pass the barriers of the joined forms (every wave of a workgroup passes the same number) and keep the ring of
+// static rows going; its register sets stay untouched -- the identity of the rotating scheme, as for MODE 1's skipped stages.  It
+// publishes NO hand-over: its left-to-right value (p of stage t) feeds the neighbour's stage t + 1 of the same step, dead as well; its
+// right-to-left value (u of stage t) feeds the P half of the neighbour's stage t at step n + 1 <= 2t + 1, whose output is not needed.
+// Not for the speculative steps (MODE 1: left as they are), the tagged hand-over (JW = 1, experiments build: a dead stage would have
+// to publish its tags) and ONE fixed-work kernel, tb_fill_form below.
+template <int T, int PPL, bool PZ, int PF, int MODE, int JW, bool MK, bool NG, bool P16, int FW, bool GAM, bool FILLB, int k>
 __device__ __forceinline__ void step_r(const CtxR<PPL> &c, Slot<PPL, GAM> (&X)[T + 1 + PF], int n0, int &slot0, unsigned long long (&acc)[T], Xchg &x)
 {
     constexpr bool JF = jw_fast(JW);
@@ -656,6 +686,8 @@ __device__ __forceinline__ void step_r(const CtxR<PPL> &c, Slot<PPL, GAM> (&X)[T
     constexpr int XAg = xarea2_bytes(T, GAM);    // bytes per wave's hand-over area
     constexpr int P = T + 1 + PF;
     constexpr int K = T > 2 ? T - 1 : 1;
+    constexpr bool FILL = FILLB && tb_fill_form(T, PPL, PZ, MODE, JW, NG, GAM);
+    constexpr int TL = !FILL ? T : (k + 1) / 2 < T ? (k + 1) / 2 : T;   // live stages of this step: t < TL
     const int n = n0 + k;
     const int r0 = c.ystart + n;
     if (P16 && !PZ) {   // the entering row's p arrives packed: two snorm16 per dword
@@ -701,7 +733,7 @@ __device__ __forceinline__ void step_r(const CtxR<PPL> &c, Slot<PPL, GAM> (&X)[T
     for (int j = 0; j < PPL; ++j) nx.ix[j] = nx.iy[j] = nx.rg[j] = nx.rc[j] = 0.f;
     if (T < 3) lds_put<PPL>(c.ring + slot0 * (256 * PPL), c.lane, X[k].s);   // (unused ring: keeps the code uniform)
 #pragma unroll
-    for (int t = 0; t < T; ++t) {
+    for (int t = 0; t < TL; ++t) {
         Stat<PPL> st;
         if (t == 0) st = X[k].s;
         else if (t == 1) st = X[(k - 1 + P) % P].s;
@@ -710,9 +742,11 @@ __device__ __forceinline__ void step_r(const CtxR<PPL> &c, Slot<PPL, GAM> (&X)[T
         if (t >= 2) st = X[k].s;
 #else
         if (t + 1 < T && t + 1 >= 2) {
-            int sl = slot0 - (t + 1);
-            if (sl < 0) sl += K;
-            lds_get<PPL>(c.ring + sl * (256 * PPL), c.lane, nx);
+            if (t + 1 < TL) {
+                int sl = slot0 - (t + 1);
+                if (sl < 0) sl += K;
+                lds_get<PPL>(c.ring + sl * (256 * PPL), c.lane, nx);
+            }
             if (t + 1 == T - 1) lds_put<PPL>(c.ring + slot0 * (256 * PPL), c.lane, X[k].s);
         }
 #endif
@@ -816,6 +850,15 @@ __device__ __forceinline__ void step_r(const CtxR<PPL> &c, Slot<PPL, GAM> (&X)[T
                                               GamK{c.gamma, 0.f, 0.f, 0.f});
         }
     }
+    // the dead stages of the fill (FILL only: TL < T): barriers and the ring of static rows, nothing else
+#pragma unroll
+    for (int t = TL; t < T; ++t) {
+        if (JW >= 2 && (k * T + t) % xk_stages(T) == 0) xbarrier();
+        if constexpr (FW != 0) if (t == 0) fw_inbox_get<PPL>(c.inbox + ((n + 1) & (FW_RING - 1)) * FW_SLOT, c.lane, X[(k + 1) % P].s);
+#ifndef TBR_X_NOLDS
+        if (t + 1 == T - 1 && t + 1 >= 2) lds_put<PPL>(c.ring + slot0 * (256 * PPL), c.lane, X[k].s);
+#endif
+    }
     if (JW >= 2) {   // the slots of the other parity for the next step (the two parities of a stage are adjacent: one address bit)
         x.own ^= XSg; x.pub_l ^= XSg;
         if (JF) x.pub_r ^= XSg;
@@ -833,9 +876,25 @@ __device__ __forceinline__ void step_r(const CtxR<PPL> &c, Slot<PPL, GAM> (&X)[T
 #endif
             const long long ro = (long long)orow * c.ld;   // wave-uniform; owned lanes have xc == 4 * xl
             unsigned xb = c.xc;
-            asm volatile("" : "+v"(xb));
-            str<PPL>(c.uout[0] + ro, xb, r.u1);
-            str<PPL>(c.uout[1] + ro, xb, r.u2);
+            if constexpr (!(MODE == 0 && tb_il_form(PPL, JW, NG))) asm volatile("" : "+v"(xb));
+            if constexpr (MODE == 0 && tb_il_form(PPL, JW, NG)) {
+                // u1, u2 as one dword each at (row base + row * pitch + column offset): the two planes of set cur^1 (pitch 4 ld, offset
+                // 4 x) or, in the final pass of the calc (TbArgs::otab), the two halves of the caller's CV_32FC2 pixel (uout[1] =
+                // uout[0] + 4 bytes, the matrix's pitch, offset 8 x; cuda::merge, cudaoptflow/src/tvl1flow.cpp:181-182) -- the same two
+                // stores, no branch, no pack launch behind the pass
+                const long long rou = (long long)orow * c.ostep;   // wave-uniform, bytes
+                unsigned xu = c.xc << c.osh;
+                asm volatile("" : "+v"(xu));
+                // (the caller's pointer comes out of the table in memory: named global here, or the two stores become flat_store)
+                typedef __attribute__((address_space(1))) char *gchar_ptr;
+                typedef __attribute__((address_space(1))) float *gfloat_ptr;
+                *reinterpret_cast<gfloat_ptr>((gchar_ptr)reinterpret_cast<char *>(c.uout[0]) + rou + xu) = r.u1[0];
+                *reinterpret_cast<gfloat_ptr>((gchar_ptr)reinterpret_cast<char *>(c.uout[1]) + rou + xu) = r.u2[0];
+                asm volatile("" : "+v"(xb));   // (the column offset of the p planes after the u stores: one temporary at a time)
+            } else {
+                str<PPL>(c.uout[0] + ro, xb, r.u1);
+                str<PPL>(c.uout[1] + ro, xb, r.u2);
+            }
             if (P16 && !c.B.skip_p_out) {
                 float pa[PPL], pb2[PPL];
 #pragma unroll
@@ -865,11 +924,11 @@ __device__ __forceinline__ void step_r(const CtxR<PPL> &c, Slot<PPL, GAM> (&X)[T
     }
     slot0 = (slot0 + 1 == K) ? 0 : slot0 + 1;
 }
-template <int T, int PPL, bool PZ, int PF, int MODE, int JW, bool MK, bool NG, bool P16, int FW, bool GAM, int... Ks>
+template <int T, int PPL, bool PZ, int PF, int MODE, int JW, bool MK, bool NG, bool P16, int FW, bool GAM, bool FILLB, int... Ks>
 __device__ __forceinline__ void steps_r(const CtxR<PPL> &c, Slot<PPL, GAM> (&X)[T + 1 + PF], int n0, int &slot0, unsigned long long (&acc)[T],
                                         Xchg &x, std::integer_sequence<int, Ks...>)
 {
-    (step_r<T, PPL, PZ, PF, MODE, JW, MK, NG, P16, FW, GAM, Ks>(c, X, n0, slot0, acc, x), ...);
+    (step_r<T, PPL, PZ, PF, MODE, JW, MK, NG, P16, FW, GAM, FILLB, Ks>(c, X, n0, slot0, acc, x), ...);
 }
 
 // MODE 0: T iterations, fixed work.
@@ -1014,6 +1073,12 @@ __global__ __launch_bounds__((JW == 3 || FW) ? 512 : 256, WPS) void k_iterate_tb
     c.uout[0] = A.pl.u[cur ^ 1][0] + pb; c.uout[1] = A.pl.u[cur ^ 1][1] + pb;
 #pragma unroll
     for (int i = 0; i < 4; ++i) { c.pin[i] = A.pl.p[cur][i] + pb; c.pout[i] = A.pl.p[cur ^ 1][i] + pb; }
+    c.ostep = 4 * c.ld; c.osh = 0;
+    if (MODE == 0 && tb_il_form(PPL, JW, NG) && A.otab) {   // wave-uniform: the pair's row of the pointer table
+        c.uout[0] = reinterpret_cast<float *>(A.otab[b].out);
+        c.uout[1] = c.uout[0] + 1;
+        c.ostep = (int)A.otab[b].step_out; c.osh = 1;   // (< 2^31: checked on the host)
+    }
     c.uin[2] = nullptr; c.uout[2] = nullptr; c.pin[4] = c.pin[5] = nullptr; c.pout[4] = c.pout[5] = nullptr;
     c.gamma = 0.f; c.eu3 = 0.f;
     if constexpr (GAM) {
@@ -1049,17 +1114,23 @@ __global__ __launch_bounds__((JW == 3 || FW) ? 512 : 256, WPS) void k_iterate_tb
     for (int t = 0; t < T; ++t) acc[t] = 0;
     if (JW >= 2 && xk_stages(T) > 1)   // the skew: wave w starts w barrier intervals after wave 0 ...
         for (int i = 0; i < wave; ++i) xbarrier();
-    for (int n0 = 0; n0 < c.nsteps; n0 += P) {
+    // one block of P steps; fill = std::true_type: the band's first block (n0 == 0) in the form without the dead stages of the pipeline
+    // fill (step_r FILLB), which the steady-state block knows nothing of
+    const auto block = [&](auto fill, int n0) {
+        constexpr bool FILLB = decltype(fill)::value;
         if (jw_fast(JW)) {
             // rows a = r0 - t seen by the stages of this block of P steps: [ystart + n0 - (T - 1), ystart + n0 + P - 1].  If neither row 0
             // nor row H is among them the block runs the form without border masks (wave-uniform, and the same for the four waves of
             // the workgroup: they share the band)
             const int ra = c.ystart + n0 - (T - 1), rb = c.ystart + n0 + P - 1;
             const bool plain = (ra > 0 || rb < 0) && (ra > c.H || rb < c.H);
-            if (plain) { steps_r<T, PPL, PZ, PF, MODE, JW, false, NG, P16, FW, GAM>(c, X, n0, slot0, acc, x, std::make_integer_sequence<int, P>{}); continue; }
+            if (plain) { steps_r<T, PPL, PZ, PF, MODE, JW, false, NG, P16, FW, GAM, FILLB>(c, X, n0, slot0, acc, x, std::make_integer_sequence<int, P>{}); return; }
         }
-        steps_r<T, PPL, PZ, PF, MODE, JW, true, NG, P16, FW, GAM>(c, X, n0, slot0, acc, x, std::make_integer_sequence<int, P>{});
-    }
+        steps_r<T, PPL, PZ, PF, MODE, JW, true, NG, P16, FW, GAM, FILLB>(c, X, n0, slot0, acc, x, std::make_integer_sequence<int, P>{});
+    };
+    int n0 = 0;
+    if constexpr (tb_fill_form(T, PPL, PZ, MODE, JW, NG, GAM)) { block(std::true_type{}, 0); n0 = P; }   // (nsteps = rows + 2T >= 1: every band has a first block)
+    for (; n0 < c.nsteps; n0 += P) block(std::false_type{}, n0);
     if (JW >= 2 && xk_stages(T) > 1)   // ... and keeps the others company for as many at the end (every live wave passes the same number)
         for (int i = wave; i < NW - 1; ++i) xbarrier();
     if (JW == 1 && x.budget < 0 && c.lane == 0) g_jw_fault = 1;
@@ -1207,14 +1278,14 @@ static const TbrEntry *tbr_pick(int T)
     return def;
 }
 
-// Band height: every wave streams rows_per_band + 2T rows, in whole blocks of P = T + 1 + PF steps.  Pick the band count
-// that minimises rounds x steps, rounds = ceil(waves / resident-wave capacity), so that the grid fills the SIMDs of the
-// device in whole rounds (no half-empty tail round) while the 2T-row band overlap stays small.
+// Band height: every wave streams rows_per_band + 2T rows, in whole blocks of P = T + 1 + PF steps.  The rule is tvl1_plan.h
+// tb_band_rows (pure; tests/cpp/tvl1_band_test.cpp): the band count that minimises rounds x steps, then the height that wastes the
+// fewest steps in the bands' last blocks.  Here: the entry's waves per band row and the device's resident-wave capacity.
 static int plan_band_rows(const TbrEntry &e, const Geo &g)
 {
     const Tuning &tn = tuning();
     if (tn.tb_rows > 0) return tn.tb_rows;
-    const int T = e.T, ppl = e.PPL, P = T + 1 + e.PF;
+    const int T = e.T, ppl = e.PPL;
     int wps = e.PLAN;
     const int ring_slots = T > 2 ? T - 1 : 1;
     const int nw = e.JW ? jw_waves(e.JW) : 4;
@@ -1227,21 +1298,26 @@ static int plan_band_rows(const TbrEntry &e, const Geo &g)
     const int LW = (e.JW ? 64 * nw : 64) * ppl;
     const long long strips = g.w <= LW - M ? 1 : 1 + div_up(g.w - (LW - M), LW - 2 * M);
     const long long per_band = strips * g.batch * (e.JW ? nw : 1);   // waves per band row
-    long long best_cost = -1;
-    int best_nb = 1;
-    for (int nb = 1; nb <= g.h; ++nb) {
-        const int R = div_up(g.h, nb);
-        if (R < 8 && nb > 1) break;
-        // a workgroup is four consecutive bands of a strip and the LDS rings admit four workgroups per CU: with fewer than four
-        // bands every workgroup has only nb live waves (the others exit at once, their ring stays allocated), i.e. at most nb
-        // waves per SIMD (r02z4: 2 bands at 32 pairs per lane ran 1.3 x slower than 4)
-        const long long cap_nb = !e.JW && nb < 4 && nb < wps ? (long long)device_simds() * nb : cap;
-        const long long rounds = (per_band * nb + cap_nb - 1) / cap_nb;
-        const long long steps = (long long)div_up(R + 2 * T, P) * P;
-        const long long cost = rounds * steps;
-        if (best_cost < 0 || cost < best_cost) { best_cost = cost; best_nb = nb; }
+    // independent waves: a workgroup is four consecutive bands of a strip and the LDS rings admit four workgroups per CU: with fewer
+    // than four bands every workgroup has only nb live waves (the others exit at once, their ring stays allocated), i.e. at most nb
+    // waves per SIMD (r02z4: 2 bands at 32 pairs per lane ran 1.3 x slower than 4)
+    const TbBandShape b{T, e.PF, g.h, per_band, cap, e.JW ? 0ll : (long long)device_simds(), wps};
+#ifdef MIFLOW_EXPERIMENTS
+    if (tn.tb_rows_equal) return tb_band_rows_equal(b);   // A/B switch: the round-3 height (equal bands)
+#endif
+    return tb_band_rows(b);
+}
+
+// block lengths (bit T) whose streaming kernel -- the one iterate_tb picks for a two-channel level -- can store the flow interleaved
+unsigned tb_interleave_mask()
+{
+    unsigned m = 0;
+    for (int T = 1; T <= kTbMaxBlock; ++T) {
+        const TbrEntry *e = tbr_pick(T);
+        if (e && tb_il_form(e->PPL, e->JW, false)) m |= 1u << T;
     }
-    return div_up(g.h, best_nb);
+    if (tb_il_form(g_tbr_ng.PPL, g_tbr_ng.JW, true)) m |= 1u << 31;   // the kernel without a |grad|^2 plane (T = 10 where tb_nograd_ok)
+    return m;
 }
 
 // What iterate_tb(T, ...) would launch for level g (introspection for the bench's accounting): kernel 0 = streaming (rows = band
@@ -1289,8 +1365,11 @@ int iterate_tb_fused(int semantics, const float *I0, const float *I1, const floa
 // T fused iterations, set cur -> cur^1.  Returns MI_ERR_BAD_ARG for unsupported T.  pl.g == nullptr (the plan's tb_nograd_ok, decided
 // before the warp, which then does not store the plane): the pass forms |grad|^2 itself.
 int iterate_tb(int T, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut, bool p_zero,
-               int cur, int rows_per_band, hipStream_t s, bool skip_p_out, bool independent_waves)
+               int cur, int rows_per_band, hipStream_t s, bool skip_p_out, bool independent_waves, const PtrTab *out_tab)
 {
+    // the flow straight into the callers' matrices: the plan (tvl1_plan.h pack_in_pass) asks for it on the streaming two-channel kernels only
+    MI_REQUIRE(!out_tab || (skip_p_out && pl.gamma == 0.f && (rows_per_band != 0 || !runs_on_tiles(g, T, tv_knobs()))), MI_ERR_BAD_ARG,
+               "the interleaved store exists in the last streaming pass of a scale without the illumination channel only");
     if (pl.gamma != 0.f && rows_per_band == 0 && runs_on_tiles(g, T, tv_knobs()))
         return iterate_tile(-1, T, pl, g, l_t, theta, taut, p_zero, cur, s);   // small levels: the register tile with the channel (bit-identical)
     if (pl.gamma != 0.f) {   // the illumination channel: its own kernels (no |grad|^2 plane read, whether or not the warp stored one)
@@ -1326,9 +1405,11 @@ int iterate_tb(int T, const IterPlanes &pl, const Geo &g, float l_t, float theta
         e = &g_tbr_ng;
 #endif
     }
+    MI_REQUIRE(!out_tab || tb_il_form(e->PPL, e->JW, !pl.g), MI_ERR_BAD_ARG, "the kernel of this launch has no interleaved store");
     TbArgs A;
     A.pl = pl; A.g = g; A.l_t = l_t; A.theta = theta; A.taut = taut; A.cur = cur; A.swz = 0; A.nstrips = 0;
     A.skip_p_out = skip_p_out ? 1 : 0;
+    A.otab = out_tab;
     A.rows_per_band = rows_per_band > 0 ? rows_per_band : plan_band_rows(*e, g);
     if (tuning().tb_verbose) {
         static int shown = 0;
@@ -1400,7 +1481,7 @@ int iterate_tb_spec(int T, const IterPlanes &pl, const Geo &g, float l_t, float 
 #endif
     if (!e) { set_error("no speculative kernel for time block %d", T); return MI_ERR_BAD_ARG; }
     TbArgs A;
-    A.pl = pl; A.g = g; A.l_t = l_t; A.theta = theta; A.taut = taut; A.cur = 0; A.swz = 0; A.nstrips = 0; A.skip_p_out = 0;
+    A.pl = pl; A.g = g; A.l_t = l_t; A.theta = theta; A.taut = taut; A.cur = 0; A.swz = 0; A.nstrips = 0; A.skip_p_out = 0; A.otab = nullptr;
     A.rows_per_band = rows_per_band > 0 ? rows_per_band : plan_band_rows(*e, g);
     A.ctl = make_ctlk(&ctl);
     A.e0 = e0;
