@@ -222,7 +222,11 @@ int mi_tvl1_query_plan(int width, int height, int pairs_per_lane, int iterations
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) { set_error("no HIP device"); return MI_ERR_NO_DEVICE; }
     const Geo g{width, height, (width + 63) / 64 * 64, (long long)((width + 63) / 64 * 64) * height, pairs_per_lane};
-    return tb_query_plan(iterations_per_launch, g, kernel, rows_per_band);
+    const TbKernel k = tb_kernel(TbUse::Fixed, iterations_per_launch, g, false, false, tv_knobs(), TbOverride{});   // the planner's own choice
+    if (!k.tile && !k.row) { set_error("unsupported time block %d", iterations_per_launch); return MI_ERR_BAD_ARG; }
+    *kernel = k.tile ? 1 : 0;
+    *rows_per_band = k.tile ? tile_owned_rows() : plan_band_rows(*k.row, g);
+    return MI_OK;
 }
 
 int mi_tvl1_set_profiling(mi_tvl1 *h, int enable)
@@ -334,9 +338,9 @@ const TvKnobs &mi::tvl1::tv_knobs()
         v.tile_variants = std::min(tile_variants(), (int)(sizeof(v.tile_rows) / sizeof(v.tile_rows[0])));
         for (int i = 0; i < v.tile_variants; ++i) v.tile_rows[i] = tile_shape_rows(i);
         v.tile_fb_block = t.tile_fb_block; v.tile_fb_model = t.tile_fb_model;
-        v.tb_force = t.tb_force != 0; v.tb_nograd = t.tb_nograd; v.tb_jw = t.tb_jw; v.tb_ppl = t.tb_ppl; v.tb_jw_spec = t.tb_jw_spec;
+        v.tb_force = t.tb_force != 0; v.tb_nograd = t.tb_nograd; v.tb_jw = t.tb_jw; v.tb_jw_spec = t.tb_jw_spec;
+        v.tb_ppl = t.tb_ppl; v.tb_wps = t.tb_wps; v.tb_pf = t.tb_pf; v.tb_p16 = t.tb_p16; v.tb_il = t.tb_il;
         v.tb_fw = t.tb_fw; v.tb_skip_p = t.tb_skip_p; v.tb_hist = t.tb_hist; v.spec = t.spec; v.exact_tb = t.exact_tb;
-        v.tb_il_mask = t.tb_il ? tb_interleave_mask() : 0u;
         v.fb_poll = t.fb_poll; v.fb_ahead = t.fb_ahead; v.warp_fast = t.warp_fast; v.warp_lds = t.warp_lds; v.x_skip = t.x_skip;
         return v;
     }();
@@ -477,7 +481,6 @@ int launch_warp(Run &r, const LevelBuf &Lv, bool ahead)
 // blocks of up to 5 fused iterations (k_iterate_tbr MODE 2), bit-identical to one launch per iteration
 int run_blocked(Run &r, LevelBuf &Lv, const TvWarp &w, long long *nlaunch)
 {
-    const int sem = r.h->P.semantics;
     float *const mu1[2] = {Lv.u[0][0], Lv.u[1][0]}, *const mu2[2] = {Lv.u[0][1], Lv.u[1][1]};
     const int nb = (int)w.blocks.size();
     int rc;
@@ -487,10 +490,9 @@ int run_blocked(Run &r, LevelBuf &Lv, const TvWarp &w, long long *nlaunch)
             ++*nlaunch;
             if (w.skip_iterations) { r.first_of_scale = false; continue; }
             const bool last_pass = w.skip_p_last && no == w.outer - 1 && k == nb - 1;
-            rc = w.form == TvForm::ExactBlocked ? iterate_tb_exact(w.blocks[k], r.planes, Lv.g, r.l_t, r.theta, r.taut, r.first_of_scale, r.cur, r.st)
-               : w.fused ? iterate_tb_fused(sem, Lv.I0, Lv.I1, r.h->cubic_tab, w.blocks[k], r.planes, Lv.g, r.l_t, r.theta, r.taut,
-                                            r.first_of_scale, r.cur, r.st, last_pass)
-                         : iterate_tb(w.blocks[k], r.planes, Lv.g, r.l_t, r.theta, r.taut, r.first_of_scale, r.cur, 0, r.st, last_pass, false,
+            rc = w.fused ? iterate_tb_fused(w.run[k], Lv.I0, Lv.I1, r.h->cubic_tab, r.planes, Lv.g, r.l_t, r.theta, r.taut, r.first_of_scale, r.cur,
+                                            r.st, last_pass)
+                         : iterate_tb(w.run[k], w.blocks[k], r.planes, Lv.g, r.l_t, r.theta, r.taut, r.first_of_scale, r.cur, r.st, last_pass,
                                       last_pass && w.pack_in_pass ? r.ln.tab.p : nullptr);
             if (rc) return rc;
             r.cur ^= 1;
@@ -643,7 +645,9 @@ int run_spec(Run &r, LevelBuf &Lv, const TvWarp &w, int s, int wp, long long *nl
         }
         MI_REQUIRE((long long)r.e_next + T <= ln.Q && r.q < ln.Q, MI_ERR_BAD_ARG,
                    "speculative steps: error-sum slot %d + %d or launch slot %d beyond the %lld slots sized for this calc", r.e_next, T, r.q, ln.Q);
-        if ((rc = iterate_tb_spec(T, r.planes, Lv.g, r.l_t, r.theta, r.taut, false, a, sk, r.e_next, r.st))) return rc;
+        // (the host feedback's cost model may have changed the block lengths: the same rule picks their kernel)
+        const TbKernel kern = tb_kernel(TbUse::Spec, T, Lv.g, r.h->P.gamma != 0.0, w.nograd, r.K);
+        if ((rc = iterate_tb_spec(kern, T, r.planes, Lv.g, r.l_t, r.theta, r.taut, a, sk, r.e_next, r.st))) return rc;
         ln.slots.push_back({s, wp});
         r.q_last = r.q++;
         ++*nlaunch;

@@ -84,20 +84,18 @@ int warp_fused(int semantics, bool fast, int lds, const float *I0, const float *
 int iterate(bool exact, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut,
             bool p_zero, const Ctl *ctl, int cur_host, hipStream_t s);
 
-// Temporally blocked fast-math iteration (tvl1_tbr_kernels.hip): T fused iterations in one HBM pass,
-// set cur -> cur^1.  Supported T: 1,2,3,4,5,6,8,10.  rows_per_band = 0: the plan decides (register tiles on small levels), -1: the
-// streaming kernel with the planner's band height, > 0: the streaming kernel with that band height.
-// skip_p_out: the launch stores u only (the last pass of a scale: nobody reads its p).  pl.g == nullptr: no |grad|^2 plane, the kernel
-// forms it from I1wx, I1wy (only where tb_nograd_ok, tvl1_plan.h, says so -- or anywhere with a streaming kernel forced, rows_per_band != 0)
-// independent_waves (test hook of the stage-level entry): the kernel whose waves each own a 64-column strip, never the joined form
-// out_tab (with skip_p_out, two-channel streaming kernels only): the pass writes the flow interleaved into the callers' MI_32FC2
-// matrices (tab.out / tab.step_out of each pair) instead of the u planes of set cur^1 -- the calc's final pass, no pack_flow behind it
-int iterate_tb(int T, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut, bool p_zero,
-               int cur, int rows_per_band, hipStream_t s, bool skip_p_out = false, bool independent_waves = false,
-               const PtrTab *out_tab = nullptr);
-// the warp of a one-pass warp INSIDE that pass (k_iterate_tbr FW, where tb_fused_ok says so): no warp launch, no I1wx / I1wy / rho_c
+// Temporally blocked iteration (tvl1_tbr_kernels.hip): T fused iterations in one HBM pass, set cur -> cur^1, on the kernel k the plan
+// or the stage-level entry chose (tvl1_plan.h tb_kernel): the register tile, or a streaming row in fast or exact math (the latter
+// bit-identical to T one-iteration launches of iterate(exact = true)).
+// skip_p_out: the launch stores u only (the last pass of a scale: nobody reads its p).  pl.g == nullptr: no |grad|^2 plane (k forms it
+// from I1wx, I1wy).  out_tab (with skip_p_out, rows with tb_il_form only): the pass writes the flow interleaved into the callers'
+// MI_32FC2 matrices (tab.out / tab.step_out of each pair) instead of the u planes of set cur^1 -- the calc's final pass, no pack_flow
+// behind it
+int iterate_tb(const TbKernel &k, int T, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut, bool p_zero, int cur,
+               hipStream_t s, bool skip_p_out = false, const PtrTab *out_tab = nullptr);
+// the warp of a one-pass warp INSIDE that pass (a row with FW, where tb_fused_ok says so): no warp launch, no I1wx / I1wy / rho_c
 // planes in HBM; bit-identical
-int iterate_tb_fused(int semantics, const float *I0, const float *I1, const float *cubic_tab_dev, int T, const IterPlanes &pl, const Geo &g,
+int iterate_tb_fused(const TbKernel &k, const float *I0, const float *I1, const float *cubic_tab_dev, const IterPlanes &pl, const Geo &g,
                      float l_t, float theta, float taut, bool p_zero, int cur, hipStream_t s, bool skip_p_out);
 // Register-tile formulation of the same fused iterations for the small pyramid levels (tvl1_tile_kernels.hip): nit in
 // 1..kTileMaxBlock iterations per launch, bit-identical to iterate_tb.  variant < 0: default of the table.
@@ -105,18 +103,8 @@ int iterate_tile(int variant, int nit, const IterPlanes &pl, const Geo &g, float
                  hipStream_t s);
 int tile_owned_rows();   // rows a tile of the default variant owns
 int tile_shape_rows(int variant);   // rows (owned + margins) of the tiles of a variant
-int tb_query_plan(int T, const Geo &g, int *kernel, int *rows);   // kernel 0 = streaming (band height), 1 = register tile
+int plan_band_rows(const TbRow &row, const Geo &g);   // the planner's band height of a streaming row on level g
 int tile_variants();
-// block lengths T (bit T) whose streaming kernel can store the flow interleaved into the callers' matrices (iterate_tb out_tab); bit 31:
-// the T = 10 kernel without a |grad|^2 plane can
-unsigned tb_interleave_mask();
-// the same in exact math (bit-identical to T one-iteration launches of iterate(exact = true)); T in 1..kTbExactMaxBlock.
-// rows_per_band <= 0: the planner's band height
-int iterate_tb_exact(int T, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut, bool p_zero, int cur, hipStream_t s,
-                     int rows_per_band = 0);
-// which kernels of block length T exist (the stage-level entry refuses what no table holds before it enqueues anything): kind 0 = the
-// streaming kernel iterate_tb picks, 1 = its independent-wave kernel, 2 = the exact-math blocks, 3 = the speculative steps
-bool tb_kernel_exists(int kind, int T, bool gam, bool nograd);
 // Speculative step of the convergence-checked path (k_iterate_tbr MODE 1), host-side constants of one launch.
 struct SpecK {
     int4 *X;            // per slot: {iterations accepted in this warp, iterations this launch ran speculatively (0: none),
@@ -140,14 +128,12 @@ struct SpecK {
     int fb_seq;
 };
 
-// the same step on register tiles (tvl1_tile_kernels.hip); iterate_tb_spec dispatches to it where runs_on_tiles(.., spec = true)
+// the same step on register tiles (tvl1_tile_kernels.hip); iterate_tb_spec runs it where the kernel it is handed is the tile
 // (variant < 0: by the size of the grid, tile_auto_variant)
 int iterate_tile_spec(int T, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut, const Ctl &ctl, const SpecK &sk, int e0,
                       hipStream_t s, int variant = -1);
-// rows_per_band as in iterate_tb: 0 = the plan decides (register tiles on small levels), -1 = the streaming kernel with the planner's
-// band height, > 0 = the streaming kernel with that band height
-int iterate_tb_spec(int T, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut, bool p_zero, const Ctl &ctl,
-                    const SpecK &sk, int e0, hipStream_t s, int rows_per_band = 0);
+int iterate_tb_spec(const TbKernel &k, int T, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut, const Ctl &ctl,
+                    const SpecK &sk, int e0, hipStream_t s);
 int dbg_lane_shift(int *out_dev, hipStream_t s);
 int tb_jw_fault(int *fault_host);   // sticky fault flag of the joined-wave blocked kernels (synchronises the device)
 

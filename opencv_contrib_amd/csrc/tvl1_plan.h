@@ -5,6 +5,7 @@
 // Reference: OpticalFlowDual_TVL1_Impl::calcImpl / procOneScale, cudaoptflow/src/tvl1flow.cpp:185-382.
 #pragma once
 #include "miflow/c_api.h"
+#include "tvl1_tb_table.h"
 #include <algorithm>
 #include <array>
 #include <cmath>
@@ -28,7 +29,7 @@ constexpr int kTbExactMaxBlock = 5;    // ... of the exact-math blocks (MODE 2)
 constexpr int kTileMaxBlock = 10;      // ... of the register-tile kernel (its margin, TILE_M)
 constexpr double kLargeLevel = 12e6;   // px x pairs from which the T = 10 kernel pays for a long first speculative block
 
-// The tuning switches and kernel-table facts a plan depends on (tvl1_api.cpp tv_knobs() fills them once from tuning() and the tables).
+// The tuning switches and register-tile facts a plan depends on (tvl1_api.cpp tv_knobs() fills them once from tuning()).
 struct TvKnobs {
     long long tile_maxpx;            // levels of at most this many pixels x pairs run on the register-tile kernel (0: never) ...
     int tile_spec;                   // ... the speculative steps too
@@ -36,11 +37,12 @@ struct TvKnobs {
                                                                      // threshold / shapes in the table and their rows (owned + margins)
     int tile_fb_block, tile_fb_model;   // one-or-two-pair calcs on tiles: block length / cost model's us per pass (0: off)
     bool tb_force;                   // greedy blocks of exactly the cap (tuning sweeps)
-    int tb_nograd, tb_jw, tb_ppl, tb_jw_spec;   // which blocked kernels exist without a |grad|^2 plane
+    int tb_nograd, tb_jw, tb_jw_spec;   // the warp leaves |grad|^2 to the passes / joined-wave form of the T = 10 pass / ... of the speculative steps too
+    int tb_ppl, tb_wps, tb_pf;       // MIFLOW_TB_VARIANT: the alternative row of a block length (-1: the default row)
+    int tb_p16;                      // p as snorm16 between passes (experiments build)
+    int tb_il;                       // the calc's final pass writes the flow into the callers' matrices itself (0: k_pack_flow behind every calc)
     int tb_fw;                       // warp fused into the pass (experiments build; 0 in the release library)
     int tb_skip_p, tb_hist, spec, exact_tb;
-    unsigned tb_il_mask;             // block lengths T (bit T; bit 31: T = 10 without a |grad|^2 plane) whose streaming kernel can write the
-                                     // flow into the callers' matrices itself (0: never -- k_pack_flow behind every calc)
     int fb_poll, fb_ahead;
     int warp_fast, warp_lds, x_skip;
 };
@@ -57,10 +59,65 @@ inline bool runs_on_tiles(const Geo &g, int T, const TvKnobs &K, bool spec = fal
 {
     return tile_eligible(g, K) && T <= kTileMaxBlock && (spec ? K.tile_spec != 0 : !K.tb_force);
 }
-// the launch iterate_tb(T) makes can run without a |grad|^2 plane: the default joined-wave T = 10 kernel on a streaming level
+
+// ---- which kernel runs a block ------------------------------------------------------------------------------------------------------
+enum class TbUse { Fixed, Indep, Exact, Spec };   // fixed work / ... on independent waves only (test hook) / exact-math blocks / speculative steps
+
+// THE selection rule of the streaming kernels: the row of kTbRows that runs T iterations, or nullptr where the build has none.
+// gam: the illumination channel (its own rows, which never read a |grad|^2 plane); nograd: no plane is stored; fw: the warp inside the
+// pass (1 / 2, fixed work).  Fixed work with a plane takes the joined-wave row of MIFLOW_TB_JW where one of that length exists, else the
+// independent-wave row named by MIFLOW_TB_VARIANT, else the first one; the speculative steps with a plane take the joined or independent
+// row that reads it where the build has one (experiments), else the row that forms |grad|^2 itself and ignores the stored plane.
+inline const TbRow *tb_select(TbUse use, int T, bool gam, bool nograd, const TvKnobs &K, int fw = 0)
+{
+    const int mode = use == TbUse::Spec ? 1 : use == TbUse::Exact ? 2 : 0;
+    const auto first = [&](auto pred) -> const TbRow * {
+        for (const TbRow &r : kTbRows)
+            if (r.MODE == mode && r.T == T && r.GAM == gam && (r.FW != 0) == (fw != 0) && pred(r)) return &r;
+        return nullptr;
+    };
+    const auto any = [](const TbRow &) { return true; };
+    const auto indep = [](const TbRow &r) { return r.JW == 0 && !r.NG; };
+    if (use == TbUse::Exact) return gam || nograd ? nullptr : first(any);
+    if (use == TbUse::Indep) return nograd ? nullptr : gam ? first([](const TbRow &r) { return r.JW == 0; }) : first(indep);
+    if (gam) return first(any);
+    if (use == TbUse::Spec) {
+        const TbRow *reads = nograd ? nullptr : (K.tb_jw >= 2 && K.tb_jw_spec) ? first([](const TbRow &r) { return r.JW == 2 && !r.NG; }) : first(indep);
+        return reads ? reads : first([](const TbRow &r) { return r.NG; });
+    }
+    if (fw) return first([&](const TbRow &r) { return r.FW == fw; });
+    if (nograd) return first([&](const TbRow &r) { return r.NG && r.P16 == (K.tb_p16 != 0); });
+    if (K.tb_jw && K.tb_ppl < 0)
+        if (const TbRow *joined = first([&](const TbRow &r) { return r.JW == K.tb_jw && !r.NG; })) return joined;
+    const TbRow *variant = first([&](const TbRow &r) { return indep(r) && r.PPL == K.tb_ppl && r.WPS == K.tb_wps && r.PF == K.tb_pf; });
+    return variant ? variant : first(indep);
+}
+
+// What runs one block: the register tile, or a streaming row with the planner's band height (rows = 0) or a given one.  Neither: the
+// build has no kernel of that length (the launch reports it).
+struct TbKernel {
+    bool tile;
+    const TbRow *row;
+    int rows;
+};
+// What a caller outside the plan may force (the stage-level entry, tvl1_stage_api.cpp); lane_calc passes none.
+struct TbOverride {
+    bool force_streaming;     // never the register tile
+    int rows;                 // band height (0: the planner's)
+    bool independent_waves;   // fixed work on the independent-wave row of the block length
+};
+inline TbKernel tb_kernel(TbUse use, int T, const Geo &g, bool gam, bool nograd, const TvKnobs &K, const TbOverride &o = TbOverride{})
+{
+    if (!o.force_streaming && (use == TbUse::Fixed || use == TbUse::Spec) && runs_on_tiles(g, T, K, use == TbUse::Spec))
+        return TbKernel{true, nullptr, 0};
+    return TbKernel{false, tb_select(o.independent_waves ? TbUse::Indep : use, T, gam, nograd, K), o.rows};
+}
+
+// a fixed-work pass of T iterations can do without a stored |grad|^2 plane: the default joined-wave kernel has a row that forms it, on a
+// streaming level
 inline bool tb_nograd_ok(int T, const Geo &g, const TvKnobs &K)
 {
-    return K.tb_nograd && T == 10 && K.tb_jw == 2 && K.tb_ppl < 0 && !runs_on_tiles(g, T, K);
+    return K.tb_nograd && K.tb_jw == 2 && K.tb_ppl < 0 && !runs_on_tiles(g, T, K) && tb_select(TbUse::Fixed, T, false, true, K);
 }
 // the same for the speculative steps (the register-tile kernel reads the stored plane)
 inline bool tb_spec_nograd_ok(const Geo &g, const TvKnobs &K)
@@ -122,7 +179,7 @@ inline std::vector<int> tb_plan(int n, int cap, const TvKnobs &K)
     for (int i = n; i > 0; i -= pick[i]) blocks.push_back(pick[i]);
     return blocks;
 }
-// the same for level g: gamma != 0 takes greedy blocks of the lengths the channel's streaming kernels exist in (g_tbr_gam,
+// the same for level g: gamma != 0 takes greedy blocks of the lengths the channel's streaming kernels exist in (the GAM rows,
 // tvl1_tbr_kernels.hip); on the register-tile kernel any block up to the margin costs one launch: fewest launches win
 inline std::vector<int> tb_plan_level(const Geo &g, int n, int cap, bool gam, const TvKnobs &K)
 {
@@ -224,9 +281,10 @@ enum class TvForm {
 struct TvWarp {
     TvForm form;
     std::vector<int> blocks;   // Blocked: the passes of one outer iteration; ExactBlocked: all passes; Spec: the speculative blocks
+    std::vector<TbKernel> run; // what runs each of them (tb_kernel); the three flags below are read from it
     int outer;                 // Blocked: outer iterations (the median filter runs before each); 1 otherwise
     bool on_tiles;             // Spec: the steps run on the register-tile kernel
-    bool nograd;               // the warp does not store |grad|^2 (every pass forms it from I1wx, I1wy)
+    bool nograd;               // the warp does not store |grad|^2 (no kernel of `run` reads the plane)
     bool fused;                // the warp runs inside its single pass (k_iterate_tbr FW): no warp launch
     bool warp_launch;          // the warp is enqueued (not fused, not dropped by the MIFLOW_X_SKIP=1 timing experiment)
     bool skip_iterations;      // MIFLOW_X_SKIP=2 timing experiment: the blocked passes are counted, not enqueued
@@ -396,38 +454,40 @@ inline TvPlan tv_make_plan(const TvShape &S, const TvKnobs &K)
             w.form = TvForm::Blocked;
             w.outer = p.median ? P.iterations : 1;
             w.blocks = tb_plan_level(g, p.median ? P.inner_iterations : p.iters, P.time_block > 0 ? P.time_block : kTbMaxBlock, gam, K);
-            // where every pass is the default T = 10 kernel the warp does not store |grad|^2 (the illumination channel's kernels never
-            // read the plane)
+            // where every pass can form |grad|^2 itself the warp does not store it (the illumination channel's kernels never read the plane)
             w.nograd = !w.blocks.empty();
             for (int v : w.blocks) w.nograd = w.nograd && (gam || tb_nograd_ok(v, g, K));
+            for (int v : w.blocks) w.run.push_back(tb_kernel(TbUse::Fixed, v, g, gam, w.nograd, K));
             w.fused = !gam && w.nograd && w.blocks.size() == 1 && !p.median && K.x_skip == 0 && K.warp_lds == 0 &&
                       tb_fused_ok(w.blocks[0], g, P.semantics, p.fast_warp, K);
+            if (w.fused) w.run[0].row = tb_select(TbUse::Fixed, w.blocks[0], false, true, K, P.semantics == MI_SEM_CPU_REF ? 1 : 2);
             w.skip_iterations = K.x_skip == 2;
         } else if (exact_blocked) {
             w.form = TvForm::ExactBlocked;
             const int cap = P.time_block > 0 ? std::min(P.time_block, kTbExactMaxBlock) : kTbExactMaxBlock;
             for (int left = p.iters; left > 0; left -= w.blocks.back()) w.blocks.push_back(std::min(left, cap));
+            for (int v : w.blocks) w.run.push_back(tb_kernel(TbUse::Exact, v, g, false, false, K));
         } else if (p.spec) {
             w.form = TvForm::Spec;
-            w.on_tiles = tile_eligible(g, K) && K.tile_spec != 0;
-            w.nograd = gam || tb_spec_nograd_ok(g, K);   // every block is a tbr launch
+            w.nograd = gam || tb_spec_nograd_ok(g, K);
         } else
             w.form = TvForm::PerIter;
         p.warp[s].assign(P.warps, w);
         for (int wp = 0; wp < P.warps; ++wp) {
             TvWarp &x = p.warp[s][wp];
-            if (x.form == TvForm::Spec)
+            if (x.form == TvForm::Spec) {
+                // (all steps of a level run on the tiles or none does: every list's blocks are within the tile margin)
+                x.on_tiles = tb_kernel(TbUse::Spec, kTileMaxBlock, g, gam, x.nograd, K).tile;
                 x.blocks = spec_list[x.on_tiles ? 3 : wp > 0 ? 2 : ((double)g.w * g.h * B >= kLargeLevel ? 0 : 1)];
+                for (int v : x.blocks) x.run.push_back(tb_kernel(TbUse::Spec, v, g, gam, x.nograd, K));
+            }
             x.warp_launch = !x.fused && !(K.x_skip == 1 && wp > 0);
             x.skip_p_last = x.form == TvForm::Blocked && K.tb_skip_p && wp == P.warps - 1 && !p.median;
-            // the flow straight into the callers' matrices: the fixed-work blocked form whose last pass runs on a streaming kernel that
+            // the flow straight into the callers' matrices: the fixed-work blocked form whose last pass runs on a streaming row that
             // has the interleaved store (two channels, one pixel per lane); register tiles, the speculative steps, the fused warp and
             // calcs that read the callers' matrices first (use_initial_flow) keep pack_flow
-            if (s == 0 && x.skip_p_last && !gam && !x.fused && !x.skip_iterations && !P.use_initial_flow && !x.blocks.empty()) {
-                const int tl = x.blocks.back();
-                x.pack_in_pass = !runs_on_tiles(g, tl, K) && tl < 31 &&
-                                 ((x.nograd ? K.tb_il_mask >> 31 : K.tb_il_mask >> tl) & 1u) != 0;
-            }
+            if (s == 0 && x.skip_p_last && !gam && !x.fused && !x.skip_iterations && !P.use_initial_flow && !x.blocks.empty())
+                x.pack_in_pass = K.tb_il != 0 && x.run.back().row && tb_il_form(*x.run.back().row);
         }
     }
     return p;

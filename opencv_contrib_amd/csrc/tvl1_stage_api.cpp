@@ -176,8 +176,8 @@ int mi_tvl1_iterate(int exact_math, int time_block, int niter, const mi_mat *I1w
         }
         if (blocked) {
             const int T = greedy_blocks(std::min(niter - it, 10), time_block, {1, 2, 3, 4, 5, 6, 8, 10})[0];   // the largest supported block
-            // rows_per_band = -1: always the streaming kernel (the tile kernel is compared against it)
-            TRY(iterate_tb(T, pl, g, l_t, theta, taut, false, cur, -1, st, false, indep));
+            // always the streaming kernel (the tile kernel is compared against it)
+            TRY(iterate_tb(tb_kernel(TbUse::Fixed, T, g, false, false, tv_knobs(), TbOverride{true, 0, indep}), T, pl, g, l_t, theta, taut, false, cur, st));
             it += T;
             cur ^= 1;
             continue;
@@ -206,7 +206,7 @@ int mi_tvl1_iterate(int exact_math, int time_block, int niter, const mi_mat *I1w
 
 // The iterations in the forms calc() runs them (c_api.h, mi_tvl1_stage_desc).  Everything the descriptor asks for is checked before
 // the first byte is staged; the launches are those of lane_calc's executors (tvl1_api.cpp run_blocked, run_per_iteration, run_spec) with
-// the streaming kernels forced where a form names them (rows_per_band != 0 in iterate_tb / iterate_tb_spec).
+// the streaming kernels forced where a form names them (TbOverride).
 int mi_tvl1_iterate_stage(const mi_tvl1_stage_desc *d, void *stream)
 {
     hipStream_t st = (hipStream_t)stream;
@@ -233,11 +233,14 @@ int mi_tvl1_iterate_stage(const mi_tvl1_stage_desc *d, void *stream)
     MI_REQUIRE(!(spec && d->blocks), MI_ERR_BAD_ARG, "the speculative steps run blocks of time_block");
 
     // the passes: the caller's block list, or greedy blocks of at most time_block over the lengths the form's table holds
-    const int kind = form == MI_TVL1_STAGE_INDEP ? 1 : form == MI_TVL1_STAGE_EXACT_BLOCKED ? 2 : spec ? 3 : 0;
+    const TbUse use = form == MI_TVL1_STAGE_EXACT_BLOCKED ? TbUse::Exact : spec ? TbUse::Spec : TbUse::Fixed;
+    const TbOverride forced{true, d->rows_per_band, form == MI_TVL1_STAGE_INDEP};   // the streaming forms: never the tile, the caller's band height
+    Geo g{};   // (a forced kernel does not depend on the level)
+    auto kernel = [&](int T) { return tb_kernel(use, T, g, gam, ng, tv_knobs(), forced); };
     auto exists = [&](int T) {
         if (form == MI_TVL1_STAGE_ONE) return T == 1;
         if (tiles) return T >= 1 && T <= kTileMaxBlock;
-        return tb_kernel_exists(kind, T, gam, ng);
+        return kernel(T).row != nullptr;
     };
     std::vector<int> blocks;
     if (form == MI_TVL1_STAGE_ONE) {
@@ -282,7 +285,7 @@ int mi_tvl1_iterate_stage(const mi_tvl1_stage_desc *d, void *stream)
         TRY(check_f32(m, "plane"));
         MI_REQUIRE(m->rows == d->I1wx->rows && m->cols == d->I1wx->cols, MI_ERR_BAD_SIZE, "plane size mismatch");
     }
-    Geo g = geo_of(d->I1wx->cols, d->I1wx->rows / B);
+    g = geo_of(d->I1wx->cols, d->I1wx->rows / B);
     g.batch = B;
 
     Stage S;
@@ -348,7 +351,7 @@ int mi_tvl1_iterate_stage(const mi_tvl1_stage_desc *d, void *stream)
             a.q = k; a.q_prev = k - 1; a.first_of_warp = (k == 0); a.reset_cur = (k == 0); a.n = 0;
             sk.e0_prev = e_prev; sk.final_launch = last ? 1 : 0; sk.t_after = t_after;
             TRY(tiles ? iterate_tile_spec(T, pl, g, d->l_t, d->theta, d->taut, a, sk, e_next, st, d->variant)
-                      : iterate_tb_spec(T, pl, g, d->l_t, d->theta, d->taut, false, a, sk, e_next, st, d->rows_per_band > 0 ? d->rows_per_band : -1));
+                      : iterate_tb_spec(kernel(T), T, pl, g, d->l_t, d->theta, d->taut, a, sk, e_next, st));
             e_prev = e_next;
             if (!last) e_next += T;
         }
@@ -366,7 +369,6 @@ int mi_tvl1_iterate_stage(const mi_tvl1_stage_desc *d, void *stream)
         for (int k = 0; k < nb; ++k) {
             const int T = blocks[k];
             const bool pzk = pz && k == 0;
-            const int rows = d->rows_per_band > 0 ? d->rows_per_band : -1;
             switch (form) {
             case MI_TVL1_STAGE_ONE:
                 if (check) {
@@ -379,13 +381,11 @@ int mi_tvl1_iterate_stage(const mi_tvl1_stage_desc *d, void *stream)
                 break;
             case MI_TVL1_STAGE_BLOCKED:
             case MI_TVL1_STAGE_INDEP:
-                TRY(iterate_tb(T, pl, g, d->l_t, d->theta, d->taut, pzk, cur, rows, st, false, form == MI_TVL1_STAGE_INDEP));
+            case MI_TVL1_STAGE_EXACT_BLOCKED:
+                TRY(iterate_tb(kernel(T), T, pl, g, d->l_t, d->theta, d->taut, pzk, cur, st));
                 break;
             case MI_TVL1_STAGE_TILE:
                 TRY(iterate_tile(d->variant, T, pl, g, d->l_t, d->theta, d->taut, pzk, cur, st));
-                break;
-            case MI_TVL1_STAGE_EXACT_BLOCKED:
-                TRY(iterate_tb_exact(T, pl, g, d->l_t, d->theta, d->taut, pzk, cur, st, d->rows_per_band));
                 break;
             }
             cur ^= 1;

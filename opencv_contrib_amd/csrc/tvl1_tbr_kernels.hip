@@ -26,6 +26,7 @@
 // kernel is tested with a stated tolerance (tests/test_tvl1_gpu.py).
 #include "tvl1_tb_dev.h"
 #include "tvl1_warp_px.h"
+#include <array>
 #include <type_traits>
 #include <utility>
 #include <cstdlib>
@@ -296,9 +297,7 @@ struct CtxR {
 // waiting cannot starve.  In steady state a wave trails its left neighbour by one to T stages.  Two buffers suffice: the writer of
 // a slot depends (through the opposite dependence) on the reader having passed the slot's previous use.  Data is written before
 // its tag and read after it; LDS executes a wave's DS operations in order.
-constexpr int XS = 32;   // bytes per slot: {p11, p21 | u1, u2 | tag | pad}
-__host__ __device__ constexpr int xarea_bytes(int T) { return 2 * T * XS; }
-__host__ __device__ constexpr int xdump_bytes(int T) { return 2 * T * XS + 64 * 8; }   // where the 63 non-publishing lanes write
+// (XS = 32 bytes per slot {p11, p21 | u1, u2 | tag | pad}, xarea_bytes, xdump_bytes: tvl1_tb_table.h)
 // pointers into LDS keep their address space (a generic pointer makes every access a flat_load / flat_store)
 #define MI_LDS __attribute__((address_space(3)))
 typedef MI_LDS char *lds_ptr;
@@ -335,12 +334,9 @@ __device__ __forceinline__ void xwrite(unsigned slot, int data_off, int tag_off,
 // bytes {p11, p21, u1, u2}: one ds_read_b128 per stage, two exec-masked ds_write_b64 (only lane 63 / lane 0 publish: no dump area,
 // 38.2 KB of LDS per workgroup = four workgroups per CU like the independent-wave kernel).  s_waitcnt lgkmcnt(0) + s_barrier, NOT
 // __syncthreads: the latter also waits for the row prefetches and stores in flight (vmcnt).
-constexpr int XS2 = 16;
 // GAM: a slot is 32 bytes {p11, p21, u1, u2 | p31, u3, -, -}: the third component's two hand-over values behind the sixteen bytes of the
-// two-channel form (one more ds_read_b64 per stage, one more exec-masked ds_write_b32 per publish)
-__host__ __device__ constexpr int xs2_bytes(bool gam) { return gam ? 32 : XS2; }
-// waves of a joined group: JW = 1, 2: four (a 256-column strip); JW = 3: eight (512 columns: 492 owned instead of 2 x 236), barrier form
-__host__ __device__ constexpr int jw_waves(int JW) { return JW == 3 ? 8 : 4; }
+// two-channel form (one more ds_read_b64 per stage, one more exec-masked ds_write_b32 per publish).  (XS2, xs2_bytes, xarea2_bytes,
+// jw_waves: tvl1_tb_table.h)
 // Stages per barrier interval.  With a constant SKEW of XK stages between neighbouring waves (wave w runs XK * w stages behind wave 0:
 // it passes w barriers before its first step) a barrier every XK stages is enough: in global stage index g = step * T + stage, wave w
 // executes g in interval floor(g / XK) + w; its left input comes from wave w-1's g - 1, executed in interval floor((g - 1) / XK) + w - 1
@@ -349,7 +345,6 @@ __host__ __device__ constexpr int jw_waves(int JW) { return JW == 3 ? 8 : 4; }
 // its global index is a multiple of XK; the step index enters through the compile-time phase k of the unrolled block (the block's
 // first step n0 is a multiple of P, and P * T is a multiple of XK: checked in the kernel).
 __host__ __device__ constexpr int xk_stages(int T) { return T >= 10 && T % 5 == 0 ? 5 : T >= 4 ? 2 : 1; }
-__host__ __device__ constexpr int xarea2_bytes(int T, bool gam = false) { return 2 * T * xs2_bytes(gam); }
 __device__ __forceinline__ void xbarrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 __device__ __forceinline__ void xread2(unsigned slot, float &l1, float &l2, float &r1, float &r2)
 {
@@ -385,8 +380,6 @@ __device__ __forceinline__ void xwrite2f(unsigned addr, float a, float b)
     f2 v; v.x = a; v.y = b;
     *reinterpret_cast<volatile MI_LDS f2 *>((lds_ptr)(unsigned long long)addr) = v;
 }
-__host__ __device__ constexpr int xdump4_bytes(int T) { return 64 * 8 + 2 * xarea2_bytes(T) + 64; }   // per workgroup, shared by its waves
-__host__ __device__ constexpr bool jw_fast(int JW) { return JW == 4; }
 __device__ int g_jw_fault;   // sticky: a bounded wait on a neighbouring wave ran out (never expected; results are then invalid)
 
 // ---- fused warp (FW; round 5): the warp INSIDE the pass kernel -- cudaoptflow/src/cuda/tvl1flow.cu:89-164 feeding :187-348 (CPU class:
@@ -407,9 +400,7 @@ __device__ int g_jw_fault;   // sticky: a bounded wait on a neighbouring wave ra
 //
 // The producer's own latency is hidden by software pipelining: the window gathers of row m+2 and the flow / I0 loads of row m+4 are
 // issued when row m is finished, and consumed two whole pipeline steps later.
-constexpr int FW_RING = 4;         // inbox slots (rows) per consumer wave: two rows of lead + the two steps of consumer skew
-constexpr int FW_SLOT = 3 * 64;    // floats per slot
-__host__ __device__ constexpr int fw_lds_floats(int NW) { return NW * FW_RING * FW_SLOT + 128; }   // inboxes + the cubic phase table
+// (FW_RING inbox slots per consumer wave of FW_SLOT floats, fw_lds_floats, FW_STAGE: tvl1_tb_table.h)
 template <int PPL>
 __device__ __forceinline__ void fw_inbox_get(const float *slot, int lane, Stat<PPL> &s)
 {
@@ -418,9 +409,6 @@ __device__ __forceinline__ void fw_inbox_get(const float *slot, int lane, Stat<P
 }
 template <int FW> struct FwSem { static constexpr int sem = FW == 2 ? MI_SEM_CUDA_COMPAT : MI_SEM_CPU_REF; static constexpr bool fast = FW == 2; };
 
-#ifndef FW_STAGE
-#define FW_STAGE 0   // 0 (default): the producers gather their windows (fw_produce); 1: they read them from a private LDS band of I1 (fw_produce_staged) -- bit-identical, measured no faster (r14g, r14h: 1 093 - 1 180 against 1 205 pairs/s): the fused form is bound by VALU issue, not by the gathers
-#endif
 #ifndef FW_X
 #define FW_X 0   // experiments build only: 1 = the producers write zeros (no loads, no arithmetic), 2 = arithmetic without loads -- wrong results
 #endif
@@ -520,10 +508,7 @@ __device__ __forceinline__ void fw_produce(const TbArgs &A, float *inbox, const 
 // with immediate offsets.  I1 is read from HBM once per strip (+ the column margins) instead of six times through L2.  A lane whose window
 // leaves the staged band (flow further than FWS_D from the band's mean, e.g. across a motion boundary) gathers it from global memory as
 // before, synchronously: same values, same sums -- bit-identical whichever path a pixel takes.
-constexpr int FWS_D1 = 5, FWS_D2 = 8;
-constexpr int FWS_CW = 64 + 2 * FWS_D1 + 6;    // 80 columns (with 88 the workgroup needs exactly 80 KB of LDS and only one fits a CU)
-constexpr int FWS_NR = 2 * FWS_D2 + 6;         // 22 rows: the six window rows of every flow within +- FWS_D2 of the band's mean
-__host__ __device__ constexpr int fws_lds_floats(int NW) { return NW * FWS_NR * FWS_CW; }
+// (FWS_D1, FWS_D2, FWS_CW x FWS_NR, fws_lds_floats: tvl1_tb_table.h)
 
 template <int FW, int NW>
 __device__ __forceinline__ void fw_produce_staged(const TbArgs &A, float *inbox, const float *tab, float *ring, int lane, int xw, int ystart,
@@ -647,10 +632,6 @@ __device__ __forceinline__ void fw_produce_staged(const TbArgs &A, float *inbox,
 #undef FWS_STEP
     for (int i = 0; i < NW - 1; ++i) xbarrier();   // the consumers' skew
 }
-
-// The kernels that can store the flow interleaved into the callers' matrices (TbArgs::otab): one pixel per lane, and not the joined waves
-// that read a |grad|^2 plane -- that kernel sits at exactly 128 VGPRs and no calc's final pass runs on it (tb_nograd_ok picks the NG form)
-__host__ __device__ constexpr bool tb_il_form(int PPL, int JW, bool NG) { return PPL == 1 && (NG || JW == 0); }
 
 // The kernels whose first block is the fill form (step_r FILLB).  Two kernels at their register limit keep their single block: the T = 10
 // joined waves that read p AND a |grad|^2 plane (the stage entry and MIFLOW_TB_NOGRAD=0 reach it; no default calc does) sit at exactly
@@ -961,7 +942,7 @@ __global__ __launch_bounds__((JW == 3 || FW) ? 512 : 256, WPS) void k_iterate_tb
     constexpr int LW = (JW ? 64 * NW : 64) * PPL;  // pixels a strip covers: a wave, or the joined waves of a workgroup
     constexpr int STRIDE = LW - 2 * M;             // owned columns of the strips >= 1 (strip 0 owns LW - M)
     constexpr int P = T + 1 + PF;                  // register sets
-    constexpr int K = T > 2 ? T - 1 : 1;           // LDS ring slots: the row of step n is read by stages 2..T-1 at steps n+2..n+T-1
+    constexpr int K = tb_ring_slots(T);            // LDS ring slots: the row of step n is read by stages 2..T-1 at steps n+2..n+T-1
     // (r19b: a static s_setprio 1 here changes nothing -- 1 412 against 1 416 pairs/s --, s_setprio 2 on the warp kernel costs 2.5 %)
     extern __shared__ __attribute__((aligned(16))) float lds[];
     CtxR<PPL> c;
@@ -1146,22 +1127,20 @@ __global__ __launch_bounds__((JW == 3 || FW) ? 512 : 256, WPS) void k_iterate_tb
     }
 }
 
-template <int T, int PPL, int WPS, int PF, int MODE, int JW = 0, bool NG = false, bool P16 = false, int FW = 0, bool GAM = false>
+// Row I of the table (tvl1_tb_table.h): the library instantiates exactly the rows, and launches them from there.
+template <int I>
 static int launch_tbr(const TbArgs &A0, bool pz, hipStream_t s)
 {
-    constexpr int M = (T + PPL - 1) / PPL * PPL;
-    constexpr int NW = jw_waves(JW);
-    constexpr int LW = (JW ? 64 * NW : 64) * PPL;
-    constexpr int STRIDE = LW - 2 * M;
+    constexpr TbRow R = kTbRows[I];
+    constexpr int T = R.T, PPL = R.PPL, WPS = R.WPS, PF = R.PF, MODE = R.MODE, JW = R.JW, FW = R.FW;
+    constexpr bool NG = R.NG, P16 = R.P16, GAM = R.GAM;
     TbArgs A = A0;
-    A.nstrips = A.g.w <= LW - M ? 1 : 1 + div_up(A.g.w - (LW - M), STRIDE);
+    A.nstrips = tb_strips(R, A.g.w);
     A.swz = tuning().tb_swz == 1 ? 1 : 0;
     // JW: a workgroup is one band of a 256-column strip; otherwise four consecutive bands of a 64-column strip
     const dim3 grid(A.nstrips, JW ? div_up(A.g.h, A.rows_per_band) : div_up(div_up(A.g.h, A.rows_per_band), 4), A.g.batch);
-    constexpr size_t lds_bytes = (size_t)NW * (T > 2 ? T - 1 : 1) * 256 * PPL * sizeof(float) +
-                                 (JW >= 2 ? NW * xarea2_bytes(T, GAM) + (jw_fast(JW) ? xdump4_bytes(T) : 0) : JW ? 4 * (xarea_bytes(T) + xdump_bytes(T)) : 0) +
-                                 (FW ? (fw_lds_floats(NW) + (FW_STAGE ? fws_lds_floats(NW) : 0)) * sizeof(float) : 0);
-    constexpr int NTHREADS = 64 * NW * (FW ? 2 : 1);
+    constexpr size_t lds_bytes = tb_lds_bytes(R);
+    constexpr int NTHREADS = 64 * jw_waves(JW) * (FW ? 2 : 1);
     // once per instantiation (thread-safe function-local static), result checked on every launch
     static const hipError_t attr_rc = [] {
         hipError_t e = hipFuncSetAttribute((const void *)k_iterate_tbr<T, PPL, true, WPS, PF, MODE, JW, NG, P16, FW, GAM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
@@ -1184,309 +1163,101 @@ static int launch_tbr(const TbArgs &A0, bool pz, hipStream_t s)
     MI_HIP_TRY(hipGetLastError());
     return MI_OK;
 }
-
-// WPS = occupancy the register allocator is held to (launch bound); PLAN = waves/SIMD the band planner assumes.  r01s: the
-// T10 kernel is resident 4 waves/SIMD but fastest when the grid is cut for 3 (394 vs 340 G px-iter/s).
 typedef int (*TbLaunchFn)(const TbArgs &, bool, hipStream_t);
-struct TbrEntry {
-    int T, PPL, WPS, PF, PLAN;
-    TbLaunchFn launch, spec;
-    int JW;   // 1 / 2: joined waves (a workgroup = one band of a 256-column strip), hand-over by tags / by one barrier per stage
-    bool GAM; // the kernel carries the illumination channel (gamma != 0)
-};
-#define TBR(T, PPL, WPS, PF, PLAN) {T, PPL, WPS, PF, PLAN, launch_tbr<T, PPL, WPS, PF, 0>, nullptr, 0}
-// Ship what is used: the release library instantiates the kernels a release build can reach -- the barrier form of
-// the joined waves (JW = 2), the independent-wave blocks of the other lengths, the exact-math blocks, the illumination channel.  The
-// forms that lost their A/B (tags, eight joined waves, branch-free publishes, the fused warp, 16-bit dual storage, alternative register
-// shapes, MIFLOW_TB_JW = 0) exist under -DMIFLOW_EXPERIMENTS only (libmiflow_exp.so), where the digest tests of their bit-identity run.
-static const TbrEntry g_tbr_jw[] = {
-#ifdef MIFLOW_EXPERIMENTS
-                                     // joined waves with tags: the hand-over registers cost 14 VGPRs (3 waves/SIMD), rings + hand-over areas 40.7 KB of LDS = 3 workgroups per CU
-                                     {10, 1, 3, 2, 3, launch_tbr<10, 1, 3, 2, 0, 1>, nullptr, 1},
-                                     // eight joined waves (MIFLOW_TB_JW=3): 512-column strips, two workgroups of eight waves per CU
-                                     {10, 1, 4, 2, 3, launch_tbr<10, 1, 4, 2, 0, 3>, nullptr, 3},
-                                     // barrier form without exec-masked publishes and without border masks in interior blocks, hand-over
-                                     // values read a stage early (MIFLOW_TB_JW=4)
-                                     {10, 1, 4, 2, 3, launch_tbr<10, 1, 4, 2, 0, 4>, nullptr, 4},
-#endif
-                                     // barrier form (MIFLOW_TB_JW=2, the default): no read-ahead registers, no dump area: four waves/SIMD and four workgroups/CU
-                                     {10, 1, 4, 2, 3, launch_tbr<10, 1, 4, 2, 0, 2>, nullptr, 2}};
-// the default kernel without a |grad|^2 plane (tb_nograd_entry)
-static const TbrEntry g_tbr_ng = {10, 1, 4, 2, 3, launch_tbr<10, 1, 4, 2, 0, 2, true>, nullptr, 2};
-// ... and with the warp inside (FW: four producer waves beside the four joined consumers; two workgroups of eight waves per CU, i.e. two
-// CONSUMER waves per SIMD is what the band planner fills): [0] the CPU class's arithmetic, tap-by-tap sums; [1] cv::cuda's, separable sums
-#ifdef MIFLOW_EXPERIMENTS
-static const TbrEntry g_tbr_fw[] = {{10, 1, 4, 2, 2, launch_tbr<10, 1, 4, 2, 0, 2, true, false, 1>, nullptr, 2},
-                                    {10, 1, 4, 2, 2, launch_tbr<10, 1, 4, 2, 0, 2, true, false, 2>, nullptr, 2}};
-#endif
-// gamma != 0 (round 6): the blocked kernel with the illumination channel -- nine dynamic registers per set (T = 10:
-// three waves/SIMD), always without a |grad|^2 plane.  Blocks of 10 and 5 as joined waves, 2 and 1 as independent waves (any iteration
-// count decomposes greedily: tb_plan_gam, tvl1_plan.h)
-// (T = 10 with ONE prefetched row: 163 VGPRs = three waves/SIMD without scratch; with two it is 168 + 12 spilled dwords)
-static const TbrEntry g_tbr_gam[] = {{10, 1, 3, 1, 3, launch_tbr<10, 1, 3, 1, 0, 2, true, false, 0, true>, nullptr, 2, true},
-                                     {5, 1, 4, 2, 3, launch_tbr<5, 1, 4, 2, 0, 2, true, false, 0, true>, nullptr, 2, true},
-                                     {2, 1, 6, 2, 6, launch_tbr<2, 1, 6, 2, 0, 0, true, false, 0, true>, nullptr, 0, true},
-                                     {1, 1, 8, 2, 8, launch_tbr<1, 1, 8, 2, 0, 0, true, false, 0, true>, nullptr, 0, true}};
-// ... and its speculative steps (convergence-checked path)
-static const TbrEntry g_spec_gam[] = {{10, 1, 2, 2, 2, nullptr, launch_tbr<10, 1, 2, 2, 1, 2, true, false, 0, true>, 2, true},
-                                      {5, 1, 3, 2, 2, nullptr, launch_tbr<5, 1, 3, 2, 1, 2, true, false, 0, true>, 2, true}};
-#ifdef MIFLOW_EXPERIMENTS
-static const TbrEntry g_tbr_ng16 = {10, 1, 4, 2, 3, launch_tbr<10, 1, 4, 2, 0, 2, true, true>, nullptr, 2};   // + p as snorm16 between passes (changes results)
-#endif
-static const TbrEntry g_tbr[] = {
-    // first entry of each T = default (r01s sweep, G px-iter/s at 1080p x 16: T10 394 | T8 353 | T6 271 | T5 256 | T4 215 | T3 152 | T2 106 | T1 64)
-    TBR(10, 1, 4, 2, 3), TBR(8, 2, 2, 2, 2), TBR(6, 1, 5, 2, 3), TBR(5, 2, 3, 2, 3), TBR(4, 2, 3, 2, 3), TBR(3, 1, 7, 2, 6), TBR(2, 1, 8, 2, 8),
-    TBR(1, 1, 8, 2, 8),
-#ifdef MIFLOW_EXPERIMENTS
-    // alternatives (tuning sweeps, MIFLOW_TB_VARIANT)
-    TBR(10, 2, 2, 2, 2), TBR(8, 1, 4, 2, 2), TBR(6, 2, 3, 2, 3),
-#endif
-};
-// The speculative steps (MODE 1: T accumulator registers more, hence one wave/SIMD less than MODE 0 at T = 10).
-#define TBRS(T, PPL, WPS, PF, PLAN) {T, PPL, WPS, PF, PLAN, nullptr, launch_tbr<T, PPL, WPS, PF, 1>, 0}
-#define TBRSJ(T, PPL, WPS, PF, PLAN) {T, PPL, WPS, PF, PLAN, nullptr, launch_tbr<T, PPL, WPS, PF, 1, 2>, 2}
-// PLAN = 2: the bands are cut for two waves per SIMD -- fewer, taller bands (less halo) than the fixed-work kernels use; the other
-// lane's kernels fill the rest of the device (r02m at 1080p x 16, class defaults: 517 -> 545 pairs/s; fixed work loses 7 %).
-// (a release build runs the speculative steps of a level either on the register tiles or, without a |grad|^2 plane, on g_spec_jw_ng:
-// the two tables below are reachable through experiment switches only)
-#ifdef MIFLOW_EXPERIMENTS
-static const TbrEntry g_spec[] = {TBRS(10, 1, 3, 2, 2), TBRS(5, 1, 4, 2, 2)};
-static const TbrEntry g_spec_jw[] = {TBRSJ(10, 1, 3, 2, 2), TBRSJ(5, 1, 4, 2, 2)};   // MIFLOW_TB_JW >= 2 and MIFLOW_TB_JW_SPEC=1
-#endif
-// ... and the same two without a |grad|^2 plane (round 4: the convergence-checked path re-reads the statics once per block)
-static const TbrEntry g_spec_jw_ng[] = {{10, 1, 3, 2, 2, nullptr, launch_tbr<10, 1, 3, 2, 1, 2, true>, 2}, {5, 1, 4, 2, 2, nullptr, launch_tbr<5, 1, 4, 2, 1, 2, true>, 2}};
-
-// Exact-math blocks (MODE 2; 1 px per lane).  The stage costs about four times the fast one (three IEEE divisions, two double
-// square roots), so short blocks already move the kernel from the HBM bound of the one-iteration kernel to the issue bound.
-#define TBRX(T, WPS, PLAN) {T, 1, WPS, 2, PLAN, launch_tbr<T, 1, WPS, 2, 2>, nullptr, 0}
-// r02y at 1080p x 16, N = 10: blocks of 2 | 3 | 5 | 10 = 345 | 423 | 532 | 451 pairs/s (one launch per iteration: 228)
-static const TbrEntry g_exact[] = {TBRX(5, 4, 3), TBRX(4, 4, 3), TBRX(3, 5, 4), TBRX(2, 6, 4), TBRX(1, 8, 4)};
-
-// First entry of time block T, or the entry matching MIFLOW_TB_VARIANT=ppl,wps,pf.  Returns nullptr if T has none.
-static const TbrEntry *tbr_pick(int T)
-{
-    const Tuning &tn = tuning();
-    if (tn.tb_jw && tn.tb_ppl < 0)
-        for (const TbrEntry &e : g_tbr_jw)
-            if (e.T == T && e.JW == tn.tb_jw) return &e;
-    const TbrEntry *def = nullptr;
-    for (const TbrEntry &e : g_tbr) {
-        if (e.T != T) continue;
-        if (!def) def = &e;
-        if (e.PPL == tn.tb_ppl && e.WPS == tn.tb_wps && e.PF == tn.tb_pf) { def = &e; break; }
-    }
-    return def;
-}
+template <int... I>
+static std::array<TbLaunchFn, sizeof...(I)> tb_launchers(std::integer_sequence<int, I...>) { return {{launch_tbr<I>...}}; }
+static const std::array<TbLaunchFn, kTbRowCount> g_tb_launch = tb_launchers(std::make_integer_sequence<int, kTbRowCount>{});
 
 // Band height: every wave streams rows_per_band + 2T rows, in whole blocks of P = T + 1 + PF steps.  The rule is tvl1_plan.h
 // tb_band_rows (pure; tests/cpp/tvl1_band_test.cpp): the band count that minimises rounds x steps, then the height that wastes the
-// fewest steps in the bands' last blocks.  Here: the entry's waves per band row and the device's resident-wave capacity.
-static int plan_band_rows(const TbrEntry &e, const Geo &g)
+// fewest steps in the bands' last blocks.  Here: the row's waves per band row and the device's resident-wave capacity.
+int plan_band_rows(const TbRow &e, const Geo &g)
 {
     const Tuning &tn = tuning();
     if (tn.tb_rows > 0) return tn.tb_rows;
-    const int T = e.T, ppl = e.PPL;
-    int wps = e.PLAN;
-    const int ring_slots = T > 2 ? T - 1 : 1;
-    const int nw = e.JW ? jw_waves(e.JW) : 4;
-    int lds_blocks = (160 * 1024) / (ring_slots * nw * 256 * ppl * 4 + (e.JW >= 2 ? nw * xarea2_bytes(T, e.GAM) + (jw_fast(e.JW) ? xdump4_bytes(T) : 0) : e.JW ? 4 * (xarea_bytes(T) + xdump_bytes(T)) : 0));
-    lds_blocks = lds_blocks * nw / 4;   // in units of four-wave workgroups (= waves per SIMD)
-    if (wps > lds_blocks) wps = lds_blocks;
-    if (tn.tb_plan_wps > 0) wps = tn.tb_plan_wps;
-    const long long cap = (long long)device_simds() * wps;
-    const int M = (T + ppl - 1) / ppl * ppl;
-    const int LW = (e.JW ? 64 * nw : 64) * ppl;
-    const long long strips = g.w <= LW - M ? 1 : 1 + div_up(g.w - (LW - M), LW - 2 * M);
-    const long long per_band = strips * g.batch * (e.JW ? nw : 1);   // waves per band row
+    const int wps = tn.tb_plan_wps > 0 ? tn.tb_plan_wps : tb_plan_wps(e);
+    const long long per_band = (long long)tb_strips(e, g.w) * g.batch * (e.JW ? jw_waves(e.JW) : 1);   // waves per band row
     // independent waves: a workgroup is four consecutive bands of a strip and the LDS rings admit four workgroups per CU: with fewer
     // than four bands every workgroup has only nb live waves (the others exit at once, their ring stays allocated), i.e. at most nb
     // waves per SIMD (r02z4: 2 bands at 32 pairs per lane ran 1.3 x slower than 4)
-    const TbBandShape b{T, e.PF, g.h, per_band, cap, e.JW ? 0ll : (long long)device_simds(), wps};
+    const TbBandShape b{e.T, e.PF, g.h, per_band, (long long)device_simds() * wps, e.JW ? 0ll : (long long)device_simds(), wps};
 #ifdef MIFLOW_EXPERIMENTS
     if (tn.tb_rows_equal) return tb_band_rows_equal(b);   // A/B switch: the round-3 height (equal bands)
 #endif
     return tb_band_rows(b);
 }
 
-// block lengths (bit T) whose streaming kernel -- the one iterate_tb picks for a two-channel level -- can store the flow interleaved
-unsigned tb_interleave_mask()
+// One launch path: the arguments every launch starts from (zeroed; the band height the kernel was handed, or the planner's), what the
+// kernel of a caller outside the plan must match, and the launch of a row.
+static TbArgs tb_args(const TbKernel &k, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut, int cur)
 {
-    unsigned m = 0;
-    for (int T = 1; T <= kTbMaxBlock; ++T) {
-        const TbrEntry *e = tbr_pick(T);
-        if (e && tb_il_form(e->PPL, e->JW, false)) m |= 1u << T;
-    }
-    if (tb_il_form(g_tbr_ng.PPL, g_tbr_ng.JW, true)) m |= 1u << 31;   // the kernel without a |grad|^2 plane (T = 10 where tb_nograd_ok)
-    return m;
-}
-
-// What iterate_tb(T, ...) would launch for level g (introspection for the bench's accounting): kernel 0 = streaming (rows = band
-// height), 1 = register tile (rows = owned rows of a tile).
-int tb_query_plan(int T, const Geo &g, int *kernel, int *rows)
-{
-    if (runs_on_tiles(g, T, tv_knobs())) {
-        *kernel = 1;
-        *rows = tile_owned_rows();
-        return MI_OK;
-    }
-    const TbrEntry *e = tbr_pick(T);
-    if (!e) { set_error("unsupported time block %d", T); return MI_ERR_BAD_ARG; }
-    *kernel = 0;
-    *rows = plan_band_rows(*e, g);
-    return MI_OK;
-}
-
-// The warp inside a single T = 10 pass (k_iterate_tbr FW): the plan (tvl1_plan.h tb_fused_ok) decides it before the warp.
-int iterate_tb_fused(int semantics, const float *I0, const float *I1, const float *cubic_tab_dev, int T, const IterPlanes &pl, const Geo &g,
-                     float l_t, float theta, float taut, bool p_zero, int cur, hipStream_t s, bool skip_p_out)
-{
-#ifndef MIFLOW_EXPERIMENTS
-    (void)semantics; (void)I0; (void)I1; (void)cubic_tab_dev; (void)T; (void)pl; (void)g; (void)l_t; (void)theta; (void)taut; (void)p_zero; (void)cur; (void)s; (void)skip_p_out;
-    set_error("the warp fused into the pass kernel exists in the experiments build only (-DMIFLOW_EXPERIMENTS)");
-    return MI_ERR_NOT_IMPL;
-#else
-    MI_REQUIRE(T == 10 && tb_nograd_ok(T, g, tv_knobs()), MI_ERR_BAD_ARG, "fused warp: one pass of the default T = 10 kernel only");
-    const TbrEntry &e = g_tbr_fw[semantics == MI_SEM_CPU_REF ? 0 : 1];
-    TbArgs A;
-    memset(&A, 0, sizeof(A));
-    A.pl = pl; A.pl.ix = A.pl.iy = A.pl.g = A.pl.rc = nullptr;
-    A.g = g; A.l_t = l_t; A.theta = theta; A.taut = taut; A.cur = cur;
-    A.skip_p_out = skip_p_out ? 1 : 0;
-    A.fI0 = I0; A.fI1 = I1; A.ftab = cubic_tab_dev;
-    A.rows_per_band = plan_band_rows(e, g);
-    if (tuning().tb_verbose) {
-        static int shown = 0;
-        if (shown++ < 40) fprintf(stderr, "[tb] fused warp T=%d %dx%d batch=%d rows_per_band=%d\n", T, g.w, g.h, g.batch, A.rows_per_band);
-    }
-    return e.launch(A, p_zero, s);
-#endif
-}
-
-// T fused iterations, set cur -> cur^1.  Returns MI_ERR_BAD_ARG for unsupported T.  pl.g == nullptr (the plan's tb_nograd_ok, decided
-// before the warp, which then does not store the plane): the pass forms |grad|^2 itself.
-int iterate_tb(int T, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut, bool p_zero,
-               int cur, int rows_per_band, hipStream_t s, bool skip_p_out, bool independent_waves, const PtrTab *out_tab)
-{
-    // the flow straight into the callers' matrices: the plan (tvl1_plan.h pack_in_pass) asks for it on the streaming two-channel kernels only
-    MI_REQUIRE(!out_tab || (skip_p_out && pl.gamma == 0.f && (rows_per_band != 0 || !runs_on_tiles(g, T, tv_knobs()))), MI_ERR_BAD_ARG,
-               "the interleaved store exists in the last streaming pass of a scale without the illumination channel only");
-    if (pl.gamma != 0.f && rows_per_band == 0 && runs_on_tiles(g, T, tv_knobs()))
-        return iterate_tile(-1, T, pl, g, l_t, theta, taut, p_zero, cur, s);   // small levels: the register tile with the channel (bit-identical)
-    if (pl.gamma != 0.f) {   // the illumination channel: its own kernels (no |grad|^2 plane read, whether or not the warp stored one)
-        const TbrEntry *e = nullptr;
-        for (const TbrEntry &c : g_tbr_gam) if (c.T == T) e = &c;
-        if (!e) { set_error("gamma != 0: unsupported time block %d", T); return MI_ERR_BAD_ARG; }
-        MI_REQUIRE(pl.u[0][2] && pl.u[1][2] && pl.p[0][4] && pl.p[0][5] && pl.p[1][4] && pl.p[1][5], MI_ERR_BAD_ARG, "gamma != 0 needs the u3 / p31 / p32 planes");
-        TbArgs A;
-        memset(&A, 0, sizeof(A));
-        A.pl = pl; A.g = g; A.l_t = l_t; A.theta = theta; A.taut = taut; A.cur = cur;
-        A.skip_p_out = skip_p_out ? 1 : 0;
-        A.rows_per_band = rows_per_band > 0 ? rows_per_band : plan_band_rows(*e, g);
-        return e->launch(A, p_zero, s);
-    }
-    if (rows_per_band == 0 && runs_on_tiles(g, T, tv_knobs())) {
-        MI_REQUIRE(pl.g, MI_ERR_BAD_ARG, "the register-tile kernel needs the |grad|^2 plane");
-        return iterate_tile(-1, T, pl, g, l_t, theta, taut, p_zero, cur, s);
-    }
-    const TbrEntry *e = tbr_pick(T);
-    if (independent_waves) {   // test hook: the first independent-wave entry of this block length
-        e = nullptr;
-        for (const TbrEntry &c : g_tbr) if (c.T == T && !e) e = &c;
-    }
-    if (!e) { set_error("unsupported time block %d", T); return MI_ERR_BAD_ARG; }
-    if (!pl.g) {
-        // (tb_nograd_ok's other conditions are the plan's choice of kernel; where the caller forces the streaming kernel, the stage-level
-        // entry, the NG kernel runs at any geometry)
-        MI_REQUIRE(!independent_waves && (rows_per_band != 0 ? T == 10 : tb_nograd_ok(T, g, tv_knobs())), MI_ERR_BAD_ARG,
-                   "no |grad|^2 plane, but the kernel of this launch needs one");
-#ifdef MIFLOW_EXPERIMENTS
-        e = tuning().tb_p16 ? &g_tbr_ng16 : &g_tbr_ng;
-#else
-        e = &g_tbr_ng;
-#endif
-    }
-    MI_REQUIRE(!out_tab || tb_il_form(e->PPL, e->JW, !pl.g), MI_ERR_BAD_ARG, "the kernel of this launch has no interleaved store");
-    TbArgs A;
-    A.pl = pl; A.g = g; A.l_t = l_t; A.theta = theta; A.taut = taut; A.cur = cur; A.swz = 0; A.nstrips = 0;
-    A.skip_p_out = skip_p_out ? 1 : 0;
-    A.otab = out_tab;
-    A.rows_per_band = rows_per_band > 0 ? rows_per_band : plan_band_rows(*e, g);
-    if (tuning().tb_verbose) {
-        static int shown = 0;
-        if (shown++ < 40)
-            fprintf(stderr, "[tb] T=%d ppl=%d wps=%d pf=%d %dx%d batch=%d rows_per_band=%d\n", T, e->PPL, e->WPS, e->PF, g.w, g.h, g.batch,
-                    A.rows_per_band);
-    }
-    return e->launch(A, p_zero, s);
-}
-
-// T fused EXACT iterations, set cur -> cur^1 (bit-identical to T launches of the one-iteration exact kernel).  T in 1..5.
-int iterate_tb_exact(int T, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut, bool p_zero, int cur, hipStream_t s,
-                     int rows_per_band)
-{
-    const TbrEntry *e = nullptr;
-    for (const TbrEntry &c : g_exact) if (c.T == T) e = &c;
-    if (!e) { set_error("no exact-math kernel for time block %d", T); return MI_ERR_BAD_ARG; }
     TbArgs A;
     memset(&A, 0, sizeof(A));
     A.pl = pl; A.g = g; A.l_t = l_t; A.theta = theta; A.taut = taut; A.cur = cur;
-    A.rows_per_band = rows_per_band > 0 ? rows_per_band : plan_band_rows(*e, g);
-    return e->launch(A, p_zero, s);
+    A.rows_per_band = k.rows > 0 ? k.rows : plan_band_rows(*k.row, g);
+    return A;
 }
-
-bool tb_kernel_exists(int kind, int T, bool gam, bool nograd)
+static int tb_check(const TbKernel &k, bool spec, int T, const IterPlanes &pl)
 {
-    auto in = [T](const TbrEntry *t, size_t n, bool spec) {
-        for (size_t i = 0; i < n; ++i) if (t[i].T == T && (spec ? t[i].spec : t[i].launch)) return true;
-        return false;
-    };
-#define TB_IN(tab, spec) in(tab, sizeof(tab) / sizeof(tab[0]), spec)
-    switch (kind) {
-    case 0: return gam ? TB_IN(g_tbr_gam, false) : nograd ? T == g_tbr_ng.T : tbr_pick(T) != nullptr;
-    case 1: {
-        if (nograd) return false;
-        if (!gam) return TB_IN(g_tbr, false);
-        for (const TbrEntry &c : g_tbr_gam) if (c.T == T && c.JW == 0) return true;
-        return false;
+    if (!k.row) { set_error("no %s kernel for time block %d", spec ? "speculative" : "blocked", T); return MI_ERR_BAD_ARG; }
+    const TbRow &e = *k.row;
+    MI_REQUIRE(e.T == T && (e.MODE == 1) == spec && e.GAM == (pl.gamma != 0.f), MI_ERR_BAD_ARG, "the kernel handed in is not one of this launch");
+    MI_REQUIRE(!e.GAM || (pl.u[0][2] && pl.u[1][2] && pl.p[0][4] && pl.p[0][5] && pl.p[1][4] && pl.p[1][5]), MI_ERR_BAD_ARG, "gamma != 0 needs the u3 / p31 / p32 planes");
+    MI_REQUIRE(pl.g || e.NG, MI_ERR_BAD_ARG, "no |grad|^2 plane, but the kernel of this launch needs one");
+    return MI_OK;
+}
+static int tb_launch(const TbRow &e, const TbArgs &A, bool p_zero, hipStream_t s)
+{
+    if (tuning().tb_verbose) {
+        static int shown[2] = {0, 0};   // (the fused warp's lines are counted on their own: tests look for them)
+        if (shown[e.FW != 0]++ < 40)
+            fprintf(stderr, "[tb] %sT=%d ppl=%d wps=%d pf=%d %dx%d batch=%d rows_per_band=%d\n", e.FW ? "fused warp " : "", e.T, e.PPL, e.WPS, e.PF,
+                    A.g.w, A.g.h, A.g.batch, A.rows_per_band);
     }
-    case 2: return !gam && !nograd && TB_IN(g_exact, false);
-    case 3: return gam ? TB_IN(g_spec_gam, true) : TB_IN(g_spec_jw_ng, true);
-    }
-#undef TB_IN
-    return false;
+    return g_tb_launch[&e - kTbRows](A, p_zero, s);
 }
 
-// One speculative step with kernel block size T (see k_iterate_tbr MODE 1); ctl carries the slot protocol, sk the step's
-// constants, e0 the index of the first per-iteration error sum this launch may write.
-int iterate_tb_spec(int T, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut, bool p_zero, const Ctl &ctl,
-                    const SpecK &sk, int e0, hipStream_t s, int rows_per_band)
+int iterate_tb(const TbKernel &k, int T, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut, bool p_zero, int cur,
+               hipStream_t s, bool skip_p_out, const PtrTab *out_tab)
+{
+    if (k.tile) {   // small levels: the register tile (bit-identical; with the illumination channel it reads no |grad|^2 plane)
+        MI_REQUIRE(!out_tab, MI_ERR_BAD_ARG, "the interleaved store exists in the last streaming pass of a scale only");
+        MI_REQUIRE(pl.g || pl.gamma != 0.f, MI_ERR_BAD_ARG, "the register-tile kernel needs the |grad|^2 plane");
+        return iterate_tile(-1, T, pl, g, l_t, theta, taut, p_zero, cur, s);
+    }
+    if (const int rc = tb_check(k, false, T, pl)) return rc;
+    MI_REQUIRE(!k.row->FW, MI_ERR_BAD_ARG, "the fused warp has its own entry");
+    MI_REQUIRE(!out_tab || (skip_p_out && tb_il_form(*k.row)), MI_ERR_BAD_ARG,
+               "the interleaved store exists in the last pass of a scale on a two-channel kernel that has it only");
+    TbArgs A = tb_args(k, pl, g, l_t, theta, taut, cur);
+    A.skip_p_out = skip_p_out ? 1 : 0;
+    A.otab = out_tab;
+    return tb_launch(*k.row, A, p_zero, s);
+}
+
+int iterate_tb_fused(const TbKernel &k, const float *I0, const float *I1, const float *cubic_tab_dev, const IterPlanes &pl, const Geo &g,
+                     float l_t, float theta, float taut, bool p_zero, int cur, hipStream_t s, bool skip_p_out)
+{
+    MI_REQUIRE(k.row && k.row->FW, MI_ERR_NOT_IMPL, "the warp fused into the pass kernel exists in the experiments build only (-DMIFLOW_EXPERIMENTS)");
+    TbArgs A = tb_args(k, pl, g, l_t, theta, taut, cur);
+    A.pl.ix = A.pl.iy = A.pl.g = A.pl.rc = nullptr;
+    A.skip_p_out = skip_p_out ? 1 : 0;
+    A.fI0 = I0; A.fI1 = I1; A.ftab = cubic_tab_dev;
+    return tb_launch(*k.row, A, p_zero, s);
+}
+
+int iterate_tb_spec(const TbKernel &k, int T, const IterPlanes &pl, const Geo &g, float l_t, float theta, float taut, const Ctl &ctl,
+                    const SpecK &sk, int e0, hipStream_t s)
 {
     // small levels: the same step on register tiles (serial depth of a launch = its iterations, not the image height); integer
     // error sums and identical per-pixel arithmetic => the same decisions and the same flows as the streaming kernel
-    if (rows_per_band == 0 && runs_on_tiles(g, T, tv_knobs(), true) && !p_zero)
-        return iterate_tile_spec(T, pl, g, l_t, theta, taut, ctl, sk, e0, s);
-    const TbrEntry *e = nullptr;
-    if (pl.gamma != 0.f) {
-        for (const TbrEntry &c : g_spec_gam) if (c.T == T) e = &c;
-    } else if (!pl.g) {
-        MI_REQUIRE(rows_per_band != 0 || tb_spec_nograd_ok(g, tv_knobs()), MI_ERR_BAD_ARG,
-                   "no |grad|^2 plane, but the speculative kernel of this launch needs one");
-        for (const TbrEntry &c : g_spec_jw_ng) if (c.T == T) e = &c;
-    }
-#ifdef MIFLOW_EXPERIMENTS
-    else if (tuning().tb_jw >= 2 && tuning().tb_jw_spec) { for (const TbrEntry &c : g_spec_jw) if (c.T == T) e = &c; }
-    else { for (const TbrEntry &c : g_spec) if (c.T == T) e = &c; }
-#else
-    else for (const TbrEntry &c : g_spec_jw_ng) if (c.T == T) e = &c;   // (the same kernel forms |grad|^2 itself and ignores the stored plane)
-#endif
-    if (!e) { set_error("no speculative kernel for time block %d", T); return MI_ERR_BAD_ARG; }
-    TbArgs A;
-    A.pl = pl; A.g = g; A.l_t = l_t; A.theta = theta; A.taut = taut; A.cur = 0; A.swz = 0; A.nstrips = 0; A.skip_p_out = 0; A.otab = nullptr;
-    A.rows_per_band = rows_per_band > 0 ? rows_per_band : plan_band_rows(*e, g);
+    if (k.tile) return iterate_tile_spec(T, pl, g, l_t, theta, taut, ctl, sk, e0, s);
+    if (const int rc = tb_check(k, true, T, pl)) return rc;
+    TbArgs A = tb_args(k, pl, g, l_t, theta, taut, 0);
     A.ctl = make_ctlk(&ctl);
     A.e0 = e0;
     A.sk = sk;
-    return e->spec(A, p_zero, s);
+    return tb_launch(*k.row, A, false, s);
 }
 
 // sticky fault flag of the joined-wave kernels (0 = no wait ever ran out of its budget); reading clears nothing

@@ -1,5 +1,7 @@
 // The plan of one lane's TV-L1 calc (csrc/tvl1_plan.h): levels, arena layout, the calc's control features and slot count, and each
-// warp's iteration form and blocks.  Plain C++, no device.  Level sizes follow cudaoptflow/src/tvl1flow.cpp:238-266.
+// warp's iteration form, blocks and the kernel of every block; the table of the streaming kernels (csrc/tvl1_tb_table.h) and its
+// selection rule against the rules they replaced.  Plain C++, no device (also compiled with -DMIFLOW_EXPERIMENTS: the experiments
+// build's rows and switches).  Level sizes follow cudaoptflow/src/tvl1flow.cpp:238-266.
 #include "tvl1_plan.h"
 #include <cstdio>
 
@@ -14,7 +16,7 @@ static TvKnobs knobs()
     TvKnobs k{};
     k.tile_maxpx = 2300000; k.tile_spec = 1; k.tile_variant = -1; k.tile_small_wgs = 1024; k.tile_variants = 2;
     k.tile_rows[0] = 64; k.tile_rows[1] = 48; k.tile_fb_block = 10; k.tile_fb_model = 7;
-    k.tb_force = false; k.tb_nograd = 1; k.tb_jw = 2; k.tb_ppl = -1; k.tb_jw_spec = 1; k.tb_fw = 0;
+    k.tb_force = false; k.tb_nograd = 1; k.tb_jw = 2; k.tb_ppl = k.tb_wps = k.tb_pf = -1; k.tb_jw_spec = 1; k.tb_fw = 0; k.tb_il = 1;
     k.tb_skip_p = 1; k.tb_hist = 1; k.spec = 1; k.exact_tb = 1; k.fb_poll = 1; k.fb_ahead = 1; k.warp_fast = -1;
     return k;
 }
@@ -76,9 +78,202 @@ static void check_arena(const TvPlan &p, int B, bool gam, bool med)
     CHECK(p.arena.total % 64 == 0);
 }
 
+// ---- the kernel tables and the rules that walked them before there was one table and tb_select (tvl1_tbr_kernels.hip up to round 20:
+// g_tbr*, g_spec*, g_exact; tbr_pick, the branches of iterate_tb / iterate_tb_spec / iterate_tb_exact, tb_kernel_exists,
+// tb_interleave_mask; the LDS size of launch_tbr and of plan_band_rows, their strip count), restated
+namespace old {
+struct E { int MODE, T, PPL, WPS, PF, PLAN, JW; bool NG, P16; int FW; bool GAM; };
+typedef std::vector<E> Tab;
+#ifdef MIFLOW_EXPERIMENTS
+static const bool exp_build = true;
+#else
+static const bool exp_build = false;
+#endif
+static Tab cat(Tab a, const Tab &b, bool on = true) { if (on) a.insert(a.end(), b.begin(), b.end()); return a; }
+static const Tab tbr_jw = cat(cat({}, {{0, 10, 1, 3, 2, 3, 1}, {0, 10, 1, 4, 2, 3, 3}, {0, 10, 1, 4, 2, 3, 4}}, exp_build), {{0, 10, 1, 4, 2, 3, 2}});
+static const E tbr_ng = {0, 10, 1, 4, 2, 3, 2, true}, tbr_ng16 = {0, 10, 1, 4, 2, 3, 2, true, true};
+static const Tab tbr_fw = {{0, 10, 1, 4, 2, 2, 2, true, false, 1}, {0, 10, 1, 4, 2, 2, 2, true, false, 2}};
+static const Tab tbr_gam = {{0, 10, 1, 3, 1, 3, 2, true, false, 0, true}, {0, 5, 1, 4, 2, 3, 2, true, false, 0, true},
+                            {0, 2, 1, 6, 2, 6, 0, true, false, 0, true}, {0, 1, 1, 8, 2, 8, 0, true, false, 0, true}};
+static const Tab spec_gam = {{1, 10, 1, 2, 2, 2, 2, true, false, 0, true}, {1, 5, 1, 3, 2, 2, 2, true, false, 0, true}};
+static const Tab tbr = cat({{0, 10, 1, 4, 2, 3, 0}, {0, 8, 2, 2, 2, 2, 0}, {0, 6, 1, 5, 2, 3, 0}, {0, 5, 2, 3, 2, 3, 0}, {0, 4, 2, 3, 2, 3, 0},
+                            {0, 3, 1, 7, 2, 6, 0}, {0, 2, 1, 8, 2, 8, 0}, {0, 1, 1, 8, 2, 8, 0}},
+                           {{0, 10, 2, 2, 2, 2, 0}, {0, 8, 1, 4, 2, 2, 0}, {0, 6, 2, 3, 2, 3, 0}}, exp_build);
+static const Tab spec = {{1, 10, 1, 3, 2, 2, 0}, {1, 5, 1, 4, 2, 2, 0}}, spec_jw = {{1, 10, 1, 3, 2, 2, 2}, {1, 5, 1, 4, 2, 2, 2}};
+static const Tab spec_jw_ng = {{1, 10, 1, 3, 2, 2, 2, true}, {1, 5, 1, 4, 2, 2, 2, true}};
+static const Tab exact = {{2, 5, 1, 4, 2, 3, 0}, {2, 4, 1, 4, 2, 3, 0}, {2, 3, 1, 5, 2, 4, 0}, {2, 2, 1, 6, 2, 4, 0}, {2, 1, 1, 8, 2, 4, 0}};
+
+static const E *of_T(const Tab &t, int T) { const E *r = nullptr; for (const E &e : t) if (e.T == T) r = &e; return r; }
+static const E *tbr_pick(int T, const TvKnobs &K)
+{
+    if (K.tb_jw && K.tb_ppl < 0)
+        for (const E &e : tbr_jw) if (e.T == T && e.JW == K.tb_jw) return &e;
+    const E *def = nullptr;
+    for (const E &e : tbr) {
+        if (e.T != T) continue;
+        if (!def) def = &e;
+        if (e.PPL == K.tb_ppl && e.WPS == K.tb_wps && e.PF == K.tb_pf) { def = &e; break; }
+    }
+    return def;
+}
+static bool kernel_exists(int kind, int T, bool gam, bool nograd, const TvKnobs &K)
+{
+    switch (kind) {
+    case 0: return gam ? of_T(tbr_gam, T) != nullptr : nograd ? T == tbr_ng.T : tbr_pick(T, K) != nullptr;
+    case 1:
+        if (nograd) return false;
+        if (!gam) return of_T(tbr, T) != nullptr;
+        return of_T(tbr_gam, T) && of_T(tbr_gam, T)->JW == 0;
+    case 2: return !gam && !nograd && of_T(exact, T);
+    default: return gam ? of_T(spec_gam, T) != nullptr : of_T(spec_jw_ng, T) != nullptr;
+    }
+}
+// what the stage-level entry launched for use = fixed / indep / exact / spec (kind 0..3) with the streaming kernels forced: nothing
+// where tb_kernel_exists said no, else the entry of the dispatcher's branch
+static const E *launched(int kind, int T, bool gam, bool nograd, const TvKnobs &K)
+{
+    if (!kernel_exists(kind, T, gam, nograd, K)) return nullptr;
+    if (kind == 2) return of_T(exact, T);                                   // iterate_tb_exact
+    if (kind == 3) {                                                        // iterate_tb_spec
+        if (gam) return of_T(spec_gam, T);
+        if (nograd || !exp_build) return of_T(spec_jw_ng, T);
+        return K.tb_jw >= 2 && K.tb_jw_spec ? of_T(spec_jw, T) : of_T(spec, T);
+    }
+    if (gam) return of_T(tbr_gam, T);                                       // iterate_tb
+    if (kind == 1) { for (const E &e : tbr) if (e.T == T) return &e; return nullptr; }
+    if (nograd) return exp_build && K.tb_p16 ? &tbr_ng16 : &tbr_ng;
+    return tbr_pick(T, K);
+}
+static unsigned interleave_mask(const TvKnobs &K)
+{
+    unsigned m = 0;
+    for (int T = 1; T <= kTbMaxBlock; ++T) {
+        const E *e = tbr_pick(T, K);
+        if (e && e->PPL == 1 && e->JW == 0) m |= 1u << T;
+    }
+    return m | 1u << 31;   // (tb_il_form of g_tbr_ng)
+}
+static int nw(const TbRow &r) { return r.JW == 3 ? 8 : 4; }
+static int handover_bytes(const TbRow &r)
+{
+    const int T = r.T, xarea2 = 2 * T * (r.GAM ? 32 : 16);
+    return r.JW >= 2 ? nw(r) * xarea2 + (r.JW == 4 ? 64 * 8 + 2 * (2 * T * 16) + 64 : 0) : r.JW ? 4 * (2 * T * 32 + 2 * T * 32 + 64 * 8) : 0;
+}
+static size_t launch_lds(const TbRow &r)    // launch_tbr (FW_STAGE = 0)
+{
+    return (size_t)nw(r) * (r.T > 2 ? r.T - 1 : 1) * 256 * r.PPL * sizeof(float) + handover_bytes(r) + (r.FW ? (nw(r) * 4 * 192 + 128) * sizeof(float) : 0);
+}
+static int planner_wps(const TbRow &r)      // plan_band_rows: no fused-warp term
+{
+    const int blocks = (160 * 1024) / ((r.T > 2 ? r.T - 1 : 1) * nw(r) * 256 * r.PPL * 4 + handover_bytes(r)) * nw(r) / 4;
+    return std::min(r.PLAN, blocks);
+}
+static int strips(const TbRow &r, int w)
+{
+    const int M = (r.T + r.PPL - 1) / r.PPL * r.PPL, LW = (r.JW ? 64 * nw(r) : 64) * r.PPL;
+    return w <= LW - M ? 1 : 1 + (w - (LW - M) + (LW - 2 * M) - 1) / (LW - 2 * M);
+}
+}  // namespace old
+
+static bool same(const old::E *e, const TbRow *r)
+{
+    if (!e || !r) return !e && !r;
+    return e->MODE == r->MODE && e->T == r->T && e->PPL == r->PPL && e->WPS == r->WPS && e->PF == r->PF && e->PLAN == r->PLAN && e->JW == r->JW &&
+           e->NG == r->NG && e->P16 == r->P16 && e->FW == r->FW && e->GAM == r->GAM;
+}
+static void check_selection(const TvKnobs &K)
+{
+    const TbUse use[4] = {TbUse::Fixed, TbUse::Indep, TbUse::Exact, TbUse::Spec};
+    for (int kind = 0; kind < 4; ++kind)
+        for (int T = 1; T <= 10; ++T)
+            for (int gam = 0; gam < 2; ++gam)
+                for (int ng = 0; ng < 2; ++ng) {
+                    const bool ok = same(old::launched(kind, T, gam, ng, K), tb_select(use[kind], T, gam, ng, K));
+                    if (!ok) std::printf("selection differs: kind %d T %d gam %d nograd %d jw %d jw_spec %d variant %d,%d,%d p16 %d\n", kind, T, gam, ng,
+                                         K.tb_jw, K.tb_jw_spec, K.tb_ppl, K.tb_wps, K.tb_pf, K.tb_p16);
+                    CHECK(ok);
+                }
+    for (int fw = 1; fw <= 2; ++fw)   // iterate_tb_fused: g_tbr_fw[semantics == MI_SEM_CPU_REF ? 0 : 1], experiments build only
+        CHECK(same(old::exp_build ? &old::tbr_fw[fw - 1] : nullptr, tb_select(TbUse::Fixed, 10, false, true, K, fw)));
+}
+// the plan's choice for the calc's last pass against the mask it was read from; what a warp leaves out, its kernels do not read
+static void check_pack_in_pass(const TvPlan &p, const TvKnobs &K, bool may)
+{
+    for (size_t s = 0; s < p.warp.size(); ++s)
+        for (size_t wp = 0; wp < p.warp[s].size(); ++wp) {
+            const TvWarp &w = p.warp[s][wp];
+            CHECK(w.run.size() == w.blocks.size());
+            for (const TbKernel &k : w.run) CHECK(k.tile || k.row);
+            if (w.nograd) for (const TbKernel &k : w.run) CHECK(k.tile ? p.arena.lv[0][4] != kNoPlane : k.row->NG);
+            bool expect = false;
+            if (may && s == 0 && wp + 1 == p.warp[s].size() && w.form == TvForm::Blocked && !w.fused && !w.blocks.empty()) {
+                const int tl = w.blocks.back();
+                const unsigned mask = K.tb_il ? old::interleave_mask(K) : 0u;
+                expect = !runs_on_tiles(p.geo[0], tl, K) && ((w.nograd ? mask >> 31 : mask >> tl) & 1u) != 0;
+            }
+            CHECK(w.pack_in_pass == expect);
+        }
+}
+
 int main()
 {
     const TvKnobs K = knobs();
+    {   // one table, one rule: the same row as the old tables and dispatchers gave, or none on both sides
+        check_selection(K);
+#ifdef MIFLOW_EXPERIMENTS
+        const int variants[][3] = {{-1, -1, -1}, {2, 2, 2}, {1, 4, 2}, {2, 3, 2}, {1, 8, 2}, {1, 4, 3}};
+        for (int jw = 0; jw <= 4; ++jw)
+            for (int jws = 0; jws < 2; ++jws)
+                for (const auto &v : variants)
+                    for (int p16 = 0; p16 < 2; ++p16) {
+                        TvKnobs X = K;
+                        X.tb_jw = jw; X.tb_jw_spec = jws; X.tb_ppl = v[0]; X.tb_wps = v[1]; X.tb_pf = v[2]; X.tb_p16 = p16;
+                        check_selection(X);
+                    }
+#endif
+        // every row: the dynamic LDS of its launch, the waves per SIMD its planner fills (the old planner's size lacked the fused warp's
+        // inboxes: the cap is the same with them), its strips
+        for (const TbRow &r : kTbRows) {
+            CHECK(tb_lds_bytes(r) == old::launch_lds(r));
+            CHECK(tb_plan_wps(r) == old::planner_wps(r));
+            for (int w = 1; w <= 4096; ++w) CHECK(tb_strips(r, w) == old::strips(r, w));
+        }
+        CHECK(kTbRowCount == (old::exp_build ? 36 : 23));
+    }
+    {   // the calc's last pass stores the flow interleaved (tests/test_tvl1_interleaved_store.py): scale 0, last warp, fixed work, two
+        // channels, a streaming row of one pixel per lane -- 1283 x 961 x 2 pairs, N = 10 (one T = 10 pass without a |grad|^2 plane) and
+        // N = 7 (1 + 6, independent waves); a single pair runs on the tiles; every other N against the old mask
+        CHECK(plan(1283, 961, 2, params(10, 0.0), K, 2).warp[0][4].pack_in_pass && plan(1283, 961, 2, params(10, 0.0), K, 2).warp[0][4].nograd);
+        const TvPlan p7 = plan(1283, 961, 2, params(7, 0.0), K, 2);
+        CHECK(p7.warp[0][4].blocks == (std::vector<int>{1, 6}) && p7.warp[0][4].pack_in_pass && !p7.warp[0][4].nograd);
+        CHECK(!p7.warp[0][3].pack_in_pass && !p7.warp[1][4].pack_in_pass);
+        CHECK(!plan(1283, 961, 1, params(10, 0.0)).warp[0][4].pack_in_pass);
+        CHECK(!plan(1283, 961, 2, params(8, 0.0)).warp[0][4].pack_in_pass && !plan(1283, 961, 2, params(5, 0.0)).warp[0][4].pack_in_pass);
+        std::vector<TvKnobs> Ks = {K};
+        Ks.push_back(K); Ks.back().tb_nograd = 0;
+        Ks.push_back(K); Ks.back().tb_il = 0;
+        Ks.push_back(K); Ks.back().tb_skip_p = 0;
+        Ks.push_back(K); Ks.back().tb_jw = 0;
+        Ks.push_back(K); Ks.back().tb_force = true;
+        for (const TvKnobs &X : Ks)
+            for (int n = 1; n <= 23; ++n)
+                for (int B : {1, 2, 16}) {
+                    check_pack_in_pass(plan(1283, 961, B, params(n, 0.0), X), X, X.tb_skip_p != 0);
+                    mi_tvl1_params P = params(n, 0.0);
+                    P.gamma = 1.0;
+                    check_pack_in_pass(plan(1283, 961, B, P, X), X, false);
+                    P = params(n, 0.0);
+                    P.use_initial_flow = 1;
+                    check_pack_in_pass(plan(1283, 961, B, P, X), X, false);
+                    P = params(n, 0.0);
+                    P.median_filtering = 5;
+                    check_pack_in_pass(plan(1283, 961, B, P, X), X, false);
+                    P = params(n, 0.0);
+                    P.exact_math = 1;
+                    check_pack_in_pass(plan(1283, 961, B, P, X), X, false);
+                    check_pack_in_pass(plan(1283, 961, B, params(n, 0.01), X), X, false);
+                }
+    }
     {   // level sizes and the usable-scale cut (round half to even of w x 0.8; a level below 16 px is built, not used)
         struct { int W, H, nscales, built, used, w_last, h_last; } cases[] = {
             {1920, 1080, 5, 5, 5, 786, 442}, {3840, 2160, 5, 5, 5, 1573, 885}, {640, 480, 5, 5, 5, 262, 197},
