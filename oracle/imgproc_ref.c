@@ -10,6 +10,22 @@
 
 int orc_scaled_dim(int n, double f) { return (int)lrint((double)n * f); }
 
+void orc_get_gaussian_kernel(int n, double sigma, float *k)
+{
+    static const float small_tab[4][7] = {{1.f}, {0.25f, 0.5f, 0.25f}, {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f},
+                                          {0.03125f, 0.109375f, 0.21875f, 0.28125f, 0.21875f, 0.109375f, 0.03125f}};
+    if (sigma <= 0 && (n & 1) && n <= 7) {
+        for (int i = 0; i < n; ++i) k[i] = small_tab[n >> 1][i];
+        return;
+    }
+    const double sx = sigma > 0 ? sigma : ((n - 1) * 0.5 - 1) * 0.3 + 0.8, s2 = -0.5 / (sx * sx);
+    double *w = (double *)malloc(sizeof(double) * (size_t)n), sum = 0;
+    for (int i = 0; i < n; ++i) { const double x = i - (n - 1) * 0.5; w[i] = exp(s2 * x * x); sum += w[i]; }
+    sum = 1. / sum;
+    for (int i = 0; i < n; ++i) k[i] = (float)(w[i] * sum);
+    free(w);
+}
+
 static inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 /* ------------------------------------------------------------------------ */

@@ -45,6 +45,12 @@ void orc_remap_cubic_cv(const float *src, int sw, int sh, const float *mapx, con
  * Call site: optflow/src/tvl1flow.cpp:1381-1384. src != dst. */
 void orc_median_blur(const float *src, float *dst, int w, int h, int ksize);
 
+/* cv::getGaussianKernel(n, sigma, CV_32F) (main repo imgproc/src/smooth.dispatch.cpp): the fixed tables for odd n <= 7 with
+ * sigma <= 0, else sigma = 0.3 ((n - 1) / 2 - 1) + 0.8 when not given, exp(-x^2 / (2 sigma^2)) over x = i - (n - 1) / 2 and the
+ * normalisation (a multiply by the reciprocal of the sum) in double, each tap rounded to float once.
+ * Call sites: cudafilters/src/filtering.cpp:573,578 (createGaussianFilter), cudaoptflow/src/farneback.cpp (the Gaussian window). */
+void orc_get_gaussian_kernel(int n, double sigma, float *k);
+
 #ifdef __cplusplus
 }
 #endif

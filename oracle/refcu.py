@@ -5,7 +5,9 @@ cudaoptflow/src/cuda/tvl1flow.cu, cudastereo/src/cuda/disparity_bilateral_filter
 rewrites only their launch sites (oracle/refshim/cu2host.py) into oracle/_ref/ and compiles the result against
 oracle/refshim/cudashim (thread blocks as cooperatively scheduled contexts, __shared__ as static storage, the few main-repo device
 headers stubbed).  Every line of kernel arithmetic that runs is the reference's.  Built where /root/reference exists; the .so
-travels with the tree.  tests/test_ref_pin_cuda.py holds the restated oracles to it.
+travels with the tree.  tests/test_ref_pin_cuda.py holds the restated oracles to it; tests/test_ref_pin_btvl1.py the NumPy restatement of
+BTV-L1 super-resolution (superres/src/cuda/btv_l1_gpu.cu, the separable filter of cudafilters, the resize / remap kernels of cudawarping,
+the cudaarithm functors, and superres/src/btv_l1_cuda.cpp itself: the section at the end of this file).
 """
 from __future__ import annotations
 
@@ -27,11 +29,22 @@ def available() -> bool:
     return os.path.exists(LIB)
 
 
+def has_btvl1() -> bool:
+    """True if the library on disk holds the BTV-L1 entry points (one built before they existed does not: it is rebuilt where the
+    reference tree is present, and the BTV-L1 pins skip where it is not)."""
+    if not available():
+        return False
+    with open(LIB, "rb") as f:
+        return b"ref_cuhost_btvl1_process" in f.read()
+
+
 def lib():
     global _lib
     if _lib is None:
         if not available():
             refocl.build()
+        elif not has_btvl1() and refocl.can_build():
+            refocl.build(force=True)
         L = C.CDLL(LIB)
         i, f, vp = C.c_int, C.c_float, C.c_void_p
         L.ref_cu_sbm_block_match.argtypes = [_u8, _u8, i, i, i, i, i, _u8, vp]
@@ -331,3 +344,232 @@ def cuda_class_dbf_apply(disp, img, ndisp=64, radius=3, iters=1, edge_threshold=
     if rc:
         raise ValueError("the reference class threw")
     return disp
+
+
+# ----------------------------------------------------------------------------------------------- BTV-L1 super-resolution (superres)
+# superres/src/cuda/btv_l1_gpu.cu and the cudafilters / cudawarping / cudaarithm kernels BTVL1_CUDA runs, on the fiber shim; the host side
+# is the reference's superres/src/btv_l1_cuda.cpp, cudawarping/src/resize.cpp and remap.cpp (verbatim) and the separable-filter slice of
+# cudafilters/src/filtering.cpp.  Images are (H, W) or (H, W, CN) float32, CN in {3, 4}; a raised ValueError = the reference threw.
+BTV_DEFAULTS = dict(scale=4, iterations=180, tau=1.3, lambda_=0.03, alpha=0.7, btv_kernel_size=7, blur_kernel_size=5, blur_sigma=0.0)
+
+
+def _img(a):
+    a = _c(a)
+    assert a.ndim in (2, 3)
+    return a, a.shape[0], a.shape[1], (1 if a.ndim == 2 else a.shape[2])
+
+
+def _p(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def _ok(rc):
+    if rc:
+        raise ValueError("the reference threw" if rc == 1 else "the reference returned an unexpected size or type")
+
+
+def btv_build_motion_maps(forward_motion, backward_motion):
+    """buildMotionMaps (btv_l1_cuda.cpp:131-144 over buildMotionMapsKernel).  -> ((forward map x, y), (backward map x, y))."""
+    fx, fy, bx, by = (_c(a) for a in (*forward_motion, *backward_motion))
+    out = [np.empty_like(fx) for _ in range(4)]
+    _ok(lib().ref_cuhost_btv_motion_maps(_p(fx), _p(fy), _p(bx), _p(by), fx.shape[0], fx.shape[1], *(_p(o) for o in out)))
+    return (out[0], out[1]), (out[2], out[3])
+
+
+def btv_upscale(src, scale):
+    """upscale (btv_l1_cuda.cpp:146-162: dst zeroed, then upscaleKernel)."""
+    s, h, w, cn = _img(src)
+    dst = np.empty((h * scale, w * scale) + s.shape[2:], np.float32)
+    _ok(lib().ref_cuhost_btv_upscale(_p(s), h, w, cn, scale, _p(dst)))
+    return dst
+
+
+def btv_diff_sign(a, b):
+    """diffSign (btv_l1_cuda.cpp:164-169: both reshaped to one channel, DiffSign through device::transform)."""
+    a, h, w, cn = _img(a)
+    b = _c(b)
+    dst = np.empty_like(a)
+    _ok(lib().ref_cuhost_btv_diff_sign(_p(a), _p(b), h, w, cn, _p(dst)))
+    return dst
+
+
+def btv_regularization(src, btv_kernel_size, weights):
+    """loadBtvWeights(weights) then calcBtvRegularization (btv_l1_cuda.cpp:189-207 over calcBtvRegularizationKernel)."""
+    s, h, w, cn = _img(src)
+    wts = _c(weights)
+    assert wts.size <= 256
+    dst = np.empty_like(s)
+    _ok(lib().ref_cuhost_btv_regularization(_p(s), h, w, cn, btv_kernel_size, _p(wts), wts.size, _p(dst)))
+    return dst
+
+
+def btv_weights(btv_kernel_size, alpha):
+    """calcBtvWeights (btv_l1_cuda.cpp:171-187): the whole vector of btvKernelSize^2 floats (only the enumerated entries are set)."""
+    out = np.zeros(btv_kernel_size * btv_kernel_size, np.float32)
+    _ok(lib().ref_cuhost_btv_weights(btv_kernel_size, C.c_double(alpha), _p(out)))
+    return out
+
+
+def _pack_motions(motions, shape):
+    present = np.array([m is not None for m in motions], np.int32)
+    planes = np.zeros((len(motions), 2) + tuple(shape), np.float32)
+    for i, m in enumerate(motions):
+        if m is not None:
+            planes[i, 0], planes[i, 1] = m
+    return planes, present
+
+
+def btv_upscale_motions(motions, scale):
+    """upscaleMotions (btv_l1_cuda.cpp:117-129): cuda::resize(INTER_CUBIC, null stream) then cuda::multiply by Scalar::all(scale)."""
+    h, w = motions[0][0].shape
+    planes, _ = _pack_motions(motions, (h, w))
+    out = np.empty((len(motions), 2, h * scale, w * scale), np.float32)
+    _ok(lib().ref_cuhost_btv_upscale_motions(_p(planes), len(motions), h, w, scale, _p(out)))
+    return [(o[0].copy(), o[1].copy()) for o in out]
+
+
+def btv_relative_motions(forward, backward, base_idx, size):
+    """calcRelativeMotions (btv_l1_cuda.cpp:80-115, cuda::add = the reference's AddOp1).  None entries stay empty GpuMats."""
+    f, fp = _pack_motions(forward, size)
+    b, bp = _pack_motions(backward, size)
+    of, ob = np.empty_like(f), np.empty_like(b)
+    _ok(lib().ref_cuhost_btv_relative_motions(_p(f), _p(fp), _p(b), _p(bp), len(forward), size[0], size[1], base_idx, _p(of), _p(ob)))
+    return [(o[0].copy(), o[1].copy()) for o in of], [(o[0].copy(), o[1].copy()) for o in ob]
+
+
+def cuda_gaussian_kernel(n, sigma):
+    """getGaussianKernel(n, sigma, CV_32F) as the stub core forwards it (oracle/imgproc_ref.c: a main-repo stand-in, not reference text)."""
+    out = np.empty(n, np.float32)
+    _ok(lib().ref_cuhost_gaussian_kernel(n, C.c_double(sigma), _p(out)))
+    return out
+
+
+def cuda_gauss_filter(src, ksize, sigma):
+    """cuda::createGaussianFilter(type, -1, Size(ksize, ksize), sigma)->apply(src, dst, a stream): filtering.cpp's createGaussianFilter and
+    SeparableLinearFilter over linearRowFilter / linearColumnFilter with the cc >= 20 geometry."""
+    s, h, w, cn = _img(src)
+    dst = np.empty_like(s)
+    _ok(lib().ref_cuhost_gauss_filter(_p(s), h, w, cn, ksize, C.c_double(sigma), _p(dst)))
+    return dst
+
+
+def cuda_separable_filter(src, kernel):
+    """cuda::createSeparableLinearFilter(type, -1, kernel, kernel)->apply: the filter createGaussianFilter builds, with any taps (1 .. 32)."""
+    s, h, w, cn = _img(src)
+    k = _c(kernel)
+    dst = np.empty_like(s)
+    _ok(lib().ref_cuhost_separable_filter(_p(s), h, w, cn, _p(k), k.size, _p(dst)))
+    return dst
+
+
+def _cuda_resize(src, dh, dw, interpolation, own_stream):
+    s, h, w, cn = _img(src)
+    dst = np.empty((dh, dw) + s.shape[2:], np.float32)
+    _ok(lib().ref_cuhost_resize(_p(s), h, w, cn, dh, dw, interpolation, int(own_stream), _p(dst)))
+    return dst
+
+
+def cuda_resize_nearest(src, dh, dw):
+    """cuda::resize(src, dst, Size(dw, dh), 0, 0, INTER_NEAREST, a stream) (resize.cpp verbatim over resize_nearest), as btv_l1_cuda.cpp:373."""
+    return _cuda_resize(src, dh, dw, 0, True)
+
+
+def cuda_resize_cubic(src, dh, dw):
+    """cuda::resize(..., INTER_CUBIC) on the null stream (resize.cpp verbatim over the generic resize kernel with CubicFilter), as
+    btv_l1_cuda.cpp:123-124,354."""
+    return _cuda_resize(src, dh, dw, 2, False)
+
+
+def cuda_remap_nearest_replicate(src, mapx, mapy):
+    """cuda::remap(src, dst, mapx, mapy, INTER_NEAREST, BORDER_REPLICATE, Scalar(), a stream) (remap.cpp verbatim over RemapDispatcherStream)."""
+    s, h, w, cn = _img(src)
+    mx, my = _c(mapx), _c(mapy)
+    dst = np.empty(mx.shape + s.shape[2:], np.float32)
+    _ok(lib().ref_cuhost_remap_nearest_replicate(_p(s), h, w, cn, _p(mx), _p(my), mx.shape[0], mx.shape[1], _p(dst)))
+    return dst
+
+
+def cuda_add_weighted(a, alpha, b, beta, gamma):
+    """cuda::addWeighted on CV_32F: AddWeightedOp<float, float, float, float> (add_weighted.cu:61-93) over every element."""
+    a, b = _c(a), _c(b)
+    dst = np.empty_like(a)
+    L = lib()
+    L.ref_cu_add_weighted_f32.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_size_t]
+    L.ref_cu_add_weighted_f32(_p(a), alpha, _p(b), beta, gamma, _p(dst), a.size)
+    return dst
+
+
+def cuda_multiply_scalar(a, val):
+    """cuda::multiply(src, Scalar::all(val), dst) on CV_32F: MulScalarOp<float, float, float> (mul_scalar.cu:61-69,151)."""
+    a = _c(a)
+    dst = np.empty_like(a)
+    L = lib()
+    L.ref_cu_mul_scalar_f32.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_size_t]
+    L.ref_cu_mul_scalar_f32(_p(a), val, _p(dst), a.size)
+    return dst
+
+
+class BTVL1Class:
+    """One object of the reference's BTVL1_CUDA kept across process() calls (its filter and weight caches, btv_l1_cuda.cpp:320-335)."""
+
+    def __init__(self):
+        L = lib()
+        L.ref_cuhost_btvl1_new.restype = C.c_void_p
+        L.ref_cuhost_btvl1_delete.argtypes = [C.c_void_p]
+        self._h = C.c_void_p(L.ref_cuhost_btvl1_new())
+        assert self._h
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            lib().ref_cuhost_btvl1_delete(self._h)
+            self._h = None
+
+    def process(self, frames, forward, backward, base_idx, **params):
+        """-> (result, btvWeights_ after the call)."""
+        p = dict(BTV_DEFAULTS, **params)
+        fr = np.ascontiguousarray(np.stack([_c(f) for f in frames]))
+        n, h, w = fr.shape[:3]
+        cn = 1 if fr.ndim == 3 else fr.shape[3]
+        f, fp = _pack_motions(forward, (h, w))
+        b, bp = _pack_motions(backward, (h, w))
+        s, bk = p["scale"], p["btv_kernel_size"]
+        out = np.empty((max(h * s - 2 * bk, 0), max(w * s - 2 * bk, 0)) + fr.shape[3:], np.float32)
+        wts = np.zeros(max(bk, 1) ** 2, np.float32)
+        L = lib()
+        L.ref_cuhost_btvl1_process.argtypes = [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_double] * 3 + [C.c_int] * 2 + \
+            [C.c_double, C.c_void_p, C.c_void_p]
+        _ok(L.ref_cuhost_btvl1_process(self._h, _p(fr), n, h, w, cn, _p(f), _p(fp), _p(b), _p(bp), base_idx, s, p["iterations"], p["tau"], p["lambda_"],
+                                       p["alpha"], bk, p["blur_kernel_size"], p["blur_sigma"], _p(out), _p(wts)))
+        return out, wts
+
+
+def cuda_class_btvl1_process(frames, fwd, bwd, base, **params):
+    """BTVL1_CUDA_Base::process (btv_l1_cuda.cpp:306-400) on a fresh object of the reference's class.  -> (result, btvWeights_).  The filter
+    taps live inside the reference's SeparableLinearFilter (another translation unit's unnamed namespace) and are not returned; they are
+    cuda_gaussian_kernel(blur_kernel_size, blur_sigma)."""
+    return BTVL1Class().process(frames, fwd, bwd, base, **params)
+
+
+def cuda_class_btvl1_sequence(frames, flows, temporal_area_radius=4, **params):
+    """createSuperResolution_BTVL1_CUDA() -> setInput(a list-backed FrameSource over `frames`, u8 or f32), setOpticalFlow(an algorithm that
+    hands out `flows` -- a list of (x, y) planes -- in call order), nextFrame until it returns nothing.
+    -> (list of u8 outputs, list of (index of frame0, index of frame1) per flow request, True if the frame after the last was empty twice)."""
+    p = dict(BTV_DEFAULTS, **params)
+    fr = np.ascontiguousarray(np.stack([np.ascontiguousarray(f) for f in frames]))
+    assert fr.dtype in (np.uint8, np.float32)
+    n, h, w = fr.shape[:3]
+    cn = 1 if fr.ndim == 3 else fr.shape[3]
+    fl = np.ascontiguousarray(np.stack([np.stack([_c(x), _c(y)]) for x, y in flows])) if len(flows) else np.zeros((0, 2, h, w), np.float32)
+    s, bk = p["scale"], p["btv_kernel_size"]
+    oh, ow = h * s - 2 * bk, w * s - 2 * bk
+    max_out = n + 3
+    out = np.zeros((max_out, oh, ow) + fr.shape[3:], np.uint8)
+    calls = np.full((4 * n + 8, 2), -2, np.int32)
+    n_out, ended, n_calls = C.c_int(0), C.c_int(0), C.c_int(0)
+    L = lib()
+    L.ref_cuhost_btvl1_sequence.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] + [C.c_int] * 4 + [C.c_double] * 3 + [C.c_int] * 2 + [C.c_double] + \
+        [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    _ok(L.ref_cuhost_btvl1_sequence(_p(fr), n, h, w, cn, 0 if fr.dtype == np.uint8 else 1, _p(fl), len(flows), temporal_area_radius, s, p["iterations"],
+                                    p["tau"], p["lambda_"], p["alpha"], bk, p["blur_kernel_size"], p["blur_sigma"], _p(out), max_out, C.byref(n_out),
+                                    C.byref(ended), _p(calls), len(calls), C.byref(n_calls)))
+    return [out[i].copy() for i in range(n_out.value)], [tuple(int(v) for v in c) for c in calls[:n_calls.value]], bool(ended.value)

@@ -12,7 +12,10 @@
 #include "opencv2/video.hpp"
 #include <cmath>
 
-extern "C" void ref_cu_resize_linear_f32(const float *src, int sr, int sc, float *dst, int dr, int dc, float fy, float fx);
+// the reference's arithmetic functors run over n floats (oracle/refshim/cudavec/btvl1_cu_host.cpp)
+extern "C" void ref_cu_add_f32(const float *a, const float *b, float *dst, size_t n);
+extern "C" void ref_cu_add_weighted_f32(const float *a, double alpha, const float *b, double beta, double gamma, float *dst, size_t n);
+extern "C" void ref_cu_mul_scalar_f32(const float *a, double val, float *dst, size_t n);
 extern "C" void ref_cu_pyr_down_f32(const float *src, int sr, int sc, float *dst, int dr, int dc);
 
 namespace cv { namespace cuda {
@@ -43,6 +46,25 @@ void GpuMat::convertTo(GpuMat &dst, int rtype, Stream &stream) const
         const unsigned char *s = ptr<unsigned char>(y);
         float *d = out.ptr<float>(y);
         for (int x = 0; x < cols; ++x) d[x] = (float)s[x];
+    }
+    dst = out;
+}
+// GpuMat::convertTo(dst, rtype) without a scale (core/src/cuda/gpu_mat.cu convertTo: saturate_cast<D>(src) per element): 8U -> 32F exact,
+// 32F -> 8U is cvt.rni.sat.u8.f32 (round to nearest even, saturate, NaN -> 0), equal depths a copy; any channel count
+void GpuMat::convertTo(GpuMat &dst, int rtype) const
+{
+    const int sd = depth(), dd = rtype & 7, n = cols * channels();
+    CV_Assert((sd == CV_8U || sd == CV_32F) && (dd == CV_8U || dd == CV_32F));
+    if (sd == dd) { if (dst.data != data) copyTo(dst); return; }
+    GpuMat out;
+    out.create(rows, cols, CV_MAKETYPE(dd, channels()));
+    for (int y = 0; y < rows; ++y) {
+        if (sd == CV_8U) { const unsigned char *s = ptr<unsigned char>(y); float *d = out.ptr<float>(y); for (int x = 0; x < n; ++x) d[x] = (float)s[x]; }
+        else {
+            const float *s = ptr<float>(y);
+            unsigned char *d = out.ptr<unsigned char>(y);
+            for (int x = 0; x < n; ++x) { const float r = nearbyintf(s[x]); d[x] = (unsigned char)(r > 0.f ? (r > 255.f ? 255 : (int)r) : 0); }
+        }
     }
     dst = out;
 }
@@ -89,13 +111,31 @@ void multiply(const GpuMat &src1, const Scalar &src2, GpuMat &dst, double scale,
     CV_Assert(src1.type() == CV_32FC1 && scale == 1 && dtype == -1);
     GpuMat out = dst.data == src1.data ? dst : GpuMat();
     out.create(src1.rows, src1.cols, CV_32FC1);
-    const float v = (float)src2[0];
-    for (int y = 0; y < src1.rows; ++y) {
-        const float *s = src1.ptr<float>(y);
-        float *d = out.ptr<float>(y);
-        for (int x = 0; x < src1.cols; ++x) d[x] = s[x] * v;
-    }
+    for (int y = 0; y < src1.rows; ++y) ref_cu_mul_scalar_f32(src1.ptr<float>(y), src2[0] * scale, out.ptr<float>(y), (size_t)src1.cols);
     dst = out;
+}
+
+// cuda::add(src1, src2, dst) of two CV_32F matrices of one type and size, no mask (cudaarithm/src/element_operations.cpp arithm_op ->
+// add_mat.cu addMat_v1<float, float>): the reference's AddOp1 over every element
+void add(InputArray _src1, InputArray _src2, OutputArray _dst, InputArray mask, int dtype, Stream &)
+{
+    const GpuMat a = _src1.getGpuMat(), b = _src2.getGpuMat();
+    CV_Assert(a.depth() == CV_32F && a.type() == b.type() && a.size() == b.size() && mask.empty() && dtype == -1);
+    _dst.create(a.size(), a.type());
+    GpuMat &d = *_dst.gpuMatPtr();
+    for (int y = 0; y < a.rows; ++y) ref_cu_add_f32(a.ptr<float>(y), b.ptr<float>(y), d.ptr<float>(y), (size_t)a.cols * a.channels());
+}
+
+// cuda::addWeighted (cudaarithm/src/cuda/add_weighted.cu:99-...: the matrices reshaped to one channel, funcs[CV_32F][CV_32F][CV_32F] =
+// addWeightedImpl<float, float, float>): the reference's AddWeightedOp with its float scalars over every element; dst may be src1
+void addWeighted(InputArray _src1, double alpha, InputArray _src2, double beta, double gamma, OutputArray _dst, int ddepth, Stream &)
+{
+    const GpuMat a = _src1.getGpuMat(), b = _src2.getGpuMat();
+    CV_Assert(a.depth() == CV_32F && a.type() == b.type() && a.size() == b.size() && ddepth == -1);
+    _dst.create(a.size(), a.type());
+    GpuMat &d = *_dst.gpuMatPtr();
+    for (int y = 0; y < a.rows; ++y)
+        ref_cu_add_weighted_f32(a.ptr<float>(y), alpha, b.ptr<float>(y), beta, gamma, d.ptr<float>(y), (size_t)a.cols * a.channels());
 }
 
 // cuda::merge of two CV_32FC1 planes into CV_32FC2 (cudaarithm/src/cuda/split_merge.cu: interleave)
@@ -171,28 +211,7 @@ void calcSum(InputArray src, OutputArray dst, InputArray mask, Stream &)
     *dst.gpuMatPtr()->ptr<double>(0) = acc;
 }
 
-// cuda::resize: cudawarping/src/resize.cpp:55-103 (the size / scale glue) around the reference's resize_linear kernel
-static int saturate_int(double v) { return (int)lrint(v); }   // saturate_cast<int>(double) = cvRound: round half to even
-void resize(InputArray _src, OutputArray _dst, Size dsize, double fx, double fy, int interpolation, Stream &stream)
-{
-    const GpuMat src = _src.getGpuMat();
-    CV_Assert(src.type() == CV_32FC1 && interpolation == INTER_LINEAR);
-    CV_Assert(!(dsize == Size()) || (fx > 0 && fy > 0));
-    if (dsize == Size()) {
-        dsize = Size(saturate_int(src.cols * fx), saturate_int(src.rows * fy));
-    } else {
-        fx = static_cast<double>(dsize.width) / src.cols;
-        fy = static_cast<double>(dsize.height) / src.rows;
-    }
-    _dst.create(dsize, src.type());
-    GpuMat &dst = *_dst.gpuMatPtr();
-    if (dsize == src.size()) { src.copyTo(dst, stream); return; }
-    // dense copies for the C entry of libref_cu.so (the kernel itself addresses through PtrStepSz: pitch-independent)
-    std::vector<float> s((size_t)src.rows * src.cols), d((size_t)dsize.height * dsize.width);
-    for (int y = 0; y < src.rows; ++y) memcpy(&s[(size_t)y * src.cols], src.ptr<float>(y), sizeof(float) * src.cols);
-    ref_cu_resize_linear_f32(s.data(), src.rows, src.cols, d.data(), dsize.height, dsize.width, static_cast<float>(1.0 / fy), static_cast<float>(1.0 / fx));
-    for (int y = 0; y < dsize.height; ++y) memcpy(dst.ptr<float>(y), &d[(size_t)y * dsize.width], sizeof(float) * dsize.width);
-}
+// cuda::resize and cuda::remap are the reference's own cudawarping/src/resize.cpp and remap.cpp, compiled verbatim (oracle/Makefile.ref)
 
 // cuda::pyrDown: cudawarping/src/pyramids.cpp:60-88 (dst size) around the reference's pyrDown kernel
 void pyrDown(InputArray _src, OutputArray _dst, Stream &)

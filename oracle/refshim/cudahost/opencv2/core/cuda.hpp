@@ -16,7 +16,14 @@
  * resize.cu and pyr_down.cu kernels: calc / calcImpl (level cropping, the per-level blur + resize or the pyrDown pyramid, the flow
  * upsampling, prepareGaussian, the iteration loop) are reference code.  Added for it: Event, Stream's bool / waitEvent, Mat_<double>
  * with the Cholesky inverse of a 6 x 6 matrix (main repo core/src/matrix_decomp.cpp CholImpl, restated), getGaussianKernel (main
- * repo imgproc/src/smooth.dispatch.cpp, restated), cuda::split / pyrDown.
+ * repo imgproc/src/smooth.dispatch.cpp, restated in oracle/imgproc_ref.c), cuda::split / pyrDown.
+ *
+ * The same for superres' BTVL1_CUDA -- modules/superres/src/btv_l1_cuda.cpp, super_resolution.cpp and frame_source.cpp, verbatim, over
+ * cudawarping/src/resize.cpp and remap.cpp (verbatim), the separable-filter slice of cudafilters/src/filtering.cpp and the reference's
+ * kernels (btv_l1_gpu.cu, row_filter.hpp / column_filter.hpp, resize.cu, remap.cu, the functors of cudaarithm) on the fiber shim.  Added
+ * for it: Point, Scalar_<float>, UMat (a name), DeviceInfo (cc 7.0), streams that are not the null stream, GpuMat::locateROI / reshape /
+ * convertTo between CV_8U and CV_32F, InputArray over a Mat, cuda::Filter, cuda::add / addWeighted (element loops over the reference's
+ * functors), and the superres glue of oracle/refshim/cudahost/btvl1_host.cpp.
  */
 #ifndef ORACLE_CUDAHOST_CORE_CUDA_HPP
 #define ORACLE_CUDAHOST_CORE_CUDA_HPP
@@ -53,11 +60,19 @@
 #define CV_32FC1 CV_MAKETYPE(CV_32F, 1)
 #define CV_32FC2 CV_MAKETYPE(CV_32F, 2)
 #define CV_64FC1 CV_MAKETYPE(CV_64F, 1)
+#define CV_MAKE_TYPE CV_MAKETYPE
+#define CV_MAT_DEPTH(type) ((type) & 7)
+#define CV_MAT_CN(type) (((type) >> 3) + 1)
+#define CV_8UC4 CV_MAKETYPE(CV_8U, 4)
+#define CV_32FC3 CV_MAKETYPE(CV_32F, 3)
+#define CV_32FC4 CV_MAKETYPE(CV_32F, 4)
+#define CV_INSTRUMENT_REGION()
+#define CV_UNUSED(name) (void)name
 
 namespace cv {
 typedef std::string String;
-enum { INTER_NEAREST = 0, INTER_LINEAR = 1, INTER_CUBIC = 2 };
-enum { BORDER_CONSTANT = 0, BORDER_REPLICATE = 1, BORDER_REFLECT = 2, BORDER_WRAP = 3, BORDER_REFLECT101 = 4 };
+enum { INTER_NEAREST = 0, INTER_LINEAR = 1, INTER_CUBIC = 2, INTER_AREA = 3, INTER_LANCZOS4 = 4, WARP_RELATIVE_MAP = 32 };
+enum { BORDER_CONSTANT = 0, BORDER_REPLICATE = 1, BORDER_REFLECT = 2, BORDER_WRAP = 3, BORDER_REFLECT101 = 4, BORDER_REFLECT_101 = 4, BORDER_DEFAULT = 4 };
 enum { NORM_INF = 1, NORM_L1 = 2, NORM_L2 = 4 };
 enum { DECOMP_LU = 0, DECOMP_SVD = 1, DECOMP_EIG = 2, DECOMP_CHOLESKY = 3 };
 inline int cvRound(double v) { return (int)lrint(v); }   // round half to even, like the SSE2 path of core/fast_math.hpp
@@ -69,6 +84,9 @@ struct Size {
     bool operator==(const Size &o) const { return width == o.width && height == o.height; }
     bool operator!=(const Size &o) const { return !(*this == o); }
 };
+struct Point { int x = 0, y = 0; Point() {} Point(int x_, int y_) : x(x_), y(y_) {} };
+template <typename T> static inline T saturate_cast(double v);
+template <> inline int saturate_cast<int>(double v) { return cvRound(v); }   // core/saturate.hpp
 struct Point2f { float x = 0, y = 0; };
 struct KeyPoint { Point2f pt; float size = 0, angle = -1, response = 0; int octave = 0, class_id = -1; };   // core/types.hpp
 class Mutex { public: void lock() {} void unlock() {} };
@@ -80,6 +98,10 @@ struct Scalar {
     Scalar(double v0) { val[0] = v0; }
     static Scalar all(double v) { Scalar s; s.val[0] = s.val[1] = s.val[2] = s.val[3] = v; return s; }
     double operator[](int i) const { return val[i]; }
+};
+template <typename T> struct Scalar_ {   // the float copy of a border value (cudawarping/src/remap.cpp)
+    T val[4] = {0, 0, 0, 0};
+    Scalar_ &operator=(const Scalar &s) { for (int i = 0; i < 4; ++i) val[i] = (T)s.val[i]; return *this; }
 };
 template <typename T> using Ptr = std::shared_ptr<T>;
 template <typename T, typename... A> Ptr<T> makePtr(A &&...a) { return std::make_shared<T>(std::forward<A>(a)...); }
@@ -107,8 +129,19 @@ public:       // descriptor transfers (7 x n CV_32F, n x 64|128 CV_32F over a ca
         data = buf_->data();
     }
     int type() const { return type_; }
+    int channels() const { return (type_ >> 3) + 1; }
     Size size() const { return Size(cols, rows); }
     bool empty() const { return data == nullptr; }
+    // what SeparableLinearFilter's constructor does to a kernel (cudafilters/src/filtering.cpp:427-439): convertTo(CV_32F) of a CV_32F
+    // matrix shares it; reshape(1, 1) of a dense n x 1 matrix is the same buffer read as 1 x n
+    void convertTo(Mat &dst, int rtype) const { CV_Assert(rtype == (type_ & 7) && rtype == CV_32F); dst = *this; }
+    Mat reshape(int cn, int nrows) const
+    {
+        CV_Assert(cn == channels() && step == (size_t)cols * elem_size_of(type_) && (rows * cols) % nrows == 0);
+        Mat m = *this;
+        m.rows = nrows; m.cols = rows * cols / nrows; m.step = (size_t)m.cols * elem_size_of(type_);
+        return m;
+    }
     template <typename T> T &at(int y, int x) { return reinterpret_cast<T *>(data + (size_t)y * step)[x]; }
     template <typename T> T *ptr(int y = 0) { return reinterpret_cast<T *>(data + (size_t)y * step); }
     template <typename T> const T *ptr(int y = 0) const { return reinterpret_cast<const T *>(data + (size_t)y * step); }
@@ -161,38 +194,41 @@ public:
         return B;
     }
 };
-// cv::getGaussianKernel(n, sigma, CV_32F) (imgproc.hpp; main repo imgproc/src/smooth.dispatch.cpp): the fixed tables for n <= 7 with
-// sigma <= 0, else exp(-x^2 / (2 sigma^2)) over x = i - (n - 1) / 2, normalised in double, rounded to float
+// cv::getGaussianKernel(n, sigma, CV_32F) (imgproc.hpp; main repo imgproc/src/smooth.dispatch.cpp): the one restatement of
+// oracle/imgproc_ref.c (orc_get_gaussian_kernel)
+extern "C" void orc_get_gaussian_kernel(int n, double sigma, float *k);
 inline Mat getGaussianKernel(int n, double sigma, int ktype)
 {
     CV_Assert(ktype == CV_32F && n > 0);
     Mat k(n, 1, CV_32FC1);
-    float *kf = k.ptr<float>(0);
-    static const float small[4][7] = {{1.f}, {0.25f, 0.5f, 0.25f}, {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f},
-                                      {0.03125f, 0.109375f, 0.21875f, 0.28125f, 0.21875f, 0.109375f, 0.03125f}};
-    if (sigma <= 0 && (n & 1) && n <= 7) {
-        for (int i = 0; i < n; ++i) kf[i] = small[n >> 1][i];
-        return k;
-    }
-    const double sx = sigma > 0 ? sigma : ((n - 1) * 0.5 - 1) * 0.3 + 0.8, s2 = -0.5 / (sx * sx);
-    std::vector<double> w(n);
-    double sum = 0;
-    for (int i = 0; i < n; ++i) { const double x = i - (n - 1) * 0.5; w[i] = std::exp(s2 * x * x); sum += w[i]; }
-    sum = 1. / sum;
-    for (int i = 0; i < n; ++i) kf[i] = (float)(w[i] * sum);
+    orc_get_gaussian_kernel(n, sigma, k.ptr<float>(0));
     return k;
 }
 
+class UMat {};   // named by superres/src/input_array_utility.hpp; never instantiated with data
 namespace cuda {
-enum FeatureSet { FEATURE_SET_COMPUTE_10 = 10, FEATURE_SET_COMPUTE_11 = 11, FEATURE_SET_COMPUTE_12 = 12, FEATURE_SET_COMPUTE_13 = 13 };
+enum FeatureSet { FEATURE_SET_COMPUTE_10 = 10, FEATURE_SET_COMPUTE_11 = 11, FEATURE_SET_COMPUTE_12 = 12, FEATURE_SET_COMPUTE_13 = 13,
+                  FEATURE_SET_COMPUTE_20 = 20 };
 inline bool deviceSupports(FeatureSet) { return true; }
+// the device the kernels are compiled "for" (oracle/Makefile.ref: -D__CUDA_ARCH__=700): cc >= 20 selects the 32 x 8 / 16 x 16 launch geometry
+// of the separable filter (cudafilters/src/cuda/row_filter.hpp:150-161, column_filter.hpp:150-161)
+class DeviceInfo {
+public:
+    int majorVersion() const { return 7; }
+    int minorVersion() const { return 0; }
+};
 class Event;
 class Stream {   // every call of this stub runs synchronously on the host: the streams only order work that is already ordered
 public:
+    Stream() : null_(false) {}   // a stream of one's own is not the null stream: StreamAccessor::getStream is non-zero for it, and the
+                                 // reference's launchers take their stream branch (cudawarping/src/cuda/remap.cu:240-243) as in the class
     void waitForCompletion() {}
     void waitEvent(const Event &) {}
-    explicit operator bool() const { return false; }   // "the default stream": FarnebackOpticalFlowImpl::calcImpl then skips its event plumbing
-    static Stream &Null() { static Stream s; return s; }
+    explicit operator bool() const { return !null_; }   // "the default stream": FarnebackOpticalFlowImpl::calcImpl then skips its event plumbing
+    static Stream &Null() { static Stream s(true); return s; }
+private:
+    explicit Stream(bool null) : null_(null) {}
+    bool null_;
 };
 class Event {
 public:
@@ -203,6 +239,7 @@ public:
     int rows = 0, cols = 0;
     size_t step = 0;
     unsigned char *data = nullptr;
+    unsigned char *datastart = nullptr;
     GpuMat() {}
     GpuMat(Size s, int type) { create(s, type); }
     GpuMat(int r, int c, int type) { create(r, c, type); }
@@ -217,9 +254,25 @@ public:
         type_ = type; rows = r; cols = c;
         step = ((size_t)c * elem_size_of(type) + 255) / 256 * 256;   // a pitched allocation, like cudaMallocPitch
         buf_ = std::make_shared<std::vector<unsigned char> >((size_t)r * step + 64);
-        data = buf_->data();
+        data = datastart = buf_->data();
+        whole_ = Size(c, r);
     }
     void create(Size s, int type) { create(s.height, s.width, type); }
+    void locateROI(Size &wholeSize, Point &ofs) const   // where this view lies in its allocation
+    {
+        const size_t d = (size_t)(data - datastart);
+        ofs.y = step ? (int)(d / step) : 0;
+        ofs.x = (int)((d - (size_t)ofs.y * step) / elem_size_of(type_));
+        wholeSize = whole_;
+    }
+    GpuMat reshape(int cn) const   // the same rows read with another channel count (cols * channels() stays)
+    {
+        CV_Assert((cols * channels()) % cn == 0);
+        GpuMat m = *this;
+        m.cols = cols * channels() / cn;
+        m.type_ = CV_MAKETYPE(depth(), cn);
+        return m;
+    }
     GpuMat operator()(const Rect &r) const
     {
         CV_Assert(r.x >= 0 && r.y >= 0 && r.x + r.width <= cols && r.y + r.height <= rows);
@@ -243,8 +296,11 @@ public:
     void download(Mat &dst) const;
     void upload(const Mat &src);
     void copyTo(GpuMat &dst, Stream &stream) const;
+    void copyTo(GpuMat &dst) const { copyTo(dst, Stream::Null()); }
+    void convertTo(GpuMat &dst, int rtype) const;   // CV_8U <-> CV_32F, any channel count (BTVL1_CUDA's frames in, results out)
 private:
     int type_ = CV_8UC1;
+    Size whole_;
     std::shared_ptr<std::vector<unsigned char> > buf_;
 };
 inline void swap(GpuMat &a, GpuMat &b) { GpuMat t = a; a = b; b = t; }
@@ -261,17 +317,23 @@ inline Mat::Mat(const cuda::GpuMat &m) { m.download(*this); }
 // InputArray / OutputArray proxies over GpuMat (the only kind this translation unit passes)
 class _InputArray {
 public:
+    enum KindFlag { NONE = 0, MAT = 1 << 16, CUDA_GPU_MAT = 9 << 16, UMAT = 10 << 16 };
     _InputArray() : m_(nullptr) {}
     _InputArray(const cuda::GpuMat &m) : m_(const_cast<cuda::GpuMat *>(&m)) {}
-    _InputArray(const Mat &) : m_(nullptr) {}   // cudastereo.hpp:360 casts a Mat Q; never called here
+    _InputArray(const Mat &m) : m_(nullptr), mat_(&m) {}   // the kernels of a separable filter (cudafilters/src/filtering.cpp:416-419)
     _InputArray(const double &v) : m_(nullptr), scalar_(v), is_scalar_(true) {}   // cuda::min(mask, 1.0, dst) of surf.cuda.cpp:164
     bool isScalar() const { return is_scalar_; }
     double scalar() const { return scalar_; }
     cuda::GpuMat getGpuMat() const { return m_ ? *m_ : cuda::GpuMat(); }
-    bool empty() const { return !m_ || m_->empty(); }
+    bool empty() const { return mat_ ? mat_->empty() : (!m_ || m_->empty()); }
     cuda::GpuMat *gpuMatPtr() const { return m_; }
+    int kind() const { return m_ ? CUDA_GPU_MAT : mat_ ? MAT : NONE; }
+    bool isMat() const { return mat_ != nullptr; }
+    bool isUMat() const { return false; }
+    Mat getMat() const { return mat_ ? *mat_ : Mat(); }
 protected:
     cuda::GpuMat *m_;
+    const Mat *mat_ = nullptr;
     double scalar_ = 0;
     bool is_scalar_ = false;
 };
@@ -280,6 +342,8 @@ public:
     _OutputArray() {}
     _OutputArray(cuda::GpuMat &m) : _InputArray(m) {}
     void create(Size s, int type) const { CV_Assert(m_); m_->create(s, type); }
+    cuda::GpuMat &getGpuMatRef() const { CV_Assert(m_); return *m_; }
+    void release() const { if (m_) m_->release(); }
 };
 typedef const _InputArray &InputArray;
 typedef const _OutputArray &OutputArray;

@@ -3,7 +3,7 @@
 #define ORACLE_CUDAHOST_PRIVATE_CUDA_HPP
 #include "opencv2/core/cuda.hpp"
 namespace cv { namespace cuda {
-struct StreamAccessor { static cudaStream_t getStream(const Stream &) { return nullptr; } };
+struct StreamAccessor { static cudaStream_t getStream(const Stream &s) { return s ? (cudaStream_t)&s : nullptr; } };
 class BufferPool {
 public:
     explicit BufferPool(Stream &) {}

@@ -44,6 +44,15 @@ struct int2 { int x, y; };
 struct float2 { float x, y; };
 struct int4 { int x, y, z, w; };
 struct float4 { float x, y, z, w; };
+struct float3 { float x, y, z; };
+// the other pixel types the dispatch tables of cudafilters / cudawarping name (never run here; float, float3 and float4 are)
+struct uchar3 { unsigned char x, y, z; };
+struct uchar4 { unsigned char x, y, z, w; };
+struct ushort3 { unsigned short x, y, z; };
+struct ushort4 { unsigned short x, y, z, w; };
+struct short3 { short x, y, z; };
+struct short4 { short x, y, z, w; };
+struct int3 { int x, y, z; };
 typedef unsigned int uint;
 typedef unsigned char uchar;
 typedef unsigned short ushort;
@@ -52,6 +61,7 @@ static inline int2 make_int2(int x, int y) { int2 r = {x, y}; return r; }
 static inline float2 make_float2(float x, float y) { float2 r = {x, y}; return r; }
 static inline int4 make_int4(int x, int y, int z, int w) { int4 r = {x, y, z, w}; return r; }
 static inline float4 make_float4(float x, float y, float z, float w) { float4 r = {x, y, z, w}; return r; }
+static inline float3 make_float3(float x, float y, float z) { float3 r = {x, y, z}; return r; }
 
 namespace cudashim {
 struct Idx { unsigned x, y, z; };
@@ -91,6 +101,7 @@ static inline int __mul24(int a, int b) { return a * b; }
 static inline int __float2int_rn(float v) { return (int)nearbyintf(v); }
 static inline int __float2int_rd(float v) { return (int)floorf(v); }
 static inline int __float2int_ru(float v) { return (int)ceilf(v); }
+static inline int __float2int_rz(float v) { return (int)v; }   // cvt.rzi: toward zero
 // atomicInc(p, limit): old = *p; *p = old >= limit ? 0 : old + 1 (threads of a block are fibers of one host thread: no race)
 static inline unsigned atomicInc(unsigned *p, unsigned limit) { const unsigned old = *p; *p = old >= limit ? 0u : old + 1u; return old; }
 #ifndef CV_PI_F

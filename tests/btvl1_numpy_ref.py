@@ -5,6 +5,12 @@ One function per reference step, deliberately UNFUSED (every intermediate plane 
 independent statement of what the fused HIP kernels must produce.  Every intermediate is np.float32, every sum runs in the
 reference's order, and no operation is contracted into an fma (the library is compiled with -ffp-contract=off).
 Frames are (H, W) or (H, W, CN) arrays, CN in {3, 4}; motions and maps are pairs (x plane, y plane).
+
+THE PIN: tests/test_ref_pin_btvl1.py holds every function here, process() and the BTVL1 ring driver BIT FOR BIT to the reference's own
+kernels and host class executed on the CPU (oracle/_ref/libref_cu.so: btv_l1_gpu.cu, row_filter.hpp / column_filter.hpp, the resize /
+remap kernels, the cudaarithm functors, btv_l1_cuda.cpp verbatim), and tests/golden/btvl1_refclass_*.npz keep that library's output of
+process where the reference tree is absent.  Main-repo pieces (getGaussianKernel, PointFilter / CubicFilter, the border index maps)
+are stand-ins there as well: DESIGN.md 2.
 """
 from __future__ import annotations
 

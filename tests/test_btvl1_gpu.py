@@ -3,6 +3,10 @@ the reference (tests/btvl1_numpy_ref.py), BIT FOR BIT: every value is a fixed se
 only nonlinearity is a comparison), so there is no tolerance anywhere in this file.  Comparisons are on VALUES (a != b counts the
 differing elements, so +0 equals -0: the fused update skips taps that add a signed zero, see csrc/btvl1_kernels.hip); a real
 mismatch flips a sign sample and shows up as a difference of order tau, never of an ulp.
+
+The restatement is itself pinned, bit for bit, on the reference's own kernels and class executed on the host
+(tests/test_ref_pin_btvl1.py, which imports CASES and BAD_PARAMS from here), and tests/test_ref_class_gpu.py compares the product with
+that reference class directly.
 """
 import os
 import sys
@@ -233,14 +237,19 @@ def test_two_launches_per_iteration_whatever_the_window(gpu):
     assert set(counts.values()) == {3}, counts
 
 
+# the parameter sets the reference's CV_Asserts reject, with the status code each maps to (tests/test_ref_pin_btvl1.py holds the
+# reference class itself to this list)
+BAD_PARAMS = ((dict(scale=1), -1), (dict(iterations=0), -1), (dict(tau=0.0), -1), (dict(alpha=0.0), -1), (dict(btv_kernel_size=0), -1),
+              (dict(btv_kernel_size=17), -1), (dict(blur_kernel_size=4), -1), (dict(blur_kernel_size=33), -1), (dict(blur_sigma=-1.0), -1))
+
+
 @pytest.mark.gpu
 def test_argument_checks(gpu):
     """The reference's CV_Asserts (btv_l1_cuda.cpp:310-316, filtering.cpp:441,568) as status codes, before any launch."""
     from opencv_contrib_amd import capi
     frames, fwd, bwd = make_case(1, 16, 16, 1, 3)
     gf, gw, gb = [to_gpu(gpu, f) for f in frames], gpu_motions(gpu, fwd), gpu_motions(gpu, bwd)
-    for kw, code in ((dict(scale=1), -1), (dict(iterations=0), -1), (dict(tau=0.0), -1), (dict(alpha=0.0), -1), (dict(btv_kernel_size=0), -1),
-                     (dict(btv_kernel_size=17), -1), (dict(blur_kernel_size=4), -1), (dict(blur_kernel_size=33), -1), (dict(blur_sigma=-1.0), -1)):
+    for kw, code in BAD_PARAMS:
         with pytest.raises(capi.MiError) as ei:
             make_alg(**kw).process(gf, gw, gb, 1)
         assert ei.value.code == code, kw

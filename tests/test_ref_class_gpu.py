@@ -7,6 +7,9 @@ farneback.cu, stereobm.cu, surf.cu, resize.cu, pyr_down.cu) executed on the host
 /root/reference exists and travels to the GPU box with the snapshot; these tests skip where it is absent.  Tolerances are those of the
 HIP-vs-oracle tests of each class (integer paths bit-exact) -- the oracle equals these classes bit for bit
 (tests/test_ref_pin_cuda.py), so this is the same statement made without the restatement in between.
+
+The last section does the same for superres' BTVL1_CUDA (superres/src/btv_l1_cuda.cpp verbatim over btv_l1_gpu.cu and the cudafilters /
+cudawarping / cudaarithm kernels it runs; pinned to the restatement by tests/test_ref_pin_btvl1.py): 0 differing values.
 """
 import numpy as np
 import pytest
@@ -106,3 +109,126 @@ def test_surf_hip_vs_the_reference_cuda_class(gpu, extended, upright):
     dd = np.abs(desc - ref["descriptors"]).max(1)
     ok = (dd <= 1e-4) | (da > 1e-2)
     assert ok.mean() >= 0.99 or (~ok).sum() <= 2, (float(dd.max()), int((~ok).sum()))
+
+
+# ------------------------------------------------------------------------------------------------ BTV-L1 super-resolution (superres)
+# The product against the reference's BTVL1_CUDA directly: superres/src/btv_l1_cuda.cpp compiled verbatim over btv_l1_gpu.cu, the
+# separable filter, resize / remap and the cudaarithm functors of libref_cu.so (tests/test_ref_pin_btvl1.py says what is verbatim and
+# what a stand-in).  Bit-exact like tests/test_btvl1_gpu.py, and with its convention: VALUES are compared (+0 equals -0, the fused
+# update skips taps that add a signed zero); 0 differing values everywhere.
+needs_btv = pytest.mark.skipif(not refcu.has_btvl1(), reason="oracle/_ref/libref_cu.so holds no BTV-L1 (needs /root/reference to build)")
+
+
+def _btv():
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import test_btvl1_gpu as G
+    return G
+
+
+def _btv_both(gpu, seed, lh, lw, cn, K, base, pitched=False, amp=6.0, **kw):
+    import torch
+    G = _btv()
+    frames, fwd, bwd = G.make_case(seed, lh, lw, cn, K, amp)
+    ref, _ = refcu.cuda_class_btvl1_process(frames, fwd, bwd, base, **kw)
+    alg = G.make_alg(**kw)
+    out = alg.process([G.to_gpu(gpu, f, pitched) for f in frames], G.gpu_motions(gpu, fwd, pitched), G.gpu_motions(gpu, bwd, pitched), base)
+    torch.cuda.synchronize()
+    out = N(out)
+    assert out.shape == ref.shape and out.dtype == ref.dtype and np.isfinite(out).all()
+    ndiff = int((out != ref).sum())
+    print(f"btvl1 vs reference class: seed {seed} {lh}x{lw}x{cn} K {K} base {base} {kw}: {ndiff} of {ref.size} values differ, max |d| "
+          f"{float(np.abs(out - ref).max()):.3g}")
+    return ndiff
+
+
+@needs_btv
+@pytest.mark.parametrize("seed,lh,lw,cn,K,base,pitched,kw", [
+    (31, 37, 53, 1, 1, 0, False, dict(scale=2, iterations=7)),
+    (32, 37, 53, 3, 5, 0, False, dict(scale=3, iterations=7)),
+    (33, 37, 53, 4, 5, 4, True, dict(scale=4, iterations=7)),
+    (34, 37, 53, 1, 5, 2, True, dict(scale=4, iterations=5, lambda_=0.0)),
+    (35, 37, 53, 3, 1, 0, True, dict(scale=2, iterations=7, btv_kernel_size=3, blur_kernel_size=3, blur_sigma=1.2)),
+    # one (blur length, scale) pair just inside and one just outside DATA_LDS_MAX (csrc/btvl1_dev.h): 9 x 4 needs 38 016 B, 13 x 3 42 432 B
+    (36, 37, 53, 1, 5, 2, False, dict(scale=4, iterations=4, blur_kernel_size=9)),
+    (37, 37, 53, 1, 5, 1, False, dict(scale=3, iterations=4, blur_kernel_size=13)),
+    (38, 24, 32, 4, 3, 1, False, dict(scale=2, iterations=4, btv_kernel_size=16, blur_kernel_size=31)),
+])
+def test_btvl1_process_hip_vs_the_reference_cuda_class(gpu, seed, lh, lw, cn, K, base, pitched, kw):
+    """superres.BTVL1_CUDA.process against BTVL1_CUDA_Base::process of the reference: CN 1 / 3 / 4, scale 2 / 3 / 4, K 1 / 5, pitched
+    inputs, lambda 0, both sides of the LDS limit of the data kernel, the largest BTV and blur kernels."""
+    assert _btv_both(gpu, seed, lh, lw, cn, K, base, pitched, **kw) == 0
+
+
+@needs_btv
+def test_btvl1_process_hip_vs_the_reference_cuda_class_at_the_tile_edges(gpu):
+    """Low-res widths 63 / 64 / 65 and heights 7 / 8 / 9: one short of, equal to and one past the HIP kernels' 64 x 4 low-res tiles."""
+    total = 0
+    for lh in (7, 8, 9):
+        for lw in (63, 64, 65):
+            total += _btv_both(gpu, 400 + lh * 100 + lw, lh, lw, 1 if lw != 64 else 3, 3, 1, scale=2 + lh % 3, iterations=3, btv_kernel_size=3)
+    assert total == 0
+
+
+@needs_btv
+def test_btvl1_process_hip_vs_the_reference_cuda_class_with_class_defaults(gpu):
+    """Every parameter at the class's default (scale 4, 180 iterations, tau 1.3, lambda 0.03, alpha 0.7, BTV 7, blur 5, sigma 0) on
+    96 x 128 low-res frames.  One frame (K = 1): the reference side runs its 180 iterations on the host, about a second per frame and
+    iteration at this size; the motion paths are covered by the cases above."""
+    assert _btv_both(gpu, 39, 96, 128, 1, 1, 0) == 0
+
+
+@needs_btv
+@pytest.mark.parametrize("cn,scale,K,base", [(1, 2, 3, 1), (3, 3, 5, 0), (4, 4, 5, 4)])
+def test_btvl1_stage_hip_vs_the_references_own_steps(gpu, cn, scale, K, base):
+    """alg.stage(...) -- the four map planes of every frame, the initial estimate, the blur taps, the BTV weights -- against the
+    reference's calcRelativeMotions -> upscaleMotions -> buildMotionMaps, cuda::resize(INTER_CUBIC), getGaussianKernel (the stub core's)
+    and calcBtvWeights."""
+    import torch
+    G = _btv()
+    frames, fwd, bwd = G.make_case(500 + cn + scale, 37, 53, cn, K)
+    kw = dict(scale=scale, blur_kernel_size=9, blur_sigma=1.2, btv_kernel_size=7, alpha=0.7)
+    alg = G.make_alg(**kw)
+    maps, init, taps, weights = alg.stage([G.to_gpu(gpu, f) for f in frames], G.gpu_motions(gpu, fwd), G.gpu_motions(gpu, bwd), base)
+    torch.cuda.synchronize()
+    rel_f, rel_b = refcu.btv_relative_motions(fwd, bwd, base, (37, 53))
+    hi_f, hi_b = refcu.btv_upscale_motions(rel_f, scale), refcu.btv_upscale_motions(rel_b, scale)
+    for k in range(K):
+        fm, bm = refcu.btv_build_motion_maps(hi_f[k], hi_b[k])
+        for name, g, w in zip(("forwardMap x", "forwardMap y", "backwardMap x", "backwardMap y"), maps[k], fm + bm):
+            g = N(g)
+            assert int((g != w).sum()) == 0, (k, name, int((g != w).sum()), float(np.abs(g - w).max()))
+    ri = refcu.cuda_resize_cubic(frames[base], 37 * scale, 53 * scale)
+    gi = N(init)
+    assert gi.shape == ri.shape and int((gi != ri).sum()) == 0, (int((gi != ri).sum()), float(np.abs(gi - ri).max()))
+    rt, rw = refcu.cuda_gaussian_kernel(9, 1.2), refcu.btv_weights(7, 0.7)
+    assert np.array_equal(np.array(taps[:9], np.float32), rt) and not any(taps[9:])
+    assert np.array_equal(np.array(weights[:49], np.float32), rw) and not any(weights[49:])
+
+
+@needs_btv
+def test_btvl1_class_hip_vs_the_reference_class_on_recorded_flows(gpu):
+    """The whole class over 12 frames, radius 2, the product's own Farneback flows recorded in call order -- and the reference's
+    BTVL1_CUDA (its ring driver, its process) fed the same frames and the same flows: the same number of outputs, every byte equal."""
+    import torch
+    from opencv_contrib_amd import superres
+    G = _btv()
+    _, low, _ = G.R.synthetic_sequence(17, n=12, hh=96, hw=128, scale=2)
+    alg = G.make_alg(scale=2, iterations=6)
+    alg.setTemporalAreaRadius(2)
+    rec = G.RecordingFlow(superres.createOptFlow_Farneback_CUDA())
+    alg.setOpticalFlow(rec)
+    alg.setInput(superres.createFrameSource_List([torch.from_numpy(f).to(gpu) for f in low]))
+    outs = []
+    while (o := alg.nextFrame()) is not None:
+        outs.append(N(o))
+        assert len(outs) <= 12
+    assert len(outs) == 12 and len(rec.log) == 22
+    assert len({f.tobytes() for f in low}) == 12          # the replaying flow of the reference side tells the frames apart by their bytes
+    ref_outs, ref_calls, ended = refcu.cuda_class_btvl1_sequence(low, rec.log, temporal_area_radius=2, scale=2, iterations=6)
+    assert len(ref_outs) == 12 and ended and len(ref_calls) == 22
+    assert ref_calls == [c for i in range(11) for c in ((i, i + 1), (i + 1, i))]
+    for i in range(12):
+        assert outs[i].dtype == np.uint8 and outs[i].shape == ref_outs[i].shape
+        assert int((outs[i] != ref_outs[i]).sum()) == 0, (i, int((outs[i] != ref_outs[i]).sum()))
