@@ -14,27 +14,17 @@ struct mi_surf {
     mi_surf_params P;
     // tables (surf.cpp:544-565 generators; see oracle/surf_ref.c for the correspondence with surf.cu:520-522,685-707)
     float *apt = nullptr, *dw = nullptr;
-    // scratch sized for (rows, cols, layers)
-    int capR = 0, capC = 0, capL = 0, capCand = 0;
-    unsigned *sum = nullptr, *msum = nullptr, *V = nullptr, *BT = nullptr, *poly = nullptr;
-    float *det = nullptr, *trace = nullptr;
-    unsigned long long *bits = nullptr, *sbits = nullptr;
-    unsigned *rowcnt = nullptr, *segcnt = nullptr;
-    int4 *cand = nullptr;
-    void *itmp = nullptr;   // per-candidate interpolation results
-    unsigned *counters = nullptr;   // [0] = features, [1 + octave] = candidates of the octave (surf.cuda.cpp:158-159)
-    int sld = 0, vld = 0, dld = 0;
-    // all octaves per launch (surf::detect_fused): region sizes and the per-(octave, layer) filter geometry on the device
-    bool fused = false;
-    bool use_poly = false;
-    int lds_tiles = 0;   // octave 0 of the fused det / trace launch on LDS tiles: this handle's decision (MIFLOW_SURF_LDS=0 switches it off)
-    int capO = 0;
-    void *geo = nullptr;
-    std::vector<unsigned char> geo_host;   // source of the asynchronous upload: outlives the call
+    // what a detect call runs and on which buffers (surf_plan.h): the plan of the last frame's shape, made with the switches as they
+    // were when the scratch was allocated (this handle's decision: no process-global state); shape.rows == 0: no scratch
+    surf::SurfPlan plan = {};
+    surf::SurfKnobs knobs = {};
+    surf::DetectBufs B = {};
+    int capCand = 0;                          // candidates the lists were allocated for (>= plan.shape.max_candidates)
+    std::vector<surf::HaarGeo> geo_host;      // source of the asynchronous upload: outlives the call
     bool geo_dirty = false;
 };
 
-static int calc_size(int octave, int layer) { return (9 + 6 * layer) << octave; }
+using surf::calc_size;
 
 // The Gaussian kernel behind surf.cu's literal weight tables (c_aptW :522, c_DW :685-707): cv::getGaussianKernel(n, sigma, CV_32F) as
 // OpenCV 2.4 rounded it -- exp() in double rounded to float, the float terms summed in double, float * (1 / sum) in double rounded to
@@ -85,7 +75,7 @@ int mi_surf_create(const mi_surf_params *p, mi_surf **out)
         MI_HIP_TRY(hipMalloc((void **)&h->dw, sizeof(dw)));
         MI_HIP_TRY(hipMemcpy(h->apt, apt, sizeof(apt), hipMemcpyHostToDevice));
         MI_HIP_TRY(hipMemcpy(h->dw, dw, sizeof(dw), hipMemcpyHostToDevice));
-        MI_HIP_TRY(hipMalloc((void **)&h->counters, sizeof(unsigned) * 64));
+        MI_HIP_TRY(hipMalloc((void **)&h->B.counters, sizeof(unsigned) * 64));
         return MI_OK;
     };
     if (const int rc = upload()) { mi_surf_destroy(h); return rc; }
@@ -98,10 +88,15 @@ int mi_surf_get_params(const mi_surf *h, mi_surf_params *p) { MI_REQUIRE(h && p,
 
 static void free_scratch(mi_surf *h)
 {
-    void *ps[] = {h->poly, h->sum, h->msum, h->V, h->BT, h->det, h->trace, h->bits, h->sbits, h->rowcnt, h->segcnt, h->cand, h->itmp, h->geo};
-    for (void *p : ps) if (p) (void)hipFree(p);
-    h->sum = h->msum = h->V = h->BT = h->poly = nullptr; h->det = h->trace = nullptr; h->bits = nullptr; h->sbits = nullptr; h->rowcnt = nullptr; h->segcnt = nullptr; h->cand = nullptr; h->itmp = nullptr; h->geo = nullptr;
-    h->capR = h->capC = h->capL = h->capCand = h->capO = 0;
+    void *ps[sizeof(surf::DetectBufs) / sizeof(void *)];
+    static_assert(sizeof(ps) == sizeof(surf::DetectBufs), "DetectBufs holds pointers only");
+    unsigned *const counters = h->B.counters;   // not scratch: the handle's for life
+    memcpy(ps, &h->B, sizeof(ps));
+    for (void *p : ps) if (p && p != counters) (void)hipFree(p);
+    h->B = surf::DetectBufs();
+    h->B.counters = counters;
+    h->plan = surf::SurfPlan();
+    h->capCand = 0;
 }
 
 void mi_surf_release_memory(mi_surf *h) { if (h) free_scratch(h); }   // SURF_CUDA::releaseMemory, surf.cuda.cpp:434-442
@@ -112,7 +107,7 @@ void mi_surf_destroy(mi_surf *h)
     free_scratch(h);
     if (h->apt) (void)hipFree(h->apt);
     if (h->dw) (void)hipFree(h->dw);
-    if (h->counters) (void)hipFree(h->counters);
+    if (h->B.counters) (void)hipFree(h->B.counters);
     delete h;
 }
 
@@ -144,64 +139,64 @@ int mi_surf_max_features(const mi_surf *h, int rows, int cols, int *max_features
     return limits(h->P, rows, cols, max_features, &mc);
 }
 
-static int ensure(mi_surf *h, int rows, int cols, int layers, int maxCand, bool need_mask, hipStream_t st)
+// The switches of the plan, read when a handle (re-)allocates its scratch.  MIFLOW_SURF_FUSED / _LDS exist in the experiments build only;
+// MIFLOW_SURF_NMS0=1 is the round 5 experiment kept as a tested opt-in: octave 0's maxima flagged inside the det kernel, no det / trace
+// planes for three quarters of the samples.  Bit-identical, but SLOWER on MI355X (r14j, 4K frame: k_det_nms0 180 us against 103 + 65 us
+// for the tile kernel + the flag launch -- the 18 % of overlapping samples cost more than the planes' 265 MB -- and the refinement's 27
+// re-evaluations per candidate 143 us against 15): 736 against 826 frames/s.  MIFLOW_SURF_POLY=0 keeps the strided gathers of octaves
+// >= 1 instead of the polyphase planes of round 5 (bit-identical either way).
+static surf::SurfKnobs read_knobs()
 {
-    const int octaves = h->P.n_octaves;
-    // the plan (fused or not, region sizes, the geometry table) is that of EXACTLY this (size, octaves, layers): a handle whose
-    // nOctaveLayers was lowered re-plans instead of running on the larger plan's table
-    if (!(h->capR == rows && h->capC == cols && h->capL == layers && h->capCand >= maxCand && h->capO == octaves)) {
-        free_scratch(h);
-        h->sld = align_up(cols + 1, 64); h->vld = align_up(cols, 64); h->dld = align_up(cols, 64);
-        // one launch per stage for all octaves where the kernel arguments hold them (surf::fused_supported), else octave by octave
-        // through one set of planes; the fused form keeps every octave's planes: ~4/3 of octave 0's
-        h->fused = surf::fused_supported(octaves, layers) && !(MI_EXP_ENV("MIFLOW_SURF_FUSED") && atoi(MI_EXP_ENV("MIFLOW_SURF_FUSED")) == 0);
-        {
-            static const bool lds_ok = surf::lds_geometry_self_check();   // the LDS path's compile-time geometry against the host's
-            const char *e = MI_EXP_ENV("MIFLOW_SURF_LDS");
-            h->lds_tiles = (lds_ok && !(e && atoi(e) == 0)) ? 1 : 0;
-            // round 5 experiment, kept as a tested opt-in (MIFLOW_SURF_NMS0=1): octave 0's maxima flagged inside the det kernel, no det /
-            // trace planes for three quarters of the samples.  Bit-identical, but SLOWER on MI355X (r14j, 4K frame: k_det_nms0 180 us
-            // against 103 + 65 us for the tile kernel + the flag launch -- the 18 % of overlapping samples cost more than the planes'
-            // 265 MB -- and the refinement's 27 re-evaluations per candidate 143 us against 15): 736 against 826 frames/s
-            const char *n0 = getenv("MIFLOW_SURF_NMS0");
-            if (h->lds_tiles && n0 && *n0 && atoi(n0) != 0) h->lds_tiles = 2;
-            // round 5: octaves >= 1 read their taps from polyphase planes of the integral image (consecutive lanes = consecutive words
-            // instead of words 2^o apart); MIFLOW_SURF_POLY=0 keeps the strided gathers (bit-identical either way)
-            const char *pp = getenv("MIFLOW_SURF_POLY");
-            h->use_poly = h->fused && octaves > 1 && !(pp && *pp && atoi(pp) == 0);
-            if (h->use_poly) h->lds_tiles |= 4;
+    static const bool lds_ok = surf::lds_geometry_self_check();   // the LDS path's compile-time geometry against the host's
+    const char *f = MI_EXP_ENV("MIFLOW_SURF_FUSED"), *l = MI_EXP_ENV("MIFLOW_SURF_LDS"), *n0 = getenv("MIFLOW_SURF_NMS0"), *pp = getenv("MIFLOW_SURF_POLY");
+    surf::SurfKnobs K;
+    K.fused = !(f && atoi(f) == 0);
+    K.lds = !(l && atoi(l) == 0);
+    K.nms0 = n0 && *n0 && atoi(n0) != 0;
+    K.poly = !(pp && *pp && atoi(pp) == 0);
+    K.lds_ok = lds_ok;
+    return K;
+}
+
+static int ensure(mi_surf *h, int rows, int cols, int maxCand, bool need_mask, hipStream_t st)
+{
+    // the plan (launch forms, region sizes, the geometry table) is that of EXACTLY this shape: a handle whose nOctaveLayers was lowered
+    // re-plans instead of running on the larger plan's table.  Only candidate lists that are large enough are kept.
+    const surf::SurfShape Z = {rows, cols, h->P.n_octaves, h->P.n_octave_layers, maxCand};
+    if (!(Z == h->plan.shape)) {
+        surf::SurfShape held = h->plan.shape;
+        held.max_candidates = maxCand;
+        if (held == Z && h->capCand >= maxCand) h->plan = surf::surf_make_plan(Z, h->knobs);
+        else {
+            free_scratch(h);
+            h->knobs = read_knobs();
+            const surf::SurfPlan p = surf::surf_make_plan(Z, h->knobs);
+            surf::DetectBufs &B = h->B;
+            MI_HIP_TRY(hipMalloc((void **)&B.sum, sizeof(unsigned) * p.sum_words));
+            MI_HIP_TRY(hipMalloc((void **)&B.V, sizeof(unsigned) * p.v_words));
+            MI_HIP_TRY(hipMalloc((void **)&B.BT, sizeof(unsigned) * p.bt_words));
+            MI_HIP_TRY(hipMalloc((void **)&B.det, sizeof(float) * p.plane_floats));
+            MI_HIP_TRY(hipMalloc((void **)&B.trace, sizeof(float) * p.plane_floats));
+            MI_HIP_TRY(hipMalloc((void **)&B.bits, sizeof(unsigned long long) * p.bits_words));
+            if (p.sbits_words) MI_HIP_TRY(hipMalloc((void **)&B.sbits, sizeof(unsigned long long) * p.sbits_words));
+            MI_HIP_TRY(hipMalloc((void **)&B.rowcnt, sizeof(unsigned) * p.row_counts));
+            MI_HIP_TRY(hipMalloc((void **)&B.segcnt, sizeof(unsigned) * p.seg_counts));
+            MI_HIP_TRY(hipMalloc((void **)&B.cand, sizeof(int4) * p.cand_items));
+            MI_HIP_TRY(hipMalloc(&B.itmp, surf::interp_tmp_bytes(p.cand_items)));
+            if (p.fused) {
+                h->geo_host.resize(p.geo_bytes / sizeof(surf::HaarGeo));
+                surf::surf_fill_geometry(p, h->geo_host.data());
+                if (p.poly_words) MI_HIP_TRY(hipMalloc((void **)&B.poly, sizeof(unsigned) * p.poly_words));
+                MI_HIP_TRY(hipMalloc(&B.geo, p.geo_bytes));
+                h->geo_dirty = true;
+            }
+            h->plan = p;   // (an allocation that failed leaves the handle without a plan)
+            h->capCand = maxCand;
         }
-        surf::FusedSizes z;
-        z.plane_floats = (size_t)h->dld * rows * (layers + 2);
-        z.bits_words = (size_t)layers * rows * div_up(cols, 64);
-        z.row_counts = (size_t)layers * rows + 1;
-        z.seg_counts = (size_t)layers * rows * surf::nms_segments(cols);
-        z.geo_bytes = 0; z.poly_words = 0;
-        if (h->fused) surf::fused_sizes(rows, cols, h->dld, octaves, layers, &z);
-        const size_t nlists = h->fused ? (size_t)octaves : 1;
-        MI_HIP_TRY(hipMalloc((void **)&h->sum, sizeof(unsigned) * (size_t)h->sld * (rows + 1)));
-        MI_HIP_TRY(hipMalloc((void **)&h->V, sizeof(unsigned) * (size_t)h->vld * rows));
-        MI_HIP_TRY(hipMalloc((void **)&h->BT, sizeof(unsigned) * (size_t)h->vld * surf::integral_bands(rows)));
-        MI_HIP_TRY(hipMalloc((void **)&h->det, sizeof(float) * z.plane_floats));
-        MI_HIP_TRY(hipMalloc((void **)&h->trace, sizeof(float) * z.plane_floats));
-        MI_HIP_TRY(hipMalloc((void **)&h->bits, sizeof(unsigned long long) * z.bits_words));
-        MI_HIP_TRY(hipMalloc((void **)&h->sbits, sizeof(unsigned long long) * z.bits_words));
-        MI_HIP_TRY(hipMalloc((void **)&h->rowcnt, sizeof(unsigned) * z.row_counts));
-        MI_HIP_TRY(hipMalloc((void **)&h->segcnt, sizeof(unsigned) * z.seg_counts));
-        MI_HIP_TRY(hipMalloc((void **)&h->cand, sizeof(int4) * (size_t)maxCand * nlists));
-        MI_HIP_TRY(hipMalloc(&h->itmp, surf::interp_tmp_bytes(maxCand) * nlists));
-        if (h->fused) {
-            h->geo_host.assign(z.geo_bytes, 0);
-            surf::fused_geometry(h->sld, octaves, layers, h->geo_host.data(), rows, cols, h->use_poly);
-            if (h->use_poly) MI_HIP_TRY(hipMalloc((void **)&h->poly, sizeof(unsigned) * z.poly_words));
-            MI_HIP_TRY(hipMalloc(&h->geo, z.geo_bytes));
-            h->geo_dirty = true;
-        }
-        h->capR = rows; h->capC = cols; h->capL = layers; h->capCand = maxCand; h->capO = octaves;
     }
-    if (need_mask && !h->msum) MI_HIP_TRY(hipMalloc((void **)&h->msum, sizeof(unsigned) * (size_t)h->sld * (rows + 1)));
+    if (need_mask && !h->B.msum) MI_HIP_TRY(hipMalloc((void **)&h->B.msum, sizeof(unsigned) * h->plan.sum_words));
     if (h->geo_dirty) {   // on the call's stream, not a blocking null-stream copy
-        MI_HIP_TRY(hipMemcpyAsync(h->geo, h->geo_host.data(), h->geo_host.size(), hipMemcpyHostToDevice, st));
+        MI_HIP_TRY(hipMemcpyAsync(h->B.geo, h->geo_host.data(), h->plan.geo_bytes, hipMemcpyHostToDevice, st));
         h->geo_dirty = false;
     }
     return MI_OK;
@@ -222,7 +217,7 @@ static int check_kp(const mi_mat *kp, int min_cols)
 }
 
 // Everything of SURF_CUDA_Invoker's detectKeypoints + findOrientation enqueued on `st`; the feature count stays on the device
-// (h->counters[0]).  *max_features = the bound the keypoint matrix was checked against.
+// (h->B.counters[0]).  *max_features = the bound the keypoint matrix was checked against.
 static int detect_enqueue(mi_surf *h, const mi_mat *img, const mi_mat *mask, mi_mat *keypoints, int *max_features, hipStream_t st)
 {
     const mi_surf_params &P = h->P;
@@ -237,27 +232,29 @@ static int detect_enqueue(mi_surf *h, const mi_mat *img, const mi_mat *mask, mi_
     int maxF, maxC;
     if ((rc = limits(P, rows, cols, &maxF, &maxC))) return rc;
     if ((rc = check_kp(keypoints, maxF))) return rc;
-    if ((rc = ensure(h, rows, cols, P.n_octave_layers, maxC, use_mask, st))) return rc;
+    if ((rc = ensure(h, rows, cols, maxC, use_mask, st))) return rc;
+    const surf::SurfPlan &Q = h->plan;
+    surf::DetectBufs B = h->B;
+    if (!use_mask) B.msum = nullptr;
     const int kld = (int)(keypoints->step / 4);
     float *kp = (float *)keypoints->data;
 
-    MI_HIP_TRY(hipMemsetAsync(h->counters, 0, sizeof(unsigned) * 64, st));                                           // :158-159
-    if ((rc = surf::integral((const unsigned char *)img->data, (long long)img->step, rows, cols, false, h->V, h->BT, h->vld, h->sum, h->sld, st))) return rc;   // :163
-    if (use_mask && (rc = surf::integral((const unsigned char *)mask->data, (long long)mask->step, rows, cols, true, h->V, h->BT, h->vld, h->msum, h->sld, st)))
+    MI_HIP_TRY(hipMemsetAsync(B.counters, 0, sizeof(unsigned) * 64, st));                                            // :158-159
+    if ((rc = surf::integral((const unsigned char *)img->data, (long long)img->step, rows, cols, false, B.V, B.BT, Q.vld, B.sum, Q.sld, st))) return rc;   // :163
+    if (use_mask && (rc = surf::integral((const unsigned char *)mask->data, (long long)mask->step, rows, cols, true, B.V, B.BT, Q.vld, B.msum, Q.sld, st)))
         return rc;                                                                                                    // :165-169
     MI_HIP_TRY(hipMemset2DAsync(kp, keypoints->step, 0, (size_t)maxF * 4, 7, st));                                   // keypoints.setTo(0) :180
-    if (h->fused) {                                                                                                  // :182-204, all octaves per launch
-        if ((rc = surf::detect_fused(h->sum, use_mask ? h->msum : nullptr, h->sld, rows, cols, P.n_octaves, P.n_octave_layers,
-                                     (float)P.hessian_threshold, h->det, h->trace, h->dld, h->bits, h->rowcnt, h->segcnt, h->cand, maxC,
-                                     h->counters + 1, h->itmp, h->geo, kp, kld, maxF, h->counters, h->lds_tiles, st, h->sbits, h->poly))) return rc;
+    if (Q.fused) {                                                                                                   // :182-204, all octaves per launch
+        if ((rc = surf::detect_all(Q, B, (float)P.hessian_threshold, kp, kld, maxF, st))) return rc;
     } else
     for (int octave = 0; octave < P.n_octaves; ++octave) {                                                           // :182-204
-        if ((rc = surf::det_trace(h->sum, h->sld, rows, cols, octave, P.n_octave_layers, h->det, h->trace, h->dld, st))) return rc;
-        if ((rc = surf::find_maxima(h->det, h->trace, h->dld, use_mask ? h->msum : nullptr, h->sld, rows, cols, octave, P.n_octave_layers,
-                                    (float)P.hessian_threshold, h->bits, h->rowcnt, h->segcnt, h->cand, maxC, h->counters + 1 + octave, st))) return rc;
-        if ((rc = surf::interpolate(h->det, h->dld, rows, cols, octave, h->cand, h->counters + 1 + octave, maxC, h->itmp, kp, kld, maxF, h->counters, st))) return rc;
+        unsigned *const ncand = B.counters + 1 + octave;
+        if ((rc = surf::det_trace(B.sum, Q.sld, rows, cols, octave, P.n_octave_layers, B.det, B.trace, Q.dld, st))) return rc;
+        if ((rc = surf::find_maxima(B.det, B.trace, Q.dld, B.msum, Q.sld, rows, cols, octave, P.n_octave_layers,
+                                    (float)P.hessian_threshold, B.bits, B.rowcnt, B.segcnt, B.cand, maxC, ncand, st))) return rc;
+        if ((rc = surf::interpolate(B.det, Q.dld, rows, cols, octave, B.cand, ncand, maxC, B.itmp, kp, kld, maxF, B.counters, st))) return rc;
     }
-    if ((rc = surf::orientation(h->sum, h->sld, rows, cols, kp, kld, h->counters, maxF, P.upright != 0, h->apt, st))) return rc;   // :211-214
+    if ((rc = surf::orientation(B.sum, Q.sld, rows, cols, kp, kld, B.counters, maxF, P.upright != 0, h->apt, st))) return rc;   // :211-214
     *max_features = maxF;
     return MI_OK;
 }
@@ -265,7 +262,7 @@ static int detect_enqueue(mi_surf *h, const mi_mat *img, const mi_mat *mask, mi_
 static int read_count(mi_surf *h, int maxF, int *n_features, hipStream_t st)
 {
     unsigned nf = 0;
-    MI_HIP_TRY(hipMemcpyAsync(&nf, h->counters, sizeof(unsigned), hipMemcpyDeviceToHost, st));                       // :205-207
+    MI_HIP_TRY(hipMemcpyAsync(&nf, h->B.counters, sizeof(unsigned), hipMemcpyDeviceToHost, st));                       // :205-207
     MI_HIP_TRY(hipStreamSynchronize(st));
     *n_features = (int)(nf < (unsigned)maxF ? nf : (unsigned)maxF);
     return MI_OK;
@@ -301,7 +298,7 @@ int mi_surf_detect_and_compute(mi_surf *h, const mi_mat *img, const mi_mat *mask
     if ((rc = detect_enqueue(h, img, mask, keypoints, &maxF, st))) return rc;
     if ((rc = surf::descriptors((const unsigned char *)img->data, (long long)img->step, img->rows, img->cols, (const float *)keypoints->data,
                                 (int)(keypoints->step / 4), maxF, h->P.extended != 0, (float *)descriptors->data,
-                                (long long)(descriptors->step / 4), h->dw, st, h->counters))) return rc;
+                                (long long)(descriptors->step / 4), h->dw, st, h->B.counters))) return rc;
     return read_count(h, maxF, n_features, st);
 }
 
@@ -327,9 +324,9 @@ int mi_surf_compute_orientation(mi_surf *h, const mi_mat *img, mi_mat *keypoints
     const int rows = img->rows, cols = img->cols;
     int maxF, maxC;
     if ((rc = limits(h->P, rows, cols, &maxF, &maxC))) return rc;
-    if ((rc = ensure(h, rows, cols, h->P.n_octave_layers, maxC, false, st))) return rc;
-    if ((rc = surf::integral((const unsigned char *)img->data, (long long)img->step, rows, cols, false, h->V, h->BT, h->vld, h->sum, h->sld, st))) return rc;
-    return surf::orientation(h->sum, h->sld, rows, cols, (float *)keypoints->data, (int)(keypoints->step / 4), nullptr, n_features,
+    if ((rc = ensure(h, rows, cols, maxC, false, st))) return rc;
+    if ((rc = surf::integral((const unsigned char *)img->data, (long long)img->step, rows, cols, false, h->B.V, h->B.BT, h->plan.vld, h->B.sum, h->plan.sld, st))) return rc;
+    return surf::orientation(h->B.sum, h->plan.sld, rows, cols, (float *)keypoints->data, (int)(keypoints->step / 4), nullptr, n_features,
                              h->P.upright != 0, h->apt, st);
 }
 

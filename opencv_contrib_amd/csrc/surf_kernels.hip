@@ -30,7 +30,6 @@ namespace surf {
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 __device__ __forceinline__ int rn(float v) { return __float2int_rn(v); }
-__host__ __device__ __forceinline__ int calc_size(int octave, int layer) { return (9 + 6 * layer) << octave; }   // surf.cu:161-173
 
 // ------------------------------------------------------------------ integral image
 // pass A: band-local vertical prefix V[y][x] = sum of img[y0..y][x] (u32) and band totals BT[band][x]
@@ -184,61 +183,9 @@ __device__ __forceinline__ float haar(const SumTex &t, const float (&src)[N][5],
 //   * workgroups walk the layer in XCD-contiguous row bands (the eight L2s each keep their own rows of the integral table, all
 //     layers of an octave back to back) -- profiles/r02u counted 3.2 x the table in FETCH_SIZE with the plain order.
 // det / trace planes stay bit-identical to the oracle (hence to surf.cl / surf.cu).
-struct HaarGeo {       // per layer: tap offsets (elements, relative to the sample's top-left corner) and 1 / area, area of the 10 boxes
-    int xx[4][2];      // Dxx corners [x edge 0..3][y edge 0..1]
-    int yy[2][4];      // Dyy corners [x edge 0..1][y edge 0..3]
-    int xy[4][4];      // Dxy corners [y edge][x edge]
-    double ry[10], area[10];   // boxes: Dxx 0..2, Dyy 3..5, Dxy 6..9
-};
-// host side (the geometry of a layer does not depend on the sample): rintf = round-half-even = __float2int_rn of the device code
-constexpr int kMaxFusedOctaves = 6;
-template <class Off>   // off(ey, ex): word offset of the tap (ey rows, ex columns) from the sample's top-left corner
-static HaarGeo haar_geo_off(int size, Off off)
-{
-    HaarGeo g;
-    const float ratio = (float)size / 9;
-    const auto rnh = [](float v) { return (int)rintf(v); };
-    const int e0369[4] = {rnh(ratio * 0.f), rnh(ratio * 3.f), rnh(ratio * 6.f), rnh(ratio * 9.f)};
-    const int e27[2] = {rnh(ratio * 2.f), rnh(ratio * 7.f)};
-    const int e1458[4] = {rnh(ratio * 1.f), rnh(ratio * 4.f), rnh(ratio * 5.f), rnh(ratio * 8.f)};
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 2; ++j) { g.xx[i][j] = off(e27[j], e0369[i]); g.yy[j][i] = off(e0369[i], e27[j]); }
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) g.xy[i][j] = off(e1458[i], e1458[j]);
-    for (int k = 0; k < 3; ++k) {
-        g.area[k] = (double)((e0369[k + 1] - e0369[k]) * (e27[1] - e27[0]));
-        g.area[3 + k] = g.area[k];   // Dyy is Dxx transposed: the same edge differences
-    }
-    g.area[6] = (double)((e1458[1] - e1458[0]) * (e1458[1] - e1458[0]));
-    g.area[7] = (double)((e1458[3] - e1458[2]) * (e1458[1] - e1458[0]));
-    g.area[8] = g.area[7];
-    g.area[9] = (double)((e1458[3] - e1458[2]) * (e1458[3] - e1458[2]));
-    for (int k = 0; k < 10; ++k) g.ry[k] = 1.0 / g.area[k];
-    return g;
-}
-static HaarGeo haar_geo(int size, int sld) { return haar_geo_off(size, [sld](int ey, int ex) { return ey * sld + ex; }); }
+// (HaarGeo, per layer: the tap offsets relative to the sample's top-left corner, the areas of the 10 boxes and their reciprocals: surf_plan.h)
 
-// ---- polyphase copies of the integral image for octaves >= 1 (round 5).  A sample of octave o sits at S[(i << o)][(j << o)] and its
-// taps at fixed offsets (ey, ex) from there: the 64 lanes of a wave (consecutive j) read words 2^o apart -- 8 .. 32 lines of 64 B per
-// load, the L1 tag-lookup rate that bounds the gather path (profiles/surf_counters.json).  With the integral image also stored as 4^o
-// PHASE PLANES per octave, plane (y & m, x & m) holding S[y][x] at (y >> o, x >> o), the same tap is
-//     plane(ey & m, ex & m)[i + (ey >> o)][j + (ex >> o)]
-// i.e. consecutive lanes read CONSECUTIVE words (4-5 lines per load), and the tap is still "lane offset + wave-uniform offset": only the
-// geometry table and the lane offset change, the integers read -- and with them every det / trace value -- are the same.
-struct PolyGeo { int prows, pld; long long plane_words, base; };   // per octave (octave 0: unused)
-static PolyGeo poly_geo(int rows, int cols, int o, long long base)
-{
-    PolyGeo g;
-    g.prows = (rows >> o) + 2; g.pld = align_up((cols >> o) + 2, 64);
-    g.plane_words = (long long)g.prows * g.pld; g.base = base;
-    return g;
-}
-static long long poly_total_words(int rows, int cols, int n_octaves)
-{
-    long long w = 0;
-    for (int o = 1; o < n_octaves; ++o) w += poly_geo(rows, cols, o, 0).plane_words << (2 * o);
-    return w;
-}
+// ---- polyphase copies of the integral image for octaves >= 1 (round 5; layout: surf_plan.h PolyGeo)
 struct PolyArgs { int n; int prows[kMaxFusedOctaves], pld[kMaxFusedOctaves]; long long plane_words[kMaxFusedOctaves], base[kMaxFusedOctaves]; };
 // one thread per word of the integral image: coalesced read, one store per octave (runs of 64 >> o consecutive words per plane)
 __global__ __launch_bounds__(256) void k_poly_build(SumTex t, unsigned *poly, PolyArgs A)
@@ -253,7 +200,6 @@ __global__ __launch_bounds__(256) void k_poly_build(SumTex t, unsigned *poly, Po
         poly[A.base[o] + (long long)(((y & m) << o) + (x & m)) * A.plane_words[o] + (long long)(y >> o) * A.pld[o] + (x >> o)] = v;
     }
 }
-constexpr int kDetLayers = 6;   // layers of one launch (nOctaveLayers + 2 <= 6; more layers: several launches)
 struct HaarGeoSet { HaarGeo l[kDetLayers]; };
 // (tt * w) / area, correctly rounded (w = +-1, +-2: the product is exact)
 __device__ __forceinline__ double box_div(unsigned tt, double w, double area, double ry)
@@ -262,36 +208,53 @@ __device__ __forceinline__ double box_div(unsigned tt, double w, double area, do
     const double q = a * ry;
     return fma(fma(-q, area, a), ry, q);
 }
-// Dxx, Dyy, Dxy of the sample whose top-left corner sits at lane byte offset voff, then det and trace (surf.cu:175-203)
-template <class Geo>   // HaarGeo in kernel-argument space, or the same struct behind a constant-address-space reference
-__device__ __forceinline__ void haar_det_trace(const SumTex &t, const Geo &g, unsigned voff, float &d, float &tr)
+// Dxx, Dyy, Dxy of one sample, then det and trace (surf.cu:175-203): THE evaluation, for every way a tap is fetched.  Src gives the corner
+// taps -- xx(a, b) = Dxx corner [x edge a][y edge b], yy(b, a) = Dyy corner [x edge b][y edge a], xy(a, b) = Dxy corner [y edge a][x edge b]
+// -- and area(k), ry(k): the area of box k (Dxx 0..2, Dyy 3..5, Dxy 6..9) and its reciprocal.
+template <class Src>
+__device__ __forceinline__ void haar_eval(const Src &src, float &d, float &tr)
 {
-    const auto T = [&](int o) { return *reinterpret_cast<const unsigned *>(reinterpret_cast<const char *>(t.s + o) + voff); };
     // the reference's order (surf.cu:133-150): per box +(y1,x1) -(y2,x1) -(y1,x2) +(y2,x2); d accumulates box by box in double
     unsigned cxx[4][2], cyy[2][4], cxy[4][4];
 #pragma unroll
     for (int a = 0; a < 4; ++a)
 #pragma unroll
-        for (int b = 0; b < 2; ++b) { cxx[a][b] = T(g.xx[a][b]); cyy[b][a] = T(g.yy[b][a]); }
+        for (int b = 0; b < 2; ++b) { cxx[a][b] = src.xx(a, b); cyy[b][a] = src.yy(b, a); }
 #pragma unroll
     for (int a = 0; a < 4; ++a)
 #pragma unroll
-        for (int b = 0; b < 4; ++b) cxy[a][b] = T(g.xy[a][b]);
+        for (int b = 0; b < 4; ++b) cxy[a][b] = src.xy(a, b);
     const double wxx[3] = {1.0, -2.0, 1.0};
     double sx = 0, sy = 0, sxy = 0;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        sx += box_div(cxx[k][0] - cxx[k][1] - cxx[k + 1][0] + cxx[k + 1][1], wxx[k], g.area[k], g.ry[k]);
-        sy += box_div(cyy[0][k] - cyy[0][k + 1] - cyy[1][k] + cyy[1][k + 1], wxx[k], g.area[3 + k], g.ry[3 + k]);
+        sx += box_div(cxx[k][0] - cxx[k][1] - cxx[k + 1][0] + cxx[k + 1][1], wxx[k], src.area(k), src.ry(k));
+        sy += box_div(cyy[0][k] - cyy[0][k + 1] - cyy[1][k] + cyy[1][k + 1], wxx[k], src.area(3 + k), src.ry(3 + k));
     }
     // c_DXY (surf.cu:159): {1,1,4,4,+1}, {5,1,8,4,-1}, {1,5,4,8,-1}, {5,5,8,8,+1}  (x1, y1, x2, y2, w); cxy[y edge][x edge]
-    sxy += box_div(cxy[0][0] - cxy[1][0] - cxy[0][1] + cxy[1][1], 1.0, g.area[6], g.ry[6]);
-    sxy += box_div(cxy[0][2] - cxy[1][2] - cxy[0][3] + cxy[1][3], -1.0, g.area[7], g.ry[7]);
-    sxy += box_div(cxy[2][0] - cxy[3][0] - cxy[2][1] + cxy[3][1], -1.0, g.area[8], g.ry[8]);
-    sxy += box_div(cxy[2][2] - cxy[3][2] - cxy[2][3] + cxy[3][3], 1.0, g.area[9], g.ry[9]);
+    sxy += box_div(cxy[0][0] - cxy[1][0] - cxy[0][1] + cxy[1][1], 1.0, src.area(6), src.ry(6));
+    sxy += box_div(cxy[0][2] - cxy[1][2] - cxy[0][3] + cxy[1][3], -1.0, src.area(7), src.ry(7));
+    sxy += box_div(cxy[2][0] - cxy[3][0] - cxy[2][1] + cxy[3][1], -1.0, src.area(8), src.ry(8));
+    sxy += box_div(cxy[2][2] - cxy[3][2] - cxy[2][3] + cxy[3][3], 1.0, src.area(9), src.ry(9));
     const float dx = (float)sx, dy = (float)sy, dxy = (float)sxy;
     d = dx * dy - 0.81f * dxy * dxy;
     tr = dx + dy;
+}
+// ... of the sample whose top-left corner sits at lane byte offset voff, taps and areas from a HaarGeo
+template <class Geo>   // HaarGeo in kernel-argument space, or the same struct behind a constant-address-space reference
+struct HaarTabSrc {
+    const SumTex &t; const Geo &g; unsigned voff;
+    __device__ __forceinline__ unsigned T(int o) const { return *reinterpret_cast<const unsigned *>(reinterpret_cast<const char *>(t.s + o) + voff); }
+    __device__ __forceinline__ unsigned xx(int a, int b) const { return T(g.xx[a][b]); }
+    __device__ __forceinline__ unsigned yy(int b, int a) const { return T(g.yy[b][a]); }
+    __device__ __forceinline__ unsigned xy(int a, int b) const { return T(g.xy[a][b]); }
+    __device__ __forceinline__ double area(int k) const { return g.area[k]; }
+    __device__ __forceinline__ double ry(int k) const { return g.ry[k]; }
+};
+template <class Geo>
+__device__ __forceinline__ void haar_det_trace(const SumTex &t, const Geo &g, unsigned voff, float &d, float &tr)
+{
+    haar_eval(HaarTabSrc<Geo>{t, g, voff}, d, tr);
 }
 __global__ __launch_bounds__(256) void k_det_trace(SumTex t, float *det, float *trace, int dld, int octave, int layer0, int nlayers2, int nbx, int nby, HaarGeoSet G)
 {
@@ -351,10 +314,6 @@ struct NmsArgs {
 // surf.cu:263-355: one wave per (layer, row); flags per 64-column chunk.  The centre values of four chunks are loaded together (the
 // round-2 loop issued one load per chunk and waited for it: 60 dependent round trips per 4K row, 176 us per octave-0 launch for
 // 66 MB); a chunk without a value above the threshold -- nearly all -- costs nothing more.
-#ifndef MI_SURF_NMS_SEG
-#define MI_SURF_NMS_SEG 8
-#endif
-constexpr int kNmsSeg = MI_SURF_NMS_SEG;   // chunks of one wave: a 4K row is 8 waves (one wave per row left the loop at 60 dependent round trips)
 __device__ __forceinline__ void nms_flag_row(const NmsArgs &A, int r, int seg)
 {
     const int lane = threadIdx.x & 63;
@@ -1235,101 +1194,49 @@ __global__ __launch_bounds__(512) void k_descriptors_staged(const unsigned char 
 // (3.9 K words for 131 K taps) and every layer reads its taps from LDS: lanes are consecutive columns (bank-conflict free) and the tap
 // offsets of octave 0 are COMPILE-TIME constants (sizes 9, 15, 21, 27 and the fixed patch stride), so a tap is a `ds_read_b32` with
 // an immediate offset -- no address arithmetic.  Same integers, same box_div, same order: the planes stay bit-identical.
-constexpr int kLdsTX = 64, kLdsTY = 16, kLdsSMax = 27, kLdsPW = 92, kLdsPH = kLdsTY + kLdsSMax;   // patch 43 rows x 92 words (91 used)
-constexpr int kLdsLayers = 4;
-__host__ __device__ constexpr int lds_rn(float v)   // round to nearest, ties to even (= __float2int_rn / rintf), v >= 0
-{
-    const int f = (int)v;
-    const float r = v - (float)f;
-    return r > 0.5f ? f + 1 : (r < 0.5f ? f : ((f & 1) ? f + 1 : f));
-}
-template <int L>
-struct LdsGeo {   // geometry of octave 0, layer L for the patch stride: the compile-time twin of haar_geo(9 + 6 L, kLdsPW)
-    static constexpr int size = 9 + 6 * L;
-    static constexpr float ratio = (float)size / 9;
-    static constexpr int e(int c) { return lds_rn(ratio * (float)c); }
-    static constexpr int xx(int i, int j) { return e(j ? 7 : 2) * kLdsPW + e(3 * i); }
-    static constexpr int yy(int j, int i) { return e(3 * i) * kLdsPW + e(j ? 7 : 2); }
-    static constexpr int xy(int i, int j) { return e(i == 0 ? 1 : i == 1 ? 4 : i == 2 ? 5 : 8) * kLdsPW + e(j == 0 ? 1 : j == 1 ? 4 : j == 2 ? 5 : 8); }
-    static constexpr double axx(int k) { return (double)((e(3 * k + 3) - e(3 * k)) * (e(7) - e(2))); }
-    static constexpr double a6 = (double)((e(4) - e(1)) * (e(4) - e(1))), a7 = (double)((e(8) - e(5)) * (e(4) - e(1))), a9 = (double)((e(8) - e(5)) * (e(8) - e(5)));
-};
-// host check that the compile-time geometry is haar_geo's (surf_api.cpp calls it once; tests/test_surf.py through the C-ABI self-test)
-template <int L>
-static bool lds_geo_matches()
-{
-    typedef LdsGeo<L> G;
-    const HaarGeo h = haar_geo(G::size, kLdsPW);
-    bool ok = true;
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 2; ++j) ok = ok && h.xx[i][j] == G::xx(i, j) && h.yy[j][i] == G::yy(j, i);
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) ok = ok && h.xy[i][j] == G::xy(i, j);
-    for (int k = 0; k < 3; ++k) ok = ok && h.area[k] == G::axx(k);
-    return ok && h.area[6] == G::a6 && h.area[7] == G::a7 && h.area[9] == G::a9;
-}
-bool lds_geometry_self_check() { return lds_geo_matches<0>() && lds_geo_matches<1>() && lds_geo_matches<2>() && lds_geo_matches<3>(); }
+// (the tile constants kLds*, LdsGeo<L> and its host check against haar_geo: surf_plan.h)
 
-// Dxx, Dyy, Dxy of one sample of octave 0, layer L from the staged patch; q = the LDS word of the sample's top-left corner
+// Octave 0, layer L: the areas are compile-time constants (LdsGeo<L>) ...
+template <int L>
+struct HaarLdsAreas {
+    typedef LdsGeo<L> G;
+    __device__ __forceinline__ static constexpr double area(int k) { return k < 6 ? G::axx(k % 3) : k == 6 ? G::a6 : k == 9 ? G::a9 : G::a7; }
+    __device__ __forceinline__ static constexpr double ry(int k) { return 1.0 / area(k); }
+};
+// ... the taps of one sample from the staged patch; q = the LDS word of the sample's top-left corner
+template <int L>
+struct HaarLdsSrc : HaarLdsAreas<L> {
+    typedef LdsGeo<L> G;
+    const unsigned *q;
+    __device__ __forceinline__ unsigned xx(int a, int b) const { return q[G::xx(a, b)]; }
+    __device__ __forceinline__ unsigned yy(int b, int a) const { return q[G::yy(b, a)]; }
+    __device__ __forceinline__ unsigned xy(int a, int b) const { return q[G::xy(a, b)]; }
+};
 template <int L>
 __device__ __forceinline__ void haar_det_trace_lds(const unsigned *q, float &d, float &tr)
 {
-    typedef LdsGeo<L> G;
-    unsigned cxx[4][2], cyy[2][4], cxy[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) { cxx[a][b] = q[G::xx(a, b)]; cyy[b][a] = q[G::yy(b, a)]; }
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) cxy[a][b] = q[G::xy(a, b)];
-    const double wxx[3] = {1.0, -2.0, 1.0};
-    double sx = 0, sy = 0, sxy = 0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        sx += box_div(cxx[k][0] - cxx[k][1] - cxx[k + 1][0] + cxx[k + 1][1], wxx[k], G::axx(k), 1.0 / G::axx(k));
-        sy += box_div(cyy[0][k] - cyy[0][k + 1] - cyy[1][k] + cyy[1][k + 1], wxx[k], G::axx(k), 1.0 / G::axx(k));
-    }
-    sxy += box_div(cxy[0][0] - cxy[1][0] - cxy[0][1] + cxy[1][1], 1.0, G::a6, 1.0 / G::a6);
-    sxy += box_div(cxy[0][2] - cxy[1][2] - cxy[0][3] + cxy[1][3], -1.0, G::a7, 1.0 / G::a7);
-    sxy += box_div(cxy[2][0] - cxy[3][0] - cxy[2][1] + cxy[3][1], -1.0, G::a7, 1.0 / G::a7);
-    sxy += box_div(cxy[2][2] - cxy[3][2] - cxy[2][3] + cxy[3][3], 1.0, G::a9, 1.0 / G::a9);
-    const float dx = (float)sx, dy = (float)sy, dxy = (float)sxy;
-    d = dx * dy - 0.81f * dxy * dxy;
-    tr = dx + dy;
+    HaarLdsSrc<L> src;
+    src.q = q;
+    haar_eval(src, d, tr);
 }
 // The same sample evaluated from the integral image itself (stride sld): p = the word of the sample's top-left corner.  The taps are
 // LdsGeo<L>'s edges with the image's stride instead of the patch's -- same integers, same box_div, same order: the same bits.
 template <int L>
+struct HaarG0Src : HaarLdsAreas<L> {
+    typedef LdsGeo<L> G;
+    const unsigned *p; int sld;
+    __device__ __forceinline__ unsigned Q(int ey, int ex) const { return p[ey * sld + ex]; }
+    __device__ __forceinline__ static constexpr int E4(int i) { return G::e(i == 0 ? 1 : i == 1 ? 4 : i == 2 ? 5 : 8); }
+    __device__ __forceinline__ unsigned xx(int a, int b) const { return Q(G::e(b ? 7 : 2), G::e(3 * a)); }
+    __device__ __forceinline__ unsigned yy(int b, int a) const { return Q(G::e(3 * a), G::e(b ? 7 : 2)); }
+    __device__ __forceinline__ unsigned xy(int a, int b) const { return Q(E4(a), E4(b)); }
+};
+template <int L>
 __device__ __forceinline__ void haar_det_trace_g0(const unsigned *p, int sld, float &d, float &tr)
 {
-    typedef LdsGeo<L> G;
-    const auto Q = [&](int ey, int ex) { return p[ey * sld + ex]; };
-    const auto E4 = [](int i) { return G::e(i == 0 ? 1 : i == 1 ? 4 : i == 2 ? 5 : 8); };
-    unsigned cxx[4][2], cyy[2][4], cxy[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) { cxx[a][b] = Q(G::e(b ? 7 : 2), G::e(3 * a)); cyy[b][a] = Q(G::e(3 * a), G::e(b ? 7 : 2)); }
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) cxy[a][b] = Q(E4(a), E4(b));
-    const double wxx[3] = {1.0, -2.0, 1.0};
-    double sx = 0, sy = 0, sxy = 0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        sx += box_div(cxx[k][0] - cxx[k][1] - cxx[k + 1][0] + cxx[k + 1][1], wxx[k], G::axx(k), 1.0 / G::axx(k));
-        sy += box_div(cyy[0][k] - cyy[0][k + 1] - cyy[1][k] + cyy[1][k + 1], wxx[k], G::axx(k), 1.0 / G::axx(k));
-    }
-    sxy += box_div(cxy[0][0] - cxy[1][0] - cxy[0][1] + cxy[1][1], 1.0, G::a6, 1.0 / G::a6);
-    sxy += box_div(cxy[0][2] - cxy[1][2] - cxy[0][3] + cxy[1][3], -1.0, G::a7, 1.0 / G::a7);
-    sxy += box_div(cxy[2][0] - cxy[3][0] - cxy[2][1] + cxy[3][1], -1.0, G::a7, 1.0 / G::a7);
-    sxy += box_div(cxy[2][2] - cxy[3][2] - cxy[2][3] + cxy[3][3], 1.0, G::a9, 1.0 / G::a9);
-    const float dx = (float)sx, dy = (float)sy, dxy = (float)sxy;
-    d = dx * dy - 0.81f * dxy * dxy;
-    tr = dx + dy;
+    HaarG0Src<L> src;
+    src.p = p; src.sld = sld;
+    haar_eval(src, d, tr);
 }
 template <int L>
 __device__ __forceinline__ float det0_layer(const SumTex &t, int ii, int jj)
@@ -1359,7 +1266,6 @@ __device__ float det0_at(const SumTex &t, int layer, int ii, int jj)
 // trace at each maximum beside it.  Tiles overlap by one sample on every side (stride 14 x 62): 18 % more samples evaluated, and the
 // 265 MB of octave-0 det / trace planes of a 4K frame are neither written nor read again.  The sub-pixel refinement evaluates its 27
 // values from the integral image (det0_at).
-constexpr int kFuseTY = kLdsTY - 2, kFuseTX = kLdsTX - 2;
 struct Fuse0Args {
     float thr;
     SumTex mask;                       // mask.s == nullptr: none
@@ -1456,26 +1362,8 @@ __device__ __forceinline__ void lds_layer(const SumTex &t, const unsigned *patch
 // The reference runs its five detector kernels once per octave (surf.cuda.cpp:182-204) and copies two counters to the host in
 // between; round 2 kept the per-octave launches (24 per 4-octave frame, the coarse octaves launch-bound: octave 3 is 1/64 of octave
 // 0's samples and took 1/6 of its time).  Here every stage covers all octaves: the planes, flag words, counts and candidate lists of
-// an octave live at their own offsets (OctSet), a workgroup finds its octave from the cumulative workgroup counts, and the last
+// an octave live at their own offsets (OctSet, surf_plan.h), a workgroup finds its octave from the cumulative workgroup counts, and the last
 // stage walks the octaves in order so that the features of octave o still follow those of octave o - 1 (deterministic order).
-struct OctSet {
-    int n;                                   // octaves
-    int nlayers;                             // nOctaveLayers
-    int rows, cols, dld;
-    long long plane0[kMaxFusedOctaves];      // float offset of the octave's first det / trace plane
-    long long bits0[kMaxFusedOctaves];       // u64 offset of its flag words
-    int row0[kMaxFusedOctaves];              // first (layer, row) index in rowcnt space (rowcnt has one extra entry per octave)
-    long long seg0[kMaxFusedOctaves];        // offset of its row-segment counts
-    int blk_dt[kMaxFusedOctaves + 1];        // cumulative workgroup counts of k_det_trace_all
-    int blk_nms[kMaxFusedOctaves + 1];       //   ... of k_nms_flag_all (row groups x segments)
-    int blk_wr[kMaxFusedOctaves + 1];        //   ... of k_nms_write_all (row groups)
-    int nbx[kMaxFusedOctaves], nby[kMaxFusedOctaves], nseg[kMaxFusedOctaves], chunks[kMaxFusedOctaves];
-    int lds0;                                // octave 0 of k_det_trace_all on LDS tiles (all its layers per workgroup): nby[0] counts 16-row tiles
-    int poly;                                // octaves >= 1 read their taps from the polyphase planes (pld / pbase per octave; geometry table built for them)
-    int pld[kMaxFusedOctaves];
-    long long pbase[kMaxFusedOctaves];
-    int fuse0;                               // ... and its maxima flagged in that kernel (no planes; tiles of 14 x 62 interior samples; no k_nms_flag_all workgroups)
-};
 __device__ __forceinline__ int find_octave(const int *cum, int n, int id)
 {
     int o = 0;
@@ -1636,7 +1524,7 @@ __global__ __launch_bounds__(1024) void k_interp_compact_all(const InterpOut *tm
 int integral(const unsigned char *img, long long istep, int rows, int cols, bool clamp1, unsigned *V, unsigned *BT, int vld,
              unsigned *sum, int sld, hipStream_t s)
 {
-    const int band_rows = 32, nbands = div_up(rows, band_rows);
+    const int band_rows = kIntBandRows, nbands = div_up(rows, band_rows);
     hipLaunchKernelGGL(k_int_cols, dim3(div_up(cols, 256), nbands), dim3(256), 0, s, img, istep, rows, cols, clamp1 ? 1 : 0, V, vld, BT, band_rows);
     hipLaunchKernelGGL(k_int_bands, dim3(div_up(cols, 256)), dim3(256), 0, s, BT, vld, cols, nbands);
     const int cpw = div_up(div_up(cols, 64), kRowWaves);
@@ -1647,7 +1535,7 @@ int integral(const unsigned char *img, long long istep, int rows, int cols, bool
     MI_HIP_TRY(hipGetLastError());
     return MI_OK;
 }
-int integral_bands(int rows) { return div_up(rows, 32); }
+int integral_bands(int rows) { return div_up(rows, kIntBandRows); }
 
 int det_trace(const unsigned *sum, int sld, int rows, int cols, int octave, int nOctaveLayers, float *det, float *trace, int dld,
               hipStream_t s)
@@ -1666,7 +1554,6 @@ int det_trace(const unsigned *sum, int sld, int rows, int cols, int octave, int 
     return MI_OK;
 }
 
-int nms_segments(int cols) { return div_up(div_up(cols, 64), kNmsSeg); }
 int find_maxima(const float *det, const float *trace, int dld, const unsigned *mask_sum, int sld, int rows, int cols, int octave,
                 int nOctaveLayers, float thr, unsigned long long *bits, unsigned *rowcnt, unsigned *segcnt, int4 *cand, int max_candidates,
                 unsigned *ncand, hipStream_t s)
@@ -1695,105 +1582,31 @@ int interpolate(const float *det, int dld, int rows, int cols, int octave, const
     MI_HIP_TRY(hipGetLastError());
     return MI_OK;
 }
-size_t interp_tmp_bytes(int max_candidates) { return sizeof(InterpOut) * (size_t)max_candidates; }
+size_t interp_tmp_bytes(size_t candidates) { return sizeof(InterpOut) * candidates; }
 
-// ---- all octaves per launch (k_*_all).  Sizes of the per-octave regions for a frame of rows x cols (the handle allocates them):
-// lds: octave 0 of the det / trace launch on LDS tiles (the HANDLE's decision, MIFLOW_SURF_LDS=0 switches it off: no process-global state)
-static OctSet make_octset(int rows, int cols, int dld, int n_octaves, int nOctaveLayers, int lds)
+// surf.cuda.cpp:182-204 for all octaves: the launches of a plan with plan.fused (surf_plan.h), on the buffers the handle allocated for it.
+// B.counters: [0] the feature counter, [1 + octave] candidates, [32 + octave] accepted candidates -- zeroed by the caller
+int detect_all(const SurfPlan &plan, const DetectBufs &Bf, float thr, float *kp, int kld, int max_features, hipStream_t s)
 {
-    OctSet S;
-    memset(&S, 0, sizeof(S));
-    S.n = n_octaves; S.nlayers = nOctaveLayers; S.rows = rows; S.cols = cols; S.dld = dld;
-    S.lds0 = (nOctaveLayers + 2 <= kLdsLayers && (lds & 3)) ? 1 : 0;
-    S.fuse0 = (S.lds0 && (lds & 3) >= 2) ? 1 : 0;   // lds & 3 = 2: octave 0's maxima flagged inside the det kernel
-    S.poly = (lds & 4) && n_octaves > 1 ? 1 : 0;     // lds & 4: octaves >= 1 on the polyphase planes
-    {
-        long long base = 0;
-        for (int o = 1; o < n_octaves; ++o) {
-            const PolyGeo pg = poly_geo(rows, cols, o, base);
-            S.pld[o] = pg.pld; S.pbase[o] = base;
-            base += pg.plane_words << (2 * o);
-        }
-    }
-    long long plane = 0, bits = 0, seg = 0;
-    int row = 0;
-    for (int o = 0; o < n_octaves; ++o) {
-        const int lr = rows >> o, lc = cols >> o;
-        S.plane0[o] = plane; S.bits0[o] = bits; S.row0[o] = row; S.seg0[o] = seg;
-        S.chunks[o] = div_up(lc, 64); S.nseg[o] = div_up(S.chunks[o], kNmsSeg);
-        S.nbx[o] = div_up(lc, 64); S.nby[o] = div_up(lr, 4);
-        if (o == 0 && S.fuse0) {   // one workgroup per 14 x 62 tile of interior samples (16 x 64 evaluated) and ALL layers
-            S.nbx[0] = div_up(lc, kFuseTX); S.nby[0] = div_up(lr, kFuseTY);
-            S.blk_dt[1] = align_up(S.nbx[0] * S.nby[0], 8);
-        } else if (o == 0 && S.lds0) {   // one workgroup per 16 x 64 tile and ALL layers
-            S.nby[0] = div_up(lr, kLdsTY);
-            S.blk_dt[1] = align_up(S.nbx[0] * S.nby[0], 8);
-        } else
-        S.blk_dt[o + 1] = S.blk_dt[o] + align_up(S.nbx[o] * S.nby[o] * (nOctaveLayers + 2), 8);   // padded: see k_det_trace_all
-        S.blk_nms[o + 1] = S.blk_nms[o] + ((o == 0 && S.fuse0) ? 0 : div_up(nOctaveLayers * lr, 4) * S.nseg[o]);
-        S.blk_wr[o + 1] = S.blk_wr[o] + div_up(nOctaveLayers * lr, 4);
-        plane += (long long)(nOctaveLayers + 2) * lr * dld;
-        bits += (long long)nOctaveLayers * lr * S.chunks[o];
-        seg += (long long)nOctaveLayers * lr * S.nseg[o];
-        row += nOctaveLayers * lr;
-    }
-    return S;
-}
-bool fused_supported(int n_octaves, int nOctaveLayers) { return n_octaves <= kMaxFusedOctaves && nOctaveLayers + 2 <= kDetLayers; }
-void fused_sizes(int rows, int cols, int dld, int n_octaves, int nOctaveLayers, FusedSizes *z)
-{
-    const OctSet S = make_octset(rows, cols, dld, n_octaves, nOctaveLayers, 0);   // the region sizes do not depend on the octave-0 path
-    const int last = n_octaves - 1, lr = rows >> last;
-    z->plane_floats = (size_t)(S.plane0[last] + (long long)(nOctaveLayers + 2) * lr * dld);
-    z->bits_words = (size_t)(S.bits0[last] + (long long)nOctaveLayers * lr * S.chunks[last]);
-    z->seg_counts = (size_t)(S.seg0[last] + (long long)nOctaveLayers * lr * S.nseg[last]);
-    z->row_counts = (size_t)(S.row0[last] + nOctaveLayers * lr + n_octaves);
-    z->geo_bytes = sizeof(HaarGeo) * (size_t)n_octaves * kDetLayers;
-    z->poly_words = (size_t)poly_total_words(rows, cols, n_octaves);
-}
-// geometry of every (octave, layer) of the frame size: uploaded by the handle when the size changes
-void fused_geometry(int sld, int n_octaves, int nOctaveLayers, void *geo_host, int rows, int cols, bool poly)
-{
-    HaarGeo *g = (HaarGeo *)geo_host;
-    memset(g, 0, sizeof(HaarGeo) * (size_t)n_octaves * kDetLayers);
-    for (int o = 0; o < n_octaves; ++o)
-        for (int l = 0; l < nOctaveLayers + 2; ++l) {
-            if (poly && o >= 1) {   // tap (ey, ex) of octave o = phase plane (ey & m, ex & m), position shifted by (ey >> o, ex >> o)
-                const PolyGeo pg = poly_geo(rows, cols, o, 0);
-                const int m = (1 << o) - 1;
-                g[o * kDetLayers + l] = haar_geo_off(calc_size(o, l), [&](int ey, int ex) {
-                    return (int)((long long)(((ey & m) << o) + (ex & m)) * pg.plane_words + (long long)(ey >> o) * pg.pld + (ex >> o));
-                });
-            } else g[o * kDetLayers + l] = haar_geo(calc_size(o, l), sld);
-        }
-}
-// surf.cuda.cpp:182-204 for all octaves: six launches.  ncand: n_octaves counters; nfeat: the feature counter (zeroed by the caller)
-int detect_fused(const unsigned *sum, const unsigned *mask_sum, int sld, int rows, int cols, int n_octaves, int nOctaveLayers, float thr,
-                 float *det, float *trace, int dld, unsigned long long *bits, unsigned *rowcnt, unsigned *segcnt, int4 *cand, int max_candidates,
-                 unsigned *ncand, void *tmp, const void *geo_dev, float *kp, int kld, int max_features, unsigned *nfeat, int lds_tiles, hipStream_t s,
-                 unsigned long long *sbits, unsigned *poly)
-{
-    int ldsf = lds_tiles;
-    if ((ldsf & 3) >= 2 && !sbits) ldsf = (ldsf & ~3) | 1;
-    if (!poly) ldsf &= ~4;
-    const OctSet S = make_octset(rows, cols, dld, n_octaves, nOctaveLayers, ldsf);
-    SumTex t = {sum, sld, rows, cols};
+    const OctSet &S = plan.S;
+    const int rows = S.rows, cols = S.cols, n_octaves = S.n, max_candidates = plan.shape.max_candidates;
+    unsigned *const nfeat = Bf.counters, *const ncand = Bf.counters + 1;
+    SumTex t = {Bf.sum, plan.sld, rows, cols};
     NmsArgs B;
     memset(&B, 0, sizeof(B));
-    B.det = det; B.trace = trace; B.dld = dld; B.rows = rows; B.cols = cols; B.nlayers = nOctaveLayers; B.thr = thr;
-    B.mask.s = mask_sum; B.mask.sld = sld; B.mask.rows = rows; B.mask.cols = cols;
-    B.bits = bits; B.sbits = sbits; B.rowcnt = rowcnt; B.segcnt = segcnt;
+    B.det = Bf.det; B.trace = Bf.trace; B.dld = plan.dld; B.rows = rows; B.cols = cols; B.nlayers = S.nlayers; B.thr = thr;
+    B.mask.s = Bf.msum; B.mask.sld = plan.sld; B.mask.rows = rows; B.mask.cols = cols;
+    B.bits = Bf.bits; B.sbits = Bf.sbits; B.rowcnt = Bf.rowcnt; B.segcnt = Bf.segcnt;
     Fuse0Args F;
     memset(&F, 0, sizeof(F));
-    if (S.fuse0) {
+    if (plan.fuse0) {
         // octave 0's flag words, sign words and segment counts are accumulated by atomics: zero them (2 x 2 MB + 0.1 MB at 4K)
-        const size_t words = (size_t)nOctaveLayers * rows * S.chunks[0];
-        MI_HIP_TRY(hipMemsetAsync(bits, 0, sizeof(unsigned long long) * words, s));
-        MI_HIP_TRY(hipMemsetAsync(sbits, 0, sizeof(unsigned long long) * words, s));
-        MI_HIP_TRY(hipMemsetAsync(segcnt, 0, sizeof(unsigned) * (size_t)nOctaveLayers * rows * S.nseg[0], s));
-        F.thr = thr; F.mask = B.mask; F.bits = bits; F.sbits = sbits; F.segcnt = segcnt; F.chunks = S.chunks[0]; F.nseg = S.nseg[0];
+        MI_HIP_TRY(hipMemsetAsync(Bf.bits, 0, sizeof(unsigned long long) * plan.sbits_words, s));
+        MI_HIP_TRY(hipMemsetAsync(Bf.sbits, 0, sizeof(unsigned long long) * plan.sbits_words, s));
+        MI_HIP_TRY(hipMemsetAsync(Bf.segcnt, 0, sizeof(unsigned) * (size_t)S.nlayers * rows * S.nseg[0], s));
+        F.thr = thr; F.mask = B.mask; F.bits = Bf.bits; F.sbits = Bf.sbits; F.segcnt = Bf.segcnt; F.chunks = S.chunks[0]; F.nseg = S.nseg[0];
     }
-    if (S.poly) {
+    if (plan.poly) {
         PolyArgs PA;
         memset(&PA, 0, sizeof(PA));
         PA.n = n_octaves;
@@ -1801,19 +1614,18 @@ int detect_fused(const unsigned *sum, const unsigned *mask_sum, int sld, int row
             const PolyGeo pg = poly_geo(rows, cols, o, S.pbase[o]);
             PA.prows[o] = pg.prows; PA.pld[o] = pg.pld; PA.plane_words[o] = pg.plane_words; PA.base[o] = pg.base;
         }
-        hipLaunchKernelGGL(k_poly_build, dim3(div_up(cols + 1, 256), rows + 1), dim3(256), 0, s, t, poly, PA);
+        hipLaunchKernelGGL(k_poly_build, dim3(plan.grid_poly_x, plan.grid_poly_y), dim3(256), 0, s, t, Bf.poly, PA);
     }
-    const int blk0 = S.fuse0 ? S.blk_dt[1] : 0;
-    if (S.fuse0) hipLaunchKernelGGL(k_det_nms0, dim3(blk0), dim3(256), 0, s, t, S, F);
-    if (S.blk_dt[n_octaves] > blk0)
-        hipLaunchKernelGGL(k_det_trace_all, dim3(S.blk_dt[n_octaves] - blk0), dim3(256), 0, s, t, det, trace, S, (const HaarGeo *)geo_dev, blk0, (const unsigned *)poly);
-    hipLaunchKernelGGL(k_nms_flag_all, dim3(S.blk_nms[n_octaves]), dim3(256), 0, s, B, S);
-    hipLaunchKernelGGL(k_scan_counts_all, dim3(n_octaves), dim3(1024), 0, s, B, S);
-    hipLaunchKernelGGL(k_nms_write_all, dim3(S.blk_wr[n_octaves]), dim3(256), 0, s, B, S, cand, max_candidates, ncand);
-    hipLaunchKernelGGL(k_interp_eval_all, dim3(div_up(max_candidates, 256), n_octaves), dim3(256), 0, s, (const float *)det, S, (const int4 *)cand,
-                       (const unsigned *)ncand, (InterpOut *)tmp, max_candidates, nfeat + 32, t);   // counters[32 + octave]: zeroed with the others
-    hipLaunchKernelGGL(k_interp_compact_all, dim3(n_octaves), dim3(1024), 0, s, (const InterpOut *)tmp, (const unsigned *)ncand, n_octaves, max_candidates, kp,
-                       kld, max_features, nfeat, (const unsigned *)(nfeat + 32));
+    if (plan.fuse0) hipLaunchKernelGGL(k_det_nms0, dim3(plan.grid_det0), dim3(256), 0, s, t, S, F);
+    if (plan.grid_det > 0)
+        hipLaunchKernelGGL(k_det_trace_all, dim3(plan.grid_det), dim3(256), 0, s, t, Bf.det, Bf.trace, S, (const HaarGeo *)Bf.geo, plan.grid_det0, (const unsigned *)Bf.poly);
+    hipLaunchKernelGGL(k_nms_flag_all, dim3(plan.grid_nms), dim3(256), 0, s, B, S);
+    hipLaunchKernelGGL(k_scan_counts_all, dim3(plan.grid_scan), dim3(1024), 0, s, B, S);
+    hipLaunchKernelGGL(k_nms_write_all, dim3(plan.grid_write), dim3(256), 0, s, B, S, Bf.cand, max_candidates, ncand);
+    hipLaunchKernelGGL(k_interp_eval_all, dim3(plan.grid_interp_x, plan.grid_interp_y), dim3(256), 0, s, (const float *)Bf.det, S, (const int4 *)Bf.cand,
+                       (const unsigned *)ncand, (InterpOut *)Bf.itmp, max_candidates, nfeat + 32, t);
+    hipLaunchKernelGGL(k_interp_compact_all, dim3(plan.grid_compact), dim3(1024), 0, s, (const InterpOut *)Bf.itmp, (const unsigned *)ncand, n_octaves,
+                       max_candidates, kp, kld, max_features, nfeat, (const unsigned *)(nfeat + 32));
     MI_HIP_TRY(hipGetLastError());
     return MI_OK;
 }

@@ -207,7 +207,8 @@ def test_maxima_flagged_inside_the_det_kernel_are_bit_identical(gpu):
     comparisons run there and only the flag words (+ the sign of the trace at each maximum) leave it; the sub-pixel refinement
     evaluates its 27 values from the integral image (MIFLOW_SURF_NMS0=1: an opt-in -- measured slower than the plane form, see
     surf_api.cpp).  Keypoints (order included) and descriptors must not change by a bit against the default plane form -- 4K at the BASELINE setting, small and odd sizes, one
-    layer, a mask, the overflow of the candidate list.  The switch is read once per process, hence the subprocesses."""
+    layer, a mask, the overflow of the candidate list, and the small frames at the tile edges (TILE_EDGE_CASES).  The switch is read once
+    per process, hence the subprocesses."""
     import re
     import subprocess
     import sys
@@ -218,10 +219,30 @@ def test_maxima_flagged_inside_the_det_kernel_are_bit_identical(gpu):
                            env=dict(os.environ, **env), timeout=900)
         assert r.returncode == 0, r.stderr[-2000:]
         out[tag] = re.findall(r"n=(\d+) digest ([0-9a-f]{16})", r.stdout)
-        assert len(out[tag]) == 5 and all(int(n) > 5 for n, _ in out[tag]), r.stdout
+        assert len(out[tag]) == 5 + len(TILE_EDGE_CASES) and all(int(n) > 5 for n, _ in out[tag]), r.stdout
     # ... and the polyphase planes of the integral image (octaves >= 1 read consecutive words, the default since round 5) against the
     # strided gathers (MIFLOW_SURF_POLY=0): the same integers, the same det / trace values
     assert out["fused"] == out["planes"] == out["strided"], out
+
+
+# Small frames at the edges of octave 0's tiles (the last lines of tools/surf_digest.py): widths one sample either side of two / three
+# 62-column tiles (maxima flagged in the det kernel) and 64-column tiles, heights around the 14- / 16-row tiles, rows of the polyphase
+# planes that cross a 64-word alignment; (3, 4) has too many layers for the LDS tiles.  (rows, cols), octaves, layers
+TILE_EDGE_CASES = (((98, 124), 2, 2), ((112, 127), 2, 2), ((113, 128), 3, 2), ((114, 129), 2, 3), ((127, 187), 2, 2), ((128, 192), 3, 4),
+                   ((129, 193), 3, 2))
+
+
+@gpu_mark
+def test_detect_at_the_tile_edges_matches_the_oracle(gpu, oracle):
+    """The default launch forms on TILE_EDGE_CASES against the oracle (threshold 50, keypointsRatio 0.05): a wrong region offset or
+    tile count of the detect plan (csrc/surf_plan.h) shows where a frame ends just before, at and just after a tile."""
+    from opencv_contrib_amd import cuda
+    for shape, octaves, layers in TILE_EDGE_CASES:
+        img = synth.blob_image(*shape, seed=41)
+        ref = oracle.surf_detect_describe(img, oracle.surf_params(hessian_threshold=50.0, n_octaves=octaves, n_octave_layers=layers, keypoints_ratio=0.05))
+        assert ref["n"] > 5, (shape, ref["n"])
+        kpg, desc = cuda.SURF_CUDA.create(50.0, octaves, layers, False, 0.05, False).detectWithDescriptors(T(img, gpu))
+        _compare(cuda.SURF_CUDA.downloadKeypoints(kpg), N(desc), ref)
 
 
 @gpu_mark
