@@ -12,7 +12,7 @@
 
 struct mi_disp_bilateral {
     mi_disp_bilateral_params P;
-    float *tab = nullptr;        // device: 255 colour weights, then (radius+1)^2 space weights
+    float *tab = nullptr;        // device: 256 colour weights, then (radius+1)^2 space weights
     int tab_radius = -1;
     float tab_sigma = -1.f;
     void *tmp = nullptr;         // ping-pong map
@@ -34,11 +34,11 @@ struct Args {
 template <typename T, int CN>
 __global__ __launch_bounds__(256) void k_pass(Args A)
 {
-    extern __shared__ float s_tab[];   // [255 colour][(r+1)^2 space]
-    const int half = A.radius, ntab = 255 + (half + 1) * (half + 1);
+    extern __shared__ float s_tab[];   // [256 colour][(r+1)^2 space]
+    const int half = A.radius, ntab = 256 + (half + 1) * (half + 1);
     for (int i = threadIdx.x; i < ntab; i += 256) s_tab[i] = A.tab[i];
     __syncthreads();
-    const float *ctab = s_tab, *stab = s_tab + 255;
+    const float *ctab = s_tab, *stab = s_tab + 256;
     const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
     const int xp = (blockIdx.x * 64 + (threadIdx.x & 63)) * 2;   // pixel pair xp, xp + 1
     if (y >= A.rows || xp >= A.cols) return;
@@ -96,14 +96,15 @@ static int build_tables(mi_disp_bilateral *h)
 {
     const mi_disp_bilateral_params &P = h->P;
     if (h->tab && h->tab_radius == P.radius && h->tab_sigma == P.sigma_range) return MI_OK;
-    const int half = P.radius, n = 255 + (half + 1) * (half + 1);
+    const int half = P.radius, n = 256 + (half + 1) * (half + 1);
     std::vector<float> t(n);
-    // calc_color_weighted_table / calc_space_weighted_filter, disparity_bilateral_filter.cpp:96-123
+    // calc_color_weighted_table / calc_space_weighted_filter, disparity_bilateral_filter.cpp:96-123.  The reference's colour table has
+    // 255 entries, but DistRgbMax of a 0 and a 255 pixel is 255 (it reads one past its table there): entry 255 continues the formula.
     const float den = 2 * P.sigma_range * P.sigma_range;
-    for (int i = 0; i < 255; ++i) t[i] = static_cast<float>(std::exp(-double(i * i) / den));
+    for (int i = 0; i < 256; ++i) t[i] = static_cast<float>(std::exp(-double(i * i) / den));
     const float dist_space = P.radius + 1.0f;
     for (int y = 0; y <= half; ++y)
-        for (int x = 0; x <= half; ++x) t[255 + y * (half + 1) + x] = std::exp(-std::sqrt(float(y * y) + float(x * x)) / dist_space);
+        for (int x = 0; x <= half; ++x) t[256 + y * (half + 1) + x] = std::exp(-std::sqrt(float(y * y) + float(x * x)) / dist_space);
     if (h->tab) { (void)hipFree(h->tab); h->tab = nullptr; }
     MI_HIP_TRY(hipMalloc(&h->tab, sizeof(float) * n));
     MI_HIP_TRY(hipMemcpy(h->tab, t.data(), sizeof(float) * n, hipMemcpyHostToDevice));
@@ -203,7 +204,7 @@ int mi_disp_bilateral_apply(mi_disp_bilateral *h, const mi_mat *disp, const mi_m
     A.edge_disc = edge_disc < 1 ? short(1) : edge_disc;
     A.max_disc = short(P.ndisp * P.max_disc_threshold + 0.5);
     const dim3 grid(div_up(div_up(A.cols, 2), 64), div_up(A.rows, 4));
-    const size_t lds = sizeof(float) * (255 + (P.radius + 1) * (P.radius + 1));
+    const size_t lds = sizeof(float) * (256 + (P.radius + 1) * (P.radius + 1));
     for (int i = 0; i < P.iters; ++i)
         for (int t = 0; t < 2; ++t) {   // cu:164-170; pass 0: dst -> tmp, pass 1: tmp -> dst
             A.t = t;

@@ -38,7 +38,8 @@ template <int WXT>
 __global__ __launch_bounds__(256) void k_dense(Args A)
 {
     extern __shared__ int smem[];
-    const int pw = 16 + 2 * A.hx, ph = 16 + 2 * A.hy;
+    // lane 15 of a tile row reads window columns up to 15 + wx - 1 (an even window reaches one past 16 + 2 * hx)
+    const int pw = 15 + A.wx, ph = 15 + A.wy;
     int *Ip = smem, *dxp = Ip + pw * ph, *dyp = dxp + pw * ph;
     const int xb = blockIdx.x * 16, yb = blockIdx.y * 16;
     const int rows = A.rows, cols = A.cols, ld = A.ld_img;
@@ -218,7 +219,7 @@ int mi_densepyrlk_calc(mi_densepyrlk *h, const mi_mat *prev, const mi_mat *next,
     lk::Args A;
     A.wx = P.win_width; A.wy = P.win_height; A.hx = (P.win_width - 1) / 2; A.hy = (P.win_height - 1) / 2; A.iters = P.iters;
     A.ld_uv = g[0].ld;
-    const size_t lds = 3 * (size_t)(16 + 2 * A.hx) * (16 + 2 * A.hy) * sizeof(int);
+    const size_t lds = 3 * (size_t)(15 + A.wx) * (15 + A.wy) * sizeof(int);   // k_dense's pw * ph; 31 x 31: 25 392 B
     int idx = 0;
     for (int l = P.max_level; l >= 0; --l) {   // pyrlk.cpp:284-295
         const int idx2 = (idx + 1) & 1;

@@ -41,9 +41,10 @@ int orc_dbf_apply(const orc_dbf_params *p, void *disp, int es, const unsigned ch
     if (!(p->ndisp > 0 && p->radius > 0 && p->iters > 0)) return -1;   /* CV_Assert, .cpp:176 */
     if ((es != 1 && es != 2) || (cn != 1 && cn != 3)) return -2;
     const int r = p->radius, half = r;
-    float ctab[255];
+    float ctab[256];   /* the reference's table has 255 entries and DistRgbMax reaches 255 (it reads one past the table: undefined);
+                          entry 255 is the formula continued */
     float *stab = (float *)malloc(sizeof(float) * (half + 1) * (half + 1));
-    color_table(ctab, p->sigma_range, 255);
+    color_table(ctab, p->sigma_range, 256);
     space_table(stab, half, r + 1.0f);
     /* .cpp:146-147 */
     short edge_disc = (short)(p->ndisp * p->edge_threshold + 0.5);

@@ -94,6 +94,114 @@ def test_setters_inplace_roi_and_edge_sizes(gpu, oracle):
         np.testing.assert_array_equal(o, oracle.dbf_apply(dd, ii, p))
 
 
+def _hip_dbf(gpu, disp, img, p):
+    import torch
+    from opencv_contrib_amd import cuda
+    f = cuda.createDisparityBilateralFilter(p.ndisp, p.radius, p.iters)
+    f.setEdgeThreshold(p.edge_threshold); f.setMaxDiscThreshold(p.max_disc_threshold); f.setSigmaRange(p.sigma_range)
+    return f.apply(torch.from_numpy(disp).to(gpu), torch.from_numpy(np.ascontiguousarray(img)).to(gpu)).cpu().numpy()
+
+
+def _blocks_case(h=48, w=64, seed=5):
+    """Guide: 3 x 3 blocks of 0 / 255; disparity: two surfaces (10 | 40) with a jagged edge (+-3 px per row) and 3 % outliers."""
+    rng = np.random.default_rng(seed)
+    img = np.kron(rng.integers(0, 2, ((h + 2) // 3, (w + 2) // 3)), np.ones((3, 3), np.int64))[:h, :w].astype(np.uint8) * 255
+    edge = w // 2 + rng.integers(-3, 4, h)
+    disp = np.where(np.arange(w)[None, :] < edge[:, None], 10, 40).astype(np.uint8)
+    out = rng.random((h, w)) < 0.03
+    disp[out] = rng.integers(0, 64, (h, w))[out].astype(np.uint8)
+    return img, disp, edge
+
+
+def _edge_pixels_with_distance_255(img, disp, radius=4, edge_disc=6):
+    """Interior pixels the first pass may refine (a 4-neighbour differs by >= edge_disc = short(64 * 0.1 + 0.5)) whose
+    (2 radius + 1)^2 window holds a guide pixel at colour distance 255 -> (those pixels, those with the distance)."""
+    d = disp.astype(int)
+    c = d[1:-1, 1:-1]
+    is_edge = np.zeros(d.shape, bool)
+    is_edge[1:-1, 1:-1] = (np.abs(d[:-2, 1:-1] - c) >= edge_disc) | (np.abs(d[2:, 1:-1] - c) >= edge_disc) | \
+                          (np.abs(d[1:-1, :-2] - c) >= edge_disc) | (np.abs(d[1:-1, 2:] - c) >= edge_disc)
+    hit = 0
+    for y, x in zip(*np.nonzero(is_edge)):
+        win = img[max(0, y - radius):y + radius + 1, max(0, x - radius):x + radius + 1].astype(int)
+        hit += int(np.abs(win - int(img[y, x])).max() == 255)
+    return int(is_edge.sum()), hit
+
+
+def test_blocks_case_reaches_colour_distance_255():
+    img, disp, _ = _blocks_case()
+    n, hit = _edge_pixels_with_distance_255(img, disp)
+    assert hit >= 100, (n, hit)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", [np.uint8, np.int16])
+@pytest.mark.parametrize("cn", [1, 3])
+@pytest.mark.parametrize("sigma", [10.0, 150.0])
+def test_colour_distance_255_bit_exact(gpu, oracle, dtype, cn, sigma):
+    """DistRgbMax of a 0 and a 255 pixel is 255; the reference's colour table has 255 entries (it reads one past it: undefined).
+    Here the table has 256, entry 255 = exp(-255^2 / (2 sigma^2)): ~0 at sigma 10, 0.236 at sigma 150 -- against the space weight
+    stab[0] = 1.0 that a 255-entry table in front of the space table would return."""
+    img, disp, _ = _blocks_case()
+    assert _edge_pixels_with_distance_255(img, disp)[1] >= 100   # (channel 0 alone; DistRgbMax of three channels is no smaller)
+    scale = 1 if dtype == np.uint8 else 16
+    disp = (disp.astype(np.int16) * scale).astype(dtype)
+    if cn == 3:
+        img = np.stack([img, np.roll(img, 3, 1), np.roll(img, 3, 0)], -1)
+    p = oracle.dbf_params(ndisp=64 * scale, radius=4, iters=2, sigma_range=sigma)
+    ref = oracle.dbf_apply(disp, img, p)
+    assert (ref != disp).sum() >= 50
+    np.testing.assert_array_equal(_hip_dbf(gpu, disp, img, p), ref)
+
+
+@pytest.mark.gpu
+def test_negative_16bit_disparities_from_sgm(gpu, oracle):
+    """StereoSGM with minDisparity -8 marks invalid pixels (-8 - 1) * 16 = -144: the filter's differences are taken on signed values."""
+    import torch
+    from opencv_contrib_amd import cuda
+    left, right, _ = synth.stereo_pair(48, 80, seed=1, max_disp=20)
+    ref_d = oracle.sgm_compute(left, right, oracle.sgm_params(min_disparity=-8, num_disparities=64))
+    assert (ref_d == -144).any() and (ref_d > 0).any()
+    d = cuda.createStereoSGM(-8, 64).compute(torch.from_numpy(left).to(gpu), torch.from_numpy(right).to(gpu))
+    np.testing.assert_array_equal(d.cpu().numpy(), ref_d)
+    p = oracle.dbf_params(ndisp=1024, radius=3, iters=2)
+    f = cuda.createDisparityBilateralFilter(1024, 3, 2)
+    out = f.apply(d, torch.from_numpy(left).to(gpu)).cpu().numpy()
+    ref = oracle.dbf_apply(ref_d, left, p)
+    assert (ref != ref_d).any()
+    np.testing.assert_array_equal(out, ref)
+
+
+@pytest.mark.gpu
+def test_thresholds_at_their_ends(gpu, oracle):
+    left, disp = _case(oracle, h=40, w=64, seed=4)
+    # max_disc_threshold 0: every cost is 0, the first candidate (the pixel itself) wins the strict minimum -> identity
+    p = oracle.dbf_params(ndisp=32, radius=3, iters=2, max_disc_threshold=0.0)
+    ref = oracle.dbf_apply(disp, left, p)
+    np.testing.assert_array_equal(ref, disp)
+    np.testing.assert_array_equal(_hip_dbf(gpu, disp, left, p), ref)
+    # edge_threshold 0: edge_disc = short(0.5) = 0 is clamped to 1 -> only pixels with a differing 4-neighbour are refined
+    p = oracle.dbf_params(ndisp=32, radius=3, iters=2, edge_threshold=0.0)
+    ref = oracle.dbf_apply(disp, left, p)
+    assert (ref != disp).sum() > 50
+    np.testing.assert_array_equal(_hip_dbf(gpu, disp, left, p), ref)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape,radius", [((3, 129), 3), ((4, 2), 3), ((12, 20), 1), ((12, 20), 8)])
+def test_pair_lane_edge_and_radius_ends(gpu, oracle, shape, radius):
+    """A lane owns the pixel pair (2k, 2k + 1) and a workgroup 128 columns: 129 columns leave a pair with one pixel in a second
+    workgroup, 2 columns one pair without interior; radius 1 (3 x 3 window) and a window (17 x 17) larger than the 12-row image."""
+    rng = np.random.default_rng(shape[1] * 10 + radius)
+    disp = np.where(rng.random(shape) < 0.5, 5, 25).astype(np.uint8)
+    img = rng.integers(0, 256, shape).astype(np.uint8)
+    p = oracle.dbf_params(ndisp=32, radius=radius, iters=2)
+    ref = oracle.dbf_apply(disp, img, p)
+    if shape[0] > 2 and shape[1] > 2:
+        assert (ref != disp).any()
+    np.testing.assert_array_equal(_hip_dbf(gpu, disp, img, p), ref)
+
+
 @pytest.mark.gpu
 def test_argument_checks(gpu):
     import torch

@@ -48,6 +48,83 @@ def test_calc_bit_exact(gpu, oracle, shape, win, levels, iters):
     np.testing.assert_array_equal(flow, oracle.pyrlk_dense(I0, I1, win, levels, iters))
 
 
+def _hip_dense(gpu, I0, I1, win, levels, iters, alg=None):
+    import torch
+    from opencv_contrib_amd import cuda
+    if alg is None:
+        alg = cuda.DensePyrLKOpticalFlow.create(win, levels, iters)
+    return alg.calc(torch.from_numpy(I0).to(gpu), torch.from_numpy(I1).to(gpu)).cpu().numpy()
+
+
+@pytest.fixture(scope="module")
+def pair21():
+    I0, I1, _ = synth.flow_pair(67, 101, seed=21, dtype="u8")
+    return I0, I1
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("win", [(8, 8), (4, 13), (13, 4), (8, 13), (21, 6), (30, 30)])
+def test_calc_even_and_mixed_windows(gpu, oracle, pair21, win):
+    """The window is columns x - hx .. x - hx + wx - 1 with hx = (wx - 1) / 2 (oracle/pyrlk_ref.c): an even width puts one more column
+    to the right of the pixel than to its left, so lane 15 of a tile reads patch column 15 + wx - 1, and the patch is 15 + wx wide.
+    (13, 4) and (21, 6) run the two register-row kernels with an even height."""
+    I0, I1 = pair21
+    np.testing.assert_array_equal(_hip_dense(gpu, I0, I1, win, 2, 10), oracle.pyrlk_dense(I0, I1, win, 2, 10))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("win", [(3, 3), (31, 31), (3, 31), (31, 3)])
+def test_calc_extreme_windows(gpu, oracle, pair21, win):
+    I0, I1 = pair21
+    np.testing.assert_array_equal(_hip_dense(gpu, I0, I1, win, 2, 10), oracle.pyrlk_dense(I0, I1, win, 2, 10))
+
+
+@pytest.mark.gpu
+def test_calc_binary_noise_wraps_the_accumulators_and_loses_tracks(gpu, oracle):
+    """Independent 0 / 255 noise frames, window 31 x 31: a Scharr response reaches 16 * 255 = 4080 and 961 * 4080^2 > 2^32, so the 32-bit
+    sums wrap (modulo 2^32 on both sides); tracks leave the image, and such a pixel keeps what an earlier level wrote into the buffer
+    of the ping-pong pair that the last level writes (or the initial zero)."""
+    rng = np.random.default_rng(1)
+    I0 = (rng.integers(0, 2, (40, 56)) * 255).astype(np.uint8)
+    I1 = (rng.integers(0, 2, (40, 56)) * 255).astype(np.uint8)
+    ref = oracle.pyrlk_dense(I0, I1, (31, 31), 3, 10)
+    zero = ((ref[..., 0] == 0) & (ref[..., 1] == 0)).mean()
+    assert np.isfinite(ref).all() and 0.30 <= zero <= 0.90, zero
+    np.testing.assert_array_equal(_hip_dense(gpu, I0, I1, (31, 31), 3, 10), ref)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape,win,levels", [((5, 7), (3, 3), 4), ((1, 1), (5, 5), 0), ((16, 16), (5, 5), 2), ((17, 33), (5, 5), 2),
+                                              ((15, 31), (5, 5), 2)])
+def test_calc_tiny_and_tile_edge_sizes(gpu, oracle, shape, win, levels):
+    """5 x 7 with maxLevel 4: the levels shrink to 1 x 1; 16 / 17 / 15: exactly one tile, a tile and a pixel, a pixel short of a tile."""
+    I0, I1, _ = synth.flow_pair(64, 64, seed=23, dtype="u8")
+    I0, I1 = np.ascontiguousarray(I0[20:20 + shape[0], 11:11 + shape[1]]), np.ascontiguousarray(I1[20:20 + shape[0], 11:11 + shape[1]])
+    np.testing.assert_array_equal(_hip_dense(gpu, I0, I1, win, levels, 10), oracle.pyrlk_dense(I0, I1, win, levels, 10))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("iters", [0, 1])
+def test_calc_zero_and_one_iteration(gpu, oracle, pair21, iters):
+    """iters 0: every non-singular pixel writes the doubled flow of the level above unchanged."""
+    I0, I1 = pair21
+    np.testing.assert_array_equal(_hip_dense(gpu, I0, I1, (13, 13), 2, iters), oracle.pyrlk_dense(I0, I1, (13, 13), 2, iters))
+
+
+@pytest.mark.gpu
+def test_calc_handle_reuse_across_sizes_and_kernel_templates(gpu, oracle):
+    """One object: 96 x 128, 20 x 24 (inside the larger scratch, with other row strides), 96 x 128 again; the window goes
+    13 -> 21 -> 8, i.e. k_dense<13>, k_dense<21>, the generic kernel."""
+    from opencv_contrib_amd import cuda
+    big = synth.flow_pair(96, 128, seed=22, dtype="u8")[:2]
+    small = synth.flow_pair(20, 24, seed=24, dtype="u8")[:2]
+    alg = cuda.DensePyrLKOpticalFlow.create((13, 13), 2, 10)
+    for (I0, I1), w in [(big, 13), (small, 21), (big, 8)]:
+        alg.setWinSize((w, w))
+        assert alg.getWinSize() == (w, w)
+        np.testing.assert_array_equal(_hip_dense(gpu, I0, I1, None, None, None, alg=alg), oracle.pyrlk_dense(I0, I1, (w, w), 2, 10))
+
+
 @pytest.mark.gpu
 def test_calc_pitched_inputs_reuse_and_errors(gpu, oracle):
     import torch

@@ -134,6 +134,97 @@ def test_winner_takes_all_wide_rows_are_segmented(gpu, oracle, D, w):
     np.testing.assert_array_equal(right.cpu().numpy(), rr)
 
 
+def _census_pair(rng, shape):
+    l = rng.integers(0, 2 ** 31 - 1, shape, dtype=np.int64).astype(np.int32)
+    r = rng.integers(0, 2 ** 31 - 1, shape, dtype=np.int64).astype(np.int32)
+    return l, r
+
+
+def _hip_path(gpu, l, r, D, min_disp, p1, p2, dxdy):
+    import torch
+    from opencv_contrib_amd import cuda
+    return cuda.sgm_aggregate_path(torch.from_numpy(l).to(gpu), torch.from_numpy(r).to(gpu), D, min_disp, p1, p2, *dxdy).cpu().numpy().reshape(-1)
+
+
+@pytest.fixture(scope="module")
+def shifted_census():
+    """right random, left = right shifted by 7: disparity 7 costs 0 all along a line while the others cost ~15.5 bits, so their path
+    costs climb to the P2 cap above the minimum and cap + popcount passes 255."""
+    r = _census_pair(np.random.default_rng(250), (40, 150))[1]
+    return np.roll(r, 7, axis=1), r
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dxdy", DIRS)
+@pytest.mark.parametrize("D", [64, 128, 256])
+def test_path_aggregation_cost_cast_wraps(gpu, oracle, shifted_census, dxdy, D):
+    """min(.., P2 = 250) + popcount > 255: static_cast<uint8_t> wraps modulo 256, it does not saturate.  With P2 = 224 (224 + 31 = 255)
+    nothing wraps; the outputs of the two must differ or the case does not reach the cast."""
+    l, r = shifted_census
+    ref = oracle.sgm_path(l, r, D, 0, 10, 250, *dxdy)
+    assert (ref != oracle.sgm_path(l, r, D, 0, 10, 224, *dxdy)).any()
+    np.testing.assert_array_equal(_hip_path(gpu, l, r, D, 0, 10, 250, dxdy), ref)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("min_disp", [-1, -5, -70])
+@pytest.mark.parametrize("D", [64, 128])
+def test_path_aggregation_negative_min_disparity(gpu, oracle, min_disp, D):
+    """j - k - minDisparity can pass the right end of the row (cost against census 0 there); at -70 on 70 columns it always does."""
+    l, r = _census_pair(np.random.default_rng(D - min_disp), (9, 70))
+    for dxdy in [(1, 0), (0, -1), (-1, 1)]:
+        np.testing.assert_array_equal(_hip_path(gpu, l, r, D, min_disp, 10, 120, dxdy), oracle.sgm_path(l, r, D, min_disp, 10, 120, *dxdy))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", [(1, 70), (70, 1), (3, 3), (2, 130)])
+def test_path_aggregation_lines_shorter_than_the_prefetch(gpu, oracle, shape):
+    """Scan lines of 1 .. 3 pixels: the 4-deep census prefetch starts outside the image."""
+    l, r = _census_pair(np.random.default_rng(shape[0] * 1000 + shape[1]), shape)
+    for dxdy in DIRS:
+        np.testing.assert_array_equal(_hip_path(gpu, l, r, 128, 1, 10, 120, dxdy), oracle.sgm_path(l, r, 128, 1, 10, 120, *dxdy))
+
+
+def _wta_widths(D):
+    return [1, 63, D - 1, D, D + 1] + ([256, 257] if D <= 128 else [512, 513])
+
+
+@pytest.fixture(scope="module")
+def wta_oracle(oracle):
+    """Oracle results of the winner-takes-all sweep, computed once per (values, D)."""
+    cache = {}
+
+    def get(values, D):
+        if (values, D) not in cache:
+            rng = np.random.default_rng(D + values)
+            cases = []
+            for w in _wta_widths(D):
+                for h in (1, 5):
+                    agg = rng.integers(0, values, (1, w * h * D * 8)).astype(np.uint8)
+                    for uniq in (0.0, 0.95, 1.0):
+                        for sub in (False, True):
+                            cases.append((w, h, agg, uniq, sub, oracle.sgm_wta(agg, w, h, D, 8, uniq, sub)))
+            cache[(values, D)] = cases
+        return cache[(values, D)]
+    return get
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("values", [256, 2])
+@pytest.mark.parametrize("D", [64, 128, 256])
+def test_winner_takes_all_at_its_ends(gpu, wta_oracle, values, D):
+    """Costs over all of 0 .. 255 on 8 paths (sums to 2040), and costs from {0, 1}: many equal sums, so the first minimum (lowest
+    disparity) rule decides both maps (it also keeps the sub-pixel denominator l - 2 best + r positive: the left neighbour of a
+    first minimum costs strictly more).  Widths below, at and above D
+    and one segment / one segment and a pixel; uniqueness 0 (only a zero best cost survives), 0.95, 1 (nothing is rejected)."""
+    import torch
+    from opencv_contrib_amd import cuda
+    for w, h, agg, uniq, sub, (rl, rr) in wta_oracle(values, D):
+        left, right = cuda.sgm_winner_takes_all(torch.from_numpy(agg).to(gpu), w, h, D, 8, uniq, sub)
+        np.testing.assert_array_equal(left.cpu().numpy(), rl, err_msg=f"left w={w} h={h} uniq={uniq} subpixel={sub}")
+        np.testing.assert_array_equal(right.cpu().numpy(), rr, err_msg=f"right w={w} h={h} uniq={uniq} subpixel={sub}")
+
+
 # ------------------------------------------------------------------ full pipeline
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode", [1, 3])
@@ -174,3 +265,34 @@ def test_compute_16bit_images_pitched_and_errors(gpu, oracle):
     sgm.setMode(3)
     with pytest.raises(capi.MiError):
         sgm.compute(tl, torch.from_numpy(right[:, :100].copy()).to(gpu))           # size mismatch
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", [(13, 15), (16, 16), (32, 48), (17, 33)])
+@pytest.mark.parametrize("mode", [1, 3])
+@pytest.mark.parametrize("quirks", [True, False])
+def test_compute_small_sizes_negative_min_disparity(gpu, oracle, shape, mode, quirks):
+    """Sizes around the 16 x 16 blocks of the reference's consistency check (13 x 15 with quirks: no pixel is checked), minDisparity -8,
+    P2 250 (the cost cast wraps), uniquenessRatio 0 and 100."""
+    import torch
+    from opencv_contrib_amd import cuda
+    left, right, _ = synth.stereo_pair(shape[0], shape[1], seed=13, max_disp=10)
+    tl, tr = torch.from_numpy(left).to(gpu), torch.from_numpy(right).to(gpu)
+    for ur in (0, 100):
+        sgm = cuda.createStereoSGM(-8, 64, 10, 250, ur, mode, emulateCudaQuirks=quirks)
+        ref = oracle.sgm_compute(left, right, oracle.sgm_params(-8, 64, 10, 250, ur, mode, int(quirks)))
+        np.testing.assert_array_equal(sgm.compute(tl, tr).cpu().numpy(), ref, err_msg=f"uniquenessRatio={ur}")
+
+
+@pytest.mark.gpu
+def test_compute_handle_reuse_across_sizes(gpu, oracle):
+    import torch
+    from opencv_contrib_amd import cuda
+    sgm = cuda.createStereoSGM(-8, 64, 10, 250, 5, 1)
+    p = oracle.sgm_params(-8, 64, 10, 250, 5, 1, 1)
+    big = synth.stereo_pair(64, 160, seed=12, max_disp=30)[:2]
+    small = synth.stereo_pair(13, 15, seed=13, max_disp=10)[:2]
+    ref = {id(big): oracle.sgm_compute(*big, p), id(small): oracle.sgm_compute(*small, p)}
+    for pair in (big, small, big):
+        out = sgm.compute(torch.from_numpy(pair[0]).to(gpu), torch.from_numpy(pair[1]).to(gpu)).cpu().numpy()
+        np.testing.assert_array_equal(out, ref[id(pair)])
