@@ -844,6 +844,34 @@ __device__ __forceinline__ bool desc_staged(float s, float s_stage, int tile_byt
 {
     return s >= s_stage && ((long long)ceilf(s) + 3) * ((long long)floorf(20.f * s + s) + 2) <= (long long)tile_bytes;
 }
+// Sine and cosine of a float, evaluated in double and rounded once: the correctly rounded values for all but ~1e-8 of the arguments.
+// The device's sincosf is an ulp off at a third of the directions (the host's sinf / cosf at 2.6 %), and from 21 s ~ 800 texels on an
+// ulp of either moves the window's outer texel coordinates across pixel edges: a whole group of large features at one such direction
+// then reads other texels than the oracle.  |x| < 1024 (a direction is < 6.3; a caller's ANGLE may be anything): Cody-Waite reduction
+// by pi / 2 in two parts, Taylor polynomials to r^15 and r^16 on |r| <= pi / 4 (truncation < 2^-45); beyond that the device's sincosf.
+// A function of its own, not inlined, and the patch kernels bounded to the 6 waves per SIMD (3 workgroups per CU) they had before:
+// inlined, the double arithmetic takes k_descriptors from 68 to 90 VGPRs and the staged kernel from 77 to 122 -- 2 workgroups per CU
+// and a tenth of the 4K frame rate.
+__device__ __noinline__ float2 sincos_rounded(float x)
+{
+    if (!(fabsf(x) < 1024.f)) { float sn, cs; sincosf(x, &sn, &cs); return make_float2(sn, cs); }
+    const double xd = x;
+    const double k = rint(xd * 0.63661977236758134308);    // 2 / pi
+    double r = fma(-k, 1.57079632679489655800, xd);         // pi / 2: the nearest double ...
+    r = fma(-k, 6.12323399573676603587e-17, r);             // ... and what it leaves
+    const double r2 = r * r;
+    double p = -1.0 / 1307674368000.0;
+    p = fma(p, r2, 1.0 / 6227020800.0); p = fma(p, r2, -1.0 / 39916800.0); p = fma(p, r2, 1.0 / 362880.0);
+    p = fma(p, r2, -1.0 / 5040.0); p = fma(p, r2, 1.0 / 120.0); p = fma(p, r2, -1.0 / 6.0);
+    const double S = fma(r * r2, p, r);
+    double q = 1.0 / 20922789888000.0;
+    q = fma(q, r2, -1.0 / 87178291200.0); q = fma(q, r2, 1.0 / 479001600.0); q = fma(q, r2, -1.0 / 3628800.0);
+    q = fma(q, r2, 1.0 / 40320.0); q = fma(q, r2, -1.0 / 720.0); q = fma(q, r2, 1.0 / 24.0); q = fma(q, r2, -0.5);
+    const double C = fma(r2, q, 1.0);
+    const int n = (int)k & 3;
+    const double a = (n & 1) ? C : S, b = (n & 1) ? S : C;
+    return make_float2((float)((n & 2) ? -a : a), (float)((n == 1 || n == 2) ? -b : b));
+}
 // window geometry of feature f (surf.cu:733-760)
 __device__ __forceinline__ float desc_window(Win &w, const unsigned char *img, long long istep, int rows, int cols, const float *kp, int kld, int f)
 {
@@ -855,14 +883,15 @@ __device__ __forceinline__ float desc_window(Win &w, const unsigned char *img, l
     float ddir = 360.0f - kp[5 * kld + f];
     if (fabsf(ddir - 360.f) < FLT_EPSILON) ddir = 0.f;
     ddir *= CV_PI_F / 180.0f;
-    sincosf(ddir, &w.s, &w.c);
+    const float2 sc = sincos_rounded(ddir);
+    w.s = sc.x; w.c = sc.y;
     return s;
 }
 
 // surf.cu:733-912: one workgroup (8 waves) per feature: 21 x 21 patch (one sample per thread, every thread walking its own s x s cell of the
 // rotated window through global memory) -> desc_tail.  Features whose cell side s reaches s_stage are left to k_descriptors_staged.
 template <bool EXT>
-__global__ __launch_bounds__(512) void k_descriptors(const unsigned char *img, long long istep, int rows, int cols, const float *kp,
+__global__ __launch_bounds__(512, 6) void k_descriptors(const unsigned char *img, long long istep, int rows, int cols, const float *kp,
                                                      int kld, int nfeat_host, const unsigned *nfeat_dev, float *desc, long long dstep /* floats */, const float *dw,
                                                      float s_stage, int tile_bytes)
 {
@@ -1005,7 +1034,7 @@ __device__ __forceinline__ void strip_row_range(const Win &w, int i0, int i1, in
 #endif
 constexpr int kStageU = MI_SURF_STAGE_U;   // staged texel loads in flight per lane
 template <bool EXT>
-__global__ __launch_bounds__(512) void k_descriptors_staged(const unsigned char *img, long long istep, int rows, int cols, const float *kp,
+__global__ __launch_bounds__(512, 6) void k_descriptors_staged(const unsigned char *img, long long istep, int rows, int cols, const float *kp,
                                                             int kld, int nfeat_host, const unsigned *nfeat_dev, float *desc, long long dstep /* floats */,
                                                             const float *dw, float s_stage, int tile_bytes, int img_bytes, float s_coal)
 {
@@ -1646,8 +1675,9 @@ int orientation(const unsigned *sum, int sld, int rows, int cols, float *kp, int
 }
 
 // Cell side (pixels) from which a feature's patch is built by the staged kernel; MIFLOW_SURF_STAGE_S (0 = never).  The tile must hold
-// one patch row of the largest feature the detector can produce: size <= 27 << 5 would be octave 5; s = size * 1.2 / 9 -- 64 KB
-// holds (s + 3) x (21 s + 2) bytes up to s = 53 (size 400: octave 3's largest is 216).
+// one patch row of the largest feature the detector can produce (octave 3's largest size is 216, s = size * 1.2 / 9 = 28.8): the 48 KB
+// tile holds (ceil(s) + 3) x (floor(21 s) + 2) bytes up to s = 46.7 (size 350; s = 46: 47 432 bytes, s = 47: 49 450) -- desc_staged
+// leaves larger provided keypoints to the global-memory path.
 static float surf_stage_s()
 {
     static const float v = [] { const char *e = getenv("MIFLOW_SURF_STAGE_S"); const float x = e ? (float)atof(e) : 5.0f; return x > 0.f ? x : 1e30f; }();

@@ -1073,6 +1073,29 @@ class SURF_CUDA:
         capi.check(capi.lib().mi_surf_detect(self._h, C.byref(capi.mat_from_tensor(img)), mm, C.byref(mk), C.byref(n), sp))
         return kp[:, : n.value]   # keypoints.cols = featureCounter (surf.cuda.cpp:209)
 
+    def detect_batch(self, imgs, masks=None, stream=None):
+        """detect() of every frame of `imgs` through this handle in one call (mi_surf_detect_batch); frames may differ in size.
+        masks: None, or one entry per frame (a tensor or None).  -> list of (7, nFeatures) keypoint tensors, one per frame."""
+        import torch
+        n = len(imgs)
+        if masks is not None and len(masks) != n:
+            raise capi.MiError(-3, "masks: one entry (a tensor or None) per frame")
+        kps = []
+        for im in imgs:
+            # a frame the limits reject gets no matrix here: the batch call runs the frames before it and returns that frame's error
+            mf = C.c_int()
+            ok = capi.lib().mi_surf_max_features(self._h, im.shape[0], im.shape[1], C.byref(mf)) == 0
+            kps.append(torch.empty((7, mf.value), dtype=torch.float32, device=im.device) if ok else None)
+        mi = (capi.Mat * n)(*[capi.mat_from_tensor(t) for t in imgs])
+        mk = (capi.Mat * n)(*[capi.mat_from_tensor(t) if t is not None else capi.Mat() for t in kps])
+        mm = None
+        if masks is not None:   # a frame without a mask: an mi_mat with a NULL data pointer
+            mm = (capi.Mat * n)(*[capi.mat_from_tensor(m) if m is not None else capi.Mat() for m in masks])
+        nf = (C.c_int * n)()
+        sp = C.c_void_p(stream) if stream is not None else capi.current_stream_ptr()
+        capi.check(capi.lib().mi_surf_detect_batch(self._h, n, mi, mm, mk, nf, sp))
+        return [kp[:, : nf[i]] for i, kp in enumerate(kps)]
+
     def detectWithDescriptors(self, img, mask=None, keypoints=None, useProvidedKeypoints=False, stream=None):
         """operator()(img, mask, keypoints, descriptors, useProvidedKeypoints) (surf.cuda.cpp:380-397)."""
         import torch

@@ -548,6 +548,54 @@ def surf_detect_describe(img, params: SURFParams | None = None, mask=None, want_
             "descriptors": desc[:n].copy() if want_desc else None}
 
 
+def surf_orientation_samples(rows, cols, x, y, size):
+    """Per keypoint, how many of compute_orientation's 113 Haar samples lie inside a rows x cols image (surf.cu:556-563, the kernel's
+    own float expressions); -1 where the kernel returns before it samples: grad_wav_size = 2 * rn(2 s) > rows + 1 or > cols + 1
+    (surf.cu:546-551)."""
+    ax, ay, _, _ = surf_tables()
+    x, y, size = (np.atleast_1d(np.asarray(v, np.float32)) for v in (x, y, size))
+    out = np.empty(len(x), np.int32)
+    for k in range(len(x)):
+        s = size[k] * np.float32(1.2) / np.float32(9.0)
+        gws = 2 * int(np.rint(np.float32(2.0) * s))
+        if rows + 1 < gws or cols + 1 < gws:
+            out[k] = -1
+            continue
+        margin = np.float32(gws - 1) / np.float32(2.0)
+        sx, sy = np.rint(x[k] + ax * s - margin), np.rint(y[k] + ay * s - margin)
+        out[k] = int(((sy >= 0) & (sy < rows + 1 - gws) & (sx >= 0) & (sx < cols + 1 - gws)).sum())
+    return out
+
+
+def surf_orientation(img, x, y, size, angle_in):
+    """compute_orientation (surf.cu:527-658) of provided keypoints -> the ANGLE row, float32.  Where the kernel returns without
+    writing (surf_orientation_samples == -1) the caller's angle_in survives -- orc_surf_orientation returns 0 there, the value
+    detectKeypoints' zeroed matrix holds."""
+    img = _u8(img)
+    rows, cols = img.shape
+    x, y, size = (np.atleast_1d(np.asarray(v, np.float32)) for v in (x, y, size))
+    out = np.broadcast_to(np.asarray(angle_in, np.float32), x.shape).copy()
+    sum_ = surf_integral(img)
+    ax, ay, aw, _ = surf_tables()
+    L = lib()
+    for k in np.flatnonzero(surf_orientation_samples(rows, cols, x, y, size) >= 0):
+        out[k] = L.orc_surf_orientation(sum_, rows, cols, x[k], y[k], size[k], ax, ay, aw)
+    return out
+
+
+def surf_descriptors(img, x, y, size, angle, extended):
+    """compute_descriptors (surf.cu:733-912) of provided keypoints -> (n, 64 | 128) float32."""
+    img = _u8(img)
+    rows, cols = img.shape
+    x, y, size, angle = (np.atleast_1d(np.asarray(v, np.float32)) for v in (x, y, size, angle))
+    dw = surf_tables()[3]
+    out = np.empty((len(x), 128 if extended else 64), np.float32)
+    L = lib()
+    for k in range(len(x)):
+        L.orc_surf_descriptor(img, rows, cols, x[k], y[k], size[k], angle[k], int(bool(extended)), dw, out[k])
+    return out
+
+
 def pyr_down_u8(src):
     """cuda::pyrDown of a CV_8UC1 image (the pyramid of SparsePyrLKOpticalFlow)."""
     src = np.ascontiguousarray(src, np.uint8)

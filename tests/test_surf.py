@@ -13,8 +13,6 @@ xfeatures2d/test/test_surf.cuda.cpp:102-107,166-173).
 """
 import os
 
-import os
-
 import numpy as np
 import pytest
 

@@ -10,8 +10,6 @@
   keyPointsEquals of the reference's test support (opencv/opencv modules/ts/src/cuda_test.cpp, un-vendored) is restated: point distance
   < 1 px, size difference < 1, angle difference < 2 degrees, response difference < 0.1, same octave and class_id (Laplacian sign).
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -146,8 +144,7 @@ def _oracle_detect(oracle):
 
 
 def _oracle_describe(oracle):
-    L = oracle.lib()
-    L.orc_surf_orientation.restype = C.c_float
+    L = oracle.lib()   # (signatures: oracle._bind_surf)
     ax, ay, aw, dw = oracle.surf_tables()
 
     def f(img, kp, thr, octaves, layers, extended, upright):
