@@ -19,8 +19,7 @@
 
 struct mi_bfmatcher {
     int norm = MI_NORM_L2;
-    void *part = nullptr;       // knn: [segment][query][K] {distance, index}; radius: [segment][query] count -> offset
-    size_t part_bytes = 0;
+    mi::DevBuf<unsigned char> part;   // knn: [segment][query][K] {distance, index}; radius: [segment][query] count -> offset
 };
 
 namespace mi {
@@ -369,15 +368,6 @@ static int plan(const mi_mat *query, const mi_mat *trains, const mi_mat *masks, 
     return MI_OK;
 }
 
-static int reserve(mi_bfmatcher *h, size_t need)
-{
-    if (h->part_bytes >= need) return MI_OK;
-    if (h->part) { (void)hipFree(h->part); h->part = nullptr; h->part_bytes = 0; }
-    MI_HIP_TRY(hipMalloc(&h->part, need));
-    h->part_bytes = need;
-    return MI_OK;
-}
-
 static void fill_args(Args &A, const mi_mat *query, const mi_mat &t, const mi_mat *mask, const Seg &s)
 {
     A.q = (const float *)query->data; A.qstep = query->step;
@@ -411,20 +401,20 @@ static int run_knn(mi_bfmatcher *h, const mi_mat *query, const mi_mat *trains, c
     int nseg = 0;
     if (int rc = plan(query, trains, masks, n_trains, sh.tt, segs, &nseg)) return rc;
     const int nq = query->rows;
-    if (int rc = reserve(h, sizeof(float2) * (size_t)nseg * nq * K)) return rc;
+    MI_TRY(h->part.ensure(sizeof(float2) * (size_t)nseg * nq * K));
     const int qblocks = div_up(nq, 64), mblocks = div_up(nq, 256);
     for (int col0 = 0; col0 < k; col0 += K) {
         for (int m = 0; m < n_trains; ++m) {
             Args A = {};
             fill_args(A, query, trains[m], masks ? &masks[m] : nullptr, segs[m]);
-            A.part = reinterpret_cast<float2 *>(h->part);
+            A.part = reinterpret_cast<float2 *>(h->part.p);
             if (col0) { A.lo_idx = o.idx + col0 - 1; A.lo_istep = o.istep; A.lo_dist = o.dist + col0 - 1; A.lo_dstep = o.dstep; }
             sh.fn(A, dim3(qblocks, segs[m].nsplit), st);
         }
         const int ncol = min(K, k - col0);
-        if (K == 2) hipLaunchKernelGGL((k_merge<2>), dim3(mblocks), dim3(256), 0, st, reinterpret_cast<const float2 *>(h->part), nq, nseg,
+        if (K == 2) hipLaunchKernelGGL((k_merge<2>), dim3(mblocks), dim3(256), 0, st, reinterpret_cast<const float2 *>(h->part.p), nq, nseg,
                                        o.idx, o.istep, o.dist, o.dstep, o.img, o.mstep, col0, ncol);
-        else hipLaunchKernelGGL((k_merge<8>), dim3(mblocks), dim3(256), 0, st, reinterpret_cast<const float2 *>(h->part), nq, nseg,
+        else hipLaunchKernelGGL((k_merge<8>), dim3(mblocks), dim3(256), 0, st, reinterpret_cast<const float2 *>(h->part.p), nq, nseg,
                                 o.idx, o.istep, o.dist, o.dstep, o.img, o.mstep, col0, ncol);
     }
     if (o.img) assign_images(o, nq, k, nullptr, segs, st);
@@ -450,11 +440,7 @@ int mi_bf_create(int norm_type, mi_bfmatcher **out)
     *out = nullptr;
     MI_REQUIRE(norm_type == MI_NORM_L2 || norm_type == MI_NORM_L1 || norm_type == MI_NORM_HAMMING, MI_ERR_BAD_ARG,
                "norm == NORM_L1 || norm == NORM_L2 || norm == NORM_HAMMING");      // BFMatcher_Impl constructor
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n == 0) {
-        set_error("no HIP device available: the miflow product path has no CPU fallback");
-        return MI_ERR_NO_DEVICE;
-    }
+    MI_TRY(require_device());
     *out = new mi_bfmatcher();
     (*out)->norm = norm_type;
     return MI_OK;
@@ -462,8 +448,6 @@ int mi_bf_create(int norm_type, mi_bfmatcher **out)
 
 void mi_bf_destroy(mi_bfmatcher *h)
 {
-    if (!h) return;
-    if (h->part) (void)hipFree(h->part);
     delete h;
 }
 
@@ -523,7 +507,7 @@ int mi_bf_radius_match(mi_bfmatcher *h, const mi_mat *query, const mi_mat *train
     int nseg = 0;
     if (int rc = bf::plan(query, trains, masks, n_trains, sh.tt, segs, &nseg)) return rc;
     const int nq = query->rows;
-    if (int rc = bf::reserve(h, sizeof(int) * (size_t)nseg * nq)) return rc;
+    MI_TRY(h->part.ensure(sizeof(int) * (size_t)nseg * nq));
     const bf::Out o = {(int *)train_idx->data, train_idx->step / 4, img_idx ? (int *)img_idx->data : nullptr, img_idx ? img_idx->step / 4 : 0,
                        (float *)distance->data, distance->step / 4};
     const int qblocks = div_up(nq, 64);
@@ -531,13 +515,13 @@ int mi_bf_radius_match(mi_bfmatcher *h, const mi_mat *query, const mi_mat *train
         for (int m = 0; m < n_trains; ++m) {
             bf::Args A = {};
             bf::fill_args(A, query, trains[m], masks ? &masks[m] : nullptr, segs[m]);
-            A.cnt = reinterpret_cast<int *>(h->part);
+            A.cnt = reinterpret_cast<int *>(h->part.p);
             A.max_dist = max_distance; A.write = pass; A.cols = cols;
             A.r_idx = o.idx; A.r_istep = o.istep; A.r_img = o.img; A.r_mstep = o.mstep; A.r_dist = o.dist; A.r_dstep = o.dstep;
             sh.fn(A, dim3(qblocks, segs[m].nsplit), st);
         }
         if (pass == 0)
-            hipLaunchKernelGGL(bf::k_radius_scan, dim3(div_up(nq, 256)), dim3(256), 0, st, reinterpret_cast<int *>(h->part), nq, nseg,
+            hipLaunchKernelGGL(bf::k_radius_scan, dim3(div_up(nq, 256)), dim3(256), 0, st, reinterpret_cast<int *>(h->part.p), nq, nseg,
                                (int *)n_matches->data);
     }
     if (o.img) bf::assign_images(o, nq, cols, (const int *)n_matches->data, segs, st);

@@ -10,8 +10,7 @@ using namespace mi::btvl1;
 
 struct mi_btvl1 {
     mi_btvl1_params P;
-    unsigned char *arena = nullptr;   // every scratch plane of the last geometry (layout()); grown lazily, freed with the handle
-    size_t cap = 0;
+    DevBuf<unsigned char> arena;      // every scratch plane of the last geometry (layout()); grown lazily, freed with the handle
     hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the last process (mi_btvl1_get_profile)
     long long launches = 0;
     bool timed = false;
@@ -125,14 +124,11 @@ int prepare(mi_btvl1 *h, int n, const mi_mat *frames, const mi_mat *fwd_x, const
         }
     }
     const size_t need = layout(g, nullptr, nullptr);
-    if (need > h->cap) {
-        if (h->arena) { MI_HIP_TRY(hipStreamSynchronize(st)); MI_HIP_TRY(hipFree(h->arena)); h->arena = nullptr; h->cap = 0; }
-        MI_HIP_TRY(hipMalloc((void **)&h->arena, need));
-        h->cap = need;
-    }
+    if (need > h->arena.n && h->arena.p) MI_HIP_TRY(hipStreamSynchronize(st));
+    MI_TRY(h->arena.ensure(need));
     IterArgs &a = *A;
     a.g = g;
-    layout(g, h->arena, &a.p);
+    layout(g, h->arena.p, &a.p);
     gaussian_taps(P.blur_kernel_size, P.blur_sigma, a.t.g);
     btv_weights(P.btv_kernel_size, P.alpha, a.t.w);
     a.kb = P.blur_kernel_size; a.ks = (P.btv_kernel_size - 1) / 2; a.cur = 0;
@@ -177,11 +173,7 @@ int mi_btvl1_create(const mi_btvl1_params *p, mi_btvl1 **out)
     *out = nullptr;
     mi_btvl1_params d;
     if (!p) { mi_btvl1_default_params(&d); p = &d; }
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n == 0) {
-        set_error("no HIP device available: the miflow product path has no CPU fallback");
-        return MI_ERR_NO_DEVICE;
-    }
+    MI_TRY(require_device());
     mi_btvl1 *h = new mi_btvl1();
     h->P = *p;   // validated at process(), like the reference (CV_Assert inside process)
     if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) {
@@ -210,7 +202,6 @@ int mi_btvl1_get_params(const mi_btvl1 *h, mi_btvl1_params *p)
 void mi_btvl1_destroy(mi_btvl1 *h)
 {
     if (!h) return;
-    if (h->arena) (void)hipFree(h->arena);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     delete h;
@@ -274,7 +265,7 @@ int mi_btvl1_stage(mi_btvl1 *h, int n, const mi_mat *frames, const mi_mat *fwd_x
     h->timed = false;
     DevTmp tmp;
     float *maps_f = nullptr;
-    MI_HIP_TRY(tmp.alloc(&maps_f, (size_t)n * 4 * (size_t)hw * (size_t)hh));
+    MI_TRY(tmp.alloc(&maps_f, (size_t)n * 4 * (size_t)hw * (size_t)hh));
     IterArgs A;
     if (const int rc = prepare(h, n, frames, fwd_x, fwd_y, bwd_x, bwd_y, base_idx, maps_f, &A, st)) return rc;
     const size_t hpx = (size_t)hw * hh;
@@ -305,8 +296,8 @@ int mi_btvl1_convert(const mi_mat *src, mi_mat *dst, void *stream)
 
 int miflow_selftest_btvl1_poison(mi_btvl1 *h, void *stream)
 {
-    MI_REQUIRE(h && h->arena, MI_ERR_BAD_ARG, "no arena yet: run a process first");
-    MI_HIP_TRY(hipMemsetAsync(h->arena, 0xff, h->cap, (hipStream_t)stream));
+    MI_REQUIRE(h && h->arena.p, MI_ERR_BAD_ARG, "no arena yet: run a process first");
+    MI_HIP_TRY(hipMemsetAsync(h->arena.p, 0xff, h->arena.n, (hipStream_t)stream));
     return MI_OK;
 }
 

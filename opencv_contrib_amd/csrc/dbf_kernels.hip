@@ -12,11 +12,10 @@
 
 struct mi_disp_bilateral {
     mi_disp_bilateral_params P;
-    float *tab = nullptr;        // device: 256 colour weights, then (radius+1)^2 space weights
-    int tab_radius = -1;
+    mi::DevBuf<float> tab;       // 256 colour weights, then (radius+1)^2 space weights
+    int tab_radius = -1;         // the parameters the table holds: recorded once its upload has succeeded
     float tab_sigma = -1.f;
-    void *tmp = nullptr;         // ping-pong map
-    size_t tmp_bytes = 0;
+    mi::DevBuf<unsigned char> tmp;   // ping-pong map
 };
 
 namespace mi {
@@ -95,7 +94,7 @@ __global__ __launch_bounds__(256) void k_pass(Args A)
 static int build_tables(mi_disp_bilateral *h)
 {
     const mi_disp_bilateral_params &P = h->P;
-    if (h->tab && h->tab_radius == P.radius && h->tab_sigma == P.sigma_range) return MI_OK;
+    if (h->tab.p && h->tab_radius == P.radius && h->tab_sigma == P.sigma_range) return MI_OK;
     const int half = P.radius, n = 256 + (half + 1) * (half + 1);
     std::vector<float> t(n);
     // calc_color_weighted_table / calc_space_weighted_filter, disparity_bilateral_filter.cpp:96-123.  The reference's colour table has
@@ -105,9 +104,14 @@ static int build_tables(mi_disp_bilateral *h)
     const float dist_space = P.radius + 1.0f;
     for (int y = 0; y <= half; ++y)
         for (int x = 0; x <= half; ++x) t[256 + y * (half + 1) + x] = std::exp(-std::sqrt(float(y * y) + float(x * x)) / dist_space);
-    if (h->tab) { (void)hipFree(h->tab); h->tab = nullptr; }
-    MI_HIP_TRY(hipMalloc(&h->tab, sizeof(float) * n));
-    MI_HIP_TRY(hipMemcpy(h->tab, t.data(), sizeof(float) * n, hipMemcpyHostToDevice));
+    // released even where it is large enough: the free synchronises the device, and an earlier apply on another stream may still
+    // read the table this synchronous upload overwrites
+    h->tab.release();
+    MI_TRY(h->tab.ensure(n));
+    if (const hipError_t e = hipMemcpy(h->tab.p, t.data(), sizeof(float) * n, hipMemcpyHostToDevice)) {
+        h->tab.release();   // never a table that holds anything but (tab_radius, tab_sigma)
+        MI_HIP_TRY(e);
+    }
     h->tab_radius = P.radius;
     h->tab_sigma = P.sigma_range;
     return MI_OK;
@@ -138,11 +142,7 @@ int mi_disp_bilateral_create(const mi_disp_bilateral_params *p, mi_disp_bilatera
 {
     MI_REQUIRE(out, MI_ERR_BAD_ARG, "null out");
     *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n == 0) {
-        set_error("no HIP device available: the miflow product path has no CPU fallback");
-        return MI_ERR_NO_DEVICE;
-    }
+    MI_TRY(require_device());
     mi_disp_bilateral *h = new mi_disp_bilateral();
     if (p) h->P = *p; else mi_disp_bilateral_default_params(&h->P);
     *out = h;
@@ -165,9 +165,6 @@ int mi_disp_bilateral_get_params(const mi_disp_bilateral *h, mi_disp_bilateral_p
 
 void mi_disp_bilateral_destroy(mi_disp_bilateral *h)
 {
-    if (!h) return;
-    if (h->tab) (void)hipFree(h->tab);
-    if (h->tmp) (void)hipFree(h->tmp);
     delete h;
 }
 
@@ -188,16 +185,12 @@ int mi_disp_bilateral_apply(mi_disp_bilateral *h, const mi_mat *disp, const mi_m
     if (rc) return rc;
     const int es = disp->type == MI_8UC1 ? 1 : 2, cn = img->type == MI_8UC1 ? 1 : 3;
     const size_t tstep = (size_t)align_up(disp->cols * es, 256), need = tstep * disp->rows;
-    if (h->tmp_bytes < need) {
-        if (h->tmp) { (void)hipFree(h->tmp); h->tmp = nullptr; h->tmp_bytes = 0; }
-        MI_HIP_TRY(hipMalloc(&h->tmp, need));
-        h->tmp_bytes = need;
-    }
+    MI_TRY(h->tmp.ensure(need));
     if (dst->data != disp->data)   // disp.copyTo(dst), .cpp:155-156
         MI_HIP_TRY(hipMemcpy2DAsync(dst->data, dst->step, disp->data, disp->step, (size_t)disp->cols * es, disp->rows, hipMemcpyDeviceToDevice, st));
     dbf::Args A;
     A.img = (const unsigned char *)img->data; A.istep = img->step;
-    A.tab = h->tab;
+    A.tab = h->tab.p;
     A.rows = disp->rows; A.cols = disp->cols; A.radius = P.radius;
     // .cpp:146-147
     short edge_disc = short(P.ndisp * P.edge_threshold + 0.5);
@@ -208,8 +201,8 @@ int mi_disp_bilateral_apply(mi_disp_bilateral *h, const mi_mat *disp, const mi_m
     for (int i = 0; i < P.iters; ++i)
         for (int t = 0; t < 2; ++t) {   // cu:164-170; pass 0: dst -> tmp, pass 1: tmp -> dst
             A.t = t;
-            if (t == 0) { A.src = (const unsigned char *)dst->data; A.sstep = dst->step; A.dst = (unsigned char *)h->tmp; A.dstep = tstep; }
-            else { A.src = (const unsigned char *)h->tmp; A.sstep = tstep; A.dst = (unsigned char *)dst->data; A.dstep = dst->step; }
+            if (t == 0) { A.src = (const unsigned char *)dst->data; A.sstep = dst->step; A.dst = h->tmp.p; A.dstep = tstep; }
+            else { A.src = h->tmp.p; A.sstep = tstep; A.dst = (unsigned char *)dst->data; A.dstep = dst->step; }
             if (es == 1) dbf::launch<unsigned char>(cn, A, grid, lds, st);
             else dbf::launch<short>(cn, A, grid, lds, st);
         }

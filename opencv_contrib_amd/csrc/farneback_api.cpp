@@ -81,7 +81,7 @@ int prepare_gaussian(int n, double sigma, PolyC *C)
 
 struct mi_farneback {
     mi_farneback_params P;
-    float *arena = nullptr;     // capB per-pair blocks of `bs` floats: every plane of pair b lives at (plane of pair 0) + b * bs
+    DevBuf<float> arena;        // capB per-pair blocks of `bs` floats: every plane of pair b lives at (plane of pair 0) + b * bs
     int capW = 0, capH = 0, capB = 0;
     long long bs = 0;
     // full-size-capacity planes
@@ -126,11 +126,7 @@ int mi_farneback_create(const mi_farneback_params *p, mi_farneback **out)
     *out = nullptr;
     mi_farneback_params d;
     if (!p) { mi_farneback_default_params(&d); p = &d; }
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n == 0) {
-        set_error("no HIP device available: the miflow product path has no CPU fallback");
-        return MI_ERR_NO_DEVICE;
-    }
+    MI_TRY(require_device());
     mi_farneback *h = new mi_farneback();
     h->P = *p;   // validated at calc(), like the reference (CV_Assert inside calcImpl)
     *out = h;
@@ -154,7 +150,6 @@ int mi_farneback_get_params(const mi_farneback *h, mi_farneback_params *p)
 void mi_farneback_destroy(mi_farneback *h)
 {
     if (!h) return;
-    if (h->arena) (void)hipFree(h->arena);
     if (h->aux) { (void)hipStreamSynchronize(h->aux); (void)hipStreamDestroy(h->aux); }
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
@@ -163,9 +158,8 @@ void mi_farneback_destroy(mi_farneback *h)
 
 static int ensure(mi_farneback *h, int W, int H, int B)
 {
-    if (h->arena && h->capW == W && h->capH == H && h->capB >= B) return MI_OK;
-    if (h->arena) (void)hipFree(h->arena);
-    h->arena = nullptr;
+    if (h->arena.p && h->capW == W && h->capH == H && h->capB >= B) return MI_OK;
+    h->arena.release();   // another frame size or a larger batch: re-made (not only grown) and carved again
     const Plane g = plane_of(W, H);
     const size_t n = (size_t)g.ld * H;
     // per pair: frames 2, blurred 2, lvl 2, R 2x5, M 5, bufM 5, flows 6 = 32 planes, + the fast-pyramid levels of both frames
@@ -173,8 +167,8 @@ static int ensure(mi_farneback *h, int W, int H, int B)
     // (frame 1 = frame 0 + one plane; R[1] = R[0] + five): the pyramid kernels run both frames in one launch
     // (round 4's all-levels-at-once expansion planes and the internal-stream pyramid they served measured slower, r08i, and are gone)
     const size_t per_pair = n * 34;
-    MI_HIP_TRY(hipMalloc((void **)&h->arena, sizeof(float) * per_pair * (size_t)B));
-    float *p = h->arena;
+    MI_TRY(h->arena.ensure(per_pair * (size_t)B));
+    float *p = h->arena.p;
     auto take = [&](size_t k) { float *q = p; p += n * k; return q; };
     h->frames[0] = take(1); h->frames[1] = take(1); h->blurred = take(2); h->lvl[0] = take(1); h->lvl[1] = take(1);
     h->R[0] = take(5); h->R[1] = take(5); h->M = take(5); h->bufM = take(5);
@@ -502,8 +496,8 @@ int mi_farneback_calc(mi_farneback *h, const mi_mat *I0, const mi_mat *I1, mi_ma
 // test hook (mi_selftest.h): NaNs over the whole arena
 int miflow_selftest_farneback_poison(mi_farneback *h, void *stream)
 {
-    MI_REQUIRE(h && h->arena, MI_ERR_BAD_ARG, "no arena yet: run a calc first");
-    MI_HIP_TRY(hipMemsetAsync(h->arena, 0xff, sizeof(float) * (size_t)h->bs * (size_t)h->capB, (hipStream_t)stream));
+    MI_REQUIRE(h && h->arena.p, MI_ERR_BAD_ARG, "no arena yet: run a calc first");
+    MI_HIP_TRY(hipMemsetAsync(h->arena.p, 0xff, sizeof(float) * (size_t)h->bs * (size_t)h->capB, (hipStream_t)stream));
     return MI_OK;
 }
 
@@ -511,17 +505,6 @@ int miflow_selftest_farneback_poison(mi_farneback *h, void *stream)
 
 // ------------------------------------------------------------------ stage-level entry points
 namespace {
-struct Stage {
-    std::vector<float *> bufs;
-    ~Stage() { for (float *p : bufs) (void)hipFree(p); }
-    float *alloc(size_t n)
-    {
-        float *p = nullptr;
-        if (hipMalloc((void **)&p, sizeof(float) * n) != hipSuccess) return nullptr;
-        bufs.push_back(p);
-        return p;
-    }
-};
 int check_f32(const mi_mat *m, const char *name)
 {
     MI_REQUIRE(m && m->data, MI_ERR_BAD_ARG, "%s: null matrix", name);
@@ -531,10 +514,10 @@ int check_f32(const mi_mat *m, const char *name)
     return MI_OK;
 }
 // rows x cols matrix (rows may be 5*h) -> dense plane(s) with pitch ld
-int stage_in(Stage &S, const mi_mat *m, int ld, float **out, hipStream_t st)
+int stage_in(DevTmp &S, const mi_mat *m, int ld, float **out, hipStream_t st)
 {
-    float *p = S.alloc((size_t)ld * m->rows);
-    MI_REQUIRE(p, MI_ERR_OOM, "stage allocation failed");
+    float *p;
+    MI_TRY(S.alloc(&p, (size_t)ld * m->rows));
     MI_HIP_TRY(hipMemcpy2DAsync(p, (size_t)ld * 4, m->data, m->step, (size_t)m->cols * 4, (size_t)m->rows, hipMemcpyDeviceToDevice, st));
     *out = p;
     return MI_OK;
@@ -544,7 +527,6 @@ int stage_out(const float *p, int ld, mi_mat *m, hipStream_t st)
     MI_HIP_TRY(hipMemcpy2DAsync(m->data, m->step, p, (size_t)ld * 4, (size_t)m->cols * 4, (size_t)m->rows, hipMemcpyDeviceToDevice, st));
     return MI_OK;
 }
-#define TRY(x) do { int _rc = (x); if (_rc) return _rc; } while (0)
 int make_win_taps(int ksize, Taps *K)
 {
     MI_REQUIRE(ksize >= 1 && (ksize & 1) && ksize / 2 <= MI_FB_MAX_KSIZE_HALF, MI_ERR_BAD_ARG, "ksize must be odd and <= 201");
@@ -561,18 +543,18 @@ extern "C" {
 int mi_farneback_poly_exp(const mi_mat *src, mi_mat *dst5, int poly_n, double poly_sigma, void *stream)
 {
     hipStream_t st = (hipStream_t)stream;
-    TRY(check_f32(src, "src")); TRY(check_f32(dst5, "dst"));
+    MI_TRY(check_f32(src, "src")); MI_TRY(check_f32(dst5, "dst"));
     MI_REQUIRE(dst5->rows == 5 * src->rows && dst5->cols == src->cols, MI_ERR_BAD_SIZE, "dst must be 5*rows x cols");
     MI_REQUIRE(poly_n == 5 || poly_n == 7, MI_ERR_BAD_ARG, "polyN must be 5 or 7");
     const Plane g = plane_of(src->cols, src->rows);
-    Stage S;
-    float *in = nullptr, *out = S.alloc((size_t)g.ld * g.h * 5);
-    MI_REQUIRE(out, MI_ERR_OOM, "stage allocation failed");
-    TRY(stage_in(S, src, g.ld, &in, st));
+    DevTmp S;
+    float *in = nullptr, *out;
+    MI_TRY(S.alloc(&out, (size_t)g.ld * g.h * 5));
+    MI_TRY(stage_in(S, src, g.ld, &in, st));
     PolyC C;
-    TRY(prepare_gaussian(poly_n, poly_sigma, &C));
-    TRY(poly_exp(in, out, g, poly_n, C, st));
-    TRY(stage_out(out, g.ld, dst5, st));
+    MI_TRY(prepare_gaussian(poly_n, poly_sigma, &C));
+    MI_TRY(poly_exp(in, out, g, poly_n, C, st));
+    MI_TRY(stage_out(out, g.ld, dst5, st));
     MI_HIP_TRY(hipStreamSynchronize(st));
     return MI_OK;
 }
@@ -580,18 +562,18 @@ int mi_farneback_poly_exp(const mi_mat *src, mi_mat *dst5, int poly_n, double po
 int mi_farneback_update_matrices(const mi_mat *flowx, const mi_mat *flowy, const mi_mat *R0, const mi_mat *R1, mi_mat *M5, void *stream)
 {
     hipStream_t st = (hipStream_t)stream;
-    TRY(check_f32(flowx, "flowx")); TRY(check_f32(flowy, "flowy")); TRY(check_f32(R0, "R0")); TRY(check_f32(R1, "R1")); TRY(check_f32(M5, "M"));
+    MI_TRY(check_f32(flowx, "flowx")); MI_TRY(check_f32(flowy, "flowy")); MI_TRY(check_f32(R0, "R0")); MI_TRY(check_f32(R1, "R1")); MI_TRY(check_f32(M5, "M"));
     const int w = flowx->cols, hh = flowx->rows;
     MI_REQUIRE(flowy->rows == hh && flowy->cols == w && R0->rows == 5 * hh && R1->rows == 5 * hh && M5->rows == 5 * hh &&
                R0->cols == w && R1->cols == w && M5->cols == w, MI_ERR_BAD_SIZE, "size mismatch");
     const Plane g = plane_of(w, hh);
-    Stage S;
-    float *fx, *fy, *r0, *r1, *m = S.alloc((size_t)g.ld * hh * 5);
-    MI_REQUIRE(m, MI_ERR_OOM, "stage allocation failed");
-    TRY(stage_in(S, flowx, g.ld, &fx, st)); TRY(stage_in(S, flowy, g.ld, &fy, st));
-    TRY(stage_in(S, R0, g.ld, &r0, st)); TRY(stage_in(S, R1, g.ld, &r1, st));
-    TRY(update_matrices(fx, fy, r0, r1, m, g, st));
-    TRY(stage_out(m, g.ld, M5, st));
+    DevTmp S;
+    float *fx, *fy, *r0, *r1, *m;
+    MI_TRY(S.alloc(&m, (size_t)g.ld * hh * 5));
+    MI_TRY(stage_in(S, flowx, g.ld, &fx, st)); MI_TRY(stage_in(S, flowy, g.ld, &fy, st));
+    MI_TRY(stage_in(S, R0, g.ld, &r0, st)); MI_TRY(stage_in(S, R1, g.ld, &r1, st));
+    MI_TRY(update_matrices(fx, fy, r0, r1, m, g, st));
+    MI_TRY(stage_out(m, g.ld, M5, st));
     MI_HIP_TRY(hipStreamSynchronize(st));
     return MI_OK;
 }
@@ -599,17 +581,17 @@ int mi_farneback_update_matrices(const mi_mat *flowx, const mi_mat *flowy, const
 int mi_farneback_blur5(const mi_mat *M5, mi_mat *dst5, int ksize, int gaussian, void *stream)
 {
     hipStream_t st = (hipStream_t)stream;
-    TRY(check_f32(M5, "M")); TRY(check_f32(dst5, "dst"));
+    MI_TRY(check_f32(M5, "M")); MI_TRY(check_f32(dst5, "dst"));
     MI_REQUIRE(M5->rows % 5 == 0 && dst5->rows == M5->rows && dst5->cols == M5->cols, MI_ERR_BAD_SIZE, "size mismatch");
     const Plane g = plane_of(M5->cols, M5->rows / 5);
     Taps K;
-    TRY(make_win_taps(ksize, &K));
-    Stage S;
-    float *m, *out = S.alloc((size_t)g.ld * g.h * 5);
-    MI_REQUIRE(out, MI_ERR_OOM, "stage allocation failed");
-    TRY(stage_in(S, M5, g.ld, &m, st));
-    TRY(blur5(m, out, g, ksize, gaussian ? &K : nullptr, st));
-    TRY(stage_out(out, g.ld, dst5, st));
+    MI_TRY(make_win_taps(ksize, &K));
+    DevTmp S;
+    float *m, *out;
+    MI_TRY(S.alloc(&out, (size_t)g.ld * g.h * 5));
+    MI_TRY(stage_in(S, M5, g.ld, &m, st));
+    MI_TRY(blur5(m, out, g, ksize, gaussian ? &K : nullptr, st));
+    MI_TRY(stage_out(out, g.ld, dst5, st));
     MI_HIP_TRY(hipStreamSynchronize(st));
     return MI_OK;
 }
@@ -617,16 +599,16 @@ int mi_farneback_blur5(const mi_mat *M5, mi_mat *dst5, int ksize, int gaussian, 
 int mi_farneback_update_flow(const mi_mat *M5, mi_mat *flowx, mi_mat *flowy, void *stream)
 {
     hipStream_t st = (hipStream_t)stream;
-    TRY(check_f32(M5, "M")); TRY(check_f32(flowx, "flowx")); TRY(check_f32(flowy, "flowy"));
+    MI_TRY(check_f32(M5, "M")); MI_TRY(check_f32(flowx, "flowx")); MI_TRY(check_f32(flowy, "flowy"));
     MI_REQUIRE(M5->rows == 5 * flowx->rows && M5->cols == flowx->cols && flowy->rows == flowx->rows && flowy->cols == flowx->cols,
                MI_ERR_BAD_SIZE, "size mismatch");
     const Plane g = plane_of(flowx->cols, flowx->rows);
-    Stage S;
-    float *m, *fx = S.alloc((size_t)g.ld * g.h), *fy = S.alloc((size_t)g.ld * g.h);
-    MI_REQUIRE(fx && fy, MI_ERR_OOM, "stage allocation failed");
-    TRY(stage_in(S, M5, g.ld, &m, st));
-    TRY(update_flow(m, fx, fy, g, st));
-    TRY(stage_out(fx, g.ld, flowx, st)); TRY(stage_out(fy, g.ld, flowy, st));
+    DevTmp S;
+    float *m, *fx, *fy;
+    MI_TRY(S.alloc(&fx, (size_t)g.ld * g.h)); MI_TRY(S.alloc(&fy, (size_t)g.ld * g.h));
+    MI_TRY(stage_in(S, M5, g.ld, &m, st));
+    MI_TRY(update_flow(m, fx, fy, g, st));
+    MI_TRY(stage_out(fx, g.ld, flowx, st)); MI_TRY(stage_out(fy, g.ld, flowy, st));
     MI_HIP_TRY(hipStreamSynchronize(st));
     return MI_OK;
 }
@@ -635,22 +617,22 @@ int mi_farneback_iterate(const mi_mat *M5, const mi_mat *R0, const mi_mat *R1, m
                          int ksize, int gaussian, int update, void *stream)
 {
     hipStream_t st = (hipStream_t)stream;
-    TRY(check_f32(M5, "M")); TRY(check_f32(R0, "R0")); TRY(check_f32(R1, "R1")); TRY(check_f32(flowx, "flowx")); TRY(check_f32(flowy, "flowy"));
-    TRY(check_f32(M5out, "Mout"));
+    MI_TRY(check_f32(M5, "M")); MI_TRY(check_f32(R0, "R0")); MI_TRY(check_f32(R1, "R1")); MI_TRY(check_f32(flowx, "flowx")); MI_TRY(check_f32(flowy, "flowy"));
+    MI_TRY(check_f32(M5out, "Mout"));
     const int w = flowx->cols, hh = flowx->rows;
     MI_REQUIRE(flowy->rows == hh && flowy->cols == w && M5->rows == 5 * hh && R0->rows == 5 * hh && R1->rows == 5 * hh && M5out->rows == 5 * hh &&
                M5->cols == w && R0->cols == w && R1->cols == w && M5out->cols == w, MI_ERR_BAD_SIZE, "size mismatch");
     MI_REQUIRE(M5->data != M5out->data, MI_ERR_BAD_ARG, "Mout must not alias M");
     const Plane g = plane_of(w, hh);
     Taps K;
-    TRY(make_win_taps(ksize, &K));
-    Stage S;
-    float *m, *r0, *r1, *fx = S.alloc((size_t)g.ld * hh), *fy = S.alloc((size_t)g.ld * hh), *mo = S.alloc((size_t)g.ld * hh * 5);
-    MI_REQUIRE(fx && fy && mo, MI_ERR_OOM, "stage allocation failed");
-    TRY(stage_in(S, M5, g.ld, &m, st)); TRY(stage_in(S, R0, g.ld, &r0, st)); TRY(stage_in(S, R1, g.ld, &r1, st));
+    MI_TRY(make_win_taps(ksize, &K));
+    DevTmp S;
+    float *m, *r0, *r1, *fx, *fy, *mo;
+    MI_TRY(S.alloc(&fx, (size_t)g.ld * hh)); MI_TRY(S.alloc(&fy, (size_t)g.ld * hh)); MI_TRY(S.alloc(&mo, (size_t)g.ld * hh * 5));
+    MI_TRY(stage_in(S, M5, g.ld, &m, st)); MI_TRY(stage_in(S, R0, g.ld, &r0, st)); MI_TRY(stage_in(S, R1, g.ld, &r1, st));
     MI_HIP_TRY(hipMemsetAsync(mo, 0, sizeof(float) * (size_t)g.ld * hh * 5, st));
-    TRY(iterate(m, r0, r1, fx, fy, mo, g, ksize, gaussian ? &K : nullptr, update != 0, st));
-    TRY(stage_out(fx, g.ld, flowx, st)); TRY(stage_out(fy, g.ld, flowy, st)); TRY(stage_out(mo, g.ld, M5out, st));
+    MI_TRY(iterate(m, r0, r1, fx, fy, mo, g, ksize, gaussian ? &K : nullptr, update != 0, st));
+    MI_TRY(stage_out(fx, g.ld, flowx, st)); MI_TRY(stage_out(fy, g.ld, flowy, st)); MI_TRY(stage_out(mo, g.ld, M5out, st));
     MI_HIP_TRY(hipStreamSynchronize(st));
     return MI_OK;
 }
@@ -658,7 +640,7 @@ int mi_farneback_iterate(const mi_mat *M5, const mi_mat *R0, const mi_mat *R1, m
 int mi_farneback_gaussian_blur(const mi_mat *src, mi_mat *dst, int ksize, double sigma, int border, void *stream)
 {
     hipStream_t st = (hipStream_t)stream;
-    TRY(check_f32(src, "src")); TRY(check_f32(dst, "dst"));
+    MI_TRY(check_f32(src, "src")); MI_TRY(check_f32(dst, "dst"));
     MI_REQUIRE(dst->rows == src->rows && dst->cols == src->cols, MI_ERR_BAD_SIZE, "size mismatch");
     MI_REQUIRE(ksize >= 1 && (ksize & 1) && ksize / 2 <= MI_FB_MAX_KSIZE_HALF, MI_ERR_BAD_ARG, "ksize must be odd and <= 201");
     const Plane g = plane_of(src->cols, src->rows);
@@ -667,12 +649,12 @@ int mi_farneback_gaussian_blur(const mi_mat *src, mi_mat *dst, int ksize, double
     Taps K;
     memset(&K, 0, sizeof(K));
     for (int i = 0; i <= ksize / 2; ++i) K.k[i] = k[ksize / 2 + i];
-    Stage S;
-    float *in, *out = S.alloc((size_t)g.ld * g.h);
-    MI_REQUIRE(out, MI_ERR_OOM, "stage allocation failed");
-    TRY(stage_in(S, src, g.ld, &in, st));
-    TRY(gaussian_blur(in, out, g, ksize / 2, K, border, st));
-    TRY(stage_out(out, g.ld, dst, st));
+    DevTmp S;
+    float *in, *out;
+    MI_TRY(S.alloc(&out, (size_t)g.ld * g.h));
+    MI_TRY(stage_in(S, src, g.ld, &in, st));
+    MI_TRY(gaussian_blur(in, out, g, ksize / 2, K, border, st));
+    MI_TRY(stage_out(out, g.ld, dst, st));
     MI_HIP_TRY(hipStreamSynchronize(st));
     return MI_OK;
 }
@@ -680,15 +662,15 @@ int mi_farneback_gaussian_blur(const mi_mat *src, mi_mat *dst, int ksize, double
 int mi_pyr_down(const mi_mat *src, mi_mat *dst, void *stream)
 {
     hipStream_t st = (hipStream_t)stream;
-    TRY(check_f32(src, "src")); TRY(check_f32(dst, "dst"));
+    MI_TRY(check_f32(src, "src")); MI_TRY(check_f32(dst, "dst"));
     MI_REQUIRE(dst->rows == (src->rows + 1) / 2 && dst->cols == (src->cols + 1) / 2, MI_ERR_BAD_SIZE, "dst must be ((rows+1)/2, (cols+1)/2)");
     const Plane gs = plane_of(src->cols, src->rows), gd = plane_of(dst->cols, dst->rows);
-    Stage S;
-    float *in, *out = S.alloc((size_t)gd.ld * gd.h);
-    MI_REQUIRE(out, MI_ERR_OOM, "stage allocation failed");
-    TRY(stage_in(S, src, gs.ld, &in, st));
-    TRY(pyr_down(in, gs, out, gd, st));
-    TRY(stage_out(out, gd.ld, dst, st));
+    DevTmp S;
+    float *in, *out;
+    MI_TRY(S.alloc(&out, (size_t)gd.ld * gd.h));
+    MI_TRY(stage_in(S, src, gs.ld, &in, st));
+    MI_TRY(pyr_down(in, gs, out, gd, st));
+    MI_TRY(stage_out(out, gd.ld, dst, st));
     MI_HIP_TRY(hipStreamSynchronize(st));
     return MI_OK;
 }

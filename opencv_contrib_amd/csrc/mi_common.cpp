@@ -268,6 +268,14 @@ void set_error(const char *fmt, ...)
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
 }
+
+int require_device()
+{
+    int n = 0;
+    MI_REQUIRE(hipGetDeviceCount(&n) == hipSuccess && n > 0, MI_ERR_NO_DEVICE,
+               "no HIP device available: the miflow product path has no CPU fallback");
+    return MI_OK;
+}
 }  // namespace mi
 
 extern "C" {

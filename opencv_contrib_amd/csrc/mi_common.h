@@ -6,10 +6,9 @@
 #include <cstdio>
 #include <cstring>
 #include "miflow/c_api.h"
+#include "mi_buf.h"
 
 namespace mi {
-
-void set_error(const char *fmt, ...);
 
 #define MI_HIP_TRY(expr)                                                                  \
     do {                                                                                  \
@@ -27,6 +26,9 @@ void set_error(const char *fmt, ...);
             return (code);                 \
         }                                  \
     } while (0)
+
+// returns a callee's error code (the callee has set the error text)
+#define MI_TRY(expr) do { if (const int _rc = (expr)) return _rc; } while (0)
 
 // Tuning switches (environment, read ONCE for the process under std::call_once; DESIGN.md lists them).  None is needed
 // in production: every default is the measured best.  The TV-L1 calc plan reads its switches through tv_knobs() (tvl1_plan.h).
@@ -85,24 +87,42 @@ const Tuning &tuning();
 #define MI_EXP_ENV(name) ((const char *)nullptr)
 #endif
 
-// SIMDs of the current device (4 per CU; 1024 on MI355X), queried once per device
+// The *_create entry points' first check: MI_ERR_NO_DEVICE and its error text unless a HIP device is there.
+int require_device();
+
+// Allocator policies of GrowBuf (mi_buf.h) and the two aliases the handles use for the scratch they own.
+struct DevAlloc {
+    static int alloc(void **p, size_t bytes) { MI_HIP_TRY(hipMalloc(p, bytes)); return MI_OK; }
+    static void free(void *p) { (void)hipFree(p); }   // synchronises the device: see GrowBuf
+};
+template <unsigned Flags>
+struct PinnedAlloc {
+    static int alloc(void **p, size_t bytes) { MI_HIP_TRY(hipHostMalloc(p, bytes, Flags)); return MI_OK; }
+    static void free(void *p) { (void)hipHostFree(p); }
+};
+template <class T> using DevBuf = GrowBuf<T, DevAlloc>;
+template <class T, unsigned Flags> using PinnedBuf = GrowBuf<T, PinnedAlloc<Flags>>;
+
 // Temporary device buffers of the stage-level / self-test entry points: freed on every return path.
 struct DevTmp {
     std::vector<void *> bufs;
     DevTmp() = default;
     DevTmp(const DevTmp &) = delete;
     DevTmp &operator=(const DevTmp &) = delete;
-    ~DevTmp() { for (void *p : bufs) (void)hipFree(p); }
+    ~DevTmp() { for (void *p : bufs) DevAlloc::free(p); }
+    // n elements of T; MI_ERR_OOM / MI_ERR_HIP with the error text set on failure (*out is null then)
     template <class T>
-    hipError_t alloc(T **out, size_t n)
+    int alloc(T **out, size_t n)
     {
         void *p = nullptr;
-        const hipError_t e = hipMalloc(&p, sizeof(T) * n);
-        if (e == hipSuccess) bufs.push_back(p);
+        *out = nullptr;
+        if (const int rc = DevAlloc::alloc(&p, sizeof(T) * n)) return rc;
+        bufs.push_back(p);
         *out = (T *)p;
-        return e;
+        return MI_OK;
     }
 };
+
 // Large device blocks (the per-lane TV-L1 arenas) come from a small process-wide cache: a block released by a handle is kept
 // (at most 4 blocks / MIFLOW_CACHE_GB = 24 GB PER DEVICE and MIFLOW_CACHE_TOTAL_GB = 4 x that per process; with an event behind
 // its previous owner's last work, which the next taker waits for: nothing of the previous owner is still in flight when the block is
@@ -113,6 +133,7 @@ struct DevTmp {
 int big_alloc(void **p, size_t bytes, size_t *capacity);
 void big_free(void *p, size_t capacity, hipEvent_t ready = nullptr, bool busy = true);
 void big_trim();
+// SIMDs of the current device (4 per CU; 1024 on MI355X), queried once per device
 int device_simds();
 
 static inline int div_up(int a, int b) { return (a + b - 1) / b; }

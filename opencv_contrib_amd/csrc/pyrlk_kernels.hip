@@ -12,8 +12,7 @@
 
 struct mi_densepyrlk {
     mi_densepyrlk_params P;
-    float *buf = nullptr;
-    size_t buf_floats = 0;
+    mi::DevBuf<float> buf;   // both pyramids and the two flow sets (carved in calc)
 };
 
 namespace mi {
@@ -147,11 +146,7 @@ int mi_densepyrlk_create(const mi_densepyrlk_params *p, mi_densepyrlk **out)
 {
     MI_REQUIRE(out, MI_ERR_BAD_ARG, "null out");
     *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n == 0) {
-        set_error("no HIP device available: the miflow product path has no CPU fallback");
-        return MI_ERR_NO_DEVICE;
-    }
+    MI_TRY(require_device());
     mi_densepyrlk *h = new mi_densepyrlk();
     if (p) h->P = *p; else mi_densepyrlk_default_params(&h->P);
     *out = h;
@@ -174,8 +169,6 @@ int mi_densepyrlk_get_params(const mi_densepyrlk *h, mi_densepyrlk_params *p)
 
 void mi_densepyrlk_destroy(mi_densepyrlk *h)
 {
-    if (!h) return;
-    if (h->buf) (void)hipFree(h->buf);
     delete h;
 }
 
@@ -200,12 +193,8 @@ int mi_densepyrlk_calc(mi_densepyrlk *h, const mi_mat *prev, const mi_mat *next,
     for (int l = 0; l < nl; ++l) total += 2 * (size_t)g[l].ld * g[l].h;
     const size_t uvn = (size_t)g[0].ld * g[0].h;
     total += 4 * uvn;
-    if (h->buf_floats < total) {
-        if (h->buf) { (void)hipFree(h->buf); h->buf = nullptr; h->buf_floats = 0; }
-        MI_HIP_TRY(hipMalloc(&h->buf, total * sizeof(float)));
-        h->buf_floats = total;
-    }
-    float *Pp[17], *Np[17], *cur = h->buf;
+    MI_TRY(h->buf.ensure(total));
+    float *Pp[17], *Np[17], *cur = h->buf.p;
     for (int l = 0; l < nl; ++l) { Pp[l] = cur; cur += (size_t)g[l].ld * g[l].h; Np[l] = cur; cur += (size_t)g[l].ld * g[l].h; }
     float *U[2] = {cur, cur + uvn}, *V[2] = {cur + 2 * uvn, cur + 3 * uvn};
     int rc;

@@ -14,8 +14,7 @@
 
 struct mi_stereosgm {
     mi_stereosgm_params P;
-    void *buf = nullptr;
-    size_t buf_bytes = 0;
+    mi::DevBuf<unsigned char> buf;   // census L/R, aggregated costs, the three int16 maps (carved in compute)
 };
 
 namespace mi {
@@ -361,16 +360,6 @@ static int census(const mi_mat *src, int *dst, size_t dstep, hipStream_t st)
     return MI_OK;
 }
 
-static int have_device()
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n == 0) {
-        set_error("no HIP device available: the miflow product path has no CPU fallback");
-        return MI_ERR_NO_DEVICE;
-    }
-    return MI_OK;
-}
-
 }  // namespace sgm
 }  // namespace mi
 
@@ -390,8 +379,7 @@ int mi_stereosgm_create(const mi_stereosgm_params *p, mi_stereosgm **out)
 {
     MI_REQUIRE(out, MI_ERR_BAD_ARG, "null out");
     *out = nullptr;
-    int rc = sgm::have_device();
-    if (rc) return rc;
+    MI_TRY(require_device());
     mi_stereosgm *h = new mi_stereosgm();
     if (p) h->P = *p; else mi_stereosgm_default_params(&h->P);
     *out = h;
@@ -414,8 +402,6 @@ int mi_stereosgm_get_params(const mi_stereosgm *h, mi_stereosgm_params *p)
 
 void mi_stereosgm_destroy(mi_stereosgm *h)
 {
-    if (!h) return;
-    if (h->buf) (void)hipFree(h->buf);
     delete h;
 }
 
@@ -438,12 +424,8 @@ int mi_stereosgm_compute(mi_stereosgm *h, const mi_mat *left, const mi_mat *righ
     const size_t off_cr = n * 4, off_agg = off_cr + n * 4, off_lt = off_agg + n * D * np;
     const size_t off_rt = off_lt + ((n * 2 + 255) / 256) * 256, off_rm = off_rt + ((n * 2 + 255) / 256) * 256;
     const size_t need = off_rm + ((n * 2 + 255) / 256) * 256;
-    if (h->buf_bytes < need) {
-        if (h->buf) { (void)hipFree(h->buf); h->buf = nullptr; h->buf_bytes = 0; }
-        MI_HIP_TRY(hipMalloc(&h->buf, need));
-        h->buf_bytes = need;
-    }
-    unsigned char *base = (unsigned char *)h->buf;
+    MI_TRY(h->buf.ensure(need));
+    unsigned char *base = h->buf.p;
     int *cl = (int *)base, *cr = (int *)(base + off_cr);
     unsigned char *agg = base + off_agg;
     short *lt = (short *)(base + off_lt), *rt = (short *)(base + off_rt), *rm = (short *)(base + off_rm);
@@ -479,8 +461,7 @@ int mi_sgm_census(const mi_mat *src, mi_mat *dst, void *stream)
     MI_REQUIRE(src && dst && src->data && dst->data, MI_ERR_BAD_ARG, "null argument");
     MI_REQUIRE(src->type == MI_8UC1 || src->type == MI_16UC1, MI_ERR_BAD_TYPE, "src.type() == CV_8UC1 || src.type() == CV_16UC1");
     MI_REQUIRE(dst->type == MI_32SC1 && dst->rows == src->rows && dst->cols == src->cols, MI_ERR_BAD_SIZE, "dst must be CV_32SC1 of src size");
-    int rc = sgm::have_device();
-    if (rc) return rc;
+    MI_TRY(require_device());
     return sgm::census(src, (int *)dst->data, dst->step, (hipStream_t)stream);
 }
 
@@ -496,8 +477,7 @@ int mi_sgm_aggregate_path(const mi_mat *left_census, const mi_mat *right_census,
     MI_REQUIRE((dx == 0 || dx == 1 || dx == -1) && (dy == 0 || dy == 1 || dy == -1) && (dx || dy), MI_ERR_BAD_ARG, "bad path direction");
     MI_REQUIRE(dst->type == MI_8UC1 && dst->rows == 1 && (long long)dst->cols == (long long)rows * cols * num_disparities, MI_ERR_BAD_SIZE,
                "dst must be CV_8UC1, 1 x (width * height * num_disparities)");
-    int rc = sgm::have_device();
-    if (rc) return rc;
+    MI_TRY(require_device());
     sgm::PathArgs A;
     A.left = (const int *)left_census->data; A.right = (const int *)right_census->data; A.dst = (unsigned char *)dst->data;
     A.rows = rows; A.cols = cols; A.min_disp = min_disparity; A.p1 = p1; A.p2 = p2;
@@ -519,8 +499,7 @@ int mi_sgm_winner_takes_all(const mi_mat *src, mi_mat *left, mi_mat *right, int 
     MI_REQUIRE(src->type == MI_8UC1 && src->rows == 1 &&
                    (long long)src->cols == (long long)left->rows * left->cols * num_disparities * num_paths, MI_ERR_BAD_SIZE,
                "src.rows == 1 && src.cols == width * height * MAX_DISPARITY * num_paths");                  // stereosgm.cu:1590
-    int rc = sgm::have_device();
-    if (rc) return rc;
+    MI_TRY(require_device());
     return sgm::launch_wta((const unsigned char *)src->data, (short *)left->data, left->step, (short *)right->data, right->step, left->cols,
                            left->rows, num_disparities, num_paths, uniqueness, subpixel, (hipStream_t)stream);
 }

@@ -8,8 +8,7 @@
 
 struct mi_sparsepyrlk {
     mi_sparsepyrlk_params P;
-    unsigned char *buf = nullptr;       // levels 1 .. max_level of both frames, dense rows
-    size_t buf_bytes = 0;
+    mi::DevBuf<unsigned char> buf;      // levels 1 .. max_level of both frames, dense rows (nothing at max_level 0)
 };
 
 namespace mi {
@@ -70,11 +69,7 @@ int mi_sparsepyrlk_create(const mi_sparsepyrlk_params *p, mi_sparsepyrlk **out)
     mi_sparsepyrlk_params d;
     if (!p) { mi_sparsepyrlk_default_params(&d); p = &d; }
     if (int rc = validate(p)) return rc;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n == 0) {
-        set_error("no HIP device available: the miflow product path has no CPU fallback");
-        return MI_ERR_NO_DEVICE;
-    }
+    MI_TRY(require_device());
     *out = new mi_sparsepyrlk();
     (*out)->P = *p;
     return MI_OK;
@@ -97,8 +92,6 @@ int mi_sparsepyrlk_get_params(const mi_sparsepyrlk *h, mi_sparsepyrlk_params *p)
 
 void mi_sparsepyrlk_destroy(mi_sparsepyrlk *h)
 {
-    if (!h) return;
-    if (h->buf) (void)hipFree(h->buf);
     delete h;
 }
 
@@ -129,16 +122,12 @@ int mi_sparsepyrlk_calc(mi_sparsepyrlk *h, const mi_mat *prev_img, const mi_mat 
         off[l] = per_frame;
         per_frame += ((size_t)pw[l] * ph[l] + 255) / 256 * 256;
     }
-    if (h->buf_bytes < 2 * per_frame) {
-        if (h->buf) { (void)hipFree(h->buf); h->buf = nullptr; h->buf_bytes = 0; }
-        if (per_frame) MI_HIP_TRY(hipMalloc((void **)&h->buf, 2 * per_frame));
-        h->buf_bytes = 2 * per_frame;
-    }
+    MI_TRY(h->buf.ensure(2 * per_frame));
     std::vector<slk::Image> I(P.max_level + 1), J(P.max_level + 1);
     I[0] = slk::Image{(const unsigned char *)prev_img->data, (long long)prev_img->step, ph[0], pw[0]};
     J[0] = slk::Image{(const unsigned char *)next_img->data, (long long)next_img->step, ph[0], pw[0]};
     for (int l = 1; l <= P.max_level; ++l) {
-        unsigned char *dp = h->buf + off[l], *dn = h->buf + per_frame + off[l];
+        unsigned char *dp = h->buf.p + off[l], *dn = h->buf.p + per_frame + off[l];
         const dim3 grid(div_up(pw[l], 64), div_up(ph[l], 4));
         hipLaunchKernelGGL(slk::k_pyr_down_u8, grid, dim3(256), 0, st, I[l - 1], dp, pw[l], ph[l]);
         hipLaunchKernelGGL(slk::k_pyr_down_u8, grid, dim3(256), 0, st, J[l - 1], dn, pw[l], ph[l]);

@@ -11,14 +11,13 @@ using namespace mi;
 struct mi_stereobm {
     mi_stereobm_params P;
     // scratch owned by the handle (stereobm.cpp:126: minSSD_, leBuf_, riBuf_)
-    unsigned *minssd = nullptr;
-    unsigned char *lebuf = nullptr, *ribuf = nullptr;
-    int *tex = nullptr;   // |Sobel| plane of the textureness filter (extended domain)
-    int cap_rows = 0, cap_cols = 0, cap_pairs = 0;
+    DevBuf<unsigned> minssd;
+    DevBuf<unsigned char> lebuf, ribuf;
+    DevBuf<int> tex;      // |Sobel| plane of the textureness filter (extended domain)
+    int cap_rows = 0, cap_cols = 0, cap_pairs = 0;   // the per-pair stride of the three above: grown together, never shrunk
     long long step = 0;   // bytes per row of lebuf/ribuf; minssd uses step elements
     // batch: per-pair pointer table (device) and the host copy the asynchronous upload reads
-    sbm::BmPair *tab_dev = nullptr;
-    int tab_cap = 0;
+    DevBuf<sbm::BmPair> tab_dev;
     std::vector<sbm::BmPair> tab_host;
 };
 
@@ -36,11 +35,7 @@ int mi_stereobm_create(const mi_stereobm_params *p, mi_stereobm **out)
 {
     MI_REQUIRE(out, MI_ERR_BAD_ARG, "null out");
     *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n == 0) {
-        set_error("no HIP device available: the miflow product path has no CPU fallback");
-        return MI_ERR_NO_DEVICE;
-    }
+    MI_TRY(require_device());
     mi_stereobm *h = new mi_stereobm();
     if (p) h->P = *p; else mi_stereobm_default_params(&h->P);
     *out = h;
@@ -63,12 +58,6 @@ int mi_stereobm_get_params(const mi_stereobm *h, mi_stereobm_params *p)
 
 void mi_stereobm_destroy(mi_stereobm *h)
 {
-    if (!h) return;
-    if (h->minssd) (void)hipFree(h->minssd);
-    if (h->lebuf) (void)hipFree(h->lebuf);
-    if (h->ribuf) (void)hipFree(h->ribuf);
-    if (h->tex) (void)hipFree(h->tex);
-    if (h->tab_dev) (void)hipFree(h->tab_dev);
     delete h;
 }
 
@@ -97,21 +86,26 @@ static int check_bm_params(int ndisp, int winsz, int rows, int cols)
 static int ensure_scratch(mi_stereobm *h, int rows, int cols, bool need_bufs, int pairs = 1)
 {
     if (h->cap_rows < rows || h->cap_cols < cols || h->cap_pairs < pairs) {
-        if (h->minssd) (void)hipFree(h->minssd);
-        if (h->lebuf) (void)hipFree(h->lebuf);
-        if (h->ribuf) (void)hipFree(h->ribuf);
-        if (h->tex) (void)hipFree(h->tex);
-        h->minssd = nullptr; h->lebuf = h->ribuf = nullptr; h->tex = nullptr;
+        // the stride changes: everything laid out by the old one goes before anything of the new one comes
+        h->minssd.release(); h->lebuf.release(); h->ribuf.release(); h->tex.release();
         h->cap_rows = std::max(h->cap_rows, rows); h->cap_cols = std::max(h->cap_cols, cols); h->cap_pairs = std::max(h->cap_pairs, pairs);
         h->step = align_up(h->cap_cols, 256);
     }
-    const size_t per_pair = (size_t)h->step * h->cap_rows;
-    if (!h->minssd) MI_HIP_TRY(hipMalloc((void **)&h->minssd, sizeof(unsigned) * per_pair * h->cap_pairs));
-    if (need_bufs && !h->lebuf) {
-        MI_HIP_TRY(hipMalloc((void **)&h->lebuf, per_pair * h->cap_pairs));
-        MI_HIP_TRY(hipMalloc((void **)&h->ribuf, per_pair * h->cap_pairs));
+    const size_t all_pairs = (size_t)h->step * h->cap_rows * h->cap_pairs;
+    MI_TRY(h->minssd.ensure(all_pairs));
+    if (need_bufs) {
+        MI_TRY(h->lebuf.ensure(all_pairs));
+        MI_TRY(h->ribuf.ensure(all_pairs));
     }
     return MI_OK;
+}
+
+// the two-pass textureness filter's plane, for the capacity the other scratch has
+static int ensure_tex(mi_stereobm *h)
+{
+    int sld, sh;
+    sbm::textureness_scratch_dims(h->cap_rows, h->cap_cols, &sld, &sh);
+    return h->tex.ensure((size_t)sld * sh);
 }
 
 int mi_stereobm_compute(mi_stereobm *h, const mi_mat *left, const mi_mat *right, mi_mat *disp, void *stream)
@@ -132,33 +126,29 @@ int mi_stereobm_compute(mi_stereobm *h, const mi_mat *left, const mi_mat *right,
     const unsigned char *le = (const unsigned char *)left->data, *ri = (const unsigned char *)right->data;
     long long ls = (long long)left->step, rs = (long long)right->step;
     if (P.prefilter_type == MI_PREFILTER_XSOBEL) {                      // stereobm.cpp:164-173
-        if ((rc = sbm::prefilter_xsobel(le, ls, h->lebuf, h->step, rows, cols, P.prefilter_cap, st))) return rc;
-        if ((rc = sbm::prefilter_xsobel(ri, rs, h->ribuf, h->step, rows, cols, P.prefilter_cap, st))) return rc;
-        le = h->lebuf; ri = h->ribuf; ls = rs = h->step;
+        if ((rc = sbm::prefilter_xsobel(le, ls, h->lebuf.p, h->step, rows, cols, P.prefilter_cap, st))) return rc;
+        if ((rc = sbm::prefilter_xsobel(ri, rs, h->ribuf.p, h->step, rows, cols, P.prefilter_cap, st))) return rc;
+        le = h->lebuf.p; ri = h->ribuf.p; ls = rs = h->step;
     } else if (P.prefilter_type == MI_PREFILTER_NORMALIZED_RESPONSE) {  // :175-185
-        if ((rc = sbm::prefilter_norm(le, ls, h->lebuf, h->step, rows, cols, P.prefilter_cap, P.prefilter_size, st))) return rc;
-        if ((rc = sbm::prefilter_norm(ri, rs, h->ribuf, h->step, rows, cols, P.prefilter_cap, P.prefilter_size, st))) return rc;
-        le = h->lebuf; ri = h->ribuf; ls = rs = h->step;
+        if ((rc = sbm::prefilter_norm(le, ls, h->lebuf.p, h->step, rows, cols, P.prefilter_cap, P.prefilter_size, st))) return rc;
+        if ((rc = sbm::prefilter_norm(ri, rs, h->ribuf.p, h->step, rows, cols, P.prefilter_cap, P.prefilter_size, st))) return rc;
+        le = h->lebuf.p; ri = h->ribuf.p; ls = rs = h->step;
     }
     // stereoBM_CUDA: memset disp = 0 (stereobm.cu:506); the 0xFF fill of minSSD (:507) is not needed -- the
     // kernel writes every element it later reads
     MI_HIP_TRY(hipMemset2DAsync(disp->data, disp->step, 0, (size_t)cols, (size_t)rows, st));
     // the winners' SSDs are the uniqueness pass's input only: without that test nothing reads them and the kernel does not store them
     // (8.3 of the 11.8 MB a 1080p pair's launch wrote, profiles/r10 StereoBM traffic)
-    if ((rc = sbm::block_match(le, ls, ri, rs, (unsigned char *)disp->data, (long long)disp->step, P.uniqueness_ratio > 0 ? h->minssd : nullptr, h->step, rows, cols,
+    if ((rc = sbm::block_match(le, ls, ri, rs, (unsigned char *)disp->data, (long long)disp->step, P.uniqueness_ratio > 0 ? h->minssd.p : nullptr, h->step, rows, cols,
                                P.num_disparities, P.block_size, P.uniqueness_ratio, P.emulate_cuda_edge, st)))
         return rc;
     if (P.texture_threshold > 0 && tuning().sbm_texfuse != 0) {         // stereobm.cpp:189-190, one launch (k_textureness_fused)
         rc = sbm::textureness_fused(le, ls, (unsigned char *)disp->data, (long long)disp->step, nullptr, 1, rows, cols, P.block_size,
                                     P.texture_threshold, st);
     } else if (P.texture_threshold > 0) {
-        if (!h->tex) {
-            int sld, sh;
-            sbm::textureness_scratch_dims(h->cap_rows, h->cap_cols, &sld, &sh);
-            MI_HIP_TRY(hipMalloc((void **)&h->tex, sizeof(int) * (size_t)sld * sh));
-        }
+        MI_TRY(ensure_tex(h));
         rc = sbm::textureness(le, ls, (unsigned char *)disp->data, (long long)disp->step, rows, cols, P.block_size,
-                              P.texture_threshold, h->tex, st);
+                              P.texture_threshold, h->tex.p, st);
     }
     return rc;
 }
@@ -187,19 +177,14 @@ int mi_stereobm_compute_batch(mi_stereobm *h, int n, const mi_mat *lefts, const 
     if ((rc = check_bm_params(P.num_disparities, P.block_size, rows, cols))) return rc;
     const bool pre = P.prefilter_type == MI_PREFILTER_XSOBEL || P.prefilter_type == MI_PREFILTER_NORMALIZED_RESPONSE;
     if ((rc = ensure_scratch(h, rows, cols, pre, n))) return rc;
-    if (h->tab_cap < n) {
-        if (h->tab_dev) (void)hipFree(h->tab_dev);
-        h->tab_dev = nullptr; h->tab_cap = 0;
-        MI_HIP_TRY(hipMalloc((void **)&h->tab_dev, sizeof(sbm::BmPair) * n));
-        h->tab_cap = n;
-    }
+    MI_TRY(h->tab_dev.ensure(n));
     const long long pp = h->step * h->cap_rows;   // bytes (lebuf / ribuf) = elements (minssd) per pair
     h->tab_host.resize(n);
     for (int i = 0; i < n; ++i) {
         const unsigned char *le = (const unsigned char *)lefts[i].data, *ri = (const unsigned char *)rights[i].data;
         long long ls = (long long)lefts[i].step, rs = (long long)rights[i].step;
         if (pre) {
-            unsigned char *lb = h->lebuf + i * pp, *rb = h->ribuf + i * pp;
+            unsigned char *lb = h->lebuf.p + i * pp, *rb = h->ribuf.p + i * pp;
             if (P.prefilter_type == MI_PREFILTER_XSOBEL) {
                 if ((rc = sbm::prefilter_xsobel(le, ls, lb, h->step, rows, cols, P.prefilter_cap, st))) return rc;
                 if ((rc = sbm::prefilter_xsobel(ri, rs, rb, h->step, rows, cols, P.prefilter_cap, st))) return rc;
@@ -211,22 +196,18 @@ int mi_stereobm_compute_batch(mi_stereobm *h, int n, const mi_mat *lefts, const 
         }
         h->tab_host[i] = {le, ri, (unsigned char *)disps[i].data, ls, rs, (long long)disps[i].step};
     }
-    MI_HIP_TRY(hipMemcpyAsync(h->tab_dev, h->tab_host.data(), sizeof(sbm::BmPair) * n, hipMemcpyHostToDevice, st));
-    if ((rc = sbm::zero_disp_batch(h->tab_dev, n, rows, cols, st))) return rc;   // stereobm.cu:506, all pairs in one launch
-    if ((rc = sbm::block_match_batch(h->tab_dev, n, P.uniqueness_ratio > 0 ? h->minssd : nullptr, h->step, pp, rows, cols, P.num_disparities, P.block_size, P.uniqueness_ratio,
+    MI_HIP_TRY(hipMemcpyAsync(h->tab_dev.p, h->tab_host.data(), sizeof(sbm::BmPair) * n, hipMemcpyHostToDevice, st));
+    if ((rc = sbm::zero_disp_batch(h->tab_dev.p, n, rows, cols, st))) return rc;   // stereobm.cu:506, all pairs in one launch
+    if ((rc = sbm::block_match_batch(h->tab_dev.p, n, P.uniqueness_ratio > 0 ? h->minssd.p : nullptr, h->step, pp, rows, cols, P.num_disparities, P.block_size, P.uniqueness_ratio,
                                      P.emulate_cuda_edge, st)))
         return rc;
     if (P.texture_threshold > 0 && tuning().sbm_texfuse != 0) {   // the post-filter of all pairs in one launch (the block matcher's table)
-        if ((rc = sbm::textureness_fused(nullptr, 0, nullptr, 0, h->tab_dev, n, rows, cols, P.block_size, P.texture_threshold, st))) return rc;
+        if ((rc = sbm::textureness_fused(nullptr, 0, nullptr, 0, h->tab_dev.p, n, rows, cols, P.block_size, P.texture_threshold, st))) return rc;
     } else if (P.texture_threshold > 0) {
-        if (!h->tex) {
-            int sld, sh;
-            sbm::textureness_scratch_dims(h->cap_rows, h->cap_cols, &sld, &sh);
-            MI_HIP_TRY(hipMalloc((void **)&h->tex, sizeof(int) * (size_t)sld * sh));
-        }
+        MI_TRY(ensure_tex(h));
         for (int i = 0; i < n; ++i)
             if ((rc = sbm::textureness(h->tab_host[i].left, h->tab_host[i].lstep, (unsigned char *)disps[i].data, (long long)disps[i].step, rows,
-                                       cols, P.block_size, P.texture_threshold, h->tex, st)))
+                                       cols, P.block_size, P.texture_threshold, h->tex.p, st)))
                 return rc;
     }
     return MI_OK;
@@ -283,7 +264,7 @@ int mi_stereobm_textureness(const mi_mat *img, mi_mat *disp, int winsz, float av
     sbm::textureness_scratch_dims(img->rows, img->cols, &sld, &sh);
     int *S = nullptr;
     DevTmp tmp;
-    MI_HIP_TRY(tmp.alloc(&S, (size_t)sld * sh));
+    MI_TRY(tmp.alloc(&S, (size_t)sld * sh));
     rc = sbm::textureness((const unsigned char *)img->data, (long long)img->step, (unsigned char *)disp->data,
                           (long long)disp->step, img->rows, img->cols, winsz, avg_texture_threshold, S, (hipStream_t)stream);
     if (rc) return rc;
@@ -296,7 +277,7 @@ int miflow_selftest_tmax16(const unsigned *in_host, unsigned *out_host)
     MI_REQUIRE(in_host && out_host, MI_ERR_BAD_ARG, "null argument");
     unsigned *d = nullptr;
     DevTmp tmp;
-    MI_HIP_TRY(tmp.alloc(&d, 1024 + 64));
+    MI_TRY(tmp.alloc(&d, 1024 + 64));
     MI_HIP_TRY(hipMemcpy(d, in_host, sizeof(unsigned) * 1024, hipMemcpyHostToDevice));
     int rc = sbm::dbg_tmax16(d, d + 1024, nullptr);
     if (!rc) { MI_HIP_TRY(hipDeviceSynchronize()); MI_HIP_TRY(hipMemcpy(out_host, d + 1024, sizeof(unsigned) * 64, hipMemcpyDeviceToHost)); }
@@ -308,7 +289,7 @@ int miflow_selftest_wave_min(const unsigned *in_host, unsigned *out_host)
     MI_REQUIRE(in_host && out_host, MI_ERR_BAD_ARG, "null argument");
     unsigned *d = nullptr;
     DevTmp tmp;
-    MI_HIP_TRY(tmp.alloc(&d, 192));
+    MI_TRY(tmp.alloc(&d, 192));
     MI_HIP_TRY(hipMemcpy(d, in_host, sizeof(unsigned) * 64, hipMemcpyHostToDevice));
     int rc = sbm::dbg_wave_min(d, d + 64, nullptr);
     if (!rc) { MI_HIP_TRY(hipDeviceSynchronize()); MI_HIP_TRY(hipMemcpy(out_host, d + 64, sizeof(unsigned) * 65, hipMemcpyDeviceToHost)); }

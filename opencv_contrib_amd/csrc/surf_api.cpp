@@ -13,12 +13,26 @@ using namespace mi;
 struct mi_surf {
     mi_surf_params P;
     // tables (surf.cpp:544-565 generators; see oracle/surf_ref.c for the correspondence with surf.cu:520-522,685-707)
-    float *apt = nullptr, *dw = nullptr;
+    DevBuf<float> apt, dw;
+    DevBuf<unsigned> counters;                // 64 (DetectBufs::counters): the handle's for life, like the tables
     // what a detect call runs and on which buffers (surf_plan.h): the plan of the last frame's shape, made with the switches as they
     // were when the scratch was allocated (this handle's decision: no process-global state); shape.rows == 0: no scratch
     surf::SurfPlan plan = {};
     surf::SurfKnobs knobs = {};
-    surf::DetectBufs B = {};
+    // the scratch of the plan, one allocation per region; msum comes with the first masked call
+    struct Scratch {
+        DevBuf<unsigned> sum, msum, V, BT, poly, rowcnt, segcnt;
+        DevBuf<float> det, trace;
+        DevBuf<unsigned long long> bits, sbits;
+        DevBuf<int4> cand;
+        DevBuf<unsigned char> itmp, geo;
+        void release()
+        {
+            sum.release(); msum.release(); V.release(); BT.release(); poly.release(); rowcnt.release(); segcnt.release();
+            det.release(); trace.release(); bits.release(); sbits.release(); cand.release(); itmp.release(); geo.release();
+        }
+    } S;
+    surf::DetectBufs B = {};                  // what the kernels are handed: the owners' pointers as of the last ensure()
     int capCand = 0;                          // candidates the lists were allocated for (>= plan.shape.max_candidates)
     std::vector<surf::HaarGeo> geo_host;      // source of the asynchronous upload: outlives the call
     bool geo_dirty = false;
@@ -53,11 +67,7 @@ int mi_surf_create(const mi_surf_params *p, mi_surf **out)
 {
     MI_REQUIRE(out, MI_ERR_BAD_ARG, "null out");
     *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n == 0) {
-        set_error("no HIP device available: the miflow product path has no CPU fallback");
-        return MI_ERR_NO_DEVICE;
-    }
+    MI_TRY(require_device());
     mi_surf *h = new mi_surf();
     if (p) h->P = *p; else mi_surf_default_params(&h->P);
     // orientation samples: disc of radius 6 (c_aptX / c_aptY, surf.cu:520-521), weights c_aptW (:522) = outer product of the 13-tap
@@ -71,11 +81,12 @@ int mi_surf_create(const mi_surf_params *p, mi_surf **out)
     gauss_tab(20, 3.3f, G);
     for (int i = 0; i < 20; i++) for (int j = 0; j < 20; j++) dw[i * 20 + j] = G[i] * G[j];
     auto upload = [&]() -> int {
-        MI_HIP_TRY(hipMalloc((void **)&h->apt, sizeof(apt)));
-        MI_HIP_TRY(hipMalloc((void **)&h->dw, sizeof(dw)));
-        MI_HIP_TRY(hipMemcpy(h->apt, apt, sizeof(apt), hipMemcpyHostToDevice));
-        MI_HIP_TRY(hipMemcpy(h->dw, dw, sizeof(dw), hipMemcpyHostToDevice));
-        MI_HIP_TRY(hipMalloc((void **)&h->B.counters, sizeof(unsigned) * 64));
+        MI_TRY(h->apt.ensure(3 * 113));
+        MI_TRY(h->dw.ensure(400));
+        MI_HIP_TRY(hipMemcpy(h->apt.p, apt, sizeof(apt), hipMemcpyHostToDevice));
+        MI_HIP_TRY(hipMemcpy(h->dw.p, dw, sizeof(dw), hipMemcpyHostToDevice));
+        MI_TRY(h->counters.ensure(64));
+        h->B.counters = h->counters.p;
         return MI_OK;
     };
     if (const int rc = upload()) { mi_surf_destroy(h); return rc; }
@@ -88,13 +99,9 @@ int mi_surf_get_params(const mi_surf *h, mi_surf_params *p) { MI_REQUIRE(h && p,
 
 static void free_scratch(mi_surf *h)
 {
-    void *ps[sizeof(surf::DetectBufs) / sizeof(void *)];
-    static_assert(sizeof(ps) == sizeof(surf::DetectBufs), "DetectBufs holds pointers only");
-    unsigned *const counters = h->B.counters;   // not scratch: the handle's for life
-    memcpy(ps, &h->B, sizeof(ps));
-    for (void *p : ps) if (p && p != counters) (void)hipFree(p);
+    h->S.release();
     h->B = surf::DetectBufs();
-    h->B.counters = counters;
+    h->B.counters = h->counters.p;
     h->plan = surf::SurfPlan();
     h->capCand = 0;
 }
@@ -103,11 +110,6 @@ void mi_surf_release_memory(mi_surf *h) { if (h) free_scratch(h); }   // SURF_CU
 
 void mi_surf_destroy(mi_surf *h)
 {
-    if (!h) return;
-    free_scratch(h);
-    if (h->apt) (void)hipFree(h->apt);
-    if (h->dw) (void)hipFree(h->dw);
-    if (h->B.counters) (void)hipFree(h->B.counters);
     delete h;
 }
 
@@ -171,30 +173,33 @@ static int ensure(mi_surf *h, int rows, int cols, int maxCand, bool need_mask, h
             free_scratch(h);
             h->knobs = read_knobs();
             const surf::SurfPlan p = surf::surf_make_plan(Z, h->knobs);
-            surf::DetectBufs &B = h->B;
-            MI_HIP_TRY(hipMalloc((void **)&B.sum, sizeof(unsigned) * p.sum_words));
-            MI_HIP_TRY(hipMalloc((void **)&B.V, sizeof(unsigned) * p.v_words));
-            MI_HIP_TRY(hipMalloc((void **)&B.BT, sizeof(unsigned) * p.bt_words));
-            MI_HIP_TRY(hipMalloc((void **)&B.det, sizeof(float) * p.plane_floats));
-            MI_HIP_TRY(hipMalloc((void **)&B.trace, sizeof(float) * p.plane_floats));
-            MI_HIP_TRY(hipMalloc((void **)&B.bits, sizeof(unsigned long long) * p.bits_words));
-            if (p.sbits_words) MI_HIP_TRY(hipMalloc((void **)&B.sbits, sizeof(unsigned long long) * p.sbits_words));
-            MI_HIP_TRY(hipMalloc((void **)&B.rowcnt, sizeof(unsigned) * p.row_counts));
-            MI_HIP_TRY(hipMalloc((void **)&B.segcnt, sizeof(unsigned) * p.seg_counts));
-            MI_HIP_TRY(hipMalloc((void **)&B.cand, sizeof(int4) * p.cand_items));
-            MI_HIP_TRY(hipMalloc(&B.itmp, surf::interp_tmp_bytes(p.cand_items)));
+            mi_surf::Scratch &S = h->S;   // empty here, so each region gets exactly the plan's size (a count of 0: none)
+            MI_TRY(S.sum.ensure(p.sum_words));
+            MI_TRY(S.V.ensure(p.v_words));
+            MI_TRY(S.BT.ensure(p.bt_words));
+            MI_TRY(S.det.ensure(p.plane_floats));
+            MI_TRY(S.trace.ensure(p.plane_floats));
+            MI_TRY(S.bits.ensure(p.bits_words));
+            MI_TRY(S.sbits.ensure(p.sbits_words));
+            MI_TRY(S.rowcnt.ensure(p.row_counts));
+            MI_TRY(S.segcnt.ensure(p.seg_counts));
+            MI_TRY(S.cand.ensure(p.cand_items));
+            MI_TRY(S.itmp.ensure(surf::interp_tmp_bytes(p.cand_items)));
             if (p.fused) {
                 h->geo_host.resize(p.geo_bytes / sizeof(surf::HaarGeo));
                 surf::surf_fill_geometry(p, h->geo_host.data());
-                if (p.poly_words) MI_HIP_TRY(hipMalloc((void **)&B.poly, sizeof(unsigned) * p.poly_words));
-                MI_HIP_TRY(hipMalloc(&B.geo, p.geo_bytes));
+                MI_TRY(S.poly.ensure(p.poly_words));
+                MI_TRY(S.geo.ensure(p.geo_bytes));
                 h->geo_dirty = true;
             }
             h->plan = p;   // (an allocation that failed leaves the handle without a plan)
             h->capCand = maxCand;
         }
     }
-    if (need_mask && !h->B.msum) MI_HIP_TRY(hipMalloc((void **)&h->B.msum, sizeof(unsigned) * h->plan.sum_words));
+    if (need_mask) MI_TRY(h->S.msum.ensure(h->plan.sum_words));
+    const mi_surf::Scratch &S = h->S;
+    h->B = {S.sum.p, S.msum.p, S.V.p, S.BT.p, S.poly.p, S.det.p, S.trace.p, S.bits.p, S.sbits.p, S.rowcnt.p, S.segcnt.p, S.cand.p, S.itmp.p,
+            S.geo.p, h->counters.p};
     if (h->geo_dirty) {   // on the call's stream, not a blocking null-stream copy
         MI_HIP_TRY(hipMemcpyAsync(h->B.geo, h->geo_host.data(), h->plan.geo_bytes, hipMemcpyHostToDevice, st));
         h->geo_dirty = false;
@@ -254,7 +259,7 @@ static int detect_enqueue(mi_surf *h, const mi_mat *img, const mi_mat *mask, mi_
                                     (float)P.hessian_threshold, B.bits, B.rowcnt, B.segcnt, B.cand, maxC, ncand, st))) return rc;
         if ((rc = surf::interpolate(B.det, Q.dld, rows, cols, octave, B.cand, ncand, maxC, B.itmp, kp, kld, maxF, B.counters, st))) return rc;
     }
-    if ((rc = surf::orientation(B.sum, Q.sld, rows, cols, kp, kld, B.counters, maxF, P.upright != 0, h->apt, st))) return rc;   // :211-214
+    if ((rc = surf::orientation(B.sum, Q.sld, rows, cols, kp, kld, B.counters, maxF, P.upright != 0, h->apt.p, st))) return rc;   // :211-214
     *max_features = maxF;
     return MI_OK;
 }
@@ -298,7 +303,7 @@ int mi_surf_detect_and_compute(mi_surf *h, const mi_mat *img, const mi_mat *mask
     if ((rc = detect_enqueue(h, img, mask, keypoints, &maxF, st))) return rc;
     if ((rc = surf::descriptors((const unsigned char *)img->data, (long long)img->step, img->rows, img->cols, (const float *)keypoints->data,
                                 (int)(keypoints->step / 4), maxF, h->P.extended != 0, (float *)descriptors->data,
-                                (long long)(descriptors->step / 4), h->dw, st, h->B.counters))) return rc;
+                                (long long)(descriptors->step / 4), h->dw.p, st, h->B.counters))) return rc;
     return read_count(h, maxF, n_features, st);
 }
 
@@ -327,7 +332,7 @@ int mi_surf_compute_orientation(mi_surf *h, const mi_mat *img, mi_mat *keypoints
     if ((rc = ensure(h, rows, cols, maxC, false, st))) return rc;
     if ((rc = surf::integral((const unsigned char *)img->data, (long long)img->step, rows, cols, false, h->B.V, h->B.BT, h->plan.vld, h->B.sum, h->plan.sld, st))) return rc;
     return surf::orientation(h->B.sum, h->plan.sld, rows, cols, (float *)keypoints->data, (int)(keypoints->step / 4), nullptr, n_features,
-                             h->P.upright != 0, h->apt, st);
+                             h->P.upright != 0, h->apt.p, st);
 }
 
 int mi_surf_compute_descriptors(mi_surf *h, const mi_mat *img, const mi_mat *keypoints, int n_features, mi_mat *descriptors, void *stream)
@@ -341,7 +346,7 @@ int mi_surf_compute_descriptors(mi_surf *h, const mi_mat *img, const mi_mat *key
                descriptors->step % 4 == 0, MI_ERR_BAD_ARG, "descriptors must be CV_32FC1, nFeatures x descriptorSize()");   // :232
     return surf::descriptors((const unsigned char *)img->data, (long long)img->step, img->rows, img->cols, (const float *)keypoints->data,
                              (int)(keypoints->step / 4), n_features, h->P.extended != 0, (float *)descriptors->data,
-                             (long long)(descriptors->step / 4), h->dw, (hipStream_t)stream);
+                             (long long)(descriptors->step / 4), h->dw.p, (hipStream_t)stream);
 }
 
 // ---- stage-level entry points (parity tests)
@@ -356,8 +361,8 @@ int mi_surf_integral(mi_surf *h, const mi_mat *img, int clamp_to_one, mi_mat *su
     const int vld = align_up(img->cols, 64);
     unsigned *V = nullptr, *BT = nullptr;
     DevTmp tmp;
-    MI_HIP_TRY(tmp.alloc(&V, (size_t)vld * img->rows));
-    MI_HIP_TRY(tmp.alloc(&BT, (size_t)vld * surf::integral_bands(img->rows)));
+    MI_TRY(tmp.alloc(&V, (size_t)vld * img->rows));
+    MI_TRY(tmp.alloc(&BT, (size_t)vld * surf::integral_bands(img->rows)));
     rc = surf::integral((const unsigned char *)img->data, (long long)img->step, img->rows, img->cols, clamp_to_one != 0, V, BT, vld,
                         (unsigned *)sum->data, (int)(sum->step / 4), st);
     if (rc) return rc;
@@ -383,7 +388,7 @@ int miflow_selftest_wave_scan(const unsigned *in_host, unsigned *out_host)
     MI_REQUIRE(in_host && out_host, MI_ERR_BAD_ARG, "null argument");
     unsigned *d = nullptr;
     DevTmp tmp;
-    MI_HIP_TRY(tmp.alloc(&d, 128));
+    MI_TRY(tmp.alloc(&d, 128));
     MI_HIP_TRY(hipMemcpy(d, in_host, sizeof(unsigned) * 64, hipMemcpyHostToDevice));
     int rc = surf::dbg_scan(d, d + 64, nullptr);
     if (!rc) { MI_HIP_TRY(hipDeviceSynchronize()); MI_HIP_TRY(hipMemcpy(out_host, d + 64, sizeof(unsigned) * 64, hipMemcpyDeviceToHost)); }

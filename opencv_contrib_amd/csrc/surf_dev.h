@@ -6,8 +6,8 @@
 namespace mi {
 namespace surf {
 
-// The device buffers of a handle, sized by its SurfPlan (surf_plan.h names the element counts).  Pointers only: the handle frees them by
-// walking the struct.  counters is the handle's for life; everything else is scratch of the plan.
+// The device buffers of a handle, sized by its SurfPlan (surf_plan.h names the element counts).  A view for the kernels: the handle
+// owns each region (surf_api.cpp) and fills this from the owners.  counters is the handle's for life; everything else is scratch of the plan.
 struct DetectBufs {
     unsigned *sum, *msum;              // integral image of the frame / of the mask (a detect call without a mask is handed msum = nullptr)
     unsigned *V, *BT;                  // scratch of the integral image

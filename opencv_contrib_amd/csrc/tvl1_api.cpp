@@ -27,31 +27,6 @@ struct LevelBuf {
 
 struct SlotInfo { int scale, warp; };
 
-// A lane's device (Host = false) or pinned host buffer of n elements: grown on demand, never shrunk, freed with the handle.
-template <class T, bool Host = false, unsigned HostFlags = 0>
-struct GrowBuf {
-    T *p = nullptr;
-    size_t n = 0;
-    GrowBuf() = default;
-    GrowBuf(const GrowBuf &) = delete;
-    ~GrowBuf() { release(); }
-    int ensure(size_t want)
-    {
-        if (n >= want) return MI_OK;
-        release();
-        void *q = nullptr;
-        if (Host) MI_HIP_TRY(hipHostMalloc(&q, sizeof(T) * want, HostFlags));
-        else MI_HIP_TRY(hipMalloc(&q, sizeof(T) * want));
-        p = (T *)q; n = want;
-        return MI_OK;
-    }
-    void release()
-    {
-        if (p) (void)(Host ? hipHostFree(p) : hipFree(p));
-        p = nullptr; n = 0;
-    }
-};
-
 }  // namespace
 
 // Everything one sub-batch needs: its own arena, pointer table, control slots and profiling events, so that two lanes can
@@ -68,24 +43,24 @@ struct Lane {
     // full-resolution-capacity scratch planes (re-laid-out densely per level)
     float *scr[6] = {};    // scr[0..1]: median-filter temporaries; I1wx, I1wy, grad, rho_c
     float *pbuf[2][6] = {};   // [set][p11,p12,p21,p22,p31,p32]
-    GrowBuf<PtrTab> tab;
+    DevBuf<PtrTab> tab;
     std::vector<PtrTab> tab_host;   // source of the asynchronous upload: must outlive the call
     // device loop control
-    GrowBuf<int2> S;
-    GrowBuf<unsigned long long> E;
-    GrowBuf<double> Pd;   // per slot prevError (cv::cuda check schedule)
-    GrowBuf<int4> X;      // per slot state of the speculative steps (SpecK::X)
+    DevBuf<int2> S;
+    DevBuf<unsigned long long> E;
+    DevBuf<double> Pd;   // per slot prevError (cv::cuda check schedule)
+    DevBuf<int4> X;      // per slot state of the speculative steps (SpecK::X)
     long long Q = 0;
     int ctlB = 0;
     // iteration counts per (scale, warp, pair slot) of the previous calc, two parities (SpecK::h_in / h_out)
-    GrowBuf<int> H;
+    DevBuf<int> H;
     unsigned long long H_sig = 0; // geometry / batch / loop shape the counts belong to (0: none)
     int H_par = 0;                // parity the NEXT calc writes
     std::vector<SlotInfo> slots;
     // host feedback (mi_tvl1_params.host_feedback): pinned landing area of the control slots read back between launches
-    GrowBuf<int2, true, hipHostMallocDefault> fb_host;
+    PinnedBuf<int2, hipHostMallocDefault> fb_host;
     hipEvent_t fb_ev = nullptr;
-    GrowBuf<int, true, hipHostMallocCoherent | hipHostMallocMapped> fb_flag;   // polled form (SpecK::fb_flag): {decision word, count} per pair
+    PinnedBuf<int, hipHostMallocCoherent | hipHostMallocMapped> fb_flag;   // polled form (SpecK::fb_flag): {decision word, count} per pair
     int fb_seq = 0;
     std::vector<int> fb_hist;        // polled form: most iterations a (scale, warp) of the previous calc needed over its pairs (0: unknown)
     unsigned long long fb_hist_sig = 0;
@@ -104,7 +79,7 @@ struct Lane {
 struct mi_tvl1 {
     mi_tvl1_params P;
     int device = 0;
-    float *cubic_tab = nullptr;
+    DevBuf<float> cubic_tab;
     static const int kMaxLanes = 4;
     Lane lane[kMaxLanes];
     hipEvent_t fork = nullptr;
@@ -165,19 +140,15 @@ int mi_tvl1_create(const mi_tvl1_params *p, mi_tvl1 **out)
     if (!p) { mi_tvl1_default_params(&d); p = &d; }
     int rc = validate_params(p);
     if (rc) return rc;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n == 0) {
-        set_error("no HIP device available: the miflow product path has no CPU fallback");
-        return MI_ERR_NO_DEVICE;
-    }
+    MI_TRY(require_device());
     mi_tvl1 *h = new mi_tvl1();
     h->P = *p;
     float tab[128];
     host_cubic_table(tab);
     auto upload = [&]() -> int {
         MI_HIP_TRY(hipGetDevice(&h->device));
-        MI_HIP_TRY(hipMalloc((void **)&h->cubic_tab, sizeof(tab)));
-        MI_HIP_TRY(hipMemcpy(h->cubic_tab, tab, sizeof(tab), hipMemcpyHostToDevice));
+        MI_TRY(h->cubic_tab.ensure(128));
+        MI_HIP_TRY(hipMemcpy(h->cubic_tab.p, tab, sizeof(tab), hipMemcpyHostToDevice));
         return MI_OK;
     };
     if (const int rc = upload()) { mi_tvl1_destroy(h); return rc; }
@@ -276,7 +247,6 @@ void mi_tvl1_destroy(mi_tvl1 *h)
         if (ln.stream) (void)hipStreamDestroy(ln.stream);
     }
     if (h->fork) (void)hipEventDestroy(h->fork);
-    if (h->cubic_tab) (void)hipFree(h->cubic_tab);
     delete h;
 }
 
@@ -474,7 +444,7 @@ int launch_warp(Run &r, const LevelBuf &Lv, bool ahead)
     c.need_done = ahead ? 1 : 0;
     const bool dev_cur = ahead || (r.pl.check && !r.first_of_scale);   // at the first warp of a scale u lives in set 0 (host-known)
     return warp_fused(r.h->P.semantics, r.pl.fast_warp, -1, Lv.I0, Lv.I1, u1v, u2v, nullptr, r.ln.scr[2], r.ln.scr[3],
-                      r.grad, r.ln.scr[5], r.h->cubic_tab, Lv.g, dev_cur ? &c : nullptr, r.cur, r.st);
+                      r.grad, r.ln.scr[5], r.h->cubic_tab.p, Lv.g, dev_cur ? &c : nullptr, r.cur, r.st);
 }
 
 // Fixed work: T iterations per HBM pass (tvl1_tbr_kernels.hip), the optional median filter between outer iterations; in exact math
@@ -490,7 +460,7 @@ int run_blocked(Run &r, LevelBuf &Lv, const TvWarp &w, long long *nlaunch)
             ++*nlaunch;
             if (w.skip_iterations) { r.first_of_scale = false; continue; }
             const bool last_pass = w.skip_p_last && no == w.outer - 1 && k == nb - 1;
-            rc = w.fused ? iterate_tb_fused(w.run[k], Lv.I0, Lv.I1, r.h->cubic_tab, r.planes, Lv.g, r.l_t, r.theta, r.taut, r.first_of_scale, r.cur,
+            rc = w.fused ? iterate_tb_fused(w.run[k], Lv.I0, Lv.I1, r.h->cubic_tab.p, r.planes, Lv.g, r.l_t, r.theta, r.taut, r.first_of_scale, r.cur,
                                             r.st, last_pass)
                          : iterate_tb(w.run[k], w.blocks[k], r.planes, Lv.g, r.l_t, r.theta, r.taut, r.first_of_scale, r.cur, r.st, last_pass,
                                       last_pass && w.pack_in_pass ? r.ln.tab.p : nullptr);

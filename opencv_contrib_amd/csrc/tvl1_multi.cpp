@@ -205,11 +205,9 @@ int mi_tvl1_multi_create(const mi_tvl1_params *p, int n_devices, const int *devi
 {
     MI_REQUIRE(out, MI_ERR_BAD_ARG, "null out");
     *out = nullptr;
+    MI_TRY(require_device());
     int avail = 0;
-    if (hipGetDeviceCount(&avail) != hipSuccess || avail == 0) {
-        set_error("no HIP device available: the miflow product path has no CPU fallback");
-        return MI_ERR_NO_DEVICE;
-    }
+    MI_HIP_TRY(hipGetDeviceCount(&avail));
     if (n_devices <= 0) n_devices = avail;
     MI_REQUIRE(n_devices <= 64, MI_ERR_BAD_ARG, "too many devices");
     mi_tvl1_params d;
@@ -278,8 +276,8 @@ int miflow_selftest_rccl_self_copy(const unsigned char *in_host, unsigned char *
     hipStream_t st = nullptr;
     int rc = MI_OK;
     auto body = [&]() -> int {
-        MI_HIP_TRY(tmp.alloc(&a, bytes));
-        MI_HIP_TRY(tmp.alloc(&b, bytes));
+        MI_TRY(tmp.alloc(&a, bytes));
+        MI_TRY(tmp.alloc(&b, bytes));
         MI_HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
         MI_HIP_TRY(hipMemcpy(a, in_host, bytes, hipMemcpyHostToDevice));
         MI_HIP_TRY(hipMemset(b, 0, bytes));

@@ -13,18 +13,8 @@ using namespace mi::tvl1;
 
 namespace {
 
-struct Stage {
-    std::vector<float *> bufs;
-    ~Stage() { for (float *p : bufs) (void)hipFree(p); }
-    float *alloc(const Geo &g) { return (float *)alloc_bytes(sizeof(float) * (size_t)g.ps * g.batch); }
-    void *alloc_bytes(size_t n)
-    {
-        void *p = nullptr;
-        if (hipMalloc(&p, n) != hipSuccess) return nullptr;
-        bufs.push_back((float *)p);
-        return p;
-    }
-};
+// a dense scratch plane of g (all its pairs)
+int plane(DevTmp &S, const Geo &g, float **out) { return S.alloc(out, (size_t)g.ps * g.batch); }
 
 Geo geo_of(int w, int h)
 {
@@ -44,10 +34,10 @@ int check_f32(const mi_mat *m, const char *name)
 
 // (the g.batch pairs of a plane are its g.batch * g.h rows: pair b's row y is row b * h + y of the caller's plane and of the scratch
 // plane, whose pair stride g.ps is g.h rows of g.ld floats)
-int stage_in(Stage &S, const mi_mat *m, const Geo &g, float **out, hipStream_t st)
+int stage_in(DevTmp &S, const mi_mat *m, const Geo &g, float **out, hipStream_t st)
 {
-    float *p = S.alloc(g);
-    MI_REQUIRE(p, MI_ERR_OOM, "stage allocation failed");
+    float *p;
+    MI_TRY(plane(S, g, &p));
     MI_HIP_TRY(hipMemcpy2DAsync(p, (size_t)g.ld * 4, m->data, m->step, (size_t)g.w * 4, (size_t)g.h * g.batch, hipMemcpyDeviceToDevice, st));
     *out = p;
     return MI_OK;
@@ -59,8 +49,6 @@ int stage_out(const float *p, const Geo &g, mi_mat *m, hipStream_t st)
     return MI_OK;
 }
 
-#define TRY(x) do { int _rc = (x); if (_rc) return _rc; } while (0)
-
 }  // namespace
 
 extern "C" {
@@ -68,16 +56,16 @@ extern "C" {
 int mi_tvl1_centered_gradient(const mi_mat *src, mi_mat *dx, mi_mat *dy, void *stream)
 {
     hipStream_t st = (hipStream_t)stream;
-    TRY(check_f32(src, "src")); TRY(check_f32(dx, "dx")); TRY(check_f32(dy, "dy"));
+    MI_TRY(check_f32(src, "src")); MI_TRY(check_f32(dx, "dx")); MI_TRY(check_f32(dy, "dy"));
     MI_REQUIRE(dx->rows == src->rows && dx->cols == src->cols && dy->rows == src->rows && dy->cols == src->cols,
                MI_ERR_BAD_SIZE, "dx/dy size != src size");
     const Geo g = geo_of(src->cols, src->rows);
-    Stage S;
-    float *s, *ox = S.alloc(g), *oy = S.alloc(g);
-    MI_REQUIRE(ox && oy, MI_ERR_OOM, "stage allocation failed");
-    TRY(stage_in(S, src, g, &s, st));
-    TRY(gradient(s, ox, oy, g, st));
-    TRY(stage_out(ox, g, dx, st)); TRY(stage_out(oy, g, dy, st));
+    DevTmp S;
+    float *s, *ox, *oy;
+    MI_TRY(plane(S, g, &ox)); MI_TRY(plane(S, g, &oy));
+    MI_TRY(stage_in(S, src, g, &s, st));
+    MI_TRY(gradient(s, ox, oy, g, st));
+    MI_TRY(stage_out(ox, g, dx, st)); MI_TRY(stage_out(oy, g, dy, st));
     MI_HIP_TRY(hipStreamSynchronize(st));
     return MI_OK;
 }
@@ -99,29 +87,27 @@ int mi_tvl1_warp_backward(int semantics, const mi_mat *I0, const mi_mat *I1, con
     MI_REQUIRE(I0 && I1, MI_ERR_BAD_ARG, "null matrix");
     const mi_mat *ins[6] = {I0, I1, fused ? I1 : I1x, fused ? I1 : I1y, u1, u2};
     mi_mat *outs[5] = {I1w, I1wx, I1wy, grad, rho};
-    for (int i = 0; i < 6; ++i) { TRY(check_f32(ins[i], "input")); MI_REQUIRE(ins[i]->rows == I0->rows && ins[i]->cols == I0->cols, MI_ERR_BAD_SIZE, "input size mismatch"); }
-    for (int i = 0; i < 5; ++i) { TRY(check_f32(outs[i], "output")); MI_REQUIRE(outs[i]->rows == I0->rows && outs[i]->cols == I0->cols, MI_ERR_BAD_SIZE, "output size mismatch"); }
+    for (int i = 0; i < 6; ++i) { MI_TRY(check_f32(ins[i], "input")); MI_REQUIRE(ins[i]->rows == I0->rows && ins[i]->cols == I0->cols, MI_ERR_BAD_SIZE, "input size mismatch"); }
+    for (int i = 0; i < 5; ++i) { MI_TRY(check_f32(outs[i], "output")); MI_REQUIRE(outs[i]->rows == I0->rows && outs[i]->cols == I0->cols, MI_ERR_BAD_SIZE, "output size mismatch"); }
     const Geo g = geo_of(I0->cols, I0->rows);
-    Stage S;
+    DevTmp S;
     float *in[6], *out[5];
-    for (int i = 0; i < 6; ++i) TRY(stage_in(S, ins[i], g, &in[i], st));
-    for (int i = 0; i < 5; ++i) { out[i] = S.alloc(g); MI_REQUIRE(out[i], MI_ERR_OOM, "stage allocation failed"); }
+    for (int i = 0; i < 6; ++i) MI_TRY(stage_in(S, ins[i], g, &in[i], st));
+    for (int i = 0; i < 5; ++i) MI_TRY(plane(S, g, &out[i]));
     float tabh[128], *tabd = nullptr;
     host_cubic_table(tabh);
-    MI_HIP_TRY(hipMalloc((void **)&tabd, sizeof(tabh)));
-    S.bufs.push_back(tabd);
+    MI_TRY(S.alloc(&tabd, 128));
     MI_HIP_TRY(hipMemcpyAsync(tabd, tabh, sizeof(tabh), hipMemcpyHostToDevice, st));
     const float *u1v[2] = {in[4], in[4]}, *u2v[2] = {in[5], in[5]};
     if (fused) {
-        TRY(warp_fused(semantics, fast, lds, in[0], in[1], u1v, u2v, out[0], out[1], out[2], out[3], out[4], tabd, g, nullptr, 0, st));
+        MI_TRY(warp_fused(semantics, fast, lds, in[0], in[1], u1v, u2v, out[0], out[1], out[2], out[3], out[4], tabd, g, nullptr, 0, st));
     } else {
         float *pk = nullptr;   // {I1, I1x, I1y, 0} per pixel, the layout the gather kernel reads
-        MI_HIP_TRY(hipMalloc((void **)&pk, sizeof(float) * 4 * (size_t)g.ps));
-        S.bufs.push_back(pk);
-        TRY(pack3(in[1], in[2], in[3], pk, g, st));
-        TRY(warp(semantics, in[0], pk, u1v, u2v, out[0], out[1], out[2], out[3], out[4], tabd, g, nullptr, 0, st));
+        MI_TRY(S.alloc(&pk, 4 * (size_t)g.ps));
+        MI_TRY(pack3(in[1], in[2], in[3], pk, g, st));
+        MI_TRY(warp(semantics, in[0], pk, u1v, u2v, out[0], out[1], out[2], out[3], out[4], tabd, g, nullptr, 0, st));
     }
-    for (int i = 0; i < 5; ++i) TRY(stage_out(out[i], g, outs[i], st));
+    for (int i = 0; i < 5; ++i) MI_TRY(stage_out(out[i], g, outs[i], st));
     MI_HIP_TRY(hipStreamSynchronize(st));
     return MI_OK;
 }
@@ -142,25 +128,23 @@ int mi_tvl1_iterate(int exact_math, int time_block, int niter, const mi_mat *I1w
     MI_REQUIRE(!(blocked && err_host), MI_ERR_BAD_ARG, "per-iteration error sums are not available from the blocked kernel");
     MI_REQUIRE(u_in && p_in && u_out && p_out, MI_ERR_BAD_ARG, "null plane array");
     const mi_mat *stat[4] = {I1wx, I1wy, grad, rho_c};
-    for (int i = 0; i < 4; ++i) { TRY(check_f32(stat[i], "static plane")); MI_REQUIRE(stat[i]->rows == I1wx->rows && stat[i]->cols == I1wx->cols, MI_ERR_BAD_SIZE, "size mismatch"); }
-    for (int i = 0; i < 2; ++i) { TRY(check_f32(&u_in[i], "u_in")); TRY(check_f32(&u_out[i], "u_out")); }
-    for (int i = 0; i < 4; ++i) { TRY(check_f32(&p_in[i], "p_in")); TRY(check_f32(&p_out[i], "p_out")); }
+    for (int i = 0; i < 4; ++i) { MI_TRY(check_f32(stat[i], "static plane")); MI_REQUIRE(stat[i]->rows == I1wx->rows && stat[i]->cols == I1wx->cols, MI_ERR_BAD_SIZE, "size mismatch"); }
+    for (int i = 0; i < 2; ++i) { MI_TRY(check_f32(&u_in[i], "u_in")); MI_TRY(check_f32(&u_out[i], "u_out")); }
+    for (int i = 0; i < 4; ++i) { MI_TRY(check_f32(&p_in[i], "p_in")); MI_TRY(check_f32(&p_out[i], "p_out")); }
     const Geo g = geo_of(I1wx->cols, I1wx->rows);
-    Stage S;
+    DevTmp S;
     float *sp[4];
-    for (int i = 0; i < 4; ++i) TRY(stage_in(S, stat[i], g, &sp[i], st));
+    for (int i = 0; i < 4; ++i) MI_TRY(stage_in(S, stat[i], g, &sp[i], st));
     IterPlanes pl;
     memset(&pl, 0, sizeof(pl));
     pl.ix = sp[0]; pl.iy = sp[1]; pl.g = sp[2]; pl.rc = sp[3];
-    for (int i = 0; i < 2; ++i) { TRY(stage_in(S, &u_in[i], g, &pl.u[0][i], st)); pl.u[1][i] = S.alloc(g); MI_REQUIRE(pl.u[1][i], MI_ERR_OOM, "oom"); }
-    for (int i = 0; i < 4; ++i) { TRY(stage_in(S, &p_in[i], g, &pl.p[0][i], st)); pl.p[1][i] = S.alloc(g); MI_REQUIRE(pl.p[1][i], MI_ERR_OOM, "oom"); }
+    for (int i = 0; i < 2; ++i) { MI_TRY(stage_in(S, &u_in[i], g, &pl.u[0][i], st)); MI_TRY(plane(S, g, &pl.u[1][i])); }
+    for (int i = 0; i < 4; ++i) { MI_TRY(stage_in(S, &p_in[i], g, &pl.p[0][i], st)); MI_TRY(plane(S, g, &pl.p[1][i])); }
     Ctl ctl;
     memset(&ctl, 0, sizeof(ctl));
     if (err_host) {
-        MI_HIP_TRY(hipMalloc((void **)&ctl.S, sizeof(int2) * niter));
-        S.bufs.push_back((float *)ctl.S);
-        MI_HIP_TRY(hipMalloc((void **)&ctl.E, sizeof(unsigned long long) * niter));
-        S.bufs.push_back((float *)ctl.E);
+        MI_TRY(S.alloc(&ctl.S, niter));
+        MI_TRY(S.alloc(&ctl.E, niter));
         MI_HIP_TRY(hipMemsetAsync(ctl.E, 0, sizeof(unsigned long long) * niter, st));
         ctl.Q = niter;
         ctl.thr = -1.0;  // always active
@@ -169,7 +153,7 @@ int mi_tvl1_iterate(int exact_math, int time_block, int niter, const mi_mat *I1w
     for (int it = 0; it < niter;) {
         if (tiled) {
             const int T = std::min(niter - it, kTileMaxBlock);
-            TRY(iterate_tile(-time_block - 1, T, pl, g, l_t, theta, taut, false, cur, st));
+            MI_TRY(iterate_tile(-time_block - 1, T, pl, g, l_t, theta, taut, false, cur, st));
             it += T;
             cur ^= 1;
             continue;
@@ -177,7 +161,7 @@ int mi_tvl1_iterate(int exact_math, int time_block, int niter, const mi_mat *I1w
         if (blocked) {
             const int T = greedy_blocks(std::min(niter - it, 10), time_block, {1, 2, 3, 4, 5, 6, 8, 10})[0];   // the largest supported block
             // always the streaming kernel (the tile kernel is compared against it)
-            TRY(iterate_tb(tb_kernel(TbUse::Fixed, T, g, false, false, tv_knobs(), TbOverride{true, 0, indep}), T, pl, g, l_t, theta, taut, false, cur, st));
+            MI_TRY(iterate_tb(tb_kernel(TbUse::Fixed, T, g, false, false, tv_knobs(), TbOverride{true, 0, indep}), T, pl, g, l_t, theta, taut, false, cur, st));
             it += T;
             cur ^= 1;
             continue;
@@ -187,14 +171,14 @@ int mi_tvl1_iterate(int exact_math, int time_block, int niter, const mi_mat *I1w
             const int it0 = it - 1;
             Ctl c = ctl;
             c.q = it0; c.q_prev = it0 - 1; c.first_of_warp = (it0 == 0); c.reset_cur = (it0 == 0);
-            TRY(iterate(exact_math != 0, pl, g, l_t, theta, taut, false, &c, 0, st));
+            MI_TRY(iterate(exact_math != 0, pl, g, l_t, theta, taut, false, &c, 0, st));
         } else {
-            TRY(iterate(exact_math != 0, pl, g, l_t, theta, taut, false, nullptr, cur, st));
+            MI_TRY(iterate(exact_math != 0, pl, g, l_t, theta, taut, false, nullptr, cur, st));
         }
         cur ^= 1;
     }
-    for (int i = 0; i < 2; ++i) TRY(stage_out(pl.u[cur][i], g, &u_out[i], st));
-    for (int i = 0; i < 4; ++i) TRY(stage_out(pl.p[cur][i], g, &p_out[i], st));
+    for (int i = 0; i < 2; ++i) MI_TRY(stage_out(pl.u[cur][i], g, &u_out[i], st));
+    for (int i = 0; i < 4; ++i) MI_TRY(stage_out(pl.p[cur][i], g, &p_out[i], st));
     MI_HIP_TRY(hipStreamSynchronize(st));
     if (err_host) {
         std::vector<unsigned long long> e(niter);
@@ -271,7 +255,7 @@ int mi_tvl1_iterate_stage(const mi_tvl1_stage_desc *d, void *stream)
 
     // the planes: h rows per pair
     MI_REQUIRE(d->I1wx && d->I1wy && d->rho_c && d->u_in && d->u_out && d->p_out && (d->p_in || pz), MI_ERR_BAD_ARG, "null plane");
-    TRY(check_f32(d->I1wx, "I1wx"));
+    MI_TRY(check_f32(d->I1wx, "I1wx"));
     MI_REQUIRE(d->I1wx->rows % B == 0, MI_ERR_BAD_SIZE, "rows (%d) must be batch (%d) x the pair height", d->I1wx->rows, B);
     const int nu = gam ? 3 : 2, np = gam ? 6 : 4;
     std::vector<const mi_mat *> ins = {d->I1wx, d->I1wy, d->rho_c};
@@ -282,36 +266,33 @@ int mi_tvl1_iterate_stage(const mi_tvl1_stage_desc *d, void *stream)
     for (int i = 0; i < nu; ++i) all.push_back(&d->u_out[i]);
     for (int i = 0; i < np; ++i) all.push_back(&d->p_out[i]);
     for (const mi_mat *m : all) {
-        TRY(check_f32(m, "plane"));
+        MI_TRY(check_f32(m, "plane"));
         MI_REQUIRE(m->rows == d->I1wx->rows && m->cols == d->I1wx->cols, MI_ERR_BAD_SIZE, "plane size mismatch");
     }
     g = geo_of(d->I1wx->cols, d->I1wx->rows / B);
     g.batch = B;
 
-    Stage S;
+    DevTmp S;
     IterPlanes pl;
     memset(&pl, 0, sizeof(pl));
     float *stat[4] = {nullptr, nullptr, nullptr, nullptr};
     const mi_mat *statm[4] = {d->I1wx, d->I1wy, d->grad, d->rho_c};
-    for (int i = 0; i < 4; ++i) if (statm[i]) TRY(stage_in(S, statm[i], g, &stat[i], st));
+    for (int i = 0; i < 4; ++i) if (statm[i]) MI_TRY(stage_in(S, statm[i], g, &stat[i], st));
     pl.ix = stat[0]; pl.iy = stat[1]; pl.g = stat[2]; pl.rc = stat[3];
     pl.gamma = d->gamma;
     pl.err_u3 = d->err_u3 ? 1 : 0;
     for (int i = 0; i < nu; ++i) {
-        TRY(stage_in(S, &d->u_in[i], g, &pl.u[0][i], st));
-        pl.u[1][i] = S.alloc(g);
-        MI_REQUIRE(pl.u[1][i], MI_ERR_OOM, "stage allocation failed");
+        MI_TRY(stage_in(S, &d->u_in[i], g, &pl.u[0][i], st));
+        MI_TRY(plane(S, g, &pl.u[1][i]));
     }
     for (int i = 0; i < np; ++i) {
         if (pz) {   // never read: NaN, so that a kernel reading them shows
-            pl.p[0][i] = S.alloc(g);
-            MI_REQUIRE(pl.p[0][i], MI_ERR_OOM, "stage allocation failed");
+            MI_TRY(plane(S, g, &pl.p[0][i]));
             MI_HIP_TRY(hipMemsetAsync(pl.p[0][i], 0xff, sizeof(float) * (size_t)g.ps * B, st));
         } else {
-            TRY(stage_in(S, &d->p_in[i], g, &pl.p[0][i], st));
+            MI_TRY(stage_in(S, &d->p_in[i], g, &pl.p[0][i], st));
         }
-        pl.p[1][i] = S.alloc(g);
-        MI_REQUIRE(pl.p[1][i], MI_ERR_OOM, "stage allocation failed");
+        MI_TRY(plane(S, g, &pl.p[1][i]));
     }
 
     // control slots: the checked one-iteration launches use slot `it` and error sum `it`; the speculative steps slot k and the error
@@ -323,10 +304,7 @@ int mi_tvl1_iterate_stage(const mi_tvl1_stage_desc *d, void *stream)
     if (check || spec) {
         const long long Q = spec ? (long long)(nb + 1) * d->time_block + nb + 2 : niter;
         const size_t n = (size_t)Q * B;
-        ctl.S = (int2 *)S.alloc_bytes(sizeof(int2) * n);
-        ctl.E = (unsigned long long *)S.alloc_bytes(sizeof(unsigned long long) * n);
-        ctl.P = (double *)S.alloc_bytes(sizeof(double) * n);
-        MI_REQUIRE(ctl.S && ctl.E && ctl.P, MI_ERR_OOM, "stage allocation failed");
+        MI_TRY(S.alloc(&ctl.S, n)); MI_TRY(S.alloc(&ctl.E, n)); MI_TRY(S.alloc(&ctl.P, n));
         MI_HIP_TRY(hipMemsetAsync(ctl.S, 0, sizeof(int2) * n, st));
         MI_HIP_TRY(hipMemsetAsync(ctl.E, 0, sizeof(unsigned long long) * n, st));
         MI_HIP_TRY(hipMemsetAsync(ctl.P, 0, sizeof(double) * n, st));
@@ -336,8 +314,8 @@ int mi_tvl1_iterate_stage(const mi_tvl1_stage_desc *d, void *stream)
     std::vector<int> cur_b(B, 0);   // per pair: the set the result is in
     if (spec) {
         // run_spec (tvl1_api.cpp) without history and host feedback: blocks of T, then the launch that settles the last of them
-        int4 *X = (int4 *)S.alloc_bytes(sizeof(int4) * (size_t)ctl.Q * B);
-        MI_REQUIRE(X, MI_ERR_OOM, "stage allocation failed");
+        int4 *X;
+        MI_TRY(S.alloc(&X, (size_t)ctl.Q * B));
         MI_HIP_TRY(hipMemsetAsync(X, 0, sizeof(int4) * (size_t)ctl.Q * B, st));
         SpecK sk;
         memset(&sk, 0, sizeof(sk));
@@ -350,7 +328,7 @@ int mi_tvl1_iterate_stage(const mi_tvl1_stage_desc *d, void *stream)
             Ctl a = ctl;
             a.q = k; a.q_prev = k - 1; a.first_of_warp = (k == 0); a.reset_cur = (k == 0); a.n = 0;
             sk.e0_prev = e_prev; sk.final_launch = last ? 1 : 0; sk.t_after = t_after;
-            TRY(tiles ? iterate_tile_spec(T, pl, g, d->l_t, d->theta, d->taut, a, sk, e_next, st, d->variant)
+            MI_TRY(tiles ? iterate_tile_spec(T, pl, g, d->l_t, d->theta, d->taut, a, sk, e_next, st, d->variant)
                       : iterate_tb_spec(kernel(T), T, pl, g, d->l_t, d->theta, d->taut, a, sk, e_next, st));
             e_prev = e_next;
             if (!last) e_next += T;
@@ -374,18 +352,18 @@ int mi_tvl1_iterate_stage(const mi_tvl1_stage_desc *d, void *stream)
                 if (check) {
                     Ctl c = ctl;
                     c.q = k; c.q_prev = k - 1; c.first_of_warp = (k == 0); c.reset_cur = (k == 0);
-                    TRY(iterate(d->exact_math != 0, pl, g, d->l_t, d->theta, d->taut, pzk, &c, 0, st));
+                    MI_TRY(iterate(d->exact_math != 0, pl, g, d->l_t, d->theta, d->taut, pzk, &c, 0, st));
                 } else {
-                    TRY(iterate(d->exact_math != 0, pl, g, d->l_t, d->theta, d->taut, pzk, nullptr, cur, st));
+                    MI_TRY(iterate(d->exact_math != 0, pl, g, d->l_t, d->theta, d->taut, pzk, nullptr, cur, st));
                 }
                 break;
             case MI_TVL1_STAGE_BLOCKED:
             case MI_TVL1_STAGE_INDEP:
             case MI_TVL1_STAGE_EXACT_BLOCKED:
-                TRY(iterate_tb(kernel(T), T, pl, g, d->l_t, d->theta, d->taut, pzk, cur, st));
+                MI_TRY(iterate_tb(kernel(T), T, pl, g, d->l_t, d->theta, d->taut, pzk, cur, st));
                 break;
             case MI_TVL1_STAGE_TILE:
-                TRY(iterate_tile(d->variant, T, pl, g, d->l_t, d->theta, d->taut, pzk, cur, st));
+                MI_TRY(iterate_tile(d->variant, T, pl, g, d->l_t, d->theta, d->taut, pzk, cur, st));
                 break;
             }
             cur ^= 1;
@@ -403,7 +381,7 @@ int mi_tvl1_iterate_stage(const mi_tvl1_stage_desc *d, void *stream)
             mi_mat m = i < nu ? d->u_out[i] : d->p_out[i - nu];
             m.data = (char *)m.data + (size_t)b * g.h * m.step;
             m.rows = g.h;
-            TRY(stage_out(src, g1, &m, st));
+            MI_TRY(stage_out(src, g1, &m, st));
         }
     }
     MI_HIP_TRY(hipStreamSynchronize(st));
@@ -419,15 +397,15 @@ int mi_resize_linear(int semantics, const mi_mat *src, mi_mat *dst, double fx, d
 {
     hipStream_t st = (hipStream_t)stream;
     MI_REQUIRE(semantics == MI_SEM_CPU_REF || semantics == MI_SEM_CUDA_COMPAT, MI_ERR_BAD_ARG, "bad semantics");
-    TRY(check_f32(src, "src")); TRY(check_f32(dst, "dst"));
+    MI_TRY(check_f32(src, "src")); MI_TRY(check_f32(dst, "dst"));
     const Geo gs = geo_of(src->cols, src->rows), gd = geo_of(dst->cols, dst->rows);
     double isx = fx, isy = fy;
     if (explicit_dsize) { isx = (double)gd.w / gs.w; isy = (double)gd.h / gs.h; }
     MI_REQUIRE(isx > 0 && isy > 0, MI_ERR_BAD_ARG, "fx, fy must be > 0 when dsize is not explicit");
-    Stage S;
-    float *s, *d = S.alloc(gd);
-    MI_REQUIRE(d, MI_ERR_OOM, "stage allocation failed");
-    TRY(stage_in(S, src, gs, &s, st));
+    DevTmp S;
+    float *s, *d;
+    MI_TRY(plane(S, gd, &d));
+    MI_TRY(stage_in(S, src, gs, &s, st));
     const float *srcs[3][2] = {{s, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};
     float *dsts[3] = {d, nullptr, nullptr};
     const float post[3] = {post_scale, 1.f, 1.f};
@@ -435,9 +413,9 @@ int mi_resize_linear(int semantics, const mi_mat *src, mi_mat *dst, double fx, d
         // dsize == src.size(): plain copy (cudawarping/src/resize.cpp:89-93)
         MI_HIP_TRY(hipMemcpyAsync(d, s, sizeof(float) * (size_t)gs.ps, hipMemcpyDeviceToDevice, st));
     } else {
-        TRY(resize(semantics, 1, srcs, 1, dsts, gs, gd, isx, isy, post, nullptr, 0, st));
+        MI_TRY(resize(semantics, 1, srcs, 1, dsts, gs, gd, isx, isy, post, nullptr, 0, st));
     }
-    TRY(stage_out(d, gd, dst, st));
+    MI_TRY(stage_out(d, gd, dst, st));
     MI_HIP_TRY(hipStreamSynchronize(st));
     return MI_OK;
 }
@@ -446,14 +424,11 @@ int miflow_selftest_lane_shift(int *out_host)
 {
     MI_REQUIRE(out_host, MI_ERR_BAD_ARG, "null out");
     int *d = nullptr;
-    MI_HIP_TRY(hipMalloc((void **)&d, 128 * sizeof(int)));
-    int rc = dbg_lane_shift(d, nullptr);
-    if (rc == MI_OK) {
-        hipError_t e = hipMemcpy(out_host, d, 128 * sizeof(int), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { set_error("hipMemcpy failed: %s", hipGetErrorString(e)); rc = MI_ERR_HIP; }
-    }
-    (void)hipFree(d);
-    return rc;
+    DevTmp tmp;
+    MI_TRY(tmp.alloc(&d, 128));
+    MI_TRY(dbg_lane_shift(d, nullptr));
+    MI_HIP_TRY(hipMemcpy(out_host, d, 128 * sizeof(int), hipMemcpyDeviceToHost));
+    return MI_OK;
 }
 
 int miflow_selftest_jw_fault(int *fault)
