@@ -157,6 +157,10 @@ def lib():
         "miflow_selftest_jw_fault": (i, [C.POINTER(i)]),
         "miflow_selftest_farneback_poison": (i, [vp, vp]),
         "miflow_selftest_tvl1_slots": (i, [vp, i, C.POINTER(i), i, vp]),
+        "miflow_selftest_farneback_iterate": (i, [i, PM, PM, PM, PM, PM, PM, PM, i, i, i, vp]),
+        "miflow_selftest_farneback_poly_exp": (i, [i, PM, PM, i, d, vp]),
+        "miflow_selftest_farneback_update_matrices": (i, [i, PM, PM, f, PM, PM, PM, PM, PM, vp]),
+        "miflow_selftest_farneback_gaussian_blur": (i, [i, PM, PM, PM, PM, i, d, i, vp]),
         "mi_stereobm_default_params": (None, [C.POINTER(StereoBMParams)]),
         "mi_stereobm_create": (i, [C.POINTER(StereoBMParams), C.POINTER(vp)]),
         "mi_stereobm_set_params": (i, [vp, C.POINTER(StereoBMParams)]),

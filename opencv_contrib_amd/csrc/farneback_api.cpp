@@ -676,3 +676,150 @@ int mi_pyr_down(const mi_mat *src, mi_mat *dst, void *stream)
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------ one named launch form per call (test hooks, mi_selftest.h)
+extern "C" {
+
+int miflow_selftest_farneback_iterate(int form, const mi_mat *M5, const mi_mat *R0, const mi_mat *R1, mi_mat *flowx, mi_mat *flowy, mi_mat *M5out,
+                                      mi_mat *merged, int ksize, int gaussian, int update, void *stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    MI_REQUIRE(form >= MI_FB_ITER_ROW && form <= MI_FB_ITER_PAIR, MI_ERR_BAD_ARG, "unknown iterate form %d", form);
+    MI_TRY(check_f32(M5, "M")); MI_TRY(check_f32(R0, "R0")); MI_TRY(check_f32(R1, "R1")); MI_TRY(check_f32(flowx, "flowx")); MI_TRY(check_f32(flowy, "flowy"));
+    MI_TRY(check_f32(M5out, "Mout"));
+    const int w = flowx->cols, hh = flowx->rows;
+    MI_REQUIRE(flowy->rows == hh && flowy->cols == w && M5->rows == 5 * hh && R0->rows == 5 * hh && R1->rows == 5 * hh && M5out->rows == 5 * hh &&
+               M5->cols == w && R0->cols == w && R1->cols == w && M5out->cols == w, MI_ERR_BAD_SIZE, "size mismatch");
+    MI_REQUIRE(M5->data != M5out->data, MI_ERR_BAD_ARG, "Mout must not alias M");
+    if (merged) {
+        MI_REQUIRE(merged->data && merged->type == MI_32FC2 && merged->rows == hh && merged->cols == w, MI_ERR_BAD_SIZE, "merged must be CV_32FC2 of the flow size");
+        MI_REQUIRE(merged->step >= (size_t)w * 8 && merged->step % 8 == 0 && ((uintptr_t)merged->data % 8) == 0, MI_ERR_BAD_ARG, "merged must be 8-byte aligned");
+    }
+    const Plane g = plane_of(w, hh);
+    Taps K;
+    MI_TRY(make_win_taps(ksize, &K));
+    DevTmp S;
+    float *m, *r0, *r1, *fx, *fy, *mo;
+    MI_TRY(S.alloc(&fx, (size_t)g.ld * hh)); MI_TRY(S.alloc(&fy, (size_t)g.ld * hh));
+    MI_TRY(stage_in(S, M5, g.ld, &m, st)); MI_TRY(stage_in(S, R0, g.ld, &r0, st)); MI_TRY(stage_in(S, R1, g.ld, &r1, st));
+    MI_TRY(stage_in(S, M5out, g.ld, &mo, st));
+    void *const mg = merged ? merged->data : nullptr;
+    const long long mstep = merged ? (long long)merged->step : 0;
+    bool did = false;
+    int rc;
+    if (form == MI_FB_ITER_PAIR) rc = iterate2(m, r0, r1, fx, fy, mo, g, ksize, gaussian ? &K : nullptr, update != 0, st, mg, mstep, &did);
+    else rc = iterate(m, r0, r1, fx, fy, mo, g, ksize, gaussian ? &K : nullptr, update != 0, st, mg, mstep, &did, (IterForm)form);
+    if (rc == MI_OK && merged && !did) { set_error("this form did not write the merged flow"); rc = MI_ERR_BAD_ARG; }
+    if (rc == MI_OK) rc = stage_out(fx, g.ld, flowx, st);
+    if (rc == MI_OK) rc = stage_out(fy, g.ld, flowy, st);
+    if (rc == MI_OK) rc = stage_out(mo, g.ld, M5out, st);
+    MI_HIP_TRY(hipStreamSynchronize(st));   // also on an error return: the staging copies read the caller's matrices
+    return rc;
+}
+
+int miflow_selftest_farneback_poly_exp(int form, const mi_mat *src, mi_mat *dst5, int poly_n, double poly_sigma, void *stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    MI_REQUIRE(form >= MI_FB_POLY_ROW && form <= MI_FB_POLY_RESIZED, MI_ERR_BAD_ARG, "unknown poly_exp form %d", form);
+    MI_TRY(check_f32(src, "src")); MI_TRY(check_f32(dst5, "dst"));
+    MI_REQUIRE(dst5->rows % 5 == 0, MI_ERR_BAD_SIZE, "dst must be 5 stacked planes");
+    const bool rs = form == MI_FB_POLY_RESIZED;
+    const bool same = dst5->rows == 5 * src->rows && dst5->cols == src->cols;
+    MI_REQUIRE(rs || same, MI_ERR_BAD_SIZE, "dst must be 5*rows x cols");
+    MI_REQUIRE(!rs || !same, MI_ERR_BAD_SIZE, "the resized form takes a source of another size");
+    MI_REQUIRE(poly_n == 5 || poly_n == 7, MI_ERR_BAD_ARG, "polyN must be 5 or 7");
+    const Plane gs = plane_of(src->cols, src->rows), g = plane_of(dst5->cols, dst5->rows / 5);
+    DevTmp S;
+    float *in = nullptr, *out;
+    MI_TRY(S.alloc(&out, (size_t)g.ld * g.h * 5));
+    MI_TRY(stage_in(S, src, gs.ld, &in, st));
+    PolyC C;
+    MI_TRY(prepare_gaussian(poly_n, poly_sigma, &C));
+    int rc = poly_exp(in, out, g, poly_n, C, st, 1, 0, 0, rs ? &gs : nullptr, form == MI_FB_POLY_TILED ? POLY_TILED : POLY_ROW);
+    if (rc == MI_OK) rc = stage_out(out, g.ld, dst5, st);
+    MI_HIP_TRY(hipStreamSynchronize(st));
+    return rc;
+}
+
+int miflow_selftest_farneback_update_matrices(int form, const mi_mat *prevx, const mi_mat *prevy, float alpha, mi_mat *flowx, mi_mat *flowy,
+                                              const mi_mat *R0, const mi_mat *R1, mi_mat *M5, void *stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    MI_REQUIRE(form >= MI_FB_UM_PLAIN && form <= MI_FB_UM_RESIZED, MI_ERR_BAD_ARG, "unknown update_matrices form %d", form);
+    MI_TRY(check_f32(R0, "R0")); MI_TRY(check_f32(R1, "R1")); MI_TRY(check_f32(M5, "M"));
+    MI_REQUIRE(M5->rows % 5 == 0, MI_ERR_BAD_SIZE, "M must be 5 stacked planes");
+    const int w = M5->cols, hh = M5->rows / 5;
+    MI_REQUIRE(R0->rows == 5 * hh && R1->rows == 5 * hh && R0->cols == w && R1->cols == w, MI_ERR_BAD_SIZE, "size mismatch");
+    if (form != MI_FB_UM_ZERO) {
+        MI_TRY(check_f32(flowx, "flowx")); MI_TRY(check_f32(flowy, "flowy"));
+        MI_REQUIRE(flowx->rows == hh && flowx->cols == w && flowy->rows == hh && flowy->cols == w, MI_ERR_BAD_SIZE, "size mismatch");
+    }
+    const Plane g = plane_of(w, hh);
+    DevTmp S;
+    float *fx = nullptr, *fy = nullptr, *r0, *r1, *m;
+    MI_TRY(S.alloc(&m, (size_t)g.ld * hh * 5));
+    MI_TRY(stage_in(S, R0, g.ld, &r0, st)); MI_TRY(stage_in(S, R1, g.ld, &r1, st));
+    int rc;
+    if (form == MI_FB_UM_RESIZED) {
+        MI_TRY(check_f32(prevx, "prevx")); MI_TRY(check_f32(prevy, "prevy"));
+        MI_REQUIRE(prevy->rows == prevx->rows && prevy->cols == prevx->cols, MI_ERR_BAD_SIZE, "size mismatch");
+        const Plane gp = plane_of(prevx->cols, prevx->rows);
+        float *px, *py;
+        MI_TRY(stage_in(S, prevx, gp.ld, &px, st)); MI_TRY(stage_in(S, prevy, gp.ld, &py, st));
+        MI_TRY(S.alloc(&fx, (size_t)g.ld * hh)); MI_TRY(S.alloc(&fy, (size_t)g.ld * hh));
+        rc = update_matrices_resized(px, py, gp, alpha, fx, fy, r0, r1, m, g, st);
+        if (rc == MI_OK) rc = stage_out(fx, g.ld, flowx, st);
+        if (rc == MI_OK) rc = stage_out(fy, g.ld, flowy, st);
+    } else {
+        if (form == MI_FB_UM_PLAIN) { MI_TRY(stage_in(S, flowx, g.ld, &fx, st)); MI_TRY(stage_in(S, flowy, g.ld, &fy, st)); }
+        rc = update_matrices(fx, fy, r0, r1, m, g, st);
+    }
+    if (rc == MI_OK) rc = stage_out(m, g.ld, M5, st);
+    MI_HIP_TRY(hipStreamSynchronize(st));
+    return rc;
+}
+
+int miflow_selftest_farneback_gaussian_blur(int form, const mi_mat *src0, const mi_mat *src1, mi_mat *dst0, mi_mat *dst1, int ksize, double sigma,
+                                            int border, void *stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    MI_REQUIRE(form >= MI_FB_BLUR_GENERIC_FAST && form <= MI_FB_BLUR_TABLE, MI_ERR_BAD_ARG, "unknown blur form %d", form);
+    MI_REQUIRE(ksize >= 1 && (ksize & 1) && ksize / 2 <= MI_FB_MAX_KSIZE_HALF, MI_ERR_BAD_ARG, "ksize must be odd and <= 201");
+    MI_TRY(check_f32(dst0, "dst"));
+    const Plane g = plane_of(dst0->cols, dst0->rows);
+    const size_t pn = (size_t)g.ld * g.h;
+    std::vector<float> k(ksize);
+    gaussian_kernel(ksize, sigma, k.data());
+    Taps K;
+    memset(&K, 0, sizeof(K));
+    for (int i = 0; i <= ksize / 2; ++i) K.k[i] = k[ksize / 2 + i];
+    DevTmp S;
+    float *in, *out;
+    MI_TRY(S.alloc(&out, pn * 2));
+    int rc;
+    if (form == MI_FB_BLUR_TABLE) {
+        MI_TRY(check_f32(dst1, "dst1"));
+        MI_REQUIRE(src0 && src1 && src0->data && src1->data, MI_ERR_BAD_ARG, "null matrix");
+        MI_REQUIRE((src0->type == MI_8UC1 || src0->type == MI_32FC1) && src1->type == src0->type, MI_ERR_BAD_TYPE, "sources must be CV_8UC1 or CV_32FC1, same type");
+        MI_REQUIRE(src0->rows == g.h && src0->cols == g.w && src1->rows == g.h && src1->cols == g.w && dst1->rows == g.h && dst1->cols == g.w, MI_ERR_BAD_SIZE, "size mismatch");
+        if (src0->type == MI_32FC1) MI_REQUIRE(src0->step % 4 == 0 && src1->step % 4 == 0, MI_ERR_BAD_ARG, "float sources must be 4-byte aligned");
+        MI_REQUIRE(border == MI_BORDER_REFLECT101, MI_ERR_BAD_ARG, "the direct-source blur is REFLECT101 only");
+        FmtTab T;
+        memset(&T, 0, sizeof(T));
+        T.a[0] = src0->data; T.sa[0] = (long long)src0->step;
+        T.b[0] = src1->data; T.sb[0] = (long long)src1->step;
+        rc = gaussian_blur_tab(T, src0->type, out, g, ksize / 2, K, st, (long long)pn);
+        if (rc == MI_OK) rc = stage_out(out + pn, g.ld, dst1, st);
+    } else {
+        MI_TRY(check_f32(src0, "src"));
+        MI_REQUIRE(src0->rows == g.h && src0->cols == g.w, MI_ERR_BAD_SIZE, "size mismatch");
+        MI_TRY(stage_in(S, src0, g.ld, &in, st));
+        rc = gaussian_blur(in, out, g, ksize / 2, K, border, st, 1, 0,
+                           form == MI_FB_BLUR_TILED ? BLUR_TILED : form == MI_FB_BLUR_GENERIC_FULL ? BLUR_GENERIC_FULL : BLUR_GENERIC_FAST);
+    }
+    if (rc == MI_OK) rc = stage_out(out, g.ld, dst0, st);
+    MI_HIP_TRY(hipStreamSynchronize(st));
+    return rc;
+}
+
+}  // extern "C"

@@ -26,14 +26,20 @@ int merge_flow_batch(const float *fx, const float *fy, const FmtTab &T, int n, l
 int convert(const void *a, long long sa, const void *b, long long sb, int type, float *A, float *B, const Plane &g, hipStream_t s);
 int split_flow(const void *flow, long long sf, float *fx, float *fy, const Plane &g, hipStream_t s);
 int merge_flow(const float *fx, const float *fy, void *flow, long long sf, const Plane &g, hipStream_t s);
+// Launch forms a stage test may force (mi_selftest.h: one process runs every form on the same planes).  Auto = the choice the level loop
+// gets, from the grid size and the process-wide tuning; a forced form that has no kernel for the request is MI_ERR_BAD_ARG, nothing launched.
+enum BlurForm { BLUR_AUTO = 0, BLUR_GENERIC_FAST, BLUR_GENERIC_FULL, BLUR_TILED };   // FULL: the border rule with every fold (kh >= w or h)
+enum PolyForm { POLY_AUTO = 0, POLY_ROW, POLY_TILED };
+enum IterForm { ITER_AUTO = 0, ITER_ROW, ITER_TILE256, ITER_TILE64 };
 // nf = 2: both frames of every pair in one launch (blockIdx.z = pair * 2 + frame; frame 1 lies fs floats behind frame 0 in src / dst)
-int gaussian_blur(const float *src, float *dst, const Plane &g, int kh, const Taps &K, int border, hipStream_t s, int nf = 1, long long fs = 0);
+int gaussian_blur(const float *src, float *dst, const Plane &g, int kh, const Taps &K, int border, hipStream_t s, int nf = 1, long long fs = 0,
+                  BlurForm form = BLUR_AUTO);
 // the same (REFLECT101, both frames of g.batch <= kFmtPairs pairs) reading the caller's CV_8UC1 / CV_32FC1 matrices T.a / T.b instead of converted planes
 bool gaussian_blur_tab_ok(const Plane &g, int kh);
 int gaussian_blur_tab(const FmtTab &T, int type, float *dst, const Plane &g, int kh, const Taps &K, hipStream_t s, long long fs);
 // resize_from: src is a plane of that (larger) geometry and the expansion reads its cuda::resize to g, sampled on the fly
 int poly_exp(const float *src, float *dst5, const Plane &g, int polyN, const PolyC &C, hipStream_t s, int nf = 1, long long fs_src = 0, long long fs_dst = 0,
-             const Plane *resize_from = nullptr);
+             const Plane *resize_from = nullptr, PolyForm form = POLY_AUTO);
 // flow = resize(prev) * alpha (stored) and M = updateMatrices(flow) in one launch
 int update_matrices_resized(const float *prevx, const float *prevy, const Plane &gprev, float alpha, float *flowx, float *flowy, const float *R0,
                             const float *R1, float *M, const Plane &g, hipStream_t s);
@@ -41,7 +47,8 @@ int update_matrices(const float *flowx, const float *flowy, const float *R0, con
 // fused blur5 (box when gauss == nullptr) + updateFlow + (update ? updateMatrices -> Mout)
 // merged / merged_step: the caller's CV_32FC2 flow matrix of a SINGLE pair, written together with the planes (tiled kernels only; *did_merge says)
 int iterate(const float *M, const float *R0, const float *R1, float *flowx, float *flowy, float *Mout, const Plane &g, int ksize,
-            const Taps *gauss, bool update, hipStream_t s, void *merged = nullptr, long long merged_step = 0, bool *did_merge = nullptr);
+            const Taps *gauss, bool update, hipStream_t s, void *merged = nullptr, long long merged_step = 0, bool *did_merge = nullptr,
+            IterForm form = ITER_AUTO);
 // two iterations in one launch (64 x 4 tiles with a recomputed halo; M and Mout must differ: ONE buffer swap per call); bit-identical to
 // iterate(update = true) followed by iterate(update)
 bool iterate2_supported(int ksize);

@@ -810,15 +810,19 @@ int merge_flow(const float *fx, const float *fy, void *flow, long long sf, const
     return MI_OK;
 }
 
-int gaussian_blur(const float *src, float *dst, const Plane &g, int kh, const Taps &K, int border, hipStream_t s, int nf, long long fs)
+int gaussian_blur(const float *src, float *dst, const Plane &g, int kh, const Taps &K, int border, hipStream_t s, int nf, long long fs, BlurForm form)
 {
     MI_REQUIRE(kh >= 0 && kh <= MI_FB_MAX_KSIZE_HALF, MI_ERR_BAD_ARG, "Gaussian kernel half size out of range");
     const dim3 grid(div_up(g.w, 256), g.h, g.batch * nf);
     const size_t lds = sizeof(float) * (256 + 2 * kh);
-    const bool fast = kh < g.w && kh < g.h && g.w >= 2 && g.h >= 2;
+    bool fast = kh < g.w && kh < g.h && g.w >= 2 && g.h >= 2;
     if (border != MI_BORDER_REFLECT101 && border != MI_BORDER_REPLICATE) { set_error("unsupported border mode %d", border); return MI_ERR_BAD_ARG; }   // farneback.cu:510-517: only these two
     // tiled form for the half sizes the pyramid of pyrScale 0.5 (1, 1, 4, 9, 19) and its neighbours use
-    if (fast && tuning().fb_blur_tiled && (kh == 1 || kh == 2 || kh == 3 || kh == 4 || kh == 9 || kh == 19)) {
+    const bool has_tile = fast && (kh == 1 || kh == 2 || kh == 3 || kh == 4 || kh == 9 || kh == 19);
+    MI_REQUIRE(form != BLUR_TILED || has_tile, MI_ERR_BAD_ARG, "no tiled blur for half size %d on a %d x %d plane", kh, g.w, g.h);
+    MI_REQUIRE(form != BLUR_GENERIC_FAST || fast, MI_ERR_BAD_ARG, "half size %d folds more than once on a %d x %d plane", kh, g.w, g.h);
+    if (form == BLUR_GENERIC_FULL) fast = false;
+    if (form == BLUR_AUTO ? has_tile && tuning().fb_blur_tiled : form == BLUR_TILED) {
 #define MI_FB_BLUR(KH) case KH: { const dim3 tg(div_up(g.w, 256), div_up(g.h, BlurTile<KH>::RB), g.batch * nf);                                  \
         if (border == MI_BORDER_REFLECT101) hipLaunchKernelGGL((k_gaussian_blur_t<MI_BORDER_REFLECT101, KH>), tg, dim3(256), 0, s, src, dst, g.w, g.h, g.ld, K, g.bs, nf, fs); \
         else hipLaunchKernelGGL((k_gaussian_blur_t<MI_BORDER_REPLICATE, KH>), tg, dim3(256), 0, s, src, dst, g.w, g.h, g.ld, K, g.bs, nf, fs); } break;
@@ -852,8 +856,9 @@ int gaussian_blur_tab(const FmtTab &T, int type, float *dst, const Plane &g, int
 }
 
 int poly_exp(const float *src, float *dst5, const Plane &g, int polyN, const PolyC &C, hipStream_t s, int nf, long long fs_src, long long fs_dst,
-             const Plane *resize_from)
+             const Plane *resize_from, PolyForm form)
 {
+    MI_REQUIRE(form != POLY_TILED || !resize_from, MI_ERR_BAD_ARG, "the tiled expansion does not sample a resize");
     RsSrc rs;
     memset(&rs, 0, sizeof(rs));
     if (resize_from) {   // the scale factors exactly as tvl1::resize forms them for cv::cuda's semantics (cudawarping/src/resize.cpp:107)
@@ -861,7 +866,7 @@ int poly_exp(const float *src, float *dst5, const Plane &g, int polyN, const Pol
         rs.scx = (double)(float)(1.0 / ((double)g.w / resize_from->w));
         rs.scy = (double)(float)(1.0 / ((double)g.h / resize_from->h));
     }
-#define MI_PE(N) do { if (!resize_from && tuning().fb_poly_tiled && (long long)div_up(g.w, 256 - 2 * N) * div_up(g.h, 8) * g.batch * nf >= 1024) hipLaunchKernelGGL((k_poly_exp_t<N, 8>), dim3(div_up(g.w, 256 - 2 * N), div_up(g.h, 8), g.batch * nf), dim3(256), 0, s, src, dst5, g.w, g.h, g.ld, C, g.bs, nf, fs_src, fs_dst); \
+#define MI_PE(N) do { if (form == POLY_AUTO ? !resize_from && tuning().fb_poly_tiled && (long long)div_up(g.w, 256 - 2 * N) * div_up(g.h, 8) * g.batch * nf >= 1024 : form == POLY_TILED) hipLaunchKernelGGL((k_poly_exp_t<N, 8>), dim3(div_up(g.w, 256 - 2 * N), div_up(g.h, 8), g.batch * nf), dim3(256), 0, s, src, dst5, g.w, g.h, g.ld, C, g.bs, nf, fs_src, fs_dst); \
                      else if (resize_from) hipLaunchKernelGGL((k_poly_exp<N, true>), dim3(div_up(g.w, 256 - 2 * N), g.h, g.batch * nf), dim3(256), 0, s, src, dst5, g.w, g.h, g.ld, C, g.bs, nf, fs_src, fs_dst, rs); \
                      else hipLaunchKernelGGL((k_poly_exp<N, false>), dim3(div_up(g.w, 256 - 2 * N), g.h, g.batch * nf), dim3(256), 0, s, src, dst5, g.w, g.h, g.ld, C, g.bs, nf, fs_src, fs_dst, rs); } while (0)
     if (polyN == 5) MI_PE(5);
@@ -914,11 +919,15 @@ int update_matrices(const float *flowx, const float *flowy, const float *R0, con
 }
 
 int iterate(const float *M, const float *R0, const float *R1, float *flowx, float *flowy, float *Mout, const Plane &g, int ksize,
-            const Taps *gauss, bool update, hipStream_t s, void *merged, long long merged_step, bool *did_merge)
+            const Taps *gauss, bool update, hipStream_t s, void *merged, long long merged_step, bool *did_merge, IterForm form)
 {
     if (did_merge) *did_merge = false;
     const int kh = ksize / 2;
     MI_REQUIRE(kh >= 0 && kh <= MI_FB_MAX_KSIZE_HALF, MI_ERR_BAD_ARG, "winSize out of range");
+    const bool has_tile = kh == 4 || kh == 6 || kh == 7 || kh == 10;   // winSize 9, 13 (the default), 15, 21
+    MI_REQUIRE((form != ITER_TILE256 && form != ITER_TILE64) || (has_tile && tuning().fb_rows == 4), MI_ERR_BAD_ARG, "no tiled iteration for winSize %d", ksize);
+    MI_REQUIRE(form != ITER_ROW || !merged, MI_ERR_BAD_ARG, "the one-row iteration does not write the merged flow");
+    const bool tiled = form == ITER_AUTO ? tuning().fb_tiled != 0 : form != ITER_ROW;
     const dim3 grid(div_up(g.w, 256), g.h, g.batch);
     const size_t lds = sizeof(float) * 5 * (256 + 2 * kh);
     const float inv = 1.f / ((1 + 2 * kh) * (1 + 2 * kh));
@@ -931,7 +940,8 @@ int iterate(const float *M, const float *R0, const float *R1, float *flowx, floa
     // narrow tiles where the 256-column grid would leave most of the device idle (fewer workgroups than two per CU): the launch then
     // costs its dependent steps, and a 64 x 4 tile has a third of them.  MIFLOW_FB_NARROW=0 / 1 forces the choice (tuning, tests).
     const int narrow_env = tuning().fb_narrow;
-    const bool narrow = narrow_env >= 0 ? narrow_env != 0 : (long long)tgrid.x * tgrid.y * tgrid.z < 2LL * (device_simds() / 4);
+    const bool narrow = form != ITER_AUTO ? form == ITER_TILE64 :
+                        narrow_env >= 0 ? narrow_env != 0 : (long long)tgrid.x * tgrid.y * tgrid.z < 2LL * (device_simds() / 4);
     if (narrow && R == 4) tgrid = dim3(div_up(g.w, 64), div_up(g.h, 4), g.batch);
 #define MI_FB_LAUNCH(G, KH, RR, TW) hipLaunchKernelGGL((k_iterate_t<G, KH, RR, TW>), tgrid, dim3(256), 0, s, M, R0, R1, flowx, flowy, Mout, g.w, g.h, g.ld, inv, upd, K, g.bs, swz, mg, merged_step)
 #ifdef MIFLOW_EXPERIMENTS   // 8-row tiles (MIFLOW_FB_ROWS=8) lost their A/B: experiments build only
@@ -944,10 +954,10 @@ int iterate(const float *M, const float *R0, const float *R1, float *flowx, floa
         if (gauss) { MI_FB_R8(true, KH) if (narrow) MI_FB_LAUNCH(true, KH, 4, 64); else MI_FB_LAUNCH(true, KH, 4, 256); }   \
         else { MI_FB_R8(false, KH) if (narrow) MI_FB_LAUNCH(false, KH, 4, 64); else MI_FB_LAUNCH(false, KH, 4, 256); }       \
         break;
-    void *mg = (merged && g.batch == 1 && tuning().fb_tiled && (kh == 4 || kh == 6 || kh == 7 || kh == 10)) ? merged : nullptr;
+    void *mg = (merged && g.batch == 1 && tiled && has_tile) ? merged : nullptr;
     if (did_merge) *did_merge = mg != nullptr;
-    switch (tuning().fb_tiled ? kh : -1) {
-        MI_FB_TILED(4) MI_FB_TILED(6) MI_FB_TILED(7) MI_FB_TILED(10)   // winSize 9, 13 (the default), 15, 21
+    switch (tiled ? kh : -1) {
+        MI_FB_TILED(4) MI_FB_TILED(6) MI_FB_TILED(7) MI_FB_TILED(10)
     default:
         if (gauss) hipLaunchKernelGGL(k_iterate<true>, grid, dim3(256), lds, s, M, R0, R1, flowx, flowy, Mout, g.w, g.h, g.ld, kh, inv, upd, K, g.bs);
         else hipLaunchKernelGGL(k_iterate<false>, grid, dim3(256), lds, s, M, R0, R1, flowx, flowy, Mout, g.w, g.h, g.ld, kh, inv, upd, K, g.bs);

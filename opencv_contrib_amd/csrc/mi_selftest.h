@@ -32,6 +32,28 @@ MI_API int miflow_selftest_rccl_self_copy(const unsigned char *in_host, unsigned
 struct mi_farneback;
 MI_API int miflow_selftest_farneback_poison(struct mi_farneback *h, void *stream);
 /* the same for a BTV-L1 handle: every scratch plane of its arena (frames, motions, maps, both estimates, the sign field) */
+/* ONE named launch form of a Farneback stage on the caller's planes (staged into dense planes exactly as the mi_farneback_* stage
+ * entries of c_api.h stage them), where the level loop would pick the form from the grid size and the process-wide tuning: one test
+ * process holds every form to the oracle and to the other forms.  A form that has no kernel for the request (two iterations per launch
+ * at winSize 21, the tiled blur at half size 5, ...) returns MI_ERR_BAD_ARG and launches nothing.  All synchronise `stream`.
+ *   iterate: M5out arrives holding a pattern of the caller's (update == 0 must leave it alone); PAIR runs two iterations (the first always
+ *     updates; `update` is the second's) and needs M5 != M5out; `merged` (NULL, or a pitched CV_32FC2 matrix, 8-byte aligned) is written
+ *     in place by the tiled and the two-iteration kernels, as the last iteration of a single-pair calc writes the caller's flow.
+ *   poly_exp: RESIZED takes `src` of ANOTHER size (the blurred full-size frame); the expansion samples its cuda::resize to dst5's size.
+ *   update_matrices: PLAIN reads flowx / flowy; ZERO takes them as NULL (the coarsest level's start); RESIZED reads prevx / prevy of
+ *     another size and WRITES flowx / flowy = resize(prev) * alpha beside M5.
+ *   gaussian_blur: src1 / dst1 only with TABLE, which blurs both (pitched CV_8UC1 or CV_32FC1, read in place; REFLECT101). */
+enum { MI_FB_ITER_ROW = 1, MI_FB_ITER_TILE256 = 2, MI_FB_ITER_TILE64 = 3, MI_FB_ITER_PAIR = 4 };
+enum { MI_FB_POLY_ROW = 1, MI_FB_POLY_TILED = 2, MI_FB_POLY_RESIZED = 3 };
+enum { MI_FB_UM_PLAIN = 1, MI_FB_UM_ZERO = 2, MI_FB_UM_RESIZED = 3 };
+enum { MI_FB_BLUR_GENERIC_FAST = 1, MI_FB_BLUR_GENERIC_FULL = 2, MI_FB_BLUR_TILED = 3, MI_FB_BLUR_TABLE = 4 };
+MI_API int miflow_selftest_farneback_iterate(int form, const mi_mat *M5, const mi_mat *R0, const mi_mat *R1, mi_mat *flowx, mi_mat *flowy,
+                                             mi_mat *M5out, mi_mat *merged, int ksize, int gaussian, int update, void *stream);
+MI_API int miflow_selftest_farneback_poly_exp(int form, const mi_mat *src, mi_mat *dst5, int poly_n, double poly_sigma, void *stream);
+MI_API int miflow_selftest_farneback_update_matrices(int form, const mi_mat *prevx, const mi_mat *prevy, float alpha, mi_mat *flowx, mi_mat *flowy,
+                                                     const mi_mat *R0, const mi_mat *R1, mi_mat *M5, void *stream);
+MI_API int miflow_selftest_farneback_gaussian_blur(int form, const mi_mat *src0, const mi_mat *src1, mi_mat *dst0, mi_mat *dst1, int ksize,
+                                                   double sigma, int border, void *stream);
 struct mi_btvl1;
 MI_API int miflow_selftest_btvl1_poison(struct mi_btvl1 *h, void *stream);
 struct mi_tvl1;

@@ -999,6 +999,64 @@ def farneback_iterate(M, R0, R1, ksize, gaussian=False, update=True):
     return fx, fy, Mo
 
 
+# ---- one named launch form per call (miflow_selftest_farneback_*, csrc/mi_selftest.h): the level loop picks a form from the grid size
+# and the process-wide tuning; these let one test process run every form on the same planes.  A form that has no kernel for the
+# request raises MiError and launches nothing.
+FB_ITERATE_FORMS = {"row": 1, "tile256": 2, "tile64": 3, "pair": 4}
+FB_POLY_FORMS = {"row": 1, "tiled": 2, "resized": 3}
+FB_UPDATE_FORMS = {"plain": 1, "zero": 2, "resized": 3}
+FB_BLUR_FORMS = {"generic_fast": 1, "generic_full": 2, "tiled": 3, "table": 4}
+
+
+def _ref(t):
+    return C.byref(_m(t)) if t is not None else None
+
+
+def farneback_iterate_form(form, M, R0, R1, ksize, gaussian=False, update=True, Mout=None, merged=None):
+    """One launch of the named iteration form -> (flowx, flowy, Mout).  'pair' runs two iterations (k_iterate2_t).  Mout: a 5h x w
+    tensor whose contents update=False must keep (default: zeros); merged: a (h, w, 2) view, rows possibly pitched, written in place."""
+    import torch
+    h = M.shape[0] // 5
+    fx = torch.empty((h, M.shape[1]), dtype=torch.float32, device=M.device)
+    fy = torch.empty_like(fx)
+    Mo = torch.zeros_like(M) if Mout is None else Mout
+    capi.check(capi.lib().miflow_selftest_farneback_iterate(FB_ITERATE_FORMS[form], _ref(M), _ref(R0), _ref(R1), _ref(fx), _ref(fy), _ref(Mo),
+                                                            _ref(merged), ksize, int(bool(gaussian)), int(bool(update)), capi.current_stream_ptr()))
+    return fx, fy, Mo
+
+
+def farneback_polyExp_form(form, src, polyN=5, polySigma=1.1, dsize=None):
+    """form 'resized': src is the plane the level image is resized FROM and dsize = (h, w) of the level."""
+    import torch
+    h, w = dsize if form == "resized" else src.shape
+    dst = torch.empty((5 * h, w), dtype=torch.float32, device=src.device)
+    capi.check(capi.lib().miflow_selftest_farneback_poly_exp(FB_POLY_FORMS[form], _ref(src), _ref(dst), polyN, polySigma, capi.current_stream_ptr()))
+    return dst
+
+
+def farneback_updateMatrices_form(form, R0, R1, flowx=None, flowy=None, prevx=None, prevy=None, alpha=1.0):
+    """'plain': M(flowx, flowy); 'zero': M of the zero flow, no flow planes; 'resized': flow = resize(prev) * alpha and M(flow) in one
+    launch.  -> (M, flowx, flowy)."""
+    import torch
+    M = torch.empty_like(R0)
+    if form == "resized":
+        flowx = torch.empty((R0.shape[0] // 5, R0.shape[1]), dtype=torch.float32, device=R0.device)
+        flowy = torch.empty_like(flowx)
+    capi.check(capi.lib().miflow_selftest_farneback_update_matrices(FB_UPDATE_FORMS[form], _ref(prevx), _ref(prevy), float(alpha), _ref(flowx), _ref(flowy),
+                                                                    _ref(R0), _ref(R1), _ref(M), capi.current_stream_ptr()))
+    return M, flowx, flowy
+
+
+def farneback_gaussianBlur_form(form, src, ksize, sigma, border=4, src1=None):
+    """'table': src and src1 are pitched uint8 or float32 views, read in place -> (dst0, dst1); the other forms -> dst."""
+    import torch
+    dst = torch.empty(tuple(src.shape), dtype=torch.float32, device=src.device)
+    dst1 = torch.empty_like(dst) if form == "table" else None
+    capi.check(capi.lib().miflow_selftest_farneback_gaussian_blur(FB_BLUR_FORMS[form], _ref(src), _ref(src1), _ref(dst), _ref(dst1), ksize, float(sigma),
+                                                                  border, capi.current_stream_ptr()))
+    return (dst, dst1) if form == "table" else dst
+
+
 def farneback_gaussianBlur(src, ksize, sigma, border=4):
     import torch
     dst = torch.empty_like(src)

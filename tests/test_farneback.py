@@ -1,23 +1,39 @@
 """Farneback: oracle self-tests (CPU) and HIP-vs-oracle parity (GPU) for cv::cuda::FarnebackOpticalFlow.
 
-Tolerances (float path, stated):
-  * stage level: same binary32 operations in the same order on both sides (-ffp-contract=off); the only
-    freedom is libm exp() in the host-side kernel tables (identical code path: both computed on the host
-    with the same formula) -> atol 1e-5 relative to plane magnitude (rtol 2e-6);
-  * full calc vs oracle: mean EPE <= 2e-3 px and |1-CCORR| <= 1e-5 -- far inside the reference's own
-    CUDA-vs-CPU acceptance |1-CCORR| <= 1e-4 (box) / 2e-2 (Gaussian), cudaoptflow/test/test_optflow.cpp:349.
+Every comparison of a kernel or of a whole calc with the oracle is EQUALITY of every value (np.testing.assert_array_equal):
+  * stage level: kernel and oracle/farneback_ref.c perform the same binary32 operations in the same order, both built with
+    -ffp-contract=off; the division of the 2 x 2 solve is correctly rounded on both sides; the Gaussian taps and the inverse moment
+    matrix are formed on the host by the same double formula.  Every launch form of every stage -- one-row, 256 x 4 and 64 x 4 tiles,
+    two iterations per launch, the merged output, update 0 / 1, tiled and resize-sampling expansion, zero-flow and resize-fused matrix
+    update, generic / tiled / in-place table blur -- is launched by name (cuda.farneback_*_form) at shapes that hold every tile edge
+    and compared with the oracle and with the other forms.  Measured on an MI355X: 0 differing values in 3 188 comparisons.
+  * whole calc (tests/fb_flow_check.py, shared with tests/test_golden.py and tests/test_ref_class_gpu.py): a calc is a fixed sequence
+    of those stages, so the flow equals the oracle's at every pixel.  Measured GPU-versus-oracle maximum over the reference's parameter
+    grid (12 cases, 388 x 584), config 1, the 24 configurations of the seeded sweep, fast pyramids, initial flow, the batches and the
+    three golden files: 0 px, 0 differing values.  The mean-EPE <= 2e-3 px / |1 - CCORR| <= 1e-5 criterion these tests used before
+    passed with 0.15 px added to a whole column of a 388 x 584 flow.
+  * for scale, the reference algorithm's own sensitivity to rounding: the oracle as committed against the same sources compiled with
+    -mfma -ffp-contract=fast, over the same configurations -- mean difference at most 2.4e-5 px, worst pixel typically 3e-6 .. 1e-4 px
+    and 0.16 px at isolated pixels of one sweep configuration (floor() of the displaced position in the matrix update amplifies one
+    ulp).  A bound derived from it would be orders looser than what holds; no bound is used.
+  * the reference's own CUDA-vs-CPU acceptance is |1 - CCORR| <= 1e-4 (box) / 2e-2 (Gaussian), cudaoptflow/test/test_optflow.cpp:349.
 """
 import os
+import sys
 
 import numpy as np
 import pytest
 
 from opencv_contrib_amd import synth
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from fb_flow_check import assert_flow_equals as _assert_flow  # noqa: E402
+
 
 def T(a, dev):
     import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    a = np.ascontiguousarray(a)
+    return torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)   # (the shared stage inputs are read-only)
 
 
 def N(t):
@@ -83,6 +99,26 @@ def test_oracle_initial_flow_and_fast_pyramids(oracle):
     assert synth.epe(f2[30:-30, 30:-30], gt[30:-30, 30:-30]) < 0.12
 
 
+def test_oracle_blur_border_is_a_reflection_while_the_half_size_stays_below_the_plane(oracle):
+    """BrdReflect101 as the oracle (and the kernels) state it, abs(abs(last - abs(last - i)) % n) % n, is the mirror image without the
+    border pixel for |offset| <= n - 1; further out its modulo wraps (the reference's formula, not a second fold).  Checked through the
+    blur against NumPy's 'reflect' padding with the taps summed in the same order: equal up to half size n - 1 of the smaller dimension."""
+    rng = np.random.default_rng(0)
+    for shape in ((5, 40), (37, 4)):
+        img = rng.random(shape, dtype=np.float32)
+        h, w = shape
+        for kh in range(1, min(shape)):
+            k = oracle.fb_gaussian_kernel(2 * kh + 1, 0.3 * kh + 0.8)
+            p = np.pad(img, kh, mode="reflect")
+            v = p[kh:kh + h] * k[kh]
+            for j in range(1, kh + 1):
+                v = v + (p[kh - j:kh - j + h] + p[kh + j:kh + j + h]) * k[kh + j]
+            out = v[:, kh:kh + w] * k[kh]
+            for j in range(1, kh + 1):
+                out = out + (v[:, kh - j:kh - j + w] + v[:, kh + j:kh + j + w]) * k[kh + j]
+            np.testing.assert_array_equal(oracle.fb_gaussian_blur(img, 2 * kh + 1, 0.3 * kh + 0.8), out, err_msg=f"{shape} half {kh}")
+
+
 def test_oracle_argument_errors(oracle):
     I = np.zeros((64, 64), np.uint8)
     with pytest.raises(ValueError):
@@ -99,9 +135,15 @@ def test_oracle_argument_errors(oracle):
 gpu_mark = pytest.mark.gpu
 
 
-def _close(a, b, name=""):
-    scale = max(float(np.abs(b).max()), 1e-6)
-    np.testing.assert_allclose(a, b, rtol=2e-6, atol=1e-6 * scale, err_msg=name)
+def _same(a, b, name):
+    """Bit equality, with the figures printed first (run with -s to see them)."""
+    a, b = np.asarray(a), np.asarray(b)
+    assert a.shape == b.shape, name
+    ne = a != b
+    if ne.any():
+        print(f"{name}: {int(ne.sum())} of {a.size} values differ, worst |a - b| {np.abs(a.astype(np.float64) - b)[ne].max():.3e} "
+              f"at scale {np.abs(b).max():.3e}")
+    np.testing.assert_array_equal(a, b, err_msg=name)
 
 
 @gpu_mark
@@ -111,7 +153,7 @@ def test_poly_exp_matches_oracle(gpu, oracle, shape, polyN, sigma):
     from opencv_contrib_amd import cuda
     img = np.random.default_rng(1).random(shape, dtype=np.float32) * 255
     ref = oracle.fb_poly_exp(img, polyN, sigma)
-    _close(N(cuda.farneback_polyExp(T(img, gpu), polyN, sigma)), ref)
+    _same(N(cuda.farneback_polyExp(T(img, gpu), polyN, sigma)), ref, "poly_exp")
 
 
 def _fb_state(h, w, seed, amp=2.0):
@@ -131,29 +173,275 @@ def test_update_matrices_matches_oracle(gpu, oracle, shape, amp):
     R0, R1 = oracle.fb_poly_exp(I0), oracle.fb_poly_exp(I1)
     ref = oracle.fb_update_matrices(fx, fy, R0, R1)
     out = cuda.farneback_updateMatrices(T(fx, gpu), T(fy, gpu), T(R0, gpu), T(R1, gpu))
-    _close(N(out), ref)
+    _same(N(out), ref, "update_matrices")
+
+
+# ---- every launch form of a stage, one by one (cuda.farneback_*_form -> miflow_selftest_farneback_*): the level loop picks a form from
+# the grid size and the tuning of the process, so a calc at a test's size runs a minority of them
+# (7, 9): smaller than any tile and than 2 KH.  (61, 277): two 256- and five 64-column tiles, the last ragged in both directions, 16 row
+# tiles.  (9, 513): a third 256-column tile of one column.  Tile grids of 2, 9 and 27 workgroups are no multiples of 8: the remainder
+# branch of the XCD tile swizzle (the 32 and 80 workgroups of 61 x 277 take the other one).
+_STAGE_SHAPES = [(7, 9), (61, 277), (9, 513)]
+_TILED_WINDOWS = (9, 13, 15, 21)                # KH 4, 6, 7, 10: k_iterate_t; the first three also k_iterate2_t
+_SENTINEL = np.float32(-12345.5)
+
+
+_stage_cache = {}
+
+
+def _stage_state(oracle, shape, seed, amp):
+    """Random planes of one shape and their oracle expansions and matrices, computed once and read-only."""
+    key = (shape, seed, amp)
+    if key not in _stage_cache:
+        I0, I1, fx, fy = _fb_state(*shape, seed=seed, amp=amp)
+        R0, R1 = oracle.fb_poly_exp(I0), oracle.fb_poly_exp(I1)
+        st = dict(I0=I0, I1=I1, fx=fx, fy=fy, R0=R0, R1=R1, M=oracle.fb_update_matrices(fx, fy, R0, R1))
+        for v in st.values():
+            v.setflags(write=False)
+        _stage_cache[key] = st
+    return _stage_cache[key]
+
+
+def _oracle_iteration(oracle, M, R0, R1, ksize, gauss):
+    """boxFilter5 / gaussianBlur5 -> updateFlow -> updateMatrices, the three launches one fused iteration stands for"""
+    Mb = oracle.fb_blur5(M, ksize, float(ksize // 2 * np.float32(0.3)) if gauss else None)
+    fx, fy = oracle.fb_update_flow(Mb)
+    return fx, fy, oracle.fb_update_matrices(fx, fy, R0, R1)
+
+
+def _check_updated_matrices(oracle, Mg, gfx, gfy, rfx, rfy, Mref, R0, R1, name):
+    """The matrix update takes floor() of the displaced position: M' is held to the oracle's update of the GPU's OWN flow, and to the
+    oracle chain wherever the flow bits agree -- a flow difference of one ulp cannot excuse a wrong M'."""
+    _same(Mg, oracle.fb_update_matrices(gfx, gfy, R0, R1), name + " M' vs the oracle update of the GPU's flow")
+    agree = np.tile((gfx == rfx) & (gfy == rfy), (5, 1))
+    _same(Mg[agree], Mref[agree], name + " M' vs the oracle chain where the flows agree")
+
+
+def _check_iterate_forms(gpu, oracle, shape, seed, amp, ksize, gauss):
+    from opencv_contrib_amd import capi, cuda
+    st = _stage_state(oracle, shape, seed, amp)
+    h, w = shape
+    M, R0, R1 = st["M"], st["R0"], st["R1"]
+    tM, tR0, tR1 = T(M, gpu), T(R0, gpu), T(R1, gpu)
+    rfx, rfy, M2 = _oracle_iteration(oracle, M, R0, R1, ksize, gauss)
+    pattern = (np.arange(5 * h * w, dtype=np.float32).reshape(5 * h, w) * np.float32(0.25) + _SENTINEL)
+    tiled = ksize in _TILED_WINDOWS
+    forms = ["row"] + (["tile256", "tile64"] if tiled else [])
+    tag = f"{shape} amp {amp} win {ksize} {'gauss' if gauss else 'box'}"
+    out = {}
+    for update in (True, False):
+        for f in forms:
+            fx, fy, Mo = cuda.farneback_iterate_form(f, tM, tR0, tR1, ksize, gauss, update, Mout=T(pattern, gpu))
+            out[f, update] = N(fx), N(fy), N(Mo)
+        gfx, gfy, gM = out["row", update]
+        for f in forms[1:]:   # 1. the forms against each other
+            for a, b, n in zip(out[f, update], out["row", update], ("flowx", "flowy", "Mout")):
+                _same(a, b, f"{tag} update {update}: {f} vs row, {n}")
+        _same(gfx, rfx, f"{tag} update {update}: flowx vs oracle")   # 2. against the oracle
+        _same(gfy, rfy, f"{tag} update {update}: flowy vs oracle")
+        if update:
+            _check_updated_matrices(oracle, gM, gfx, gfy, rfx, rfy, M2, R0, R1, tag)
+        else:
+            _same(gM, pattern, f"{tag}: update = 0 must leave Mout alone")
+    if not tiled:
+        for f in ("tile256", "tile64", "pair"):
+            with pytest.raises(capi.MiError):
+                cuda.farneback_iterate_form(f, tM, tR0, tR1, ksize, gauss, True)
+        return
+    # 3. the merged CV_32FC2 output: a pitched matrix inside a buffer of sentinels
+    import torch
+
+    def merged_buf():
+        buf = torch.full((h, w + 5, 2), float(_SENTINEL), dtype=torch.float32, device=gpu)
+        return buf, buf[:, 2:2 + w]
+
+    def check_merged(buf, fx, fy, name):
+        b = N(buf)
+        _same(b[:, 2:2 + w], np.stack([fx, fy], -1), name + ": merged flow vs the planes")
+        assert (b[:, :2] == _SENTINEL).all() and (b[:, 2 + w:] == _SENTINEL).all(), name + ": padding of the merged matrix written"
+
+    for f in forms[1:]:
+        for update in (True, False):
+            buf, view = merged_buf()
+            fx, fy, Mo = cuda.farneback_iterate_form(f, tM, tR0, tR1, ksize, gauss, update, Mout=T(pattern, gpu), merged=view)
+            for a, b, n in zip((N(fx), N(fy), N(Mo)), out[f, update], ("flowx", "flowy", "Mout")):
+                _same(a, b, f"{tag} update {update}: {f} with the merged output, {n}")
+            check_merged(buf, N(fx), N(fy), f"{tag} {f} update {update}")
+    with pytest.raises(capi.MiError):
+        cuda.farneback_iterate_form("row", tM, tR0, tR1, ksize, gauss, True, merged=merged_buf()[1])
+    # two iterations per launch = two launches of a one-iteration form with M and Mout swapped in between, as the level loop swaps them
+    if ksize == 21:
+        with pytest.raises(capi.MiError):
+            cuda.farneback_iterate_form("pair", tM, tR0, tR1, ksize, gauss, True)
+        return
+    tM1 = T(out["tile64", True][2], gpu)
+    r2fx, r2fy, M3 = _oracle_iteration(oracle, M2, R0, R1, ksize, gauss)
+    for update in (True, False):
+        two = cuda.farneback_iterate_form("tile64", tM1, tR0, tR1, ksize, gauss, update, Mout=T(pattern, gpu))
+        buf, view = merged_buf()
+        pair = cuda.farneback_iterate_form("pair", tM, tR0, tR1, ksize, gauss, update, Mout=T(pattern, gpu), merged=view)
+        bare = cuda.farneback_iterate_form("pair", tM, tR0, tR1, ksize, gauss, update, Mout=T(pattern, gpu))
+        for a, b, c, n in zip(pair, bare, two, ("flowx", "flowy", "Mout")):
+            _same(N(a), N(c), f"{tag} update {update}: pair vs two launches, {n}")
+            _same(N(b), N(c), f"{tag} update {update}: pair without the merged output vs two launches, {n}")
+        check_merged(buf, N(pair[0]), N(pair[1]), f"{tag} pair update {update}")
+        pfx, pfy, pM = (N(t) for t in pair)
+        if np.array_equal(out["tile64", True][2], M2):   # the first iteration equals the oracle's: so must the second
+            _same(pfx, r2fx, f"{tag} update {update}: pair flowx vs two oracle iterations")
+            _same(pfy, r2fy, f"{tag} update {update}: pair flowy vs two oracle iterations")
+        if update:
+            _check_updated_matrices(oracle, pM, pfx, pfy, r2fx, r2fy, M3, R0, R1, tag + " pair")
+        else:
+            _same(pM, pattern, f"{tag}: pair with update = 0 must leave Mout alone")
 
 
 @gpu_mark
 @pytest.mark.parametrize("ksize,gauss", [(13, False), (13, True), (5, False), (31, True)])
 def test_blur5_update_flow_and_fused_iteration_match_oracle(gpu, oracle, ksize, gauss):
+    """blur5 and updateFlow as separate launches, then the fused iteration in every form it has at this window size: the forms equal each
+    other and the oracle's boxFilter5 / gaussianBlur5 -> updateFlow -> updateMatrices chain bit for bit (same binary32 operations in
+    the same order on both sides, -ffp-contract=off, correctly rounded division; the Gaussian taps come from the same host formula)."""
     from opencv_contrib_amd import cuda
     h, w = 61, 277
-    I0, I1, fx, fy = _fb_state(h, w, seed=7)
-    R0, R1 = oracle.fb_poly_exp(I0), oracle.fb_poly_exp(I1)
-    M = oracle.fb_update_matrices(fx, fy, R0, R1)
+    st = _stage_state(oracle, (h, w), 7, 2.0)
+    M = st["M"]
     sig = (ksize // 2 * np.float32(0.3)) if gauss else None
     Mb = oracle.fb_blur5(M, ksize, float(sig) if gauss else None)
-    _close(N(cuda.farneback_blur5(T(M, gpu), ksize, gauss)), Mb, "blur5")
+    _same(N(cuda.farneback_blur5(T(M, gpu), ksize, gauss)), Mb, "blur5")
     rfx, rfy = oracle.fb_update_flow(Mb)
     gfx, gfy = cuda.farneback_updateFlow(T(Mb, gpu))
-    _close(N(gfx), rfx, "flowx"); _close(N(gfy), rfy, "flowy")
-    M2 = oracle.fb_update_matrices(rfx, rfy, R0, R1)
-    ifx, ify, iM = cuda.farneback_iterate(T(M, gpu), T(R0, gpu), T(R1, gpu), ksize, gauss, True)
-    # the fused kernel divides once per pixel like updateFlow; flows agree to float rounding, M' follows
-    np.testing.assert_allclose(N(ifx), rfx, rtol=1e-4, atol=1e-5)
-    np.testing.assert_allclose(N(ify), rfy, rtol=1e-4, atol=1e-5)
-    np.testing.assert_allclose(N(iM), M2, rtol=1e-3, atol=1e-3 * np.abs(M2).max())
+    _same(N(gfx), rfx, "flowx"); _same(N(gfy), rfy, "flowy")
+    # the entry calc()'s dispatch serves (whatever form it picks here) ...
+    ifx, ify, iM = (N(t) for t in cuda.farneback_iterate(T(M, gpu), T(st["R0"], gpu), T(st["R1"], gpu), ksize, gauss, True))
+    M2 = oracle.fb_update_matrices(rfx, rfy, st["R0"], st["R1"])
+    _same(ifx, rfx, "iterate flowx"); _same(ify, rfy, "iterate flowy")
+    _check_updated_matrices(oracle, iM, ifx, ify, rfx, rfy, M2, st["R0"], st["R1"], "iterate")
+    # ... and every named form
+    _check_iterate_forms(gpu, oracle, (h, w), 7, 2.0, ksize, gauss)
+
+
+@gpu_mark
+@pytest.mark.parametrize("ksize,gauss", [(k, g) for k in _TILED_WINDOWS for g in (False, True)] + [(11, False), (27, True)])
+@pytest.mark.parametrize("amp", [1.5, 30.0])
+@pytest.mark.parametrize("shape", _STAGE_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_every_iterate_form_matches_oracle_and_the_other_forms(gpu, oracle, shape, amp, ksize, gauss):
+    """One-row k_iterate, k_iterate_t on 256 x 4 and on 64 x 4 tiles, k_iterate2_t (two iterations per launch; windows 9 / 13 / 15), box
+    and Gaussian windows, update 0 / 1, with and without the merged CV_32FC2 output, on planes whose matrices come from flows of 1.5 and
+    30 px (many displaced positions leave the image).  1. all forms give the same bytes; 2. they are the bytes of the oracle chain
+    (M' against the oracle's update of the GPU's own flow as well); 3. the merged matrix holds the interleaved planes and its padding
+    is untouched, update = 0 leaves Mout alone; a form without a kernel for the window is an error."""
+    _check_iterate_forms(gpu, oracle, shape, 11, amp, ksize, gauss)
+
+
+_POLY_SHAPES = {5: _STAGE_SHAPES + [(9, 246), (9, 247), (17, 484), (9, 485)],     # usable tile width 256 - 2 N: one / two tiles exactly, and
+                7: _STAGE_SHAPES + [(9, 242), (9, 243), (17, 484), (9, 485)]}     # one column more; 9 and 17 rows: a ragged second / third row tile
+
+
+@gpu_mark
+@pytest.mark.parametrize("polyN,sigma,shape", [(n, s, shp) for n, s in ((5, 1.1), (7, 1.5)) for shp in _POLY_SHAPES[n]],
+                         ids=lambda v: f"{v[0]}x{v[1]}" if isinstance(v, tuple) else str(v))
+def test_every_poly_exp_form_matches_oracle_and_the_other_forms(gpu, oracle, polyN, sigma, shape):
+    """k_poly_exp (one row), k_poly_exp_t (8-row tiles; calc() runs it from 1024 workgroups on) and k_poly_exp<N, true>, which samples
+    cuda::resize of a larger blurred plane on the fly (scale factors formed as poly_exp() forms them): equal to each other and to the
+    oracle's fb_poly_exp (after resize_linear_cuda for the resized form) bit for bit."""
+    from opencv_contrib_amd import capi, cuda
+    h, w = shape
+    img = np.random.default_rng(1).random(shape, dtype=np.float32) * 255
+    ref = oracle.fb_poly_exp(img, polyN, sigma)
+    row = N(cuda.farneback_polyExp_form("row", T(img, gpu), polyN, sigma))
+    _same(N(cuda.farneback_polyExp_form("tiled", T(img, gpu), polyN, sigma)), row, "tiled vs row")
+    _same(row, ref, "row vs oracle")
+    for sshape in ((2 * h + 1, 2 * w - 1), (int(h / 0.8) + 1, int(w / 0.8))):   # about pyrScale 0.5 and 0.8
+        big = np.random.default_rng(2).random(sshape, dtype=np.float32) * 255
+        lvl = oracle.resize_linear_cuda(big, dsize=(w, h))
+        _same(N(cuda.farneback_polyExp_form("resized", T(big, gpu), polyN, sigma, dsize=shape)), oracle.fb_poly_exp(lvl, polyN, sigma),
+              f"resized from {sshape} vs oracle")
+        _same(N(cuda.farneback_polyExp_form("row", T(lvl, gpu), polyN, sigma)), oracle.fb_poly_exp(lvl, polyN, sigma), "row on the resized plane")
+    with pytest.raises(capi.MiError):
+        cuda.farneback_polyExp_form("resized", T(img, gpu), polyN, sigma, dsize=shape)   # nothing to resize
+
+
+@gpu_mark
+@pytest.mark.parametrize("amp", [1.5, 30.0])
+@pytest.mark.parametrize("shape", _STAGE_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_every_update_matrices_form_matches_oracle(gpu, oracle, shape, amp):
+    """k_update_matrices with flow planes, with the zero flow of the coarsest level (null planes), and k_update_matrices_rs, which
+    samples cuda::resize of the coarser level's flow, multiplies by 1 / pyrScale, stores the flow and updates in one launch."""
+    from opencv_contrib_amd import cuda
+    h, w = shape
+    st = _stage_state(oracle, shape, 3, amp)
+    fx, fy, R0, R1 = st["fx"], st["fy"], st["R0"], st["R1"]
+    tR0, tR1 = T(R0, gpu), T(R1, gpu)
+    M, _, _ = cuda.farneback_updateMatrices_form("plain", tR0, tR1, T(fx, gpu), T(fy, gpu))
+    _same(N(M), st["M"], "plain vs oracle")
+    _same(N(cuda.farneback_updateMatrices(T(fx, gpu), T(fy, gpu), tR0, tR1)), st["M"], "the stage entry vs oracle")
+    M, _, _ = cuda.farneback_updateMatrices_form("zero", tR0, tR1)
+    z = np.zeros(shape, np.float32)
+    _same(N(M), oracle.fb_update_matrices(z, z, R0, R1), "zero flow vs oracle")
+    for pshape, scale in (((max(h // 2, 2), max(w // 2, 2)), 0.5), ((max(int(h * 0.8), 2), max(int(w * 0.8), 2)), 0.8), (shape, 0.5)):
+        _, _, px, py = _fb_state(*pshape, seed=5, amp=amp)
+        alpha = np.float32(1.0 / scale)
+        rx, ry = (oracle.resize_linear_cuda(p, dsize=(w, h)) * alpha for p in (px, py))
+        if pshape == shape:
+            continue   # (the level loop never fuses a zoom between equal sizes: cuda::resize is a copy there)
+        M, gx, gy = (N(t) for t in cuda.farneback_updateMatrices_form("resized", tR0, tR1, prevx=T(px, gpu), prevy=T(py, gpu), alpha=alpha))
+        _same(gx, rx, f"resized from {pshape}: flowx vs oracle"); _same(gy, ry, f"resized from {pshape}: flowy vs oracle")
+        _check_updated_matrices(oracle, M, gx, gy, rx, ry, oracle.fb_update_matrices(rx, ry, R0, R1), R0, R1, f"resized from {pshape}")
+
+
+# the stage shapes, a plane of five rows and one of four columns (kernel half size >= a plane dimension: REFLECT101 folds more than once)
+_BLUR_SHAPES = _STAGE_SHAPES + [(5, 300), (53, 4)]
+
+
+@gpu_mark
+@pytest.mark.parametrize("border", [4, 1], ids=["reflect101", "replicate"])
+@pytest.mark.parametrize("shape", _BLUR_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_every_gaussian_blur_form_matches_oracle_and_the_other_forms(gpu, oracle, shape, border):
+    """The generic kernel with the one-fold border index (FAST) and with the reference's full BrdReflect101 formula, the tiled kernel
+    (half sizes 1, 2, 3, 4, 9, 19), and the table kernels that read a pitched 8-bit / float pair of the caller's in place.  Half sizes
+    up to 19 on planes down to 4 columns / 5 rows: where the half size reaches a plane dimension only the full formula may run (the
+    one-fold forms must refuse).  Out there BrdReflect101's modulo wraps instead of folding a second time
+    (test_oracle_blur_border_is_a_reflection_while_the_half_size_stays_below_the_plane); oracle and kernel state that same formula, so
+    equality is asked for every half size."""
+    import torch
+    from opencv_contrib_amd import capi, cuda
+    h, w = shape
+    rng = np.random.default_rng(2)
+    img = rng.random(shape, dtype=np.float32) * 255
+    u8 = [rng.integers(0, 256, shape, dtype=np.uint8) for _ in range(2)]
+    t = T(img, gpu)
+    for kh in (1, 2, 3, 4, 5, 6, 8, 9, 19):
+        ksize, sigma = 2 * kh + 1, 0.3 * kh + 0.8
+        ref = oracle.fb_gaussian_blur(img, ksize, sigma, border)
+        one_fold = kh < w and kh < h
+        has_tile = one_fold and kh in (1, 2, 3, 4, 9, 19)
+        tag = f"{shape} half {kh} border {border}"
+        _same(N(cuda.farneback_gaussianBlur_form("generic_full", t, ksize, sigma, border)), ref, tag + ": generic, full border formula, vs oracle")
+        _same(N(cuda.farneback_gaussianBlur(t, ksize, sigma, border)), ref, tag + ": the stage entry vs oracle")
+        for form, ok in (("generic_fast", one_fold), ("tiled", has_tile)):
+            if ok:
+                _same(N(cuda.farneback_gaussianBlur_form(form, t, ksize, sigma, border)), ref, f"{tag}: {form} vs oracle")
+            else:
+                with pytest.raises(capi.MiError):
+                    cuda.farneback_gaussianBlur_form(form, t, ksize, sigma, border)
+        if border != 4:
+            continue
+        # table forms: pitched sources read in place, 8-bit converted on the fly; the oracle blurs the converted image
+        b8 = [torch.full((h, w + 7), 77, dtype=torch.uint8, device=gpu) for _ in range(2)]
+        bf = [torch.full((h, w + 5), 1e9, dtype=torch.float32, device=gpu) for _ in range(2)]
+        for k in range(2):
+            b8[k][:, 3:3 + w] = T(u8[k], gpu)
+            bf[k][:, 1 + k:1 + k + w] = T(img if k == 0 else img[::-1, ::-1], gpu)
+        srcs = {"8-bit": ([b8[0][:, 3:3 + w], b8[1][:, 3:3 + w]], [u8[0].astype(np.float32), u8[1].astype(np.float32)]),
+                "float": ([bf[0][:, 1:1 + w], bf[1][:, 2:2 + w]], [img, np.ascontiguousarray(img[::-1, ::-1])])}
+        for name, (views, hosts) in srcs.items():
+            if has_tile:
+                d0, d1 = cuda.farneback_gaussianBlur_form("table", views[0], ksize, sigma, border, src1=views[1])
+                _same(N(d0), oracle.fb_gaussian_blur(hosts[0], ksize, sigma, border), f"{tag}: table form, {name} frame 0 vs oracle")
+                _same(N(d1), oracle.fb_gaussian_blur(hosts[1], ksize, sigma, border), f"{tag}: table form, {name} frame 1 vs oracle")
+            else:
+                with pytest.raises(capi.MiError):
+                    cuda.farneback_gaussianBlur_form("table", views[0], ksize, sigma, border, src1=views[1])
 
 
 @gpu_mark
@@ -162,18 +450,15 @@ def test_blur5_update_flow_and_fused_iteration_match_oracle(gpu, oracle, ksize, 
 def test_gaussian_blur_and_pyr_down_match_oracle(gpu, oracle, border, ksize, sigma):
     from opencv_contrib_amd import cuda
     img = np.random.default_rng(2).random((53, 300), dtype=np.float32) * 255
-    _close(N(cuda.farneback_gaussianBlur(T(img, gpu), ksize, sigma, border)), oracle.fb_gaussian_blur(img, ksize, sigma, border))
+    _same(N(cuda.farneback_gaussianBlur(T(img, gpu), ksize, sigma, border)), oracle.fb_gaussian_blur(img, ksize, sigma, border), "gaussian_blur")
     if border == 4 and ksize == 3:
         for shp in ((53, 300), (32, 33), (7, 9)):
             im = np.random.default_rng(3).random(shp, dtype=np.float32)
             np.testing.assert_array_equal(N(cuda.pyrDown(T(im, gpu))), oracle.fb_pyr_down(im))
 
 
-def _assert_flow_close(flow, ref, mean_epe=2e-3, ccorr=1e-5):
-    assert np.isfinite(flow).all()
-    d = np.sqrt(((flow - ref) ** 2).sum(-1))
-    assert d.mean() <= mean_epe, f"mean EPE {d.mean()}"
-    assert synth.ccorr_dissimilarity(flow, ref) <= ccorr
+def _assert_flow_equal(flow, ref, what=""):
+    _assert_flow(flow, ref, what)   # tests/fb_flow_check.py: the one whole-calc criterion, shared with test_golden.py and test_ref_class_gpu.py
 
 
 @gpu_mark
@@ -189,7 +474,7 @@ def test_calc_matches_oracle_reference_test_parameters(gpu, oracle, pyrScale, po
     ref = oracle.fb_calc(I0, I1, p)
     alg = cuda.FarnebackOpticalFlow.create(pyrScale=pyrScale, polyN=polyN, polySigma=sigma, flags=flags)
     flow = N(alg.calc(T(I0, gpu), T(I1, gpu)))
-    _assert_flow_close(flow, ref)
+    _assert_flow_equal(flow, ref)
 
 
 @gpu_mark
@@ -201,7 +486,7 @@ def test_calc_config1_defaults_640x480(gpu, oracle):
     alg = cuda.FarnebackOpticalFlow.create()
     assert alg.getDefaultName() == "DenseOpticalFlow.FarnebackOpticalFlow" and alg.getWinSize() == 13
     flow = N(alg.calc(T(I0, gpu), T(I1, gpu)))
-    _assert_flow_close(flow, ref)
+    _assert_flow_equal(flow, ref)
     assert synth.epe(flow[40:-40, 40:-40], gt[40:-40, 40:-40]) < 0.08
 
 
@@ -213,7 +498,7 @@ def test_calc_initial_flow_fast_pyramids_f32_and_pitched(gpu, oracle):
     # fastPyramids
     ref = oracle.fb_calc(I0, I1, oracle.fb_params(fast_pyramids=1))
     alg = cuda.FarnebackOpticalFlow.create(fastPyramids=True)
-    _assert_flow_close(N(alg.calc(T(I0, gpu), T(I1, gpu))), ref)
+    _assert_flow_equal(N(alg.calc(T(I0, gpu), T(I1, gpu))), ref)
     # initial flow (flags = USE_INITIAL_FLOW), pitched float frames and pitched flow
     F0, F1 = I0.astype(np.float32), I1.astype(np.float32)
     ref = oracle.fb_calc(F0, F1, oracle.fb_params(flags=4, num_iters=3, num_levels=3), init_flow=gt)
@@ -222,7 +507,7 @@ def test_calc_initial_flow_fast_pyramids_f32_and_pitched(gpu, oracle):
     buf0[:, 5:325] = T(F0, gpu); buf1[:, 1:321] = T(F1, gpu); fbuf[:, 3:323] = T(gt, gpu)
     alg = cuda.FarnebackOpticalFlow.create(numLevels=3, numIters=3, flags=cuda.OPTFLOW_USE_INITIAL_FLOW)
     out = alg.calc(buf0[:, 5:325], buf1[:, 1:321], fbuf[:, 3:323])
-    _assert_flow_close(N(out), ref)
+    _assert_flow_equal(N(out), ref)
 
 
 @gpu_mark
@@ -270,7 +555,7 @@ def test_calc_batch_equals_single_calcs(gpu, oracle, kw):
     assert not torch.equal(out[0], out[1])
     if not kw.get("flags", 0) & 4:
         p = oracle.fb_params(fast_pyramids=int(kw.get("fastPyramids", False)), flags=kw.get("flags", 0), win_size=kw.get("winSize", 13))
-        _assert_flow_close(N(out[3]), oracle.fb_calc(pairs[3][0], pairs[3][1], p))
+        _assert_flow_equal(N(out[3]), oracle.fb_calc(pairs[3][0], pairs[3][1], p))
     # a smaller batch through the same handle afterwards (capacity is kept), and a larger one (arena regrown)
     again = alg.calc_batch(I0s[:2], I1s[:2], None if flows is None else torch.stack(init[:2]).clone())
     assert torch.equal(again[1], singles[1])
@@ -460,7 +745,7 @@ def test_random_configuration_matches_oracle(gpu, oracle, cfg):
     else:
         flows = list(alg.calc_batch([T(p[0], gpu) for p in pairs], [T(p[1], gpu) for p in pairs]))
     for b, p in enumerate(pairs):
-        _assert_flow_close(N(flows[b]), oracle.fb_calc(p[0], p[1], oracle.fb_params(**okw)))
+        _assert_flow_equal(N(flows[b]), oracle.fb_calc(p[0], p[1], oracle.fb_params(**okw)))
 
 
 @pytest.mark.gpu

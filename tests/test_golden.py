@@ -4,11 +4,14 @@ them (GPU) with the same tolerances as the direct HIP-vs-oracle tests."""
 import glob
 import json
 import os
+import sys
 
 import numpy as np
 import pytest
 
-from opencv_contrib_amd import synth
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from fb_flow_check import assert_flow_equals  # noqa: E402
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
@@ -152,8 +155,7 @@ def test_farneback_hip_matches_golden(gpu, path):
     alg = cuda.FarnebackOpticalFlow.create(numLevels=kw.get("num_levels", 5), fastPyramids=bool(kw.get("fast_pyramids", 0)),
                                            polyN=kw.get("poly_n", 5), polySigma=kw.get("poly_sigma", 1.1), flags=kw.get("flags", 0))
     flow = alg.calc(T(z["I0"], gpu), T(z["I1"], gpu)).cpu().numpy()
-    d = np.sqrt(((flow - z["flow"]) ** 2).sum(-1))
-    assert d.mean() <= 2e-3 and synth.ccorr_dissimilarity(flow, z["flow"]) <= 1e-5
+    assert_flow_equals(flow, z["flow"], os.path.basename(path))   # tests/fb_flow_check.py
 
 
 @pytest.mark.gpu

@@ -11,11 +11,17 @@ HIP-vs-oracle tests of each class (integer paths bit-exact) -- the oracle equals
 The last section does the same for superres' BTVL1_CUDA (superres/src/btv_l1_cuda.cpp verbatim over btv_l1_gpu.cu and the cudafilters /
 cudawarping / cudaarithm kernels it runs; pinned to the restatement by tests/test_ref_pin_btvl1.py): 0 differing values.
 """
+import os
+import sys
+
 import numpy as np
 import pytest
 
 from opencv_contrib_amd import synth
 from oracle import refcu
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from fb_flow_check import assert_flow_equals  # noqa: E402
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not refcu.available(), reason="oracle/_ref/libref_cu.so not built (needs /root/reference)")]
 
@@ -65,9 +71,7 @@ def test_farneback_hip_vs_the_reference_cuda_class(gpu, kw_ref, kw_hip):
     I0, I1, _ = synth.flow_pair(240, 320, seed=31, dtype="u8")
     ref = refcu.cuda_class_farneback_calc(I0, I1, **kw_ref)
     flow = N(cuda.FarnebackOpticalFlow.create(**kw_hip).calc(T(I0, gpu), T(I1, gpu)))
-    d = np.sqrt(((flow - ref) ** 2).sum(-1))
-    assert np.isfinite(flow).all() and d.mean() <= 2e-3, float(d.mean())       # tests/test_farneback.py::_assert_flow_close
-    assert synth.ccorr_dissimilarity(flow, ref) <= 1e-5
+    assert_flow_equals(flow, ref, str(kw_ref))   # tests/fb_flow_check.py
 
 
 @pytest.mark.parametrize("kw", [dict(), dict(prefilter_type=1), dict(ndisp=128, block=15, uniqueness_ratio=10, texture_threshold=0)])
