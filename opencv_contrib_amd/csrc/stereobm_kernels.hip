@@ -22,7 +22,6 @@
 // caller's GpuMat), then read as aligned dwords + v_alignbyte.
 #include "stereobm_dev.h"
 #include <climits>
-#include <cstdlib>
 #include <type_traits>
 
 namespace mi {
@@ -162,19 +161,6 @@ struct BmArgs {
     long long mpair;
 };
 
-template <int R>
-struct Cfg {
-    static constexpr int TWr = (64 - 2 * R) & ~3;
-    // R <= 12: max SSD (2R+1)^2 * 255^2 < 2^26, so (2^26-1 - SSD) << 6 | tie-break key fits one u32 and the winner is a
-    // single max-reduction, done 16 columns at a time (tile width 48 = 3 groups); larger windows: generic path
-    static constexpr bool PACKED = R <= 12;
-    static constexpr int TW = PACKED ? 48 : (TWr < 16 ? 16 : TWr);   // output columns per tile
-    static constexpr int NC = TW + 2 * R;            // column sums per lane
-    static constexpr int LS = (NC + 15) / 16 * 16;   // LDS bytes per staged left row
-    static constexpr int NLW = LS / 4;               // dwords per left row
-    static constexpr int NRW = (NC + 3) / 4 + 1;     // aligned dwords a lane reads per right row
-};
-
 // MODE 0: winner-take-all.  MODE 1: uniqueness verification of the pass-0 winner.
 // WT (MODE 0, packed windows R <= 12; round 4): winner-take-all through an LDS TRANSPOSITION instead of the transposed DPP reduction.
 // A lane (= disparity) writes the complemented window SSDs of the tile's columns to T[column][lane]; lane i then reads column i's 64
@@ -220,14 +206,13 @@ __global__ __launch_bounds__(256) void k_block_match(BmArgs A)
     const int ncols = min(TW, A.cols - R - X0);        // valid output columns (X < cols - R)
     if (nrows <= 0 || ncols <= 0) return;
     const int srows = nrows + 2 * R;                   // staged rows: Y0-R .. Y0+nrows+R-1
-    const int RS = (NC + ndp - 1 + 3) / 4 * 4 + 4;     // LDS bytes per staged right row
+    const BmLdsT<std::integral_constant<int, R>> lay = {{}, nsets, A.rb, WT};
+    const int RS = lay.RS();                           // LDS bytes per staged right row
     unsigned char *Ls = smem;
-    unsigned char *Rs = smem + (size_t)(A.rb + 2 * R) * LS;
-    unsigned *comb = reinterpret_cast<unsigned *>(Rs + (size_t)(A.rb + 2 * R) * RS);  // [2][nsets][2][64]
-    constexpr int TP = 68;                                                               // dwords per row of the transposition buffer
-    // WT: [16][TP] per wave (one group of 16 columns at a time), behind comb at the next 16-byte boundary (b128 reads)
-    unsigned *Tb = reinterpret_cast<unsigned *>(smem + (((size_t)(A.rb + 2 * R) * (LS + RS) + (size_t)2 * nsets * 128 * sizeof(unsigned) + 15) / 16 * 16)) +
-                   (WT ? (size_t)wset * 16 * TP : 0);
+    unsigned char *Rs = Ls + lay.left();
+    unsigned *comb = reinterpret_cast<unsigned *>(Rs + lay.right());   // [2][nsets][2][64]
+    constexpr int TP = BM_TP;
+    unsigned *Tb = reinterpret_cast<unsigned *>(smem + lay.tbuf()) + (WT ? wset * lay.tstride() / sizeof(unsigned) : 0);   // WT: this wave's [16][TP], one group of 16 columns at a time
 
     // ---- stage the tile rows (byte copies; columns outside the image read as 0 and are never used
     //      by an active lane / valid column)
@@ -642,8 +627,6 @@ __device__ __forceinline__ int tex_sobel(const unsigned char *img, long long ste
 
 // pass 1: S = |x-Sobel of B| on the extended domain x in [-TEX_MX, ...), y in [-TEX_MY, rows + TEX_MY) (coordinates are
 // clamped texel-wise inside tex_box4, exactly like reading the clamp-addressed texture out of range)
-#define TEX_MX 32
-#define TEX_MY 26
 __global__ __launch_bounds__(256) void k_tex_sobel(const unsigned char *img, long long istep, int rows, int cols, int *S, int sld, int sh)
 {
     const int xe = blockIdx.x * 64 + (threadIdx.x & 63);
@@ -699,7 +682,6 @@ __global__ __launch_bounds__(256) void k_textureness(const int *S, int sld, unsi
 // extended by W2, both as 16-bit words in LDS (B <= 1020, S <= 4080), then every wave slides the column sums of its 8 rows exactly
 // as k_textureness does.  Integer arithmetic throughout: the same sums, the same comparison, the same disparities.  blockIdx.z = pair
 // of a batch (images and maps from the block matcher's table).
-#define TEXF_ROWS 32
 __global__ __launch_bounds__(256) void k_textureness_fused(const unsigned char *img, long long istep, unsigned char *disp, long long dstep,
                                                            const BmPair *tab, int rows, int cols, int winsz, float threshold)
 {
@@ -709,11 +691,11 @@ __global__ __launch_bounds__(256) void k_textureness_fused(const unsigned char *
         img = p.left; istep = p.lstep; disp = p.disp; dstep = p.dstep;
     }
     const int W2 = winsz / 2;                          // <= 25
-    const int TC = 64 + 2 * W2, TRR = TEXF_ROWS + 2 * W2;   // S tile
-    const int BC = TC + 2, BR = TRR + 2;               // B tile
+    const TexfLds lay = texf_lds(W2);
+    const int TC = lay.TC, TRR = lay.TRR, BC = lay.BC, BR = lay.BR;   // S tile, B tile
     unsigned short *Bs = reinterpret_cast<unsigned short *>(smem);
-    unsigned short *Ss = Bs + BR * BC;
-    int *cs = reinterpret_cast<int *>(Ss + ((TRR * TC + 1) & ~1)) + (threadIdx.x >> 6) * 128;
+    unsigned short *Ss = Bs + lay.B;
+    int *cs = reinterpret_cast<int *>(Ss + lay.S) + (threadIdx.x >> 6) * 128;
     const int x0 = blockIdx.x * 64, y0 = blockIdx.y * TEXF_ROWS;
     for (int i = threadIdx.x; i < BR * BC; i += 256) {
         const int r = i / BC, c = i - r * BC;
@@ -762,105 +744,45 @@ __global__ __launch_bounds__(256) void k_textureness_fused(const unsigned char *
     }
 }
 
-// ------------------------------------------------------------------ host launchers
+// ------------------------------------------------------------------ host launchers: they EXECUTE a BmPlan (sbm_plan.h)
 template <int R>
-static int launch_bm(const BmArgs &A, int mode, hipStream_t s)
+static int launch_bm(const BmArgs &A, const BmPlan &P, hipStream_t s)
 {
-    using C = Cfg<R>;
-    const int RS = (C::NC + A.nsets * 64 - 1 + 3) / 4 * 4 + 4;
-    size_t lds = (size_t)(A.rb + 2 * R) * (C::LS + RS) + (size_t)2 * A.nsets * 128 * sizeof(unsigned);
-    lds = (lds + 15) / 16 * 16;   // the transposition buffer behind it is read as b128
-    const dim3 grid(div_up(A.cols - A.ndisp - 2 * R, C::TW), div_up(A.rows - 2 * R, A.rb), A.tab ? A.batch : 1);
-    const dim3 block(64 * A.nsets);
-    // one first-pass kernel per radius in the release library: the transposed winner-take-all where the column sums are packed (C::PACKED),
-    // the plain form elsewhere; the experiments build keeps both for MIFLOW_SBM_WT
-#ifdef MIFLOW_EXPERIMENTS
-    const bool wt = C::PACKED && tuning().sbm_wt;
-#else
-    constexpr bool wt = C::PACKED;
-#endif
-    if (mode == 0 && wt) {
-        if constexpr (C::PACKED) {
-            const size_t ldst = lds + (size_t)A.nsets * 16 * 68 * sizeof(unsigned);
-            (void)hipFuncSetAttribute((const void *)k_block_match<R, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldst);
-            hipLaunchKernelGGL((k_block_match<R, 0, true>), grid, block, ldst, s, A);
-        }
-    } else if (mode == 0) {
-#ifndef MIFLOW_EXPERIMENTS
-        if constexpr (!C::PACKED)
-#endif
-        {
-            (void)hipFuncSetAttribute((const void *)k_block_match<R, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL((k_block_match<R, 0>), grid, block, lds, s, A);
-        }
+    const auto go = [&](auto kernel, size_t lds) {
+        (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(kernel, dim3(P.grid[0], P.grid[1], P.grid[2]), dim3(P.block), lds, s, A);
+    };
+    // the release library holds ONE first-pass kernel per radius (there P.wt == Cfg<R>::PACKED), the experiments build both
+    if (P.wt) {
+        if constexpr (Cfg<R>::PACKED) go(k_block_match<R, 0, true>, P.lds_first);
     } else {
-        (void)hipFuncSetAttribute((const void *)k_block_match<R, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((k_block_match<R, 1>), grid, block, lds, s, A);
+#ifndef MIFLOW_EXPERIMENTS
+        if constexpr (!Cfg<R>::PACKED)
+#endif
+            go(k_block_match<R, 0>, P.lds_first);
     }
+    MI_HIP_TRY(hipGetLastError());
+    if (P.verify) go(k_block_match<R, 1>, P.lds_verify);
     MI_HIP_TRY(hipGetLastError());
     return MI_OK;
 }
 
-template <int R>
-static int tile_w() { return Cfg<R>::TW; }
-
-typedef int (*bm_launch_t)(const BmArgs &, int, hipStream_t);
 #define L1(r) launch_bm<r>
-static const bm_launch_t g_bm[26] = {nullptr, L1(1), L1(2), L1(3), L1(4), L1(5), L1(6), L1(7), L1(8), L1(9), L1(10),
+static int (*const g_bm[26])(const BmArgs &, const BmPlan &, hipStream_t) = {nullptr, L1(1), L1(2), L1(3), L1(4), L1(5), L1(6), L1(7), L1(8), L1(9), L1(10),
                                      L1(11), L1(12), L1(13), L1(14), L1(15), L1(16), L1(17), L1(18), L1(19), L1(20),
                                      L1(21), L1(22), L1(23), L1(24), L1(25)};
 
-static int tile_w_of(int R)
+int block_match(const BmImages &I, const BmPlan &P, hipStream_t s)
 {
-    const int t = (64 - 2 * R) & ~3;
-    return t < 16 ? 16 : t;
-}
-
-static int block_match_impl(BmArgs &A, int winsz, int uniqueness_ratio, int pairs, hipStream_t s)
-{
-    const int R = winsz >> 1;
-    MI_REQUIRE(R >= 1 && R <= 25, MI_ERR_BAD_ARG, "Unsupported window size");   // stereobm.cu:503-504
-    A.nsets = div_up(A.ndisp, 64);
-    A.thresh_scale = (float)(1.0 + uniqueness_ratio / 100.0f);
-    // rows per band: enough waves for the 1024 SIMDs (target ~5 per SIMD) but keep the 2R-row start-up of every band (column
-    // sums of the first window) a modest fraction of the work.  A batch supplies the waves, so its bands can be taller.
-    const int xt = div_up(A.cols - A.ndisp - 2 * R, tile_w_of(R));
-    const int vrows = A.rows - 2 * R;
-    int bands = div_up(5120, xt * A.nsets * pairs);   // r01f sweep: ~16 rows per band is the optimum for ONE 1080p / 128-disparity pair
-    int rb = div_up(vrows, bands > 0 ? bands : 1);
-    rb = rb < 2 * R + 2 ? 2 * R + 2 : rb;
-    rb = rb > 48 ? 48 : rb;   // taller bands cost occupancy (LDS per workgroup grows with rb): r02w at 1080p x 16: 32 | 48 | 64 | 96 rows = 4990 | 5070 | . | 4575 pairs/s
-    if (const char *e = MI_EXP_ENV("MIFLOW_SBM_ROWS")) rb = atoi(e) > 0 ? atoi(e) : rb;
-    A.rb = rb;
-    A.swz = tuning().sbm_swz != 0 ? 1 : 0;
-    MI_REQUIRE(uniqueness_ratio <= 0 || A.minssd, MI_ERR_BAD_ARG, "the uniqueness test needs the winners' SSD plane");
-    int rc = g_bm[R](A, 0, s);
-    if (rc) return rc;
-    if (uniqueness_ratio > 0) rc = g_bm[R](A, 1, s);
-    return rc;
-}
-
-int block_match(const unsigned char *left, long long lstep, const unsigned char *right, long long rstep, unsigned char *disp,
-                long long dstep, unsigned *minssd, long long mstep, int rows, int cols, int ndisp, int winsz,
-                int uniqueness_ratio, int emulate_edge, hipStream_t s)
-{
+    MI_TRY(sbm_fail(P.err));
+    MI_REQUIRE(!P.verify || I.minssd, MI_ERR_BAD_ARG, "the uniqueness test needs the winners' SSD plane");
     BmArgs A;
     memset(&A, 0, sizeof(A));
-    A.left = left; A.right = right; A.lstep = lstep; A.rstep = rstep; A.disp = disp; A.dstep = dstep;
-    A.minssd = minssd; A.mstep = mstep; A.rows = rows; A.cols = cols; A.ndisp = ndisp;
-    A.emulate_edge = emulate_edge;
-    return block_match_impl(A, winsz, uniqueness_ratio, 1, s);
-}
-
-int block_match_batch(const BmPair *tab_dev, int pairs, unsigned *minssd, long long mstep, long long mpair, int rows, int cols, int ndisp,
-                      int winsz, int uniqueness_ratio, int emulate_edge, hipStream_t s)
-{
-    BmArgs A;
-    memset(&A, 0, sizeof(A));
-    A.tab = tab_dev; A.batch = pairs; A.mpair = mpair;
-    A.minssd = minssd; A.mstep = mstep; A.rows = rows; A.cols = cols; A.ndisp = ndisp;
-    A.emulate_edge = emulate_edge;
-    return block_match_impl(A, winsz, uniqueness_ratio, pairs, s);
+    if (I.tab) { A.tab = I.tab; A.batch = P.grid[2]; A.mpair = I.mpair; }
+    else { A.left = I.one.left; A.right = I.one.right; A.lstep = I.one.lstep; A.rstep = I.one.rstep; A.disp = I.one.disp; A.dstep = I.one.dstep; }
+    A.minssd = I.minssd; A.mstep = I.mstep; A.rows = P.rows; A.cols = P.cols; A.ndisp = P.ndisp; A.nsets = P.nsets; A.rb = P.rb;
+    A.emulate_edge = I.emulate_edge; A.thresh_scale = P.thresh_scale; A.swz = P.swz;
+    return g_bm[P.R](A, P, s);
 }
 
 int prefilter_xsobel(const unsigned char *src, long long sstep, unsigned char *dst, long long dstep, int rows, int cols,
@@ -883,12 +805,6 @@ int prefilter_norm(const unsigned char *src, long long sstep, unsigned char *dst
                        dstep, rows, cols, cap, scale_g, scale_s, winsize);
     MI_HIP_TRY(hipGetLastError());
     return MI_OK;
-}
-
-void textureness_scratch_dims(int rows, int cols, int *sld, int *sh)
-{
-    *sld = align_up(cols, 64) + 2 * TEX_MX;
-    *sh = rows + 2 * TEX_MY;
 }
 
 int textureness(const unsigned char *img, long long istep, unsigned char *disp, long long dstep, int rows, int cols,
@@ -930,10 +846,7 @@ int textureness_fused(const unsigned char *img, long long istep, unsigned char *
                       int rows, int cols, int winsz, float avg_threshold, hipStream_t s)
 {
     const float threshold = avg_threshold * (float)(winsz * winsz);   // stereobm.cu:700
-    const int W2 = winsz / 2;
-    MI_REQUIRE(W2 >= 0 && W2 <= 25, MI_ERR_BAD_ARG, "Unsupported window size");
-    const int TC = 64 + 2 * W2, TRR = TEXF_ROWS + 2 * W2;
-    const size_t lds = sizeof(unsigned short) * ((size_t)(TRR + 2) * (TC + 2) + (((size_t)TRR * TC + 1) & ~(size_t)1)) + sizeof(int) * 4 * 128;
+    const size_t lds = texf_lds(winsz / 2).bytes;
     (void)hipFuncSetAttribute((const void *)k_textureness_fused, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(k_textureness_fused, dim3(div_up(cols, 64), div_up(rows, TEXF_ROWS), tab_dev ? pairs : 1), dim3(256), lds, s, img, istep, disp,
                        dstep, tab_dev, rows, cols, winsz, threshold);

@@ -374,3 +374,30 @@ def test_random_configuration_bit_exact(gpu, oracle, cfg):
     out = [bm.compute(L[0], R[0])] if cfg["batch"] == 1 else list(bm.compute_batch(L, R))
     for b, q in enumerate(pairs):
         np.testing.assert_array_equal(out[b].cpu().numpy(), oracle.sbm_compute(q[0], q[1], p), err_msg=f"pair {b}")
+
+
+@gpu_mark
+@pytest.mark.parametrize("ndisp", [8, 256])
+@pytest.mark.parametrize("winsz", [3, 25, 27, 51])
+def test_lds_layout_corners_bit_exact(gpu, oracle, winsz, ndisp):
+    """The corners of the block matcher's LDS layout (csrc/sbm_plan.h), where a wrong offset shows first: the smallest and the largest
+    radius of the packed kernels (R = 1, 12: winner-take-all through the per-wave transposition buffers) and of the generic ones
+    (R = 13, 25), each with one and with four disparity sets (waves per workgroup), uniqueness pass and textureness filter on.  The image
+    is 6R + 5 rows (two bands, the second one short) x ndisp + 2R + TW + 5 columns (two tiles, the second one ragged; TW = the kernel's tile
+    width), noisy planes.  One pair through compute() and three distinct pairs through compute_batch(): every map equals the oracle's
+    (which accepts all eight parameter sets at these sizes)."""
+    from opencv_contrib_amd import cuda
+    R = winsz // 2
+    tw = 48 if R <= 12 else max(16, (64 - 2 * R) & ~3)
+    rows, cols = 6 * R + 5, ndisp + 2 * R + tw + 5
+    disps = (1, 3, 6) if ndisp == 8 else (5, 100, 200)   # winners in the first, second and fourth disparity set
+    pairs = [_planes_pair(rows, cols, 300 + 10 * k + R, disps=disps, noise=3)[:2] for k in range(3)]
+    p = oracle.sbm_params(num_disparities=ndisp, block_size=winsz, uniqueness_ratio=10, texture_threshold=3.0)
+    ref = [oracle.sbm_compute(q[0], q[1], p) for q in pairs]
+    assert any(r.any() for r in ref) and not np.array_equal(ref[0], ref[1])
+    bm = cuda.createStereoBM(ndisp, winsz)
+    bm._set(uniqueness_ratio=10, texture_threshold=3.0)
+    L, Rr = [T(q[0], gpu) for q in pairs], [T(q[1], gpu) for q in pairs]
+    np.testing.assert_array_equal(N(bm.compute(L[0], Rr[0])), ref[0], err_msg="compute()")
+    for k, out in enumerate(bm.compute_batch(L, Rr)):
+        np.testing.assert_array_equal(N(out), ref[k], err_msg=f"compute_batch() pair {k}")
