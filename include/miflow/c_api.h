@@ -552,6 +552,52 @@ MI_API int mi_disp_bilateral_get_params(const mi_disp_bilateral *h, mi_disp_bila
 MI_API int mi_disp_bilateral_apply(mi_disp_bilateral *h, const mi_mat *disp, const mi_mat *img, mi_mat *dst, void *stream);
 MI_API void mi_disp_bilateral_destroy(mi_disp_bilateral *h);
 
+/* ================================================= StereoBeliefPropagation ===== */
+
+/* cv::cuda::createStereoBeliefPropagation(ndisp = 64, iters = 5, levels = 5, msg_type = CV_32F), cudastereo.hpp:189, + the DEFAULT_*
+ * weights of cudastereo/src/stereobp.cpp:147-158 (data term 10, data weight 0.07, disc term 1.7, single jump 1).
+ * msg_type: CV_32F (5) or CV_16S (3); 16-bit messages scale the three weights by 10 (stereobp.cpp:176,271). */
+typedef struct mi_stereobp_params {
+    int ndisp, iters, levels;
+    float max_data_term, data_weight, max_disc_term, disc_single_jump;
+    int msg_type;
+} mi_stereobp_params;
+typedef struct mi_stereobp mi_stereobp;
+enum { MI_STEREOBP_FORM_AUTO = 0, MI_STEREOBP_FORM_REG = 1 /* ndisp <= 64: messages in registers */, MI_STEREOBP_FORM_GEN = 2 /* any ndisp */ };
+/* Replaces: StereoBPImpl::StereoBPImpl, stereobp.cpp:152-158 */
+MI_API void mi_stereobp_default_params(mi_stereobp_params *p);
+/* Replaces: cv::cuda::createStereoBeliefPropagation, stereobp.cpp:362-365 */
+MI_API int mi_stereobp_create(const mi_stereobp_params *p, mi_stereobp **out);
+/* Replaces: the setters / getters of StereoBPImpl, stereobp.cpp:87-124 (validated at compute, as there) */
+MI_API int mi_stereobp_set_params(mi_stereobp *h, const mi_stereobp_params *p);
+MI_API int mi_stereobp_get_params(const mi_stereobp *h, mi_stereobp_params *p);
+MI_API void mi_stereobp_destroy(mi_stereobp *h);
+/* Replaces: StereoBPImpl::compute(left, right, disparity, stream) + init + calcBP, stereobp.cpp:165-204,234-359.  left, right:
+ * MI_8UC1 / MI_8UC3 / MI_8UC4 of one size and type, rows may be pitched; disparity: of the image size, MI_16SC1, or MI_8UC1 /
+ * MI_32SC1 / MI_32FC1 (saturate_cast of the 16-bit map, as convertTo); its border is 0.  The reference's asserts (:178-195) come
+ * back as errors whose text is the asserted condition.  Stream-ordered, no host wait. */
+MI_API int mi_stereobp_compute(mi_stereobp *h, const mi_mat *left, const mi_mat *right, mi_mat *disparity, void *stream);
+/* Replaces: StereoBPImpl::compute(data, disparity, stream), stereobp.cpp:206-232.  data: the caller's cost volume, (ndisp * rows) x
+ * cols of the message type (MI_16SC1 / MI_32FC1), disparity k of pixel (y, x) at row k * rows + y; read in place. */
+MI_API int mi_stereobp_compute_data(mi_stereobp *h, const mi_mat *data, mi_mat *disparity, void *stream);
+/* Device scratch the handle owns (the message sets and the data pyramid of stereobp.cpp:142-144): grown by compute, reused, never
+ * touched by a rejected call. */
+MI_API int mi_stereobp_scratch_bytes(const mi_stereobp *h, size_t *bytes);
+/* Replaces: StereoBeliefPropagation::estimateRecommendedParams, stereobp.cpp:367-378 */
+MI_API int mi_stereobp_estimate_recommended_params(int width, int height, int *ndisp, int *iters, int *levels);
+/* Stage level = the reference's device-layer functions (stereobp.cpp:60-72), each the kernel compute() launches, on the reference's
+ * planar matrices ((ndisp * rows) x cols of the message type).  p supplies ndisp, msg_type and the weights (scaled as compute does).
+ * Replaces: comp_data_gpu<T, D>, cuda/stereobp.cu:132-251; border elements of data are left as they are */
+MI_API int mi_stereobp_comp_data(const mi_stereobp_params *p, const mi_mat *left, const mi_mat *right, mi_mat *data, void *stream);
+/* Replaces: data_step_down_gpu<T>, cuda/stereobp.cu:257-299; dst is ((rows + 1) / 2) x ((cols + 1) / 2) per disparity */
+MI_API int mi_stereobp_data_step_down(const mi_mat *src, mi_mat *dst, int ndisp, void *stream);
+/* Replaces: level_up_messages_gpu<T>, cuda/stereobp.cu:305-352; src_udlr[4] / dst_udlr[4]: the messages u, d, l, r (one step per four) */
+MI_API int mi_stereobp_level_up(const mi_mat *src_udlr, mi_mat *dst_udlr, int ndisp, void *stream);
+/* Replaces: calc_all_iterations_gpu<T>, cuda/stereobp.cu:358-475, for t = t0 .. t0 + n_iters - 1, in place; form: MI_STEREOBP_FORM_* */
+MI_API int mi_stereobp_iterate(const mi_stereobp_params *p, mi_mat *udlr, const mi_mat *data, int t0, int n_iters, int form, void *stream);
+/* Replaces: output_gpu<T>, cuda/stereobp.cu:481-539, + out.setTo(0) and convertTo, stereobp.cpp:342-358; disparity as mi_stereobp_compute's */
+MI_API int mi_stereobp_output(const mi_mat *udlr, const mi_mat *data, int ndisp, mi_mat *disparity, void *stream);
+
 /* ================================================= superres optical-flow adapters ===== */
 
 /* Replaces: cv::superres::convertToType(GpuMat, CV_8UC1) as used by GpuOpticalFlow::calc, superres/src/optical_flow.cpp:469-470

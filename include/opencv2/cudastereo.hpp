@@ -1,4 +1,5 @@
-// Drop-in for modules/cudastereo/include/opencv2/cudastereo.hpp (cuda::StereoBM + createStereoBM).
+// Drop-in for modules/cudastereo/include/opencv2/cudastereo.hpp (cuda::StereoBM, StereoBeliefPropagation, StereoSGM,
+// DisparityBilateralFilter and their create functions).
 #ifndef MIFLOW_OPENCV_CUDASTEREO_HPP
 #define MIFLOW_OPENCV_CUDASTEREO_HPP
 
@@ -173,6 +174,89 @@ inline Ptr<cuda::StereoSGM> createStereoSGM(int minDisparity = 0, int numDispari
                                             int mode = cuda::StereoSGM::MODE_HH4)
 {
     return makePtr<miflow_detail::StereoSGMImpl>(minDisparity, numDisparities, P1, P2, uniquenessRatio, mode);
+}
+
+#ifndef CV_16S
+#define CV_16S 3
+#endif
+
+/** cudastereo.hpp:128-179 */
+class CV_EXPORTS_W StereoBeliefPropagation : public cv::StereoMatcher {
+public:
+    virtual void compute(InputArray left, InputArray right, OutputArray disparity) = 0;
+    virtual void compute(InputArray left, InputArray right, OutputArray disparity, Stream &stream) = 0;
+    /** data: the caller's cost volume, (ndisp * rows) x cols of the message type */
+    virtual void compute(InputArray data, OutputArray disparity, Stream &stream = Stream::Null()) = 0;
+    virtual int getNumIters() const = 0;           virtual void setNumIters(int iters) = 0;
+    virtual int getNumLevels() const = 0;          virtual void setNumLevels(int levels) = 0;
+    virtual double getMaxDataTerm() const = 0;     virtual void setMaxDataTerm(double max_data_term) = 0;
+    virtual double getDataWeight() const = 0;      virtual void setDataWeight(double data_weight) = 0;
+    virtual double getMaxDiscTerm() const = 0;     virtual void setMaxDiscTerm(double max_disc_term) = 0;
+    virtual double getDiscSingleJump() const = 0;  virtual void setDiscSingleJump(double disc_single_jump) = 0;
+    virtual int getMsgType() const = 0;            virtual void setMsgType(int msg_type) = 0;
+    /** stereobp.cpp:367-378 */
+    static void estimateRecommendedParams(int width, int height, int &ndisp, int &iters, int &levels)
+    {
+        miCheck(mi_stereobp_estimate_recommended_params(width, height, &ndisp, &iters, &levels));
+    }
+};
+
+namespace miflow_detail {
+/** twin of StereoBPImpl, cudastereo/src/stereobp.cpp:78-359 (no-op setters and constant getters included) */
+class StereoBPImpl final : public cuda::StereoBeliefPropagation {
+public:
+    StereoBPImpl(int ndisp, int iters, int levels, int msg_type)
+    {
+        mi_stereobp_default_params(&p_);
+        p_.ndisp = ndisp; p_.iters = iters; p_.levels = levels; p_.msg_type = msg_type;
+        miCheck(mi_stereobp_create(&p_, &h_));
+    }
+    ~StereoBPImpl() override { mi_stereobp_destroy(h_); }
+    StereoBPImpl(const StereoBPImpl &) = delete;
+    StereoBPImpl &operator=(const StereoBPImpl &) = delete;
+    void compute(InputArray left, InputArray right, OutputArray disparity) override { compute(left, right, disparity, Stream::Null()); }
+    void compute(InputArray left, InputArray right, OutputArray disparity, Stream &stream) override
+    {
+        disparity.create(left.size(), out_type(disparity));
+        mi_mat l = miMat(left), r = miMat(right), d = miMat(disparity);
+        miCheck(mi_stereobp_compute(h_, &l, &r, &d, stream.hipStream()));
+    }
+    void compute(InputArray data, OutputArray disparity, Stream &stream) override
+    {
+        if (p_.ndisp > 0) disparity.create(data.rows / p_.ndisp, data.cols, out_type(disparity));
+        mi_mat m = miMat(data), d = miMat(disparity);
+        miCheck(mi_stereobp_compute_data(h_, &m, &d, stream.hipStream()));
+    }
+    int getMinDisparity() const override { return 0; }           void setMinDisparity(int) override {}
+    int getNumDisparities() const override { return p_.ndisp; }  void setNumDisparities(int v) override { p_.ndisp = v; push(); }
+    int getBlockSize() const override { return 0; }              void setBlockSize(int) override {}
+    int getSpeckleWindowSize() const override { return 0; }      void setSpeckleWindowSize(int) override {}
+    int getSpeckleRange() const override { return 0; }           void setSpeckleRange(int) override {}
+    int getDisp12MaxDiff() const override { return 0; }          void setDisp12MaxDiff(int) override {}
+    int getNumIters() const override { return p_.iters; }        void setNumIters(int v) override { p_.iters = v; push(); }
+    int getNumLevels() const override { return p_.levels; }      void setNumLevels(int v) override { p_.levels = v; push(); }
+    double getMaxDataTerm() const override { return p_.max_data_term; }       void setMaxDataTerm(double v) override { p_.max_data_term = (float)v; push(); }
+    double getDataWeight() const override { return p_.data_weight; }          void setDataWeight(double v) override { p_.data_weight = (float)v; push(); }
+    double getMaxDiscTerm() const override { return p_.max_disc_term; }       void setMaxDiscTerm(double v) override { p_.max_disc_term = (float)v; push(); }
+    double getDiscSingleJump() const override { return p_.disc_single_jump; } void setDiscSingleJump(double v) override { p_.disc_single_jump = (float)v; push(); }
+    int getMsgType() const override { return p_.msg_type; }      void setMsgType(int v) override { p_.msg_type = v; push(); }
+private:
+    // stereobp.cpp:342: a disparity matrix the caller has given a supported type keeps it (the reference asks fixedType()); else CV_16SC1
+    static int out_type(const GpuMat &d)
+    {
+        const int t = d.type();
+        return !d.empty() && (t == CV_8UC1 || t == CV_32SC1 || t == CV_32FC1) ? t : CV_MAKETYPE(CV_16S, 1);
+    }
+    void push() { miCheck(mi_stereobp_set_params(h_, &p_)); }   // values are validated at compute, as in the reference
+    mi_stereobp_params p_;
+    mi_stereobp *h_ = nullptr;
+};
+}  // namespace miflow_detail
+
+/** cudastereo.hpp:188-189 */
+inline Ptr<cuda::StereoBeliefPropagation> createStereoBeliefPropagation(int ndisp = 64, int iters = 5, int levels = 5, int msg_type = CV_32F)
+{
+    return makePtr<miflow_detail::StereoBPImpl>(ndisp, iters, levels, msg_type);
 }
 
 /** cudastereo.hpp:298-330 */

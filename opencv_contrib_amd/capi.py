@@ -87,6 +87,14 @@ class StereoBMParams(C.Structure):
                 ("uniqueness_ratio", C.c_int), ("emulate_cuda_edge", C.c_int)]
 
 
+class StereoBPParams(C.Structure):
+    _fields_ = [("ndisp", C.c_int), ("iters", C.c_int), ("levels", C.c_int), ("max_data_term", C.c_float), ("data_weight", C.c_float),
+                ("max_disc_term", C.c_float), ("disc_single_jump", C.c_float), ("msg_type", C.c_int)]
+
+
+MI_STEREOBP_FORM_AUTO, MI_STEREOBP_FORM_REG, MI_STEREOBP_FORM_GEN = 0, 1, 2
+
+
 class BTVL1Params(C.Structure):
     _fields_ = [("scale", C.c_int), ("iterations", C.c_int), ("tau", C.c_double), ("lambda_", C.c_double), ("alpha", C.c_double),
                 ("btv_kernel_size", C.c_int), ("blur_kernel_size", C.c_int), ("blur_sigma", C.c_double)]
@@ -239,6 +247,20 @@ def lib():
         "mi_bf_knn_match2": (i, [vp, PM, PM, PM, PM, PM, vp]),
         "mi_bf_knn_match": (i, [vp, PM, PM, PM, i, i, PM, PM, PM, vp]),
         "mi_bf_radius_match": (i, [vp, PM, PM, PM, i, C.c_float, PM, PM, PM, PM, vp]),
+        "mi_stereobp_default_params": (None, [C.POINTER(StereoBPParams)]),
+        "mi_stereobp_create": (i, [C.POINTER(StereoBPParams), C.POINTER(vp)]),
+        "mi_stereobp_set_params": (i, [vp, C.POINTER(StereoBPParams)]),
+        "mi_stereobp_get_params": (i, [vp, C.POINTER(StereoBPParams)]),
+        "mi_stereobp_destroy": (None, [vp]),
+        "mi_stereobp_compute": (i, [vp, PM, PM, PM, vp]),
+        "mi_stereobp_compute_data": (i, [vp, PM, PM, vp]),
+        "mi_stereobp_scratch_bytes": (i, [vp, C.POINTER(C.c_size_t)]),
+        "mi_stereobp_estimate_recommended_params": (i, [i, i, C.POINTER(i), C.POINTER(i), C.POINTER(i)]),
+        "mi_stereobp_comp_data": (i, [C.POINTER(StereoBPParams), PM, PM, PM, vp]),
+        "mi_stereobp_data_step_down": (i, [PM, PM, i, vp]),
+        "mi_stereobp_level_up": (i, [PM, PM, i, vp]),
+        "mi_stereobp_iterate": (i, [C.POINTER(StereoBPParams), PM, PM, i, i, i, vp]),
+        "mi_stereobp_output": (i, [PM, PM, i, PM, vp]),
         "mi_superres_to_gray8": (i, [PM, PM, vp]),
         "mi_split_flow": (i, [PM, PM, PM, vp]),
         "mi_btvl1_default_params": (None, [C.POINTER(BTVL1Params)]),

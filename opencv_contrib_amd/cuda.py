@@ -840,6 +840,155 @@ def createDisparityBilateralFilter(ndisp=64, radius=3, iters=1) -> DisparityBila
     return DisparityBilateralFilter(ndisp, radius, iters)
 
 
+CV_16S, CV_32F = 3, 5   # the depth codes StereoBeliefPropagation's msg_type takes
+
+
+def _bp_dtype(msg_type):
+    import torch
+    return torch.float32 if msg_type == CV_32F else torch.int16
+
+
+class StereoBeliefPropagation:
+    """cv::cuda::StereoBeliefPropagation (cudastereo.hpp:128-189; cudastereo/src/stereobp.cpp:78-378): hierarchical belief propagation
+    on a checkerboard schedule, 16-bit or f32 messages, bit-exact to the reference."""
+
+    def __init__(self, ndisp=64, iters=5, levels=5, msg_type=CV_32F):
+        self._p = capi.StereoBPParams()
+        capi.lib().mi_stereobp_default_params(C.byref(self._p))
+        self._p.ndisp, self._p.iters, self._p.levels, self._p.msg_type = ndisp, iters, levels, msg_type
+        self._h = C.c_void_p()
+        capi.check(capi.lib().mi_stereobp_create(C.byref(self._p), C.byref(self._h)))
+
+    def __del__(self):
+        _destroy(self, "mi_stereobp_destroy")
+
+    def _set(self, **kw):
+        for k, v in kw.items():
+            setattr(self._p, k, v)
+        capi.check(capi.lib().mi_stereobp_set_params(self._h, C.byref(self._p)))
+
+    def getMinDisparity(self): return 0
+    def setMinDisparity(self, v): pass
+    def getNumDisparities(self): return self._p.ndisp
+    def setNumDisparities(self, v): self._set(ndisp=v)
+    def getBlockSize(self): return 0
+    def setBlockSize(self, v): pass
+    def getSpeckleWindowSize(self): return 0
+    def setSpeckleWindowSize(self, v): pass
+    def getSpeckleRange(self): return 0
+    def setSpeckleRange(self, v): pass
+    def getDisp12MaxDiff(self): return 0
+    def setDisp12MaxDiff(self, v): pass
+    def getNumIters(self): return self._p.iters
+    def setNumIters(self, v): self._set(iters=v)
+    def getNumLevels(self): return self._p.levels
+    def setNumLevels(self, v): self._set(levels=v)
+    def getMaxDataTerm(self): return float(self._p.max_data_term)
+    def setMaxDataTerm(self, v): self._set(max_data_term=float(v))
+    def getDataWeight(self): return float(self._p.data_weight)
+    def setDataWeight(self, v): self._set(data_weight=float(v))
+    def getMaxDiscTerm(self): return float(self._p.max_disc_term)
+    def setMaxDiscTerm(self, v): self._set(max_disc_term=float(v))
+    def getDiscSingleJump(self): return float(self._p.disc_single_jump)
+    def setDiscSingleJump(self, v): self._set(disc_single_jump=float(v))
+    def getMsgType(self): return self._p.msg_type
+    def setMsgType(self, v): self._set(msg_type=v)
+
+    def compute(self, left, right, disparity=None, stream=None):
+        """left, right: uint8 (H, W), (H, W, 3) or (H, W, 4); returns the disparity, int16 (H, W) unless `disparity` (uint8, int16,
+        int32 or float32) is given (stereobp.cpp:342)."""
+        import torch
+        if disparity is None:
+            disparity = torch.empty(left.shape[:2], dtype=torch.int16, device=left.device)
+        s = capi.current_stream_ptr() if stream is None else C.c_void_p(stream.cuda_stream)
+        capi.check(capi.lib().mi_stereobp_compute(self._h, C.byref(_m(left)), C.byref(_m(right)), C.byref(_m(disparity)), s))
+        return disparity
+
+    def compute_data(self, data, disparity=None, stream=None):
+        """compute(data, disparity, stream), stereobp.cpp:206-232: data is the caller's cost volume (ndisp * H, W) of the message type."""
+        import torch
+        if disparity is None:
+            nd = max(int(self._p.ndisp), 1)
+            disparity = torch.empty((data.shape[0] // nd, data.shape[1]), dtype=torch.int16, device=data.device)
+        s = capi.current_stream_ptr() if stream is None else C.c_void_p(stream.cuda_stream)
+        capi.check(capi.lib().mi_stereobp_compute_data(self._h, C.byref(_m(data)), C.byref(_m(disparity)), s))
+        return disparity
+
+    def scratchBytes(self):
+        """miflow extension: bytes of device scratch the handle holds."""
+        n = C.c_size_t()
+        capi.check(capi.lib().mi_stereobp_scratch_bytes(self._h, C.byref(n)))
+        return n.value
+
+    @staticmethod
+    def estimateRecommendedParams(width, height):
+        """-> (ndisp, iters, levels), stereobp.cpp:367-378."""
+        nd, it, lv = C.c_int(), C.c_int(), C.c_int()
+        capi.check(capi.lib().mi_stereobp_estimate_recommended_params(width, height, C.byref(nd), C.byref(it), C.byref(lv)))
+        return nd.value, it.value, lv.value
+
+
+def createStereoBeliefPropagation(ndisp=64, iters=5, levels=5, msg_type=CV_32F) -> StereoBeliefPropagation:
+    """cv::cuda::createStereoBeliefPropagation (cudastereo.hpp:189)."""
+    return StereoBeliefPropagation(ndisp, iters, levels, msg_type)
+
+
+def _bp_params(ndisp, msg_type, max_data_term=10.0, data_weight=0.07, max_disc_term=1.7, disc_single_jump=1.0):
+    p = capi.StereoBPParams()
+    capi.lib().mi_stereobp_default_params(C.byref(p))
+    p.ndisp, p.msg_type = ndisp, msg_type
+    p.max_data_term, p.data_weight, p.max_disc_term, p.disc_single_jump = max_data_term, data_weight, max_disc_term, disc_single_jump
+    return p
+
+
+def _mats(tensors):
+    return (capi.Mat * len(tensors))(*[_m(t) for t in tensors])
+
+
+def stereobp_comp_data(left, right, ndisp, msg_type=CV_32F, data=None, **weights):
+    """comp_data_gpu (stereobp.cu:132-251) -> data (ndisp * H, W); border elements keep what `data` held (zeros if it is made here)."""
+    import torch
+    if data is None:
+        data = torch.zeros((ndisp * left.shape[0], left.shape[1]), dtype=_bp_dtype(msg_type), device=left.device)
+    p = _bp_params(ndisp, msg_type, **weights)
+    capi.check(capi.lib().mi_stereobp_comp_data(C.byref(p), C.byref(_m(left)), C.byref(_m(right)), C.byref(_m(data)), capi.current_stream_ptr()))
+    return data
+
+
+def stereobp_data_step_down(src, ndisp):
+    """data_step_down_gpu (stereobp.cu:257-299)."""
+    import torch
+    rows = src.shape[0] // ndisp
+    dst = torch.empty((ndisp * ((rows + 1) // 2), (src.shape[1] + 1) // 2), dtype=src.dtype, device=src.device)
+    capi.check(capi.lib().mi_stereobp_data_step_down(C.byref(_m(src)), C.byref(_m(dst)), ndisp, capi.current_stream_ptr()))
+    return dst
+
+
+def stereobp_level_up(msgs, ndisp, rows, cols):
+    """level_up_messages_gpu (stereobp.cu:305-352): msgs = (u, d, l, r) of the coarser level -> the four of the rows x cols level."""
+    import torch
+    out = [torch.empty((ndisp * rows, cols), dtype=msgs[0].dtype, device=msgs[0].device) for _ in range(4)]
+    capi.check(capi.lib().mi_stereobp_level_up(_mats(msgs), _mats(out), ndisp, capi.current_stream_ptr()))
+    return out
+
+
+def stereobp_iterate(msgs, data, ndisp, t0=0, n_iters=1, form=capi.MI_STEREOBP_FORM_AUTO, **weights):
+    """calc_all_iterations_gpu (stereobp.cu:358-475) for t = t0 .. t0 + n_iters - 1 on copies of msgs = (u, d, l, r)."""
+    import torch
+    out = [m.clone() for m in msgs]
+    p = _bp_params(ndisp, CV_32F if data.dtype == torch.float32 else CV_16S, **weights)
+    capi.check(capi.lib().mi_stereobp_iterate(C.byref(p), _mats(out), C.byref(_m(data)), t0, n_iters, form, capi.current_stream_ptr()))
+    return out
+
+
+def stereobp_output(msgs, data, ndisp, dtype=None):
+    """output_gpu (stereobp.cu:481-539) with the zero border and the conversion of calcBP (stereobp.cpp:342-358)."""
+    import torch
+    disp = torch.empty((data.shape[0] // ndisp, data.shape[1]), dtype=dtype or torch.int16, device=data.device)
+    capi.check(capi.lib().mi_stereobp_output(_mats(msgs), C.byref(_m(data)), ndisp, C.byref(_m(disp)), capi.current_stream_ptr()))
+    return disp
+
+
 def stereobm_prefilter_xsobel(img, cap=31):
     import torch
     out = torch.empty_like(img)
