@@ -1,9 +1,7 @@
-// cv::cuda::FarnebackOpticalFlow: handle, level loop and C-ABI entry points.  Host-side twin of
+// cv::cuda::FarnebackOpticalFlow: handle, the executor of a call's plan (fb_plan.h) and C-ABI entry points.  Host-side twin of
 // FarnebackOpticalFlowImpl (modules/cudaoptflow/src/farneback.cpp:96-492), ordered on ONE stream (the
 // reference fans out over 5 streams and blocks the host once per level, :319-324,366,456).
 #include "farneback_dev.h"
-#include "fb_groups.h"
-#include "fb_plan.h"
 #include "mi_selftest.h"
 #include "tvl1_dev.h"   // tvl1::resize == cuda::resize(INTER_LINEAR) on dense f32 planes
 #include <cfloat>
@@ -81,22 +79,13 @@ int prepare_gaussian(int n, double sigma, PolyC *C)
 
 struct mi_farneback {
     mi_farneback_params P;
-    DevBuf<float> arena;        // capB per-pair blocks of `bs` floats: every plane of pair b lives at (plane of pair 0) + b * bs
+    DevBuf<float> arena;        // capB per-pair blocks (FbLayout, fb_plan.h): every plane of pair b lives at (plane of pair 0) + b * bs
     int capW = 0, capH = 0, capB = 0;
-    long long bs = 0;
-    // full-size-capacity planes
-    float *frames[2] = {}, *blurred = nullptr, *lvl[2] = {}, *R[2] = {}, *M = nullptr, *bufM = nullptr;
-    float *flow[3][2] = {};   // [slot][x,y]: slot 0 = level 0 (and the initial flow), slots 1,2 alternate over the coarse levels
-    std::vector<float *> pyr[2];
-    std::vector<Plane> pyrg;
-    float *pyr_base = nullptr;  // fast-pyramid levels of pair 0 (inside the pair block)
-    // internal stream + events of the two-chain pair groups (enqueue_level).  ONE calc in flight per handle: a handle used from two host
+    // internal stream + events of the two-chain pair groups (chain 1 of the plan).  ONE calc in flight per handle: a handle used from two host
     // threads, or on two streams without a synchronisation in between, races on the arena AND on this stream's ordering (c_api.h).
     hipStream_t aux = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
 };
-
-static int cv_round(double v) { return (int)std::lrint(v); }
 
 extern "C" {
 
@@ -159,22 +148,8 @@ void mi_farneback_destroy(mi_farneback *h)
 static int ensure(mi_farneback *h, int W, int H, int B)
 {
     if (h->arena.p && h->capW == W && h->capH == H && h->capB >= B) return MI_OK;
-    h->arena.release();   // another frame size or a larger batch: re-made (not only grown) and carved again
-    const Plane g = plane_of(W, H);
-    const size_t n = (size_t)g.ld * H;
-    // per pair: frames 2, blurred 2, lvl 2, R 2x5, M 5, bufM 5, flows 6 = 32 planes, + the fast-pyramid levels of both frames
-    // (sum over the half-size levels < 2/3 of a plane per frame: 2 planes reserved).  The two frames' planes of a kind are ADJACENT
-    // (frame 1 = frame 0 + one plane; R[1] = R[0] + five): the pyramid kernels run both frames in one launch
-    // (round 4's all-levels-at-once expansion planes and the internal-stream pyramid they served measured slower, r08i, and are gone)
-    const size_t per_pair = n * 34;
-    MI_TRY(h->arena.ensure(per_pair * (size_t)B));
-    float *p = h->arena.p;
-    auto take = [&](size_t k) { float *q = p; p += n * k; return q; };
-    h->frames[0] = take(1); h->frames[1] = take(1); h->blurred = take(2); h->lvl[0] = take(1); h->lvl[1] = take(1);
-    h->R[0] = take(5); h->R[1] = take(5); h->M = take(5); h->bufM = take(5);
-    for (int a = 0; a < 3; ++a) for (int b = 0; b < 2; ++b) h->flow[a][b] = take(1);
-    h->pyr_base = take(2);
-    h->bs = (long long)per_pair;
+    h->arena.release();   // another frame size or a larger batch: re-made (not only grown)
+    MI_TRY(h->arena.ensure((size_t)fb_layout(W, H).bs * (size_t)B));
     h->capW = W; h->capH = H; h->capB = B;
     return MI_OK;
 }
@@ -211,173 +186,33 @@ static int check_pair(const mi_mat *I0, const mi_mat *I1, const mi_mat *flow, co
     return MI_OK;
 }
 
-// ---- one mi_farneback_calc_batch call: what the level loop needs besides the plan, and the state it carries from level to level
-struct FbCall {
-    mi_farneback *h;
-    const FbPlan *plan;
-    int B;
-    long long bs, pn;          // floats between consecutive pairs' blocks / in one full-resolution plane (= the distance between the two frames' planes of a kind)
-    Plane g0;                  // full-resolution geometry of the batch
-    const mi_mat *I0s, *I1s;
-    mi_mat *flows;
-    hipStream_t st;            // the caller's stream
-    bool gauss, direct;        // OPTFLOW_FARNEBACK_GAUSSIAN; the pre-blur reads the caller's matrices itself
-    PolyC C;
-    Taps wk;                   // the Gaussian window of the iterations (gauss)
-    float *fx0, *fy0;          // level-0 flow planes (and the caller's initial flow)
-    float *prevx = nullptr, *prevy = nullptr;   // the coarser level's flow
-    Plane gprev;
-    bool merged = false;       // the last iteration wrote the caller's flow matrix itself
-};
-
-// blur + resize + polynomial expansion of BOTH frames for level k (the reference's loop over the two frames, farneback.cpp:434-454,
-// each stage once for both: 3 launches instead of 6), for pairs b0 .. b0 + nb - 1 of the batch: a pair group of the level runs its own
-// stage, so that the expansions it is about to iterate on are still in the last-level cache
-static int pyramid_stage(const FbCall &c, int k, hipStream_t sx, int b0, int nb)
+// the caller's matrices of n pairs as the by-value table of a batched format step (b == nullptr: one matrix per pair)
+static FmtTab fmt_tab(const mi_mat *a, const mi_mat *b, int n)
 {
-    mi_farneback *h = c.h;
-    const mi_farneback_params &P = h->P;
-    const FbLevel &L = c.plan->lv[k];
-    const long long po = (long long)b0 * c.bs, pn = c.pn;
-    Plane g = plane_of(L.w, L.h, c.bs, nb), gf = c.g0;
-    gf.batch = nb;
-    float *const R0 = h->R[0] + po;
-    const long long fsR = 5 * pn;   // R[1] = R[0] + five full-size planes
-    if (P.fast_pyramids)
-        return poly_exp(h->pyr[0][k] + po, R0, g, P.poly_n, c.C, sx, 2, h->pyr[1][k] - h->pyr[0][k], fsR);
-    const int smoothSize = L.smooth;
-    std::vector<float> gk(smoothSize);
-    gaussian_kernel(smoothSize, L.sigma, gk.data());
-    Taps K;
-    memset(&K, 0, sizeof(K));
-    for (int i = 0; i <= smoothSize / 2; ++i) K.k[i] = gk[smoothSize / 2 + i];
-    int r;
-    if (c.direct) {
-        for (int c0 = 0; c0 < nb; c0 += kFmtPairs) {
-            FmtTab T;
-            memset(&T, 0, sizeof(T));
-            Plane gc = gf;
-            gc.batch = std::min(kFmtPairs, nb - c0);
-            for (int j = 0; j < gc.batch; ++j) {
-                T.a[j] = c.I0s[b0 + c0 + j].data; T.sa[j] = (long long)c.I0s[b0 + c0 + j].step;
-                T.b[j] = c.I1s[b0 + c0 + j].data; T.sb[j] = (long long)c.I1s[b0 + c0 + j].step;
-            }
-            if ((r = gaussian_blur_tab(T, c.I0s[0].type, h->blurred + po + (long long)c0 * c.bs, gc, smoothSize / 2, K, sx, pn))) return r;
-        }
-    } else if ((r = gaussian_blur(h->frames[0] + po, h->blurred + po, gf, smoothSize / 2, K, MI_BORDER_REFLECT101, sx, 2, pn))) return r;
-    const float *src = h->blurred + po;
-    if (!(g.w == gf.w && g.h == gf.h)) {
-        // the level image = cuda::resize of the blurred frame (:447-448).  Few pairs: sampled inside the expansion kernel (same
-        // arithmetic, same bits, one launch less); many pairs: through the level planes (the expansion reads each sample 11 times)
-        if (c.plan->fuse_small) return poly_exp(h->blurred + po, R0, g, P.poly_n, c.C, sx, 2, pn, fsR, &gf);
-        if ((r = resize2(h->blurred + po, h->blurred + po + pn, gf, h->lvl[0] + po, h->lvl[1] + po, g, 1.f, sx))) return r;
-        src = h->lvl[0] + po;
+    FmtTab T;
+    memset(&T, 0, sizeof(T));
+    for (int j = 0; j < n; ++j) {
+        T.a[j] = a[j].data; T.sa[j] = (long long)a[j].step;
+        if (b) { T.b[j] = b[j].data; T.sb[j] = (long long)b[j].step; }
     }
-    return poly_exp(src, R0, g, P.poly_n, c.C, sx, 2, pn, fsR);
+    return T;
 }
 
-// Level k of the plan: the flow planes' start, then -- for the whole batch or pair group by pair group (fb_groups.h) -- the frames' side,
-// the first matrix update and the iterations (farneback.cpp:396-471; updateFlow_boxFilter / _gaussianBlur :278-312 fused into `iterate`).
-static int enqueue_level(FbCall &c, int k)
+// centre + positive half of cv::getGaussianKernel(n, sigma)
+static Taps half_taps(int n, double sigma)
 {
-    mi_farneback *h = c.h;
-    const mi_farneback_params &P = h->P;
-    const FbLevel &L = c.plan->lv[k];
-    const int B = c.B;
-    const long long bs = c.bs, pn = c.pn;
-    hipStream_t const caller_st = c.st;
-    const Plane g = plane_of(L.w, L.h, bs, B);
-    float *curx, *cury;
-    if (k > 0) { curx = h->flow[1 + (k & 1)][0]; cury = h->flow[1 + (k & 1)][1]; }
-    else { curx = c.fx0; cury = c.fy0; }
-    int rc;
-    if (L.init_resize) {   // :398-404
-        if ((rc = resize2(c.fx0, c.fy0, c.g0, curx, cury, g, (float)L.scale, caller_st))) return rc;
-    } else if (L.clear_flow) {
-        const size_t bytes = sizeof(float) * (size_t)g.ld * g.h;
-        // the two planes are neighbours in the arena: one fill over both and the gap between them while that gap is small (a single
-        // pair: one launch less); a batch would clear B full-size planes for two coarse ones (r16d: 57 us of a 32-pair calc)
-        if (cury == curx + pn && bytes <= sizeof(float) * (size_t)pn && sizeof(float) * (size_t)pn * B <= (8u << 20)) {
-            MI_HIP_TRY(hipMemset2DAsync(curx, sizeof(float) * (size_t)bs, 0, sizeof(float) * (size_t)pn + bytes, (size_t)B, caller_st));
-        } else {
-            MI_HIP_TRY(hipMemset2DAsync(curx, sizeof(float) * (size_t)bs, 0, bytes, (size_t)B, caller_st));
-            MI_HIP_TRY(hipMemset2DAsync(cury, sizeof(float) * (size_t)bs, 0, bytes, (size_t)B, caller_st));
-        }
-    }   // (L.zero_flow: no fill -- the first matrix update takes the flow as zero and the iterations write every pixel of both planes;
-        //  tests/test_farneback.py poisons the arena to hold every iterate variant to that)
-    const float *R0 = h->R[0], *R1 = h->R[0] + 5 * pn;
-    // Pair GROUPS (round 5; the plan: fb_groups.h).  An iteration of a level streams 22 planes per pair (M in and out, both expansions,
-    // the flow); with the whole batch per launch a 640 x 480 level of 32 pairs is 0.9 GB per iteration -- every iteration comes from
-    // HBM.  Group by group instead: the matrix update and ALL iterations of a few pairs whose planes fit the 256 MB last-level cache,
-    // then the next group.  The same launches on the same data in the same order per pair: bit-identical.  Groups are independent
-    // chains of launches: two of them run side by side, the second on the handle's internal stream, each half the size -- the
-    // launches of a chain wait for each other's last workgroups (r16g), and the other chain fills those tails.
-    const int G = L.groups.pairs;
-    const bool two = L.groups.two;
-    if (!L.staged) {   // once for the batch, as the reference orders them
-        if (L.zoom && (rc = resize2(c.prevx, c.prevy, c.gprev, curx, cury, g, (float)(1. / P.pyr_scale), caller_st))) return rc;
-        if ((rc = pyramid_stage(c, k, caller_st, 0, B))) return rc;
-    }
-    if (two) {
-        if (!h->aux) MI_HIP_TRY(hipStreamCreateWithFlags(&h->aux, hipStreamNonBlocking));
-        if (!h->ev_fork) MI_HIP_TRY(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-        if (!h->ev_join) MI_HIP_TRY(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-        MI_HIP_TRY(hipEventRecord(h->ev_fork, caller_st));
-        MI_HIP_TRY(hipStreamWaitEvent(h->aux, h->ev_fork, 0));
-    }
-    // an error return from inside the group loop still orders the caller's stream behind whatever the internal one was given
-    struct ChainJoin {
-        hipStream_t st, aux; hipEvent_t ev; bool armed;
-        ~ChainJoin() { if (armed) { (void)hipEventRecord(ev, aux); (void)hipStreamWaitEvent(st, ev, 0); } }
-    } chain_join = {caller_st, h->aux, h->ev_join, two};
-    int gi = 0;
-    for (int b0 = 0; b0 < B; b0 += G, ++gi) {
-        hipStream_t st = (two && (gi & 1)) ? h->aux : caller_st;   // this group's chain
-        const long long goff = (long long)b0 * bs;
-        Plane gg = g;
-        gg.batch = std::min(G, B - b0);
-        float *M = h->M + goff, *bufM = h->bufM + goff;
-        float *gx = curx + goff, *gy = cury + goff;
-        const float *gR0 = R0 + goff, *gR1 = R1 + goff;
-        Plane gp = c.gprev;
-        gp.batch = gg.batch;
-        if (L.staged) {
-            if (L.zoom && (rc = resize2(c.prevx + goff, c.prevy + goff, gp, gx, gy, gg, (float)(1. / P.pyr_scale), st))) return rc;
-            if ((rc = pyramid_stage(c, k, st, b0, gg.batch))) return rc;
-        }
-        if (L.zoom_fused) {
-            if ((rc = update_matrices_resized(c.prevx + goff, c.prevy + goff, gp, (float)(1. / P.pyr_scale), gx, gy, gR0, gR1, M, gg, st))) return rc;
-        } else if ((rc = update_matrices(L.zero_flow ? nullptr : gx, L.zero_flow ? nullptr : gy, gR0, gR1, M, gg, st))) return rc;   // :458
-        for (int i = 0; i < P.num_iters; i++) {   // :465-471 -> :278-312, fused
-            if (L.pair_it && i + 1 < P.num_iters) {
-                const bool last2 = k == 0 && i + 1 == P.num_iters - 1 && B == 1;
-                bool dm2 = false;
-                if ((rc = iterate2(M, gR0, gR1, gx, gy, bufM, gg, P.win_size, c.gauss ? &c.wk : nullptr, i + 1 < P.num_iters - 1, st,
-                                   last2 ? c.flows[0].data : nullptr, last2 ? (long long)c.flows[0].step : 0, &dm2))) return rc;
-                c.merged = c.merged || dm2;
-                std::swap(M, bufM);
-                ++i;
-                continue;
-            }
-            const bool last = k == 0 && i == P.num_iters - 1 && B == 1 && c.plan->fuse_small;
-            bool dm = false;
-            if ((rc = iterate(M, gR0, gR1, gx, gy, bufM, gg, P.win_size, c.gauss ? &c.wk : nullptr, i < P.num_iters - 1, st,
-                              last ? c.flows[0].data : nullptr, last ? (long long)c.flows[0].step : 0, &dm))) return rc;
-            c.merged = c.merged || dm;
-            std::swap(M, bufM);
-        }
-    }
-    if (two) {
-        chain_join.armed = false;
-        MI_HIP_TRY(hipEventRecord(h->ev_join, h->aux));
-        MI_HIP_TRY(hipStreamWaitEvent(caller_st, h->ev_join, 0));
-    }
-    c.prevx = curx; c.prevy = cury; c.gprev = g;
-    return MI_OK;
+    std::vector<float> k(n);
+    gaussian_kernel(n, sigma, k.data());
+    Taps K;
+    memset(&K, 0, sizeof(K));
+    for (int i = 0; i <= n / 2; ++i) K.k[i] = k[n / 2 + i];
+    return K;
 }
 
 // n independent pairs per launch sequence: blockIdx.z = pair in every kernel of the level loop (a 640 x 480 pair alone is about
 // 70 launches of 5-50 us, i.e. launch-latency bound; batched, the same 70 launches carry n pairs).
+// Every decision of the call is the plan's (fb_plan.h: levels, forms, scratch layout, the ordered launches and their chains; unit-tested
+// without a device).  Here: validation, the host constants, and ONE loop that turns the plan's offsets into pointers and launches.
 int mi_farneback_calc_batch(mi_farneback *h, int nb, const mi_mat *I0s, const mi_mat *I1s, mi_mat *flows, void *stream)
 {
     MI_REQUIRE(h, MI_ERR_BAD_ARG, "null handle");
@@ -387,106 +222,100 @@ int mi_farneback_calc_batch(mi_farneback *h, int nb, const mi_mat *I0s, const mi
     int rc = validate(&P);
     if (rc) return rc;
     for (int i = 0; i < nb; ++i) if ((rc = check_pair(&I0s[i], &I1s[i], &flows[i], &I0s[0]))) return rc;
-    const int W = I0s[0].cols, H = I0s[0].rows, B = nb;
+    const int W = I0s[0].cols, H = I0s[0].rows, B = nb, type = I0s[0].type;
     MI_REQUIRE(W >= 2 && H >= 2, MI_ERR_BAD_SIZE, "frames too small");
-    if ((rc = ensure(h, W, H, B))) return rc;
-    const long long bs = h->bs;
-    const Plane g0 = plane_of(W, H, bs, B);
-    const Plane g0s = plane_of(W, H);   // single-pair view for the per-pair conversion kernels
-    const bool use_init = (P.flags & MI_OPTFLOW_USE_INITIAL_FLOW) != 0;
-    const bool gauss = (P.flags & MI_OPTFLOW_FARNEBACK_GAUSSIAN) != 0;
 
-    // flowx0/flowy0 (level-0 flow planes; also the caller's initial flow)
-    float *fx0 = h->flow[0][0], *fy0 = h->flow[0][1];
-    // convertTo(CV_32F), farneback.cpp:342-345; the caller's initial flow split into planes
-    auto convert_frames = [&]() -> int {
-        if (B > 1) {   // one launch per 64 pairs (blockIdx.z = pair) instead of one per pair
-            for (int b0 = 0; b0 < B; b0 += kFmtPairs) {
-                const int nb = std::min(kFmtPairs, B - b0);
-                FmtTab T;
-                memset(&T, 0, sizeof(T));
-                for (int j = 0; j < nb; ++j) {
-                    T.a[j] = I0s[b0 + j].data; T.sa[j] = (long long)I0s[b0 + j].step;
-                    T.b[j] = I1s[b0 + j].data; T.sb[j] = (long long)I1s[b0 + j].step;
-                }
-                const int r = convert_batch(T, nb, I0s[0].type, h->frames[0] + b0 * bs, h->frames[1] + b0 * bs, bs, g0s, st);
-                if (r) return r;
-            }
-            return MI_OK;
-        }
-        return convert(I0s[0].data, (long long)I0s[0].step, I1s[0].data, (long long)I1s[0].step, I0s[0].type, h->frames[0], h->frames[1], g0s, st);
-    };
-    if (P.fast_pyramids && (rc = convert_frames())) return rc;   // the fast pyramid is built from the converted frames, below
-    for (int b = 0; b < B && use_init; ++b)
-        if ((rc = split_flow(flows[b].data, (long long)flows[b].step, fx0 + b * bs, fy0 + b * bs, g0s, st))) return rc;
-
-    // ---- the plan (fb_plan.h: pure arithmetic over the call's shape and the tuning knobs, unit-tested without a device)
-    FbKnobs knobs;
-    knobs.fuse = tuning().fb_fuse; knobs.pair = tuning().fb_pair; knobs.group_mb = tuning().fb_group_mb;
-    knobs.chains = tuning().fb_group_streams == 2 ? 2 : 1;
+    FbKnobs knobs = fb_knobs();
     {   // groups alternate over two streams only while the caller's stream is NOT being captured (a captured graph stays one chain);
         // asked once per call
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         if (knobs.chains == 2 && (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone)) { (void)hipGetLastError(); knobs.chains = 1; }
     }
-    knobs.simds = device_simds();
-    knobs.iterate2_ok = iterate2_supported(P.win_size);
-    const FbShape shape = {W, H, B, P.num_levels, P.pyr_scale, P.fast_pyramids != 0, P.num_iters, use_init};
+    const bool gauss = (P.flags & MI_OPTFLOW_FARNEBACK_GAUSSIAN) != 0;
+    const FbShape shape = {W, H, B, P.num_levels, P.pyr_scale, P.fast_pyramids != 0, P.num_iters, (P.flags & MI_OPTFLOW_USE_INITIAL_FLOW) != 0, P.win_size, P.poly_n};
     const FbPlan plan = fb_make_plan(shape, knobs);
-    const int levels = plan.levels;
-    for (int k = 0; k <= levels; ++k)
+    for (int k = 0; k <= plan.levels; ++k)
         MI_REQUIRE(plan.lv[k].smooth / 2 <= MI_FB_MAX_KSIZE_HALF, MI_ERR_BAD_ARG, "pyramid smoothing kernel too large (MAX_KSIZE_HALF)");
+    if ((rc = ensure(h, W, H, B))) return rc;
 
-    FbCall c;
-    c.h = h; c.plan = &plan; c.B = B; c.bs = bs; c.g0 = g0; c.pn = (long long)g0.ld * H;
-    c.I0s = I0s; c.I1s = I1s; c.flows = flows; c.st = st; c.gauss = gauss;
-    c.fx0 = fx0; c.fy0 = fy0; c.gprev = g0;
-    if (P.fast_pyramids) {   // :346-359
-        std::vector<Plane> pg(levels + 1);
-        for (int i = 0; i <= levels; ++i) pg[i] = plane_of(plan.lv[i].w, plan.lv[i].h, bs, B);
-        h->pyrg = pg;
-        for (int f = 0; f < 2; ++f) {
-            h->pyr[f].assign(levels + 1, nullptr);
-            h->pyr[f][0] = h->frames[f];
-        }
-        float *p = h->pyr_base;
-        for (int i = 1; i <= levels; ++i)
-            for (int f = 0; f < 2; ++f) {
-                h->pyr[f][i] = p; p += (size_t)pg[i].ld * pg[i].h;
-                if ((rc = pyr_down(h->pyr[f][i - 1], pg[i - 1], h->pyr[f][i], pg[i], st))) return rc;
+    // host constants: setPolynomialExpansionConsts :361, the Gaussian window of the iterations :460-464, each level's pre-blur :434-446
+    PolyC C;
+    if ((rc = prepare_gaussian(P.poly_n, P.poly_sigma, &C))) return rc;
+    const Taps wk = gauss ? half_taps(P.win_size, (double)(P.win_size / 2 * 0.3f)) : Taps();
+    std::vector<Taps> blur_taps(P.fast_pyramids ? 0 : plan.levels + 1);
+    for (size_t k = 0; k < blur_taps.size(); ++k) blur_taps[k] = half_taps(plan.lv[k].smooth, plan.lv[k].sigma);
+
+    const FbLayout &A = plan.lay;
+    const long long pn = A.pn, bs = A.bs;
+    const Plane g0s = plane_of(W, H);   // single-pair view for the per-pair format kernels
+    const float zoom_alpha = (float)(1. / P.pyr_scale);
+    // an error return between a fork and its join still orders the caller's stream behind whatever the internal one was given
+    struct ChainJoin {
+        hipStream_t st, aux; hipEvent_t ev; bool armed;
+        ~ChainJoin() { if (armed) { (void)hipEventRecord(ev, aux); (void)hipStreamWaitEvent(st, ev, 0); } }
+    } chain_join = {st, nullptr, nullptr, false};
+    for (const FbLaunch &l : plan.launches) {
+        const FbLevel &L = plan.lv[l.level], &Lc = plan.lv[std::min(l.level + 1, plan.levels)], &Lf = plan.lv[std::max(l.level - 1, 0)];   // the level, the coarser, the finer
+        hipStream_t sx = l.chain ? h->aux : st;
+        float *const pb = h->arena.p + (long long)l.b0 * bs;   // the block of the group's first pair
+        const Plane g = plane_of(L.w, L.h, bs, l.nb), gf = plane_of(W, H, bs, l.nb), gc = plane_of(Lc.w, Lc.h, bs, l.nb);
+        float *const fx = pb + L.flow, *const fy = fx + pn, *const cx = pb + Lc.flow, *const cy = cx + pn;
+        float *const frames = pb + A.frames, *const blurred = pb + A.blurred, *const lvl = pb + A.lvl;
+        float *const R0 = pb + A.R, *const R1 = R0 + 5 * pn;
+        float *const Min = pb + (l.flip ? A.bufM : A.M), *const Mout = pb + (l.flip ? A.M : A.bufM);
+        void *const mg = l.writes_merged ? flows[0].data : nullptr;
+        const long long mg_step = l.writes_merged ? (long long)flows[0].step : 0;
+        switch (l.op) {
+        case FB_CONVERT:   // convertTo(CV_32F), farneback.cpp:342-345
+            rc = l.form ? convert_batch(fmt_tab(I0s + l.b0, I1s + l.b0, l.nb), l.nb, type, frames, frames + pn, bs, g0s, sx)
+                        : convert(I0s[0].data, (long long)I0s[0].step, I1s[0].data, (long long)I1s[0].step, type, frames, frames + pn, g0s, sx);
+            break;
+        case FB_SPLIT_FLOW: rc = split_flow(flows[l.b0].data, (long long)flows[l.b0].step, fx, fy, g0s, sx); break;
+        case FB_PYR_DOWN: rc = pyr_down(pb + Lf.img[l.iter], plane_of(Lf.w, Lf.h, bs, l.nb), pb + L.img[l.iter], g, sx); break;
+        case FB_INIT_RESIZE: rc = resize2(pb + A.flow[0], pb + A.flow[0] + pn, gf, fx, fy, g, (float)L.scale, sx); break;
+        case FB_CLEAR_FLOW: {
+            const size_t bytes = sizeof(float) * (size_t)g.ld * g.h, pitch = sizeof(float) * (size_t)bs;
+            if (l.form == 1) MI_HIP_TRY(hipMemset2DAsync(fx, pitch, 0, sizeof(float) * (size_t)pn + bytes, (size_t)l.nb, sx));
+            else {
+                MI_HIP_TRY(hipMemset2DAsync(fx, pitch, 0, bytes, (size_t)l.nb, sx));
+                MI_HIP_TRY(hipMemset2DAsync(fy, pitch, 0, bytes, (size_t)l.nb, sx));
             }
-    }
-    if ((rc = prepare_gaussian(P.poly_n, P.poly_sigma, &c.C))) return rc;   // setPolynomialExpansionConsts :361
-    memset(&c.wk, 0, sizeof(c.wk));
-    if (gauss) {   // :460-464
-        std::vector<float> k(P.win_size);
-        gaussian_kernel(P.win_size, (double)(P.win_size / 2 * 0.3f), k.data());
-        for (int i = 0; i <= P.win_size / 2; ++i) c.wk.k[i] = k[P.win_size / 2 + i];
-    }
-    // The frames as f32 planes -- unless every level's pre-blur can read the caller's matrices itself (`direct`, round 5: the tiled blur
-    // has an instantiation for every level's kernel size): then the conversion pass and its planes are not needed at all.
-    c.direct = !P.fast_pyramids && tuning().fb_direct != 0;
-    for (int k = 0; k <= levels && c.direct; ++k) c.direct = gaussian_blur_tab_ok(g0, plan.lv[k].smooth / 2);
-    if (!P.fast_pyramids && !c.direct && (rc = convert_frames())) return rc;
-
-    for (int k = levels; k >= 0; k--)
-        if ((rc = enqueue_level(c, k))) return rc;
-    const bool merged = c.merged;
-    if (merged) return MI_OK;
-    if (B > 1) {
-        for (int b0 = 0; b0 < B; b0 += kFmtPairs) {
-            const int nb = std::min(kFmtPairs, B - b0);
-            FmtTab T;
-            memset(&T, 0, sizeof(T));
-            for (int j = 0; j < nb; ++j) { T.a[j] = flows[b0 + j].data; T.sa[j] = (long long)flows[b0 + j].step; }
-            if ((rc = merge_flow_batch(fx0 + b0 * bs, fy0 + b0 * bs, T, nb, bs, g0s, st))) return rc;   // cuda::merge :197-198
+        } break;
+        case FB_ZOOM: rc = resize2(cx, cy, gc, fx, fy, g, zoom_alpha, sx); break;
+        case FB_BLUR: rc = gaussian_blur(frames, blurred, gf, L.smooth / 2, blur_taps[l.level], MI_BORDER_REFLECT101, sx, 2, pn, (BlurForm)l.form); break;
+        case FB_BLUR_DIRECT:
+            rc = gaussian_blur_tab(fmt_tab(I0s + l.b0, I1s + l.b0, l.nb), type, blurred, gf, L.smooth / 2, blur_taps[l.level], sx, pn);
+            break;
+        case FB_LEVEL_RESIZE: rc = resize2(blurred, blurred + pn, gf, lvl, lvl + pn, g, 1.f, sx); break;
+        case FB_POLY_EXP: rc = poly_exp(pb + L.img[0], R0, g, P.poly_n, C, sx, 2, L.img[1] - L.img[0], 5 * pn, nullptr, (PolyForm)l.form); break;
+        case FB_POLY_EXP_RESIZED: rc = poly_exp(blurred, R0, g, P.poly_n, C, sx, 2, pn, 5 * pn, &gf, (PolyForm)l.form); break;
+        case FB_UPDATE_MATRICES: rc = update_matrices(L.zero_flow ? nullptr : fx, L.zero_flow ? nullptr : fy, R0, R1, pb + A.M, g, sx); break;
+        case FB_UPDATE_MATRICES_ZOOM: rc = update_matrices_resized(cx, cy, gc, zoom_alpha, fx, fy, R0, R1, pb + A.M, g, sx); break;
+        case FB_ITERATE: rc = iterate(Min, R0, R1, fx, fy, Mout, g, P.win_size, gauss ? &wk : nullptr, l.update, sx, mg, mg_step, (IterForm)l.form); break;
+        case FB_ITERATE2: rc = iterate2(Min, R0, R1, fx, fy, Mout, g, P.win_size, gauss ? &wk : nullptr, l.update, sx, mg, mg_step); break;
+        case FB_MERGE:   // cuda::merge :197-198
+            rc = l.form ? merge_flow_batch(fx, fy, fmt_tab(flows + l.b0, nullptr, l.nb), l.nb, bs, g0s, sx)
+                        : merge_flow(fx, fy, flows[l.b0].data, (long long)flows[l.b0].step, g0s, sx);
+            break;
+        case FB_FORK:
+            if (!h->aux) MI_HIP_TRY(hipStreamCreateWithFlags(&h->aux, hipStreamNonBlocking));
+            if (!h->ev_fork) MI_HIP_TRY(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
+            if (!h->ev_join) MI_HIP_TRY(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
+            MI_HIP_TRY(hipEventRecord(h->ev_fork, st));
+            MI_HIP_TRY(hipStreamWaitEvent(h->aux, h->ev_fork, 0));
+            chain_join.aux = h->aux; chain_join.ev = h->ev_join; chain_join.armed = true;
+            break;
+        case FB_JOIN:
+            chain_join.armed = false;
+            MI_HIP_TRY(hipEventRecord(h->ev_join, h->aux));
+            MI_HIP_TRY(hipStreamWaitEvent(st, h->ev_join, 0));
+            break;
         }
-        return MI_OK;
+        if (rc) return rc;
     }
-    for (int b = 0; b < B; ++b)
-        if ((rc = merge_flow(fx0 + b * bs, fy0 + b * bs, flows[b].data, (long long)flows[b].step, g0s, st))) return rc;   // cuda::merge :197-198
     return MI_OK;
 }
+
 
 int mi_farneback_calc(mi_farneback *h, const mi_mat *I0, const mi_mat *I1, mi_mat *flow, void *stream)
 {
@@ -497,7 +326,7 @@ int mi_farneback_calc(mi_farneback *h, const mi_mat *I0, const mi_mat *I1, mi_ma
 int miflow_selftest_farneback_poison(mi_farneback *h, void *stream)
 {
     MI_REQUIRE(h && h->arena.p, MI_ERR_BAD_ARG, "no arena yet: run a calc first");
-    MI_HIP_TRY(hipMemsetAsync(h->arena.p, 0xff, sizeof(float) * (size_t)h->bs * (size_t)h->capB, (hipStream_t)stream));
+    MI_HIP_TRY(hipMemsetAsync(h->arena.p, 0xff, sizeof(float) * (size_t)fb_layout(h->capW, h->capH).bs * (size_t)h->capB, (hipStream_t)stream));
     return MI_OK;
 }
 
@@ -530,10 +359,7 @@ int stage_out(const float *p, int ld, mi_mat *m, hipStream_t st)
 int make_win_taps(int ksize, Taps *K)
 {
     MI_REQUIRE(ksize >= 1 && (ksize & 1) && ksize / 2 <= MI_FB_MAX_KSIZE_HALF, MI_ERR_BAD_ARG, "ksize must be odd and <= 201");
-    std::vector<float> k(ksize);
-    gaussian_kernel(ksize, (double)(ksize / 2 * 0.3f), k.data());
-    memset(K, 0, sizeof(*K));
-    for (int i = 0; i <= ksize / 2; ++i) K->k[i] = k[ksize / 2 + i];
+    *K = half_taps(ksize, (double)(ksize / 2 * 0.3f));
     return MI_OK;
 }
 }  // namespace
@@ -644,11 +470,7 @@ int mi_farneback_gaussian_blur(const mi_mat *src, mi_mat *dst, int ksize, double
     MI_REQUIRE(dst->rows == src->rows && dst->cols == src->cols, MI_ERR_BAD_SIZE, "size mismatch");
     MI_REQUIRE(ksize >= 1 && (ksize & 1) && ksize / 2 <= MI_FB_MAX_KSIZE_HALF, MI_ERR_BAD_ARG, "ksize must be odd and <= 201");
     const Plane g = plane_of(src->cols, src->rows);
-    std::vector<float> k(ksize);
-    gaussian_kernel(ksize, sigma, k.data());
-    Taps K;
-    memset(&K, 0, sizeof(K));
-    for (int i = 0; i <= ksize / 2; ++i) K.k[i] = k[ksize / 2 + i];
+    const Taps K = half_taps(ksize, sigma);
     DevTmp S;
     float *in, *out;
     MI_TRY(S.alloc(&out, (size_t)g.ld * g.h));
@@ -705,11 +527,9 @@ int miflow_selftest_farneback_iterate(int form, const mi_mat *M5, const mi_mat *
     MI_TRY(stage_in(S, M5out, g.ld, &mo, st));
     void *const mg = merged ? merged->data : nullptr;
     const long long mstep = merged ? (long long)merged->step : 0;
-    bool did = false;
-    int rc;
-    if (form == MI_FB_ITER_PAIR) rc = iterate2(m, r0, r1, fx, fy, mo, g, ksize, gaussian ? &K : nullptr, update != 0, st, mg, mstep, &did);
-    else rc = iterate(m, r0, r1, fx, fy, mo, g, ksize, gaussian ? &K : nullptr, update != 0, st, mg, mstep, &did, (IterForm)form);
-    if (rc == MI_OK && merged && !did) { set_error("this form did not write the merged flow"); rc = MI_ERR_BAD_ARG; }
+    int rc;   // (a form that cannot write the merged flow is the launcher's MI_ERR_BAD_ARG)
+    if (form == MI_FB_ITER_PAIR) rc = iterate2(m, r0, r1, fx, fy, mo, g, ksize, gaussian ? &K : nullptr, update != 0, st, mg, mstep);
+    else rc = iterate(m, r0, r1, fx, fy, mo, g, ksize, gaussian ? &K : nullptr, update != 0, st, mg, mstep, (IterForm)form);
     if (rc == MI_OK) rc = stage_out(fx, g.ld, flowx, st);
     if (rc == MI_OK) rc = stage_out(fy, g.ld, flowy, st);
     if (rc == MI_OK) rc = stage_out(mo, g.ld, M5out, st);
@@ -788,11 +608,7 @@ int miflow_selftest_farneback_gaussian_blur(int form, const mi_mat *src0, const 
     MI_TRY(check_f32(dst0, "dst"));
     const Plane g = plane_of(dst0->cols, dst0->rows);
     const size_t pn = (size_t)g.ld * g.h;
-    std::vector<float> k(ksize);
-    gaussian_kernel(ksize, sigma, k.data());
-    Taps K;
-    memset(&K, 0, sizeof(K));
-    for (int i = 0; i <= ksize / 2; ++i) K.k[i] = k[ksize / 2 + i];
+    const Taps K = half_taps(ksize, sigma);
     DevTmp S;
     float *in, *out;
     MI_TRY(S.alloc(&out, pn * 2));

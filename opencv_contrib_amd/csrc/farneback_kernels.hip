@@ -744,6 +744,22 @@ __global__ __launch_bounds__(256) void k_pyr_down(const float *src, int sw, int 
 }
 
 // ------------------------------------------------------------------ host launchers
+// the ONE place the form rules' switches are read (fb_plan.h holds the rules; a launcher asked for *_AUTO and the plan of a calc use the same)
+static FbKnobs fb_switches()   // ... without asking the device (simds 0): for the rules that do not read it
+{
+    const Tuning &t = tuning();
+    FbKnobs k;
+    k.fuse = t.fb_fuse; k.pair = t.fb_pair; k.group_mb = t.fb_group_mb; k.chains = t.fb_group_streams == 2 ? 2 : 1; k.simds = 0;
+    k.fb_tiled = t.fb_tiled; k.fb_rows = t.fb_rows; k.fb_narrow = t.fb_narrow;
+    k.fb_poly_tiled = t.fb_poly_tiled; k.fb_blur_tiled = t.fb_blur_tiled; k.fb_direct = t.fb_direct;
+    return k;
+}
+FbKnobs fb_knobs()
+{
+    FbKnobs k = fb_switches();
+    k.simds = device_simds();
+    return k;
+}
 static inline dim3 grid2d(int w, int h) { return dim3(div_up(w, 64), div_up(h, 4)); }
 
 // ---- the per-pair format steps of a BATCH in one launch each (round 5: a 32-pair batch spent 64 launches of ~5 us on them, 7 % of its
@@ -815,14 +831,12 @@ int gaussian_blur(const float *src, float *dst, const Plane &g, int kh, const Ta
     MI_REQUIRE(kh >= 0 && kh <= MI_FB_MAX_KSIZE_HALF, MI_ERR_BAD_ARG, "Gaussian kernel half size out of range");
     const dim3 grid(div_up(g.w, 256), g.h, g.batch * nf);
     const size_t lds = sizeof(float) * (256 + 2 * kh);
-    bool fast = kh < g.w && kh < g.h && g.w >= 2 && g.h >= 2;
     if (border != MI_BORDER_REFLECT101 && border != MI_BORDER_REPLICATE) { set_error("unsupported border mode %d", border); return MI_ERR_BAD_ARG; }   // farneback.cu:510-517: only these two
-    // tiled form for the half sizes the pyramid of pyrScale 0.5 (1, 1, 4, 9, 19) and its neighbours use
-    const bool has_tile = fast && (kh == 1 || kh == 2 || kh == 3 || kh == 4 || kh == 9 || kh == 19);
-    MI_REQUIRE(form != BLUR_TILED || has_tile, MI_ERR_BAD_ARG, "no tiled blur for half size %d on a %d x %d plane", kh, g.w, g.h);
-    MI_REQUIRE(form != BLUR_GENERIC_FAST || fast, MI_ERR_BAD_ARG, "half size %d folds more than once on a %d x %d plane", kh, g.w, g.h);
-    if (form == BLUR_GENERIC_FULL) fast = false;
-    if (form == BLUR_AUTO ? has_tile && tuning().fb_blur_tiled : form == BLUR_TILED) {
+    if (form == BLUR_AUTO) form = fb_blur_form(g.w, g.h, kh, fb_switches());
+    MI_REQUIRE(form != BLUR_TILED || fb_blur_has_tile(g.w, g.h, kh), MI_ERR_BAD_ARG, "no tiled blur for half size %d on a %d x %d plane", kh, g.w, g.h);
+    MI_REQUIRE(form != BLUR_GENERIC_FAST || fb_blur_fast(g.w, g.h, kh), MI_ERR_BAD_ARG, "half size %d folds more than once on a %d x %d plane", kh, g.w, g.h);
+    const bool fast = form == BLUR_GENERIC_FAST;
+    if (form == BLUR_TILED) {
 #define MI_FB_BLUR(KH) case KH: { const dim3 tg(div_up(g.w, 256), div_up(g.h, BlurTile<KH>::RB), g.batch * nf);                                  \
         if (border == MI_BORDER_REFLECT101) hipLaunchKernelGGL((k_gaussian_blur_t<MI_BORDER_REFLECT101, KH>), tg, dim3(256), 0, s, src, dst, g.w, g.h, g.ld, K, g.bs, nf, fs); \
         else hipLaunchKernelGGL((k_gaussian_blur_t<MI_BORDER_REPLICATE, KH>), tg, dim3(256), 0, s, src, dst, g.w, g.h, g.ld, K, g.bs, nf, fs); } break;
@@ -837,15 +851,10 @@ int gaussian_blur(const float *src, float *dst, const Plane &g, int kh, const Ta
     return MI_OK;
 }
 
-// the tiled blur straight from the caller's matrices (both frames of g.batch <= kFmtPairs pairs); false: no instantiation for this case
-bool gaussian_blur_tab_ok(const Plane &g, int kh)
-{
-    const bool fast = kh < g.w && kh < g.h && g.w >= 2 && g.h >= 2;
-    return fast && tuning().fb_blur_tiled && (kh == 1 || kh == 2 || kh == 3 || kh == 4 || kh == 9 || kh == 19);
-}
+// the tiled blur straight from the caller's matrices (both frames of g.batch <= kFmtPairs pairs)
 int gaussian_blur_tab(const FmtTab &T, int type, float *dst, const Plane &g, int kh, const Taps &K, hipStream_t s, long long fs)
 {
-    MI_REQUIRE(gaussian_blur_tab_ok(g, kh) && g.batch <= kFmtPairs && (type == MI_8UC1 || type == MI_32FC1), MI_ERR_BAD_ARG, "no direct-source blur for this case");
+    MI_REQUIRE(fb_blur_direct_ok(g.w, g.h, kh, fb_switches()) && g.batch <= kFmtPairs && (type == MI_8UC1 || type == MI_32FC1), MI_ERR_BAD_ARG, "no direct-source blur for this case");
 #define MI_FB_BLUR(KH) case KH: { const dim3 tg(div_up(g.w, 256), div_up(g.h, BlurTile<KH>::RB), g.batch * 2);                                  \
         if (type == MI_8UC1) hipLaunchKernelGGL((k_gaussian_blur_tab<MI_BORDER_REFLECT101, KH, true>), tg, dim3(256), 0, s, T, dst, g.w, g.h, g.ld, K, g.bs, fs); \
         else hipLaunchKernelGGL((k_gaussian_blur_tab<MI_BORDER_REFLECT101, KH, false>), tg, dim3(256), 0, s, T, dst, g.w, g.h, g.ld, K, g.bs, fs); } break;
@@ -858,6 +867,7 @@ int gaussian_blur_tab(const FmtTab &T, int type, float *dst, const Plane &g, int
 int poly_exp(const float *src, float *dst5, const Plane &g, int polyN, const PolyC &C, hipStream_t s, int nf, long long fs_src, long long fs_dst,
              const Plane *resize_from, PolyForm form)
 {
+    MI_REQUIRE(polyN == 5 || polyN == 7, MI_ERR_BAD_ARG, "polyN must be 5 or 7");   // CV_Assert, farneback.cpp:316
     MI_REQUIRE(form != POLY_TILED || !resize_from, MI_ERR_BAD_ARG, "the tiled expansion does not sample a resize");
     RsSrc rs;
     memset(&rs, 0, sizeof(rs));
@@ -866,12 +876,12 @@ int poly_exp(const float *src, float *dst5, const Plane &g, int polyN, const Pol
         rs.scx = (double)(float)(1.0 / ((double)g.w / resize_from->w));
         rs.scy = (double)(float)(1.0 / ((double)g.h / resize_from->h));
     }
-#define MI_PE(N) do { if (form == POLY_AUTO ? !resize_from && tuning().fb_poly_tiled && (long long)div_up(g.w, 256 - 2 * N) * div_up(g.h, 8) * g.batch * nf >= 1024 : form == POLY_TILED) hipLaunchKernelGGL((k_poly_exp_t<N, 8>), dim3(div_up(g.w, 256 - 2 * N), div_up(g.h, 8), g.batch * nf), dim3(256), 0, s, src, dst5, g.w, g.h, g.ld, C, g.bs, nf, fs_src, fs_dst); \
+    if (form == POLY_AUTO) form = fb_poly_form(g.w, g.h, g.batch * nf, polyN, resize_from != nullptr, fb_switches());
+#define MI_PE(N) do { if (form == POLY_TILED) hipLaunchKernelGGL((k_poly_exp_t<N, 8>), dim3(div_up(g.w, 256 - 2 * N), div_up(g.h, 8), g.batch * nf), dim3(256), 0, s, src, dst5, g.w, g.h, g.ld, C, g.bs, nf, fs_src, fs_dst); \
                      else if (resize_from) hipLaunchKernelGGL((k_poly_exp<N, true>), dim3(div_up(g.w, 256 - 2 * N), g.h, g.batch * nf), dim3(256), 0, s, src, dst5, g.w, g.h, g.ld, C, g.bs, nf, fs_src, fs_dst, rs); \
                      else hipLaunchKernelGGL((k_poly_exp<N, false>), dim3(div_up(g.w, 256 - 2 * N), g.h, g.batch * nf), dim3(256), 0, s, src, dst5, g.w, g.h, g.ld, C, g.bs, nf, fs_src, fs_dst, rs); } while (0)
     if (polyN == 5) MI_PE(5);
-    else if (polyN == 7) MI_PE(7);
-    else { set_error("polyN must be 5 or 7"); return MI_ERR_BAD_ARG; }   // CV_Assert, farneback.cpp:316
+    else MI_PE(7);
 #undef MI_PE
     MI_HIP_TRY(hipGetLastError());
     return MI_OK;
@@ -919,30 +929,25 @@ int update_matrices(const float *flowx, const float *flowy, const float *R0, con
 }
 
 int iterate(const float *M, const float *R0, const float *R1, float *flowx, float *flowy, float *Mout, const Plane &g, int ksize,
-            const Taps *gauss, bool update, hipStream_t s, void *merged, long long merged_step, bool *did_merge, IterForm form)
+            const Taps *gauss, bool update, hipStream_t s, void *merged, long long merged_step, IterForm form)
 {
-    if (did_merge) *did_merge = false;
     const int kh = ksize / 2;
     MI_REQUIRE(kh >= 0 && kh <= MI_FB_MAX_KSIZE_HALF, MI_ERR_BAD_ARG, "winSize out of range");
-    const bool has_tile = kh == 4 || kh == 6 || kh == 7 || kh == 10;   // winSize 9, 13 (the default), 15, 21
-    MI_REQUIRE((form != ITER_TILE256 && form != ITER_TILE64) || (has_tile && tuning().fb_rows == 4), MI_ERR_BAD_ARG, "no tiled iteration for winSize %d", ksize);
+    const FbKnobs kn = form == ITER_AUTO ? fb_knobs() : fb_switches();   // (the narrow rule counts workgroups per CU)
+    if (form == ITER_AUTO) form = fb_iter_form(g.w, g.h, g.batch, kh, kn);
+    // tile256 = 256 columns x MIFLOW_FB_ROWS rows; the 64-column tiles have four rows only
+    MI_REQUIRE(form == ITER_ROW || (fb_iter_has_tile(kh) && (form == ITER_TILE256 || kn.fb_rows == 4)), MI_ERR_BAD_ARG, "no tiled iteration for winSize %d", ksize);
     MI_REQUIRE(form != ITER_ROW || !merged, MI_ERR_BAD_ARG, "the one-row iteration does not write the merged flow");
-    const bool tiled = form == ITER_AUTO ? tuning().fb_tiled != 0 : form != ITER_ROW;
+    const bool narrow = form == ITER_TILE64;
     const dim3 grid(div_up(g.w, 256), g.h, g.batch);
     const size_t lds = sizeof(float) * 5 * (256 + 2 * kh);
     const float inv = 1.f / ((1 + 2 * kh) * (1 + 2 * kh));
     Taps none;
     memset(&none, 0, sizeof(none));
-    const int R = tuning().fb_rows, swz = tuning().fb_swz;
-    dim3 tgrid(div_up(g.w, 256), div_up(g.h, R), g.batch);
+    const int R = kn.fb_rows, swz = tuning().fb_swz;
+    const dim3 tgrid = narrow ? dim3(div_up(g.w, 64), div_up(g.h, 4), g.batch) : dim3(div_up(g.w, 256), div_up(g.h, R), g.batch);
     const Taps &K = gauss ? *gauss : none;
     const int upd = update ? 1 : 0;
-    // narrow tiles where the 256-column grid would leave most of the device idle (fewer workgroups than two per CU): the launch then
-    // costs its dependent steps, and a 64 x 4 tile has a third of them.  MIFLOW_FB_NARROW=0 / 1 forces the choice (tuning, tests).
-    const int narrow_env = tuning().fb_narrow;
-    const bool narrow = form != ITER_AUTO ? form == ITER_TILE64 :
-                        narrow_env >= 0 ? narrow_env != 0 : (long long)tgrid.x * tgrid.y * tgrid.z < 2LL * (device_simds() / 4);
-    if (narrow && R == 4) tgrid = dim3(div_up(g.w, 64), div_up(g.h, 4), g.batch);
 #define MI_FB_LAUNCH(G, KH, RR, TW) hipLaunchKernelGGL((k_iterate_t<G, KH, RR, TW>), tgrid, dim3(256), 0, s, M, R0, R1, flowx, flowy, Mout, g.w, g.h, g.ld, inv, upd, K, g.bs, swz, mg, merged_step)
 #ifdef MIFLOW_EXPERIMENTS   // 8-row tiles (MIFLOW_FB_ROWS=8) lost their A/B: experiments build only
 #define MI_FB_R8(G, KH) if (R == 8) MI_FB_LAUNCH(G, KH, 8, 256); else
@@ -954,9 +959,8 @@ int iterate(const float *M, const float *R0, const float *R1, float *flowx, floa
         if (gauss) { MI_FB_R8(true, KH) if (narrow) MI_FB_LAUNCH(true, KH, 4, 64); else MI_FB_LAUNCH(true, KH, 4, 256); }   \
         else { MI_FB_R8(false, KH) if (narrow) MI_FB_LAUNCH(false, KH, 4, 64); else MI_FB_LAUNCH(false, KH, 4, 256); }       \
         break;
-    void *mg = (merged && g.batch == 1 && tiled && has_tile) ? merged : nullptr;
-    if (did_merge) *did_merge = mg != nullptr;
-    switch (tiled ? kh : -1) {
+    void *mg = (merged && g.batch == 1) ? merged : nullptr;
+    switch (form != ITER_ROW ? kh : -1) {
         MI_FB_TILED(4) MI_FB_TILED(6) MI_FB_TILED(7) MI_FB_TILED(10)
     default:
         if (gauss) hipLaunchKernelGGL(k_iterate<true>, grid, dim3(256), lds, s, M, R0, R1, flowx, flowy, Mout, g.w, g.h, g.ld, kh, inv, upd, K, g.bs);
@@ -969,19 +973,17 @@ int iterate(const float *M, const float *R0, const float *R1, float *flowx, floa
     return MI_OK;
 }
 
-// two fused iterations (k_iterate2_t); false when the window size has no instantiation (the caller then launches twice)
-bool iterate2_supported(int ksize) { const int kh = ksize / 2; return tuning().fb_tiled && (kh == 4 || kh == 6 || kh == 7); }
+// two fused iterations (k_iterate2_t)
 int iterate2(const float *M, const float *R0, const float *R1, float *flowx, float *flowy, float *Mout, const Plane &g, int ksize, const Taps *gauss,
-             bool update, hipStream_t s, void *merged, long long merged_step, bool *did_merge)
+             bool update, hipStream_t s, void *merged, long long merged_step)
 {
     const int kh = ksize / 2;
-    MI_REQUIRE(iterate2_supported(ksize) && M != Mout, MI_ERR_BAD_ARG, "no two-iteration kernel for this window size");
+    MI_REQUIRE(fb_iter2_ok(kh, fb_switches()) && M != Mout, MI_ERR_BAD_ARG, "no two-iteration kernel for this window size");
     const float inv = 1.f / ((1 + 2 * kh) * (1 + 2 * kh));
     Taps none;
     memset(&none, 0, sizeof(none));
     const Taps &K = gauss ? *gauss : none;
     void *mg = (merged && g.batch == 1) ? merged : nullptr;
-    if (did_merge) *did_merge = mg != nullptr;
     const dim3 grid(div_up(g.w, 64), div_up(g.h, 4), g.batch);
 #define MI_FB2(KH) case KH: if (gauss) hipLaunchKernelGGL((k_iterate2_t<true, KH>), grid, dim3(1024), 0, s, M, R0, R1, flowx, flowy, Mout, g.w, g.h, g.ld, inv, update ? 1 : 0, K, g.bs, mg, merged_step); \
                             else hipLaunchKernelGGL((k_iterate2_t<false, KH>), grid, dim3(1024), 0, s, M, R0, R1, flowx, flowy, Mout, g.w, g.h, g.ld, inv, update ? 1 : 0, K, g.bs, mg, merged_step); break;

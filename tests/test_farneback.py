@@ -590,7 +590,9 @@ def test_call_plan_host_arithmetic(tmp_path):
     """tests/cpp/fb_plan_test.cpp: the plan of a mi_farneback_calc_batch call (csrc/fb_plan.h, round 6 -- the level crop and geometry of
     cudaoptflow/src/farneback.cpp:330-395, how each level's flow starts, fused / plain zoom, pair groups, two iterations per launch) for
     the class defaults, the bench's batch, the initial-flow and zero-iteration cases, fast pyramids, forced switches, and its invariants
-    over a sweep of shapes.  The level loop (enqueue_level) only executes a plan.  Plain C++, no device."""
+    over a sweep of shapes; the form rules against a table, the scratch layout, and the ordered launch list: exact for four calls, and over
+    the sweep no plane read before an entry wrote it, every launch kind covering the batch once, chains inside fork / join, M and bufM
+    alternating.  mi_farneback_calc_batch only executes the list.  Plain C++, no device."""
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     exe = str(tmp_path / "fb_plan_test")
