@@ -11,7 +11,7 @@ using namespace mi::btvl1;
 struct mi_btvl1 {
     mi_btvl1_params P;
     DevBuf<unsigned char> arena;      // every scratch plane of the last geometry (layout()); grown lazily, freed with the handle
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the last process (mi_btvl1_get_profile)
+    TimingEvent ev1, ev0;             // around the last process (mi_btvl1_get_profile)
     long long launches = 0;
     bool timed = false;
 };
@@ -176,11 +176,8 @@ int mi_btvl1_create(const mi_btvl1_params *p, mi_btvl1 **out)
     MI_TRY(require_device());
     mi_btvl1 *h = new mi_btvl1();
     h->P = *p;   // validated at process(), like the reference (CV_Assert inside process)
-    if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) {
-        mi_btvl1_destroy(h);
-        set_error("hipEventCreate failed");
-        return MI_ERR_HIP;
-    }
+    int rc = h->ev0.ensure();
+    if (rc || (rc = h->ev1.ensure())) { delete h; return rc; }
     *out = h;
     return MI_OK;
 }
@@ -199,13 +196,7 @@ int mi_btvl1_get_params(const mi_btvl1 *h, mi_btvl1_params *p)
     return MI_OK;
 }
 
-void mi_btvl1_destroy(mi_btvl1 *h)
-{
-    if (!h) return;
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    delete h;
-}
+void mi_btvl1_destroy(mi_btvl1 *h) { delete h; }
 
 int mi_btvl1_process(mi_btvl1 *h, int n, const mi_mat *frames, const mi_mat *fwd_x, const mi_mat *fwd_y, const mi_mat *bwd_x,
                      const mi_mat *bwd_y, int base_idx, mi_mat *dst, void *stream)
@@ -220,7 +211,7 @@ int mi_btvl1_process(mi_btvl1 *h, int n, const mi_mat *frames, const mi_mat *fwd
     hipStream_t st = (hipStream_t)stream;
     IterArgs A;
     h->timed = false;
-    MI_HIP_TRY(hipEventRecord(h->ev0, st));
+    MI_HIP_TRY(hipEventRecord(h->ev0.get(), st));
     if (const int rc = prepare(h, n, frames, fwd_x, fwd_y, bwd_x, bwd_y, base_idx, nullptr, &A, st)) return rc;
     // two launches per iteration, no host wait in between; iteration i reads X[i & 1] and writes the other
     for (int i = 0; i < h->P.iterations; ++i) {
@@ -231,7 +222,7 @@ int mi_btvl1_process(mi_btvl1 *h, int n, const mi_mat *frames, const mi_mat *fwd
     }
     MI_HIP_TRY(hipGetLastError());
     h->launches += 2LL * h->P.iterations;
-    MI_HIP_TRY(hipEventRecord(h->ev1, st));
+    MI_HIP_TRY(hipEventRecord(h->ev1.get(), st));
     h->timed = true;
     return MI_OK;
 }
@@ -240,9 +231,9 @@ int mi_btvl1_get_profile(mi_btvl1 *h, double *ms, long long *launches)
 {
     MI_REQUIRE(h && ms && launches, MI_ERR_BAD_ARG, "mi_btvl1_get_profile: null argument");
     MI_REQUIRE(h->timed, MI_ERR_BAD_ARG, "mi_btvl1_get_profile: no completed process call");
-    MI_HIP_TRY(hipEventSynchronize(h->ev1));
+    MI_HIP_TRY(hipEventSynchronize(h->ev1.get()));
     float t = 0.f;
-    MI_HIP_TRY(hipEventElapsedTime(&t, h->ev0, h->ev1));
+    MI_HIP_TRY(hipEventElapsedTime(&t, h->ev0.get(), h->ev1.get()));
     *ms = t;
     *launches = h->launches;
     return MI_OK;

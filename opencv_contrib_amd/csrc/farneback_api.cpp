@@ -83,8 +83,9 @@ struct mi_farneback {
     int capW = 0, capH = 0, capB = 0;
     // internal stream + events of the two-chain pair groups (chain 1 of the plan).  ONE calc in flight per handle: a handle used from two host
     // threads, or on two streams without a synchronisation in between, races on the arena AND on this stream's ordering (c_api.h).
-    hipStream_t aux = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    Event ev_join, ev_fork;
+    Stream aux;   // (declared last: it goes first, drained, then the events, then the arena)
+    ~mi_farneback() { if (aux.get()) (void)hipStreamSynchronize(aux.get()); }
 };
 
 extern "C" {
@@ -136,14 +137,7 @@ int mi_farneback_get_params(const mi_farneback *h, mi_farneback_params *p)
     return MI_OK;
 }
 
-void mi_farneback_destroy(mi_farneback *h)
-{
-    if (!h) return;
-    if (h->aux) { (void)hipStreamSynchronize(h->aux); (void)hipStreamDestroy(h->aux); }
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-    delete h;
-}
+void mi_farneback_destroy(mi_farneback *h) { delete h; }
 
 static int ensure(mi_farneback *h, int W, int H, int B)
 {
@@ -256,7 +250,7 @@ int mi_farneback_calc_batch(mi_farneback *h, int nb, const mi_mat *I0s, const mi
     } chain_join = {st, nullptr, nullptr, false};
     for (const FbLaunch &l : plan.launches) {
         const FbLevel &L = plan.lv[l.level], &Lc = plan.lv[std::min(l.level + 1, plan.levels)], &Lf = plan.lv[std::max(l.level - 1, 0)];   // the level, the coarser, the finer
-        hipStream_t sx = l.chain ? h->aux : st;
+        hipStream_t sx = l.chain ? h->aux.get() : st;
         float *const pb = h->arena.p + (long long)l.b0 * bs;   // the block of the group's first pair
         const Plane g = plane_of(L.w, L.h, bs, l.nb), gf = plane_of(W, H, bs, l.nb), gc = plane_of(Lc.w, Lc.h, bs, l.nb);
         float *const fx = pb + L.flow, *const fy = fx + pn, *const cx = pb + Lc.flow, *const cy = cx + pn;
@@ -298,17 +292,17 @@ int mi_farneback_calc_batch(mi_farneback *h, int nb, const mi_mat *I0s, const mi
                         : merge_flow(fx, fy, flows[l.b0].data, (long long)flows[l.b0].step, g0s, sx);
             break;
         case FB_FORK:
-            if (!h->aux) MI_HIP_TRY(hipStreamCreateWithFlags(&h->aux, hipStreamNonBlocking));
-            if (!h->ev_fork) MI_HIP_TRY(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-            if (!h->ev_join) MI_HIP_TRY(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-            MI_HIP_TRY(hipEventRecord(h->ev_fork, st));
-            MI_HIP_TRY(hipStreamWaitEvent(h->aux, h->ev_fork, 0));
-            chain_join.aux = h->aux; chain_join.ev = h->ev_join; chain_join.armed = true;
+            MI_TRY(h->aux.ensure());
+            MI_TRY(h->ev_fork.ensure());
+            MI_TRY(h->ev_join.ensure());
+            MI_HIP_TRY(hipEventRecord(h->ev_fork.get(), st));
+            MI_HIP_TRY(hipStreamWaitEvent(h->aux.get(), h->ev_fork.get(), 0));
+            chain_join.aux = h->aux.get(); chain_join.ev = h->ev_join.get(); chain_join.armed = true;
             break;
         case FB_JOIN:
             chain_join.armed = false;
-            MI_HIP_TRY(hipEventRecord(h->ev_join, h->aux));
-            MI_HIP_TRY(hipStreamWaitEvent(st, h->ev_join, 0));
+            MI_HIP_TRY(hipEventRecord(h->ev_join.get(), h->aux.get()));
+            MI_HIP_TRY(hipStreamWaitEvent(st, h->ev_join.get(), 0));
             break;
         }
         if (rc) return rc;

@@ -1,5 +1,7 @@
 // The one owner of a handle's scratch memory.  No HIP in here: the allocator is a policy (mi_common.h has the device and the
 // pinned-host one), so tests/cpp/grow_buf_test.cpp runs the same code on the host with an allocator that counts and fails.
+// Its sibling mi_own.h owns what is not a buffer: streams, events and the cached TV-L1 arenas.  Together they make every
+// mi_*_destroy a `delete h`.
 #pragma once
 #include <cstddef>
 #include "miflow/c_api.h"

@@ -1,6 +1,5 @@
 // Error channel, device selection and device-memory helpers of the C-ABI.
 #include "mi_common.h"
-#include <vector>
 #include <cstdlib>
 #include <cstring>
 #include <cstdio>
@@ -117,133 +116,22 @@ const Tuning &tuning()
     return g_tuning;
 }
 
-namespace {
-struct BigBlock { void *p; size_t cap; int dev; hipEvent_t ready; };   // ready: the previous owner's last work on the block (may be null)
-std::mutex g_big_mu;
-std::vector<BigBlock> g_big;
-const size_t kBigMaxBlocks = 4;   // PER DEVICE (two lanes of two handles): eight GPUs of a node each keep their own
-// upper bounds of what the cache may hold: MIFLOW_CACHE_GB per DEVICE (0 = cache nothing, for hosts whose own allocator wants the
-// memory back) and MIFLOW_CACHE_TOTAL_GB for the whole process (all devices together; default 4 x the per-device bound)
-size_t big_max_bytes()
+// The arena cache (ArenaCache, mi_own.h) of the process.  Upper bounds of what it may hold: 4 blocks PER DEVICE (two lanes of two
+// handles; eight GPUs of a node each keep their own), MIFLOW_CACHE_GB per DEVICE (0 = cache nothing, for hosts whose own allocator
+// wants the memory back) and MIFLOW_CACHE_TOTAL_GB for the whole process (all devices together; default 4 x the per-device bound)
+ArenaCache<HipArenaBackend> &big_cache()
 {
-    static const size_t v = [] {
-        const char *e = getenv("MIFLOW_CACHE_GB");
-        const long long gb = e && *e ? atoll(e) : 24;
-        return (size_t)(gb < 0 ? 0 : gb) << 30;
+    static ArenaCache<HipArenaBackend> *const c = [] {
+        const auto gb = [](const char *e, long long dflt) { const long long v = e && *e ? atoll(e) : dflt; return (size_t)(v < 0 ? 0 : v) << 30; };
+        const size_t per_dev = gb(getenv("MIFLOW_CACHE_GB"), 24);
+        const char *t = getenv("MIFLOW_CACHE_TOTAL_GB");
+        return new ArenaCache<HipArenaBackend>(4, per_dev, t && *t ? gb(t, 0) : 4 * per_dev);
     }();
-    return v;
+    return *c;
 }
-size_t big_max_bytes_total()
-{
-    static const size_t v = [] {
-        const char *e = getenv("MIFLOW_CACHE_TOTAL_GB");
-        if (e && *e) { const long long gb = atoll(e); return (size_t)(gb < 0 ? 0 : gb) << 30; }
-        return 4 * big_max_bytes();
-    }();
-    return v;
-}
-}  // namespace
-
-int big_alloc(void **p, size_t bytes, size_t *capacity)
-{
-    int dev = 0;
-    MI_HIP_TRY(hipGetDevice(&dev));
-    {
-        hipEvent_t ready = nullptr;
-        bool hit = false;
-        {
-            std::lock_guard<std::mutex> lk(g_big_mu);
-            int best = -1;
-            for (size_t i = 0; i < g_big.size(); ++i)
-                if (g_big[i].dev == dev && g_big[i].cap >= bytes && g_big[i].cap <= bytes + bytes / 2 + (64u << 20) &&
-                    (best < 0 || g_big[i].cap < g_big[best].cap))
-                    best = (int)i;
-            if (best >= 0) {
-                *p = g_big[best].p; *capacity = g_big[best].cap; ready = g_big[best].ready;
-                g_big.erase(g_big.begin() + best);
-                hit = true;
-            }
-        }
-        if (hit) {
-            // nothing the block's previous owner enqueued may still touch it: wait for ITS last work only (an event recorded when the
-            // block was returned) -- no device-wide synchronisation, other handles' streams keep running
-            if (ready) {
-                const hipError_t we = hipEventSynchronize(ready);
-                (void)hipEventDestroy(ready);
-                if (we != hipSuccess) {
-                    // The event could not be waited for.  Seen on ROCm 7.2 when the stream it was recorded on has since been
-                    // destroyed (hipErrorCapturedEvent: the runtime looks at the dead stream).  Clear the thread's sticky error -- it
-                    // would surface at the next hipGetLastError() after an unrelated launch -- and fall back to what vouches for the
-                    // block without the event: the whole device idle.  If even that fails the block is dropped for a fresh one.
-                    (void)hipGetLastError();
-                    if (hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); (void)hipFree(*p); *p = nullptr; hit = false; }
-                }
-            }
-            if (hit) return MI_OK;
-        }
-    }
-    hipError_t e = hipMalloc(p, bytes);
-    if (e != hipSuccess) {   // make room and retry once
-        big_trim();
-        e = hipMalloc(p, bytes);
-    }
-    if (e != hipSuccess) { set_error("hipMalloc of %zu bytes failed: %s", bytes, hipGetErrorString(e)); return MI_ERR_OOM; }
-    *capacity = bytes;
-    return MI_OK;
-}
-
-// `ready`: an event the owner recorded behind its last work on the block WHILE ITS STREAM WAS ALIVE (ownership passes to the cache; the
-// next taker waits for it and destroys it).  No event and `busy`: the owner cannot vouch for the block (e.g. its last calc was
-// enqueued under stream capture) -- the device is synchronised instead, which keeps the old guarantee.  Nothing here touches a
-// caller's stream: at destroy time it may no longer exist.
-void big_free(void *p, size_t capacity, hipEvent_t ready, bool busy)
-{
-    if (!p) { if (ready) (void)hipEventDestroy(ready); return; }
-    int dev = 0;
-    void *drop = nullptr;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        hipPointerAttribute_t at;
-        const int cur = dev;
-        if (hipPointerGetAttributes(&at, p) == hipSuccess) dev = at.device;
-        if (dev != cur) (void)hipSetDevice(dev);
-        bool idle = true;
-        if (!ready && busy) idle = hipDeviceSynchronize() == hipSuccess;
-        if (dev != cur) (void)hipSetDevice(cur);
-        std::lock_guard<std::mutex> lk(g_big_mu);
-        size_t total = capacity, all = capacity, blocks = 0;
-        for (const BigBlock &b : g_big) {
-            all += b.cap;
-            if (b.dev == dev) { total += b.cap; ++blocks; }
-        }
-        if (idle && blocks < kBigMaxBlocks && total <= big_max_bytes() && all <= big_max_bytes_total()) {
-            g_big.push_back({p, capacity, dev, ready});
-            return;
-        }
-        if (ready) { (void)hipEventSynchronize(ready); (void)hipEventDestroy(ready); }
-        drop = p;
-    } else {
-        if (ready) (void)hipEventDestroy(ready);   // the cache does not take the block: its event goes with it
-        drop = p;
-    }
-    const hipError_t fe = hipFree(drop);
-    if (fe != hipSuccess) set_error("hipFree of a %zu-byte arena failed: %s", capacity, hipGetErrorString(fe));
-}
-
-void big_trim()
-{
-    std::vector<BigBlock> all;
-    {
-        std::lock_guard<std::mutex> lk(g_big_mu);
-        all.swap(g_big);
-    }
-    int cur = 0;
-    const bool have = hipGetDevice(&cur) == hipSuccess;
-    for (const BigBlock &b : all) {
-        if (b.ready) { (void)hipEventSynchronize(b.ready); (void)hipEventDestroy(b.ready); }
-        (void)hipFree(b.p);   // hipFree takes pointers of any device
-    }
-    if (have) (void)hipSetDevice(cur);
-}
+int big_alloc(void **p, size_t bytes, size_t *capacity) { return big_cache().alloc(p, bytes, capacity); }
+void big_free(void *p, size_t capacity, hipEvent_t ready, bool busy) { big_cache().free(p, capacity, ArenaCache<HipArenaBackend>::Event((void *)ready), busy); }
+void big_trim() { big_cache().trim(); }
 
 int device_simds()
 {

@@ -7,6 +7,7 @@
 #include <cstring>
 #include "miflow/c_api.h"
 #include "mi_buf.h"
+#include "mi_own.h"
 
 namespace mi {
 
@@ -123,13 +124,63 @@ struct DevTmp {
     }
 };
 
-// Large device blocks (the per-lane TV-L1 arenas) come from a small process-wide cache: a block released by a handle is kept
+// Creation policies of Owned (mi_own.h) and the three owners the handles hold: the only places that create or destroy a stream or an
+// event of the library's own (the caller's streams are mi_stream_create / mi_stream_destroy, the multi-GPU workers' tvl1_multi.cpp).
+struct StreamPolicy {
+    using handle = hipStream_t;
+    static int create(handle *s) { MI_HIP_TRY(hipStreamCreateWithFlags(s, hipStreamNonBlocking)); return MI_OK; }
+    static void destroy(handle s) { (void)hipStreamDestroy(s); }
+};
+struct EventPolicy {   // ordering only
+    using handle = hipEvent_t;
+    static int create(handle *e) { MI_HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming)); return MI_OK; }
+    static void destroy(handle e) { (void)hipEventDestroy(e); }
+};
+struct TimingEventPolicy {
+    using handle = hipEvent_t;
+    static int create(handle *e) { MI_HIP_TRY(hipEventCreate(e)); return MI_OK; }
+    static void destroy(handle e) { (void)hipEventDestroy(e); }
+};
+using Stream = Owned<StreamPolicy>;
+using Event = Owned<EventPolicy>;
+using TimingEvent = Owned<TimingEventPolicy>;
+
+// Large device blocks (the per-lane TV-L1 arenas) come from a small process-wide cache (ArenaCache, mi_own.h): a block released by a handle is kept
 // (at most 4 blocks / MIFLOW_CACHE_GB = 24 GB PER DEVICE and MIFLOW_CACHE_TOTAL_GB = 4 x that per process; with an event behind
 // its previous owner's last work, which the next taker waits for: nothing of the previous owner is still in flight when the block is
 // used again, and no other handle's stream is stalled by a destroy) and handed to the next request of a similar size on the same device.  Measured on
 // MI355X / ROCm 7.2 (r02q): an arena obtained by hipMalloc right after a hipFree of the same size runs the same kernels 25 %
 // slower than the freed one did (390 vs 520 pairs/s, class defaults), i.e. create / destroy cycles of handles must not go
 // through the driver.  mi_release_cached_memory() returns everything to the driver.
+struct HipArenaBackend {   // what the cache and a lane's CachedArena do to the device
+    static int dev_malloc(void **p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+    static int dev_free(void *p) { return (int)hipFree(p); }   // (pointers of any device)
+    static int get_device(int *dev) { return (int)hipGetDevice(dev); }
+    static int pointer_device(const void *p, int *dev)
+    {
+        hipPointerAttribute_t at;
+        const hipError_t e = hipPointerGetAttributes(&at, p);
+        if (e == hipSuccess) *dev = at.device;
+        return (int)e;
+    }
+    static int set_device(int dev) { return (int)hipSetDevice(dev); }
+    static int device_sync() { return (int)hipDeviceSynchronize(); }
+    static int event_sync(void *e) { return (int)hipEventSynchronize((hipEvent_t)e); }
+    static int event_create(void **e) { return EventPolicy::create((hipEvent_t *)e); }
+    static void event_destroy(void *e) { EventPolicy::destroy((hipEvent_t)e); }
+    static int event_record(void *e, void *stream) { return (int)hipEventRecord((hipEvent_t)e, (hipStream_t)stream); }
+    static int stream_capturing(void *stream, bool *capturing)
+    {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        const hipError_t e = hipStreamIsCapturing((hipStream_t)stream, &cs);
+        *capturing = cs != hipStreamCaptureStatusNone;
+        return (int)e;
+    }
+    static void clear_error() { (void)hipGetLastError(); }
+    static const char *error_string(int e) { return hipGetErrorString((hipError_t)e); }
+};
+ArenaCache<HipArenaBackend> &big_cache();   // the process-wide instance (never destroyed: the runtime may be gone at exit)
+using HipArena = CachedArena<HipArenaBackend>;
 int big_alloc(void **p, size_t bytes, size_t *capacity);
 void big_free(void *p, size_t capacity, hipEvent_t ready = nullptr, bool busy = true);
 void big_trim();

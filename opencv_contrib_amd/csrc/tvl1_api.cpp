@@ -29,16 +29,20 @@ struct SlotInfo { int scale, warp; };
 
 }  // namespace
 
+// What a lane's arena was carved for: kept while the frame, the pyramid and the optional planes stay (and the batch does not grow)
+struct ArenaKey {
+    int W = 0, H = 0, scales = 0;
+    double step = 0;
+    bool gamma = false, median = false;
+    bool operator==(const ArenaKey &o) const { return W == o.W && H == o.H && scales == o.scales && step == o.step && gamma == o.gamma && median == o.median; }
+};
+
 // Everything one sub-batch needs: its own arena, pointer table, control slots and profiling events, so that two lanes can
 // run concurrently on two internal streams (the warp kernel is bound by the vector-memory path, the blocked iteration
 // kernel by VALU issue: they overlap, profiles/r02*).
 struct Lane {
-    // capacity the arena was built for
-    int capW = 0, capH = 0, capB = 0, capScales = 0;
-    double capStep = 0;
-    bool capGamma = false, capMedian = false;
-    float *arena = nullptr;
-    size_t arena_bytes = 0;
+    // the arena: a block out of the process-wide cache (mi_own.h) and what it was carved for; below it, the planes carved out of it
+    struct { HipArena blk{&big_cache()}; ArenaKey key; int capB = 0; } arena;
     std::vector<LevelBuf> L;
     // full-resolution-capacity scratch planes (re-laid-out densely per level)
     float *scr[6] = {};    // scr[0..1]: median-filter temporaries; I1wx, I1wy, grad, rho_c
@@ -46,43 +50,57 @@ struct Lane {
     DevBuf<PtrTab> tab;
     std::vector<PtrTab> tab_host;   // source of the asynchronous upload: must outlive the call
     // device loop control
-    DevBuf<int2> S;
-    DevBuf<unsigned long long> E;
-    DevBuf<double> Pd;   // per slot prevError (cv::cuda check schedule)
-    DevBuf<int4> X;      // per slot state of the speculative steps (SpecK::X)
-    long long Q = 0;
-    int ctlB = 0;
-    // iteration counts per (scale, warp, pair slot) of the previous calc, two parities (SpecK::h_in / h_out)
-    DevBuf<int> H;
-    unsigned long long H_sig = 0; // geometry / batch / loop shape the counts belong to (0: none)
-    int H_par = 0;                // parity the NEXT calc writes
-    std::vector<SlotInfo> slots;
+    struct {
+        DevBuf<int2> S;
+        DevBuf<unsigned long long> E;
+        DevBuf<double> Pd;   // per slot prevError (cv::cuda check schedule)
+        DevBuf<int4> X;      // per slot state of the speculative steps (SpecK::X)
+        long long Q = 0;
+        int B = 0;
+        std::vector<SlotInfo> slots;   // (scale, warp) of every launch slot the last calc used
+    } loop;
+    // history: iteration counts per (scale, warp, pair slot) of the previous calc, two parities (SpecK::h_in / h_out)
+    struct {
+        DevBuf<int> H;
+        unsigned long long sig = 0; // geometry / batch / loop shape the counts belong to (0: none)
+        int par = 0;                // parity the NEXT calc writes
+    } hist;
     // host feedback (mi_tvl1_params.host_feedback): pinned landing area of the control slots read back between launches
-    PinnedBuf<int2, hipHostMallocDefault> fb_host;
-    hipEvent_t fb_ev = nullptr;
-    PinnedBuf<int, hipHostMallocCoherent | hipHostMallocMapped> fb_flag;   // polled form (SpecK::fb_flag): {decision word, count} per pair
-    int fb_seq = 0;
-    std::vector<int> fb_hist;        // polled form: most iterations a (scale, warp) of the previous calc needed over its pairs (0: unknown)
-    unsigned long long fb_hist_sig = 0;
+    struct {
+        PinnedBuf<int2, hipHostMallocDefault> host;
+        Event ev;
+        PinnedBuf<int, hipHostMallocCoherent | hipHostMallocMapped> flag;   // polled form (SpecK::fb_flag): {decision word, count} per pair
+        int seq = 0;
+        std::vector<int> hist;        // polled form: most iterations a (scale, warp) of the previous calc needed over its pairs (0: unknown)
+        unsigned long long hist_sig = 0;
+    } fb;
     // profiling (mi_tvl1_set_profiling)
-    std::vector<hipEvent_t> ev_pool;
     struct Region { int e0, e1; long long launches; double bytes; int kind; int level; };   // kind 0: iteration launches, 1: warp launch; level = pyramid scale
-    std::vector<Region> regions;
+    struct { std::vector<TimingEvent> events; std::vector<Region> regions; } prof;
     // internal stream of a concurrent lane + its completion event
-    hipStream_t stream = nullptr;
-    hipEvent_t done = nullptr;
-    hipEvent_t idle_ev = nullptr;        // recorded behind the lane's last calc on the stream it ran on
-    bool idle_valid = false;             // ... and usable (not recorded under stream capture, no error)
-    bool used = false;                   // a calc has been enqueued on the current arena
+    struct { Stream stream; Event done; } internal;
+
+    // THE destruction order of a lane.  Profiling events first (nothing waits for them).  Then the arena goes back to the cache, which
+    // takes the idle event with it where that is valid.  Then the remaining events, while the stream they were recorded on is alive,
+    // then that stream (the last join made the caller's stream wait for its work).  The buffers go last, as members: hipFree /
+    // hipHostFree synchronise the device, so nothing still running reads freed control slots or a freed pointer table.
+    ~Lane()
+    {
+        prof.events.clear();
+        arena.blk.reset();
+        internal.done.reset();
+        fb.ev.reset();
+        internal.stream.reset();
+    }
 };
 
 struct mi_tvl1 {
     mi_tvl1_params P;
     int device = 0;
     DevBuf<float> cubic_tab;
+    Event fork;   // one for all internal lanes; declared before them: it goes after them
     static const int kMaxLanes = 4;
     Lane lane[kMaxLanes];
-    hipEvent_t fork = nullptr;
     int last_nscales = 0, last_batch = 0, last_lanes = 1;
     int last_first[kMaxLanes + 1] = {};   // pairs [last_first[i], last_first[i + 1]) ran on lane i
     bool last_check = false;
@@ -151,7 +169,7 @@ int mi_tvl1_create(const mi_tvl1_params *p, mi_tvl1 **out)
         MI_HIP_TRY(hipMemcpy(h->cubic_tab.p, tab, sizeof(tab), hipMemcpyHostToDevice));
         return MI_OK;
     };
-    if (const int rc = upload()) { mi_tvl1_destroy(h); return rc; }
+    if (const int rc = upload()) { delete h; return rc; }
     *out = h;
     return MI_OK;
 }
@@ -170,20 +188,6 @@ int mi_tvl1_get_params(const mi_tvl1 *h, mi_tvl1_params *p)
     MI_REQUIRE(h && p, MI_ERR_BAD_ARG, "null argument");
     *p = h->P;
     return MI_OK;
-}
-
-static void free_arena(Lane &ln)
-{
-    // the block goes back to the cache with the event the lane recorded behind its last calc (while that calc's stream was alive):
-    // whoever takes the block next waits for that event only -- destroying one handle no longer stalls the other handles' streams
-    if (ln.arena) {
-        big_free(ln.arena, ln.arena_bytes, ln.idle_valid ? ln.idle_ev : nullptr, ln.used);
-        if (ln.idle_valid) ln.idle_ev = nullptr;   // ownership went with the block
-    }
-    ln.idle_valid = false;
-    ln.used = false;
-    ln.arena = nullptr;
-    ln.L.clear();
 }
 
 int mi_tvl1_query_plan(int width, int height, int pairs_per_lane, int iterations_per_launch, int *kernel, int *rows_per_band)
@@ -224,43 +228,28 @@ int mi_tvl1_get_profile_level(mi_tvl1 *h, int kind, int level, double *ms_total,
     *ms_total = 0; *launches = 0; *algo_bytes = 0;
     for (int li = 0; li < h->last_lanes; ++li) {
         Lane &ln = h->lane[li];
-        for (const auto &r : ln.regions) {
+        for (const auto &r : ln.prof.regions) {
             if (r.kind != kind || (level >= 0 && r.level != level)) continue;
-            MI_HIP_TRY(hipEventSynchronize(ln.ev_pool[r.e1]));
+            MI_HIP_TRY(hipEventSynchronize(ln.prof.events[r.e1].get()));
             float ms = 0.f;
-            MI_HIP_TRY(hipEventElapsedTime(&ms, ln.ev_pool[r.e0], ln.ev_pool[r.e1]));
+            MI_HIP_TRY(hipEventElapsedTime(&ms, ln.prof.events[r.e0].get(), ln.prof.events[r.e1].get()));
             *ms_total += ms; *launches += r.launches; *algo_bytes += r.bytes;
         }
     }
     return MI_OK;
 }
 
-void mi_tvl1_destroy(mi_tvl1 *h)
-{
-    if (!h) return;
-    for (Lane &ln : h->lane) {
-        for (hipEvent_t e : ln.ev_pool) (void)hipEventDestroy(e);
-        free_arena(ln);
-        if (ln.idle_ev) { (void)hipEventDestroy(ln.idle_ev); ln.idle_ev = nullptr; }
-        if (ln.done) (void)hipEventDestroy(ln.done);
-        if (ln.fb_ev) (void)hipEventDestroy(ln.fb_ev);
-        if (ln.stream) (void)hipStreamDestroy(ln.stream);
-    }
-    if (h->fork) (void)hipEventDestroy(h->fork);
-    delete h;
-}
+void mi_tvl1_destroy(mi_tvl1 *h) { delete h; }
 
 // The lane's arena in the plan's layout (kept while the frame, the pyramid and the optional planes stay and the batch does not grow)
 static int ensure_arena(const mi_tvl1_params &P, Lane &ln, const TvPlan &pl, int W, int H, int B)
 {
-    const bool gam = P.gamma != 0.0, med = pl.median != 0;
-    if (!(ln.arena && ln.capW == W && ln.capH == H && ln.capB >= B && ln.capScales == P.nscales && ln.capStep == P.scale_step &&
-          ln.capGamma == gam && ln.capMedian == med)) {
-        free_arena(ln);
-        void *blk = nullptr;
-        if (const int rc = big_alloc(&blk, pl.arena.total * sizeof(float), &ln.arena_bytes)) return rc;
-        ln.arena = (float *)blk;
-        const auto at = [&](size_t o) { return o == kNoPlane ? nullptr : ln.arena + o; };
+    const ArenaKey key{W, H, P.nscales, P.scale_step, P.gamma != 0.0, pl.median != 0};
+    if (!(ln.arena.blk.get() && ln.arena.key == key && ln.arena.capB >= B)) {
+        ln.L.clear();
+        if (const int rc = ln.arena.blk.acquire(pl.arena.total * sizeof(float))) return rc;
+        float *const base = (float *)ln.arena.blk.get();
+        const auto at = [&](size_t o) { return o == kNoPlane ? nullptr : base + o; };
         ln.L.resize(pl.geo.size());
         for (size_t l = 0; l < pl.geo.size(); ++l) {
             ln.L[l].I0 = at(pl.arena.lv[l][0]); ln.L[l].I1 = at(pl.arena.lv[l][1]);
@@ -268,7 +257,7 @@ static int ensure_arena(const mi_tvl1_params &P, Lane &ln, const TvPlan &pl, int
         }
         for (int k = 0; k < 6; ++k) ln.scr[k] = at(pl.arena.scr[k]);
         for (int k = 0; k < 12; ++k) ln.pbuf[k / 6][k % 6] = at(pl.arena.p[k]);
-        ln.capGamma = gam; ln.capMedian = med; ln.capW = W; ln.capH = H; ln.capB = B; ln.capScales = P.nscales; ln.capStep = P.scale_step;
+        ln.arena.key = key; ln.arena.capB = B;
     }
     for (size_t l = 0; l < pl.geo.size(); ++l) ln.L[l].g = pl.geo[l];   // (this calc's batch)
     return MI_OK;
@@ -329,34 +318,34 @@ static int ensure_buffers(const TvPlan &pl, Lane &ln, int B, const mi_mat *I0s, 
     MI_HIP_TRY(hipMemcpyAsync(ln.tab.p, ln.tab_host.data(), sizeof(PtrTab) * B, hipMemcpyHostToDevice, st));
     if (pl.check) {
         MI_REQUIRE(pl.Q <= kMaxSlots, MI_ERR_BAD_ARG, "scales x warps x iterations = %lld control slots exceed the limit of %lld", pl.Q, kMaxSlots);
-        if (ln.Q < pl.Q || ln.ctlB < B) {
+        if (ln.loop.Q < pl.Q || ln.loop.B < B) {
             const size_t n = (size_t)pl.Q * B;
-            if ((rc = ln.S.ensure(n)) || (rc = ln.E.ensure(n)) || (rc = ln.Pd.ensure(n)) || (rc = ln.X.ensure(n))) return rc;
-            ln.Q = pl.Q; ln.ctlB = B;
+            if ((rc = ln.loop.S.ensure(n)) || (rc = ln.loop.E.ensure(n)) || (rc = ln.loop.Pd.ensure(n)) || (rc = ln.loop.X.ensure(n))) return rc;
+            ln.loop.Q = pl.Q; ln.loop.B = B;
         }
-        MI_HIP_TRY(hipMemsetAsync(ln.E.p, 0, sizeof(unsigned long long) * (size_t)ln.Q * B, st));
-        MI_HIP_TRY(hipMemsetAsync(ln.S.p, 0, sizeof(int2) * (size_t)ln.Q * B, st));
+        MI_HIP_TRY(hipMemsetAsync(ln.loop.E.p, 0, sizeof(unsigned long long) * (size_t)ln.loop.Q * B, st));
+        MI_HIP_TRY(hipMemsetAsync(ln.loop.S.p, 0, sizeof(int2) * (size_t)ln.loop.Q * B, st));
     }
     if (pl.hist) {   // counts of the previous calc of this lane
         const int nw = (int)pl.warp[0].size();
         const size_t h_n = (size_t)pl.used * nw * B;
-        if (ln.H.n < 2 * h_n) ln.H_sig = 0;
-        if ((rc = ln.H.ensure(2 * h_n))) return rc;
-        if (ln.H_sig != pl.hist_sig) {   // counts of another geometry say nothing: start from none (0 = no estimate)
-            MI_HIP_TRY(hipMemsetAsync(ln.H.p, 0, sizeof(int) * ln.H.n, st));
-            ln.H_sig = pl.hist_sig;
+        if (ln.hist.H.n < 2 * h_n) ln.hist.sig = 0;
+        if ((rc = ln.hist.H.ensure(2 * h_n))) return rc;
+        if (ln.hist.sig != pl.hist_sig) {   // counts of another geometry say nothing: start from none (0 = no estimate)
+            MI_HIP_TRY(hipMemsetAsync(ln.hist.H.p, 0, sizeof(int) * ln.hist.H.n, st));
+            ln.hist.sig = pl.hist_sig;
         }
-        if (ln.fb_hist_sig != pl.hist_sig || ln.fb_hist.size() != (size_t)pl.used * nw) {
-            ln.fb_hist.assign((size_t)pl.used * nw, 0);
-            ln.fb_hist_sig = pl.hist_sig;
+        if (ln.fb.hist_sig != pl.hist_sig || ln.fb.hist.size() != (size_t)pl.used * nw) {
+            ln.fb.hist.assign((size_t)pl.used * nw, 0);
+            ln.fb.hist_sig = pl.hist_sig;
         }
-        ln.H_par ^= 1;
+        ln.hist.par ^= 1;
     }
     if (pl.fb) {
-        const bool fresh = ln.fb_flag.n < 2 * (size_t)B;
-        if ((rc = ln.fb_host.ensure(2 * (size_t)B)) || (rc = ln.fb_flag.ensure(2 * (size_t)B))) return rc;
-        if (fresh) memset(ln.fb_flag.p, 0, sizeof(int) * ln.fb_flag.n);
-        if (!ln.fb_ev) MI_HIP_TRY(hipEventCreateWithFlags(&ln.fb_ev, hipEventDisableTiming));
+        const bool fresh = ln.fb.flag.n < 2 * (size_t)B;
+        if ((rc = ln.fb.host.ensure(2 * (size_t)B)) || (rc = ln.fb.flag.ensure(2 * (size_t)B))) return rc;
+        if (fresh) memset(ln.fb.flag.p, 0, sizeof(int) * ln.fb.flag.n);
+        MI_TRY(ln.fb.ev.ensure());
     }
     return MI_OK;
 }
@@ -387,13 +376,13 @@ struct Run {
 // records a profiling event on the lane's stream
 int record(Run &r, int *idx)
 {
-    if (r.ev_used == r.ln.ev_pool.size()) {
-        hipEvent_t e;
-        MI_HIP_TRY(hipEventCreate(&e));
-        r.ln.ev_pool.push_back(e);
+    if (r.ev_used == r.ln.prof.events.size()) {
+        TimingEvent e;
+        MI_TRY(e.ensure());
+        r.ln.prof.events.push_back(std::move(e));
     }
     *idx = (int)r.ev_used++;
-    MI_HIP_TRY(hipEventRecord(r.ln.ev_pool[*idx], r.st));
+    MI_HIP_TRY(hipEventRecord(r.ln.prof.events[*idx].get(), r.st));
     return MI_OK;
 }
 
@@ -490,7 +479,7 @@ int run_per_iteration(Run &r, LevelBuf &Lv, int s, int wp, long long *nlaunch)
             Ctl ic = r.ctl;
             ic.q = r.q; ic.q_prev = r.q_last; ic.first_of_warp = (it == 0); ic.reset_cur = r.first_of_scale; ic.n = it;
             rc = iterate(P.exact_math != 0, r.planes, Lv.g, r.l_t, r.theta, r.taut, r.first_of_scale, &ic, 0, r.st);
-            r.ln.slots.push_back({s, wp});
+            r.ln.loop.slots.push_back({s, wp});
             r.q_last = r.q++;
         } else {
             rc = iterate(P.exact_math != 0, r.planes, Lv.g, r.l_t, r.theta, r.taut, r.first_of_scale, nullptr, r.cur, r.st);
@@ -511,7 +500,7 @@ struct Feedback { bool all = true, all_before = true; int n_most = 0; };
 // only; a wall-clock bound ends a wait no launch will ever answer.
 int poll_feedback(Run &r, int seq, Feedback *f)
 {
-    const int *flag = r.ln.fb_flag.p;
+    const int *flag = r.ln.fb.flag.p;
     for (int b = 0; b < r.B; ++b) {
         int v = 0;
         const auto t_wait0 = std::chrono::steady_clock::now();
@@ -549,13 +538,13 @@ int poll_feedback(Run &r, int seq, Feedback *f)
 int copy_feedback(Run &r, Feedback *f)
 {
     Lane &ln = r.ln;
-    MI_HIP_TRY(hipMemcpy2DAsync(ln.fb_host.p, 2 * sizeof(int2), ln.S.p + (r.q_last - 1), sizeof(int2) * (size_t)ln.Q, 2 * sizeof(int2),
+    MI_HIP_TRY(hipMemcpy2DAsync(ln.fb.host.p, 2 * sizeof(int2), ln.loop.S.p + (r.q_last - 1), sizeof(int2) * (size_t)ln.loop.Q, 2 * sizeof(int2),
                                 (size_t)r.B, hipMemcpyDeviceToHost, r.st));
-    MI_HIP_TRY(hipEventRecord(ln.fb_ev, r.st));
-    MI_HIP_TRY(hipEventSynchronize(ln.fb_ev));
+    MI_HIP_TRY(hipEventRecord(ln.fb.ev.get(), r.st));
+    MI_HIP_TRY(hipEventSynchronize(ln.fb.ev.get()));
     for (int b = 0; b < r.B; ++b) {
-        f->all_before = f->all_before && (ln.fb_host.p[2 * b].y & MI_SLOT_DONE);
-        f->all = f->all && (ln.fb_host.p[2 * b + 1].y & MI_SLOT_DONE);
+        f->all_before = f->all_before && (ln.fb.host.p[2 * b].y & MI_SLOT_DONE);
+        f->all = f->all && (ln.fb.host.p[2 * b + 1].y & MI_SLOT_DONE);
     }
     return MI_OK;
 }
@@ -575,7 +564,7 @@ int run_spec(Run &r, LevelBuf &Lv, const TvWarp &w, int s, int wp, long long *nl
     const int nw = (int)pl.warp[s].size();
     int rc, hprev = 0;   // the previous calc's count for this warp, where the host has seen it (polled host feedback)
     if (pl.fb_poll && pl.hist) {
-        int &hc = ln.fb_hist[(size_t)s * nw + wp];
+        int &hc = ln.fb.hist[(size_t)s * nw + wp];
         hprev = hc;
         hc = 0;   // known again once this warp's stop has been seen
     }
@@ -584,14 +573,14 @@ int run_spec(Run &r, LevelBuf &Lv, const TvWarp &w, int s, int wp, long long *nl
     for (int v : plan) t_after += v;
     SpecK sk;
     memset(&sk, 0, sizeof(sk));
-    sk.X = ln.X.p; sk.iters = pl.iters;
+    sk.X = ln.loop.X.p; sk.iters = pl.iters;
     sk.q_hist = wp > 0 ? r.q_settle_prev : r.q_settle_scale;
     spec_hist_fraction(wp, &sk.hist_num, &sk.hist_den);
     sk.slack = r.h->P.stop_slack;
     if (pl.hist) {
-        const size_t o = ((size_t)s * nw + wp) * r.B, half = ln.H.n / 2;
-        sk.h_in = ln.H.p + (size_t)(ln.H_par ^ 1) * half + o;
-        sk.h_out = ln.H.p + (size_t)ln.H_par * half + o;
+        const size_t o = ((size_t)s * nw + wp) * r.B, half = ln.hist.H.n / 2;
+        sk.h_in = ln.hist.H.p + (size_t)(ln.hist.par ^ 1) * half + o;
+        sk.h_out = ln.hist.H.p + (size_t)ln.hist.par * half + o;
     }
     if (r.first_of_scale) {   // a replay of the scale's first block must see p = 0 in the input set as well
         const size_t n = (size_t)Lv.g.ps * r.B;
@@ -610,15 +599,15 @@ int run_spec(Run &r, LevelBuf &Lv, const TvWarp &w, int s, int wp, long long *nl
         a.q = r.q; a.q_prev = r.q_last; a.first_of_warp = (k == 0); a.reset_cur = (k == 0 && r.first_of_scale); a.n = 0;
         sk.e0_prev = e_prev; sk.final_launch = last ? 1 : 0; sk.t_after = t_after;
         if (pl.fb_poll) {
-            ln.fb_seq = (ln.fb_seq + 1) & 0x0fffffff;
-            sk.fb_flag = ln.fb_flag.p; sk.fb_seq = ln.fb_seq;
+            ln.fb.seq = (ln.fb.seq + 1) & 0x0fffffff;
+            sk.fb_flag = ln.fb.flag.p; sk.fb_seq = ln.fb.seq;
         }
-        MI_REQUIRE((long long)r.e_next + T <= ln.Q && r.q < ln.Q, MI_ERR_BAD_ARG,
-                   "speculative steps: error-sum slot %d + %d or launch slot %d beyond the %lld slots sized for this calc", r.e_next, T, r.q, ln.Q);
+        MI_REQUIRE((long long)r.e_next + T <= ln.loop.Q && r.q < ln.loop.Q, MI_ERR_BAD_ARG,
+                   "speculative steps: error-sum slot %d + %d or launch slot %d beyond the %lld slots sized for this calc", r.e_next, T, r.q, ln.loop.Q);
         // (the host feedback's cost model may have changed the block lengths: the same rule picks their kernel)
         const TbKernel kern = tb_kernel(TbUse::Spec, T, Lv.g, r.h->P.gamma != 0.0, w.nograd, r.K);
         if ((rc = iterate_tb_spec(kern, T, r.planes, Lv.g, r.l_t, r.theta, r.taut, a, sk, r.e_next, r.st))) return rc;
-        ln.slots.push_back({s, wp});
+        ln.loop.slots.push_back({s, wp});
         r.q_last = r.q++;
         ++*nlaunch;
         e_prev = r.e_next;
@@ -630,10 +619,10 @@ int run_spec(Run &r, LevelBuf &Lv, const TvWarp &w, int s, int wp, long long *nl
         const bool ahead = pl.fb_poll && r.K.fb_ahead != 0 && r.K.x_skip == 0 && !r.h->profiling && wp + 1 < nw;
         if (ahead && (rc = launch_warp(r, Lv, true))) return rc;
         Feedback f;
-        if ((rc = pl.fb_poll ? poll_feedback(r, ln.fb_seq, &f) : copy_feedback(r, &f))) return rc;
+        if ((rc = pl.fb_poll ? poll_feedback(r, ln.fb.seq, &f) : copy_feedback(r, &f))) return rc;
         if (f.all) {
             r.pre_warped = ahead;
-            if (pl.fb_poll && pl.hist) ln.fb_hist[(size_t)s * nw + wp] = f.n_most;
+            if (pl.fb_poll && pl.hist) ln.fb.hist[(size_t)s * nw + wp] = f.n_most;
             fb_done_at = f.all_before ? (int)k - 1 : (int)k;   // where the next warp's first read-back goes
             break;
         }
@@ -662,7 +651,7 @@ int run_warp(Run &r, LevelBuf &Lv, int s, int wp)
     else if (w.warp_launch && (rc = launch_warp(r, Lv, false))) return rc;
     if (prof && !w.fused) {
         if ((rc = record(r, &w1))) return rc;
-        r.ln.regions.push_back({w0, w1, 1, 44.0 * g.w * g.h * r.B, 1, s});   // 44 B/px per warp
+        r.ln.prof.regions.push_back({w0, w1, 1, 44.0 * g.w * g.h * r.B, 1, s});   // 44 B/px per warp
     }
     if (prof && r.pl.iters > 0 && (rc = record(r, &e0))) return rc;
     long long nlaunch = 0;
@@ -675,7 +664,7 @@ int run_warp(Run &r, LevelBuf &Lv, int s, int wp)
     if (rc) return rc;
     if (e0 >= 0) {
         if ((rc = record(r, &e1))) return rc;
-        r.ln.regions.push_back({e0, e1, nlaunch, 64.0 * g.w * g.h * r.B * r.pl.iters, 0, s});
+        r.ln.prof.regions.push_back({e0, e1, nlaunch, 64.0 * g.w * g.h * r.B * r.pl.iters, 0, s});
     }
     return MI_OK;
 }
@@ -710,18 +699,7 @@ static int lane_calc(mi_tvl1 *h, Lane &ln, int n, const mi_mat *I0s, const mi_ma
 {
     // behind everything this call enqueues for the lane (also on an error return: part of the calc may be in flight): the event the
     // arena cache waits for before it hands the lane's block to somebody else
-    struct Mark {
-        Lane &l; hipStream_t s;
-        ~Mark()
-        {
-            if (!l.arena) return;
-            l.used = true; l.idle_valid = false;
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return; }
-            if (!l.idle_ev && hipEventCreateWithFlags(&l.idle_ev, hipEventDisableTiming) != hipSuccess) { l.idle_ev = nullptr; (void)hipGetLastError(); return; }
-            if (hipEventRecord(l.idle_ev, s) == hipSuccess) l.idle_valid = true; else (void)hipGetLastError();
-        }
-    } mark{ln, st};
+    struct Mark { HipArena &a; hipStream_t s; ~Mark() { a.mark(s); } } mark{ln.arena.blk, st};
     const mi_tvl1_params &P = h->P;
     hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;
     const bool capturing = hipStreamIsCapturing(st, &cap_st) == hipSuccess && cap_st != hipStreamCaptureStatusNone;
@@ -731,12 +709,12 @@ static int lane_calc(mi_tvl1 *h, Lane &ln, int n, const mi_mat *I0s, const mi_ma
     if (!pl.warp.empty() && !pl.warp[0].empty() && pl.warp[0].back().pack_in_pass)   // the pass keeps the matrices' pitch in 32 bits
         for (int i = 0; i < n; ++i) MI_REQUIRE(flows[i].step < (1ll << 31), MI_ERR_BAD_ARG, "flow matrix pitch of %lld bytes", (long long)flows[i].step);
     *ns_out = pl.used;
-    ln.slots.clear();
-    ln.regions.clear();
+    ln.loop.slots.clear();
+    ln.prof.regions.clear();
 
     Run r{h, ln, pl, tv_knobs(), st, n};
     memset(&r.ctl, 0, sizeof(r.ctl));
-    r.ctl.S = ln.S.p; r.ctl.E = ln.E.p; r.ctl.Q = (int)ln.Q; r.ctl.P = ln.Pd.p;
+    r.ctl.S = ln.loop.S.p; r.ctl.E = ln.loop.E.p; r.ctl.Q = (int)ln.loop.Q; r.ctl.P = ln.loop.Pd.p;
     r.ctl.sched = P.semantics == MI_SEM_CUDA_COMPAT ? 1 : 0;   // cv::cuda's check schedule vs the CPU class's every-iteration check
     r.l_t = (float)(P.lambda * P.theta); r.taut = (float)(P.tau / P.theta); r.theta = (float)P.theta;
     if ((rc = enqueue_pyramid(r, I0s[0].type))) return rc;
@@ -785,13 +763,13 @@ int mi_tvl1_calc_batch(mi_tvl1 *h, int n, const mi_mat *I0s, const mi_mat *I1s, 
         // land on one queue run back to back: measured 400 instead of 520 pairs/s when enough streams of other handles were alive.)
         // every stream and event the fork / join needs exists BEFORE anything is enqueued, so no failure between the fork and the
         // join can leave an internal lane un-joined
-        if (!h->fork) MI_HIP_TRY(hipEventCreateWithFlags(&h->fork, hipEventDisableTiming));
+        MI_TRY(h->fork.ensure());
         for (int li = 1; li < lanes; ++li) {
             Lane &ln = h->lane[li];
-            if (!ln.stream) MI_HIP_TRY(hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking));
-            if (!ln.done) MI_HIP_TRY(hipEventCreateWithFlags(&ln.done, hipEventDisableTiming));
+            MI_TRY(ln.internal.stream.ensure());
+            MI_TRY(ln.internal.done.ensure());
         }
-        MI_HIP_TRY(hipEventRecord(h->fork, st));
+        MI_HIP_TRY(hipEventRecord(h->fork.get(), st));
         int rc_first = MI_OK;
         auto note = [&](hipError_t e) {
             if (e != hipSuccess && !rc_first) { set_error("HIP error in the lane fork / join: %s", hipGetErrorString(e)); rc_first = MI_ERR_HIP; }
@@ -800,9 +778,9 @@ int mi_tvl1_calc_batch(mi_tvl1 *h, int n, const mi_mat *I0s, const mi_mat *I1s, 
         for (int li = lanes - 1; li >= 0; --li) {   // the internal lanes first: they start while lane 0 is still being enqueued
             Lane &ln = h->lane[li];
             const int off = h->last_first[li], cnt = h->last_first[li + 1] - off;
-            hipStream_t ls = li > 0 ? ln.stream : st;
+            hipStream_t ls = li > 0 ? ln.internal.stream.get() : st;
             // a lane that could not be forked behind the caller's stream must not run at all (it would read inputs too early)
-            const bool forked = li == 0 || note(hipStreamWaitEvent(ln.stream, h->fork, 0));
+            const bool forked = li == 0 || note(hipStreamWaitEvent(ln.internal.stream.get(), h->fork.get(), 0));
             if (forked && !rc_first) {
                 const int rc = lane_calc(h, ln, cnt, I0s + off, I1s + off, flows + off, ls, &ns);
                 if (rc && !rc_first) rc_first = rc;
@@ -811,8 +789,8 @@ int mi_tvl1_calc_batch(mi_tvl1 *h, int n, const mi_mat *I0s, const mi_mat *I1s, 
         // always join, also after an error: the caller's stream must not run ahead of work already enqueued.  If the join itself
         // fails, fall back to blocking the host until the lane has drained.
         for (int li = 1; li < lanes; ++li) {
-            Lane &ln = h->lane[li];
-            if (!(note(hipEventRecord(ln.done, ln.stream)) && note(hipStreamWaitEvent(st, ln.done, 0)))) (void)hipStreamSynchronize(ln.stream);
+            auto &in = h->lane[li].internal;
+            if (!(note(hipEventRecord(in.done.get(), in.stream.get())) && note(hipStreamWaitEvent(st, in.done.get(), 0)))) (void)hipStreamSynchronize(in.stream.get());
         }
         if (rc_first) return rc_first;
     }
@@ -834,16 +812,16 @@ static int read_slots(mi_tvl1 *h, int pair, hipStream_t stream, const Lane **lan
     int li = 0;
     while (li + 1 < h->last_lanes && pair >= h->last_first[li + 1]) ++li;
     const Lane &ln = h->lane[li];
-    const size_t off = (size_t)(pair - h->last_first[li]) * ln.Q;
-    const int nq = (int)ln.slots.size();
+    const size_t off = (size_t)(pair - h->last_first[li]) * ln.loop.Q;
+    const int nq = (int)ln.loop.slots.size();
     MI_REQUIRE(cap_launches < 0 || nq <= cap_launches, MI_ERR_BAD_ARG, "capacity too small");
     *lane = &ln;
     S->resize(nq);
     MI_HIP_TRY(hipStreamSynchronize(stream));
-    MI_HIP_TRY(hipMemcpy(S->data(), ln.S.p + off, sizeof(int2) * nq, hipMemcpyDeviceToHost));
+    MI_HIP_TRY(hipMemcpy(S->data(), ln.loop.S.p + off, sizeof(int2) * nq, hipMemcpyDeviceToHost));
     if (X) {
         X->resize(nq);
-        if (ln.X.p) MI_HIP_TRY(hipMemcpy(X->data(), ln.X.p + off, sizeof(int4) * nq, hipMemcpyDeviceToHost));
+        if (ln.loop.X.p) MI_HIP_TRY(hipMemcpy(X->data(), ln.loop.X.p + off, sizeof(int4) * nq, hipMemcpyDeviceToHost));
     }
     return MI_OK;
 }
@@ -866,7 +844,7 @@ int mi_tvl1_last_iterations(mi_tvl1 *h, int pair, int *nscales_used, int *iters,
     for (size_t i = 0; i < S.size(); ++i) {
         // one-iteration launches: bit 0 = the iteration was executed; speculative launches: bits 8..15 = iterations kept
         const int k = (S[i].y >> 8) & 0xff;
-        iters[ln->slots[i].scale * nw + ln->slots[i].warp] += k ? k : (S[i].y & 1);
+        iters[ln->loop.slots[i].scale * nw + ln->loop.slots[i].warp] += k ? k : (S[i].y & 1);
     }
     return MI_OK;
 }
@@ -883,7 +861,7 @@ int miflow_selftest_tvl1_slots(mi_tvl1 *h, int pair, int *out_host, int cap_laun
     const int nq = (int)S.size();
     for (int i = 0; i < nq; ++i) {
         int *o = out_host + 8 * i;
-        o[0] = ln->slots[i].scale; o[1] = ln->slots[i].warp; o[2] = S[i].x; o[3] = S[i].y;
+        o[0] = ln->loop.slots[i].scale; o[1] = ln->loop.slots[i].warp; o[2] = S[i].x; o[3] = S[i].y;
         o[4] = X[i].x; o[5] = X[i].y; o[6] = X[i].z; o[7] = X[i].w;
     }
     return nq;

@@ -2,7 +2,9 @@
 the same parameters on the same inputs at every step: bit for bit, no tolerance, no oracle.  The scratch of every handle is a set of
 grow-only owners (csrc/mi_buf.h) that each call ensures before it uses them; a buffer that arrives late (StereoBM's prefilter planes,
 SURF's mask integral), a re-grow between two layouts (the batch stride of StereoBM, BFMatcher's knn / radius partials) or a handle that
-goes back to a small frame after a large one must give what a handle that never saw anything else gives.  StereoSGM and DensePyrLK have
+goes back to a small frame after a large one must give what a handle that never saw anything else gives.  A TV-L1 handle owns more than
+buffers -- per lane an internal stream, events and an arena out of the process-wide cache (csrc/mi_own.h) -- and has the same test over
+the calls that create each of them.  StereoSGM and DensePyrLK have
 the same test next to their others (test_compute_handle_reuse_across_sizes, test_calc_handle_reuse_across_sizes_and_kernel_templates).
 Inputs: the seeded generators of opencv_contrib_amd.synth and seeded random descriptors / points."""
 import os
@@ -117,6 +119,52 @@ def test_farneback_arena_follows_size_and_batch(gpu):
         out = run(reused, ps)
         assert float(out.abs().max()) > 0.1, name
         same_bits(out, run(cuda.FarnebackOpticalFlow.create(), ps), f"Farneback {name}")
+
+
+def test_tvl1_lanes_events_and_cached_arena_follow_the_calls(gpu):
+    """96 x 80 and 160 x 120 (five pyramid levels above the 16-px cut each), 20 iterations.  One handle through: a single pair; a batch
+    of 4 (two lanes: the internal stream, the fork and the done event); epsilon 0.01 with host_feedback 1 set through the params struct,
+    on the batch of 4 and on a single pair (one lane: the feedback flags in pinned memory and the feedback event); the same two with
+    profiling on (the pool of timing events, read through getProfile); the other frame size, single and batch (each lane's arena goes
+    back to the cache and another is acquired).  Then the handle is destroyed with its last calc still in flight and a new handle runs
+    the batch of 4 of the first geometry -- on the blocks, with their idle events, that the cache just took -- and
+    release_cached_memory() returns."""
+    from opencv_contrib_amd import cuda
+
+    def pairs(h, w, n, seed):
+        return [tuple(T(a, gpu) for a in synth.flow_pair(h, w, seed=seed + k)[:2]) for k in range(n)]
+
+    def make(epsilon=0.0, fb=0):
+        return cuda.OpticalFlowDual_TVL1.create(iterations=20, epsilon=epsilon, hostFeedback=fb)
+
+    def run(alg, ps):
+        if len(ps) == 1:
+            return alg.calc(ps[0][0], ps[0][1])
+        return alg.calc_batch([p[0] for p in ps], [p[1] for p in ps])
+
+    small, large = pairs(80, 96, 4, 800), pairs(120, 160, 4, 810)
+    reused = make()
+    first_batch = None
+    for name, eps, fb, prof, ps in (("96x80", 0.0, 0, False, small[:1]), ("4 x 96x80", 0.0, 0, False, small),
+                                    ("4 x 96x80, epsilon", 0.01, 1, False, small), ("96x80, epsilon + host feedback", 0.01, 1, False, small[:1]),
+                                    ("4 x 96x80, profiling", 0.01, 1, True, small), ("96x80, profiling", 0.01, 1, True, small[:1]),
+                                    ("160x120", 0.01, 1, True, large[:1]), ("4 x 160x120", 0.01, 1, True, large)):
+        reused._set(epsilon=eps, host_feedback=fb)
+        reused.setProfiling(prof)
+        out = run(reused, ps)
+        assert float(out.abs().max()) > 0.1, name
+        fresh = run(make(eps, fb), ps)
+        same_bits(out, fresh, f"TV-L1 {name}")
+        if prof:
+            ms, launches, _ = reused.getProfile()
+            assert ms > 0.0 and launches > 0, name
+        if first_batch is None and len(ps) == 4:
+            first_batch = fresh.clone()
+    reused.__del__()   # mi_tvl1_destroy, behind the 160 x 120 batch it has just enqueued
+    again = make()
+    same_bits(run(again, small), first_batch, "TV-L1 4 x 96x80 on a new handle after the destroy")
+    again.__del__()
+    cuda.release_cached_memory()
 
 
 def test_bfmatcher_partials_follow_size_and_layout(gpu):
