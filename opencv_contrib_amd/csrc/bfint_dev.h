@@ -8,6 +8,7 @@
 #pragma once
 #include <cfloat>
 #include <cstdint>
+#include "bf_shared.h"   // T, MAX_D, MAX_K, Lists
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -27,15 +28,11 @@
 namespace mi {
 namespace bfint {
 
-constexpr int T = 64;          // queries per workgroup
 constexpr int TT = 32;         // train rows per tile
-constexpr int MAX_D = 128;     // descriptor elements (ORB 32, BRISK / FREAK 64, AKAZE 61)
-constexpr int MAX_K = 16;
 constexpr int NORM_L1 = 2, NORM_HAMMING = 6;
 
 struct Desc { const void *p; long long step; int rows, cols, depth; };      // depth: 0 = 8U, 2 = 16U, 3 = 16S, 4 = 32S (cv depths)
 struct Mask { const unsigned char *p; long long step; };                    // p == nullptr: none
-struct Lists { int *idx; long long istep; int *img; long long mstep; float *dist; long long dstep; };   // n_q x k, element strides; img may be null
 
 struct Shared {
     int q[MAX_D][T];

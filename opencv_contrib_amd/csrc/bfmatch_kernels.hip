@@ -10,38 +10,12 @@
 // further passes that only admit candidates after the last entry found so far (no distance matrix).  Distances follow the
 // reference's summation order exactly (k ascending; L2: sum = fma(d, d, sum) then sqrtf; L1: sum += |d|), so the HIP result is
 // bit-identical to oracle/bfmatch_ref.c.
-#include "mi_common.h"
 #include "bf_dispatch.h"
 #include <cfloat>
 #include <climits>
-#include <cstdlib>
-#include <vector>
-
-struct mi_bfmatcher {
-    int norm = MI_NORM_L2;
-    mi::DevBuf<unsigned char> part;   // knn: [segment][query][K] {distance, index}; radius: [segment][query] count -> offset
-};
 
 namespace mi {
 namespace bf {
-
-struct Args {
-    const float *q; size_t qstep;      // bytes
-    const float *t; size_t tstep;
-    const unsigned char *mask; size_t mstep;
-    int nq, nt, d;
-    int rows_per_split;
-    int t_base;                        // index of this train set's row 0 in the concatenated collection
-    int seg0;                          // first segment (split) of this train set in `part` / `cnt`
-    float2 *part;                      // knn: [(seg0 + split) * nq + query][K] = {distance, as_float(collection index)}
-    // knn continuation pass (k > K): only candidates after (lo_dist, lo_idx) in (distance, index) order; per-query element strides
-    const float *lo_dist; const int *lo_idx; size_t lo_dstep, lo_istep;
-    // radius
-    int *cnt;                          // [(seg0 + split) * nq + query]: hits of the segment (count pass) / first output slot (write pass)
-    float max_dist;
-    int write, cols;
-    int *r_idx, *r_img; float *r_dist; size_t r_istep, r_mstep, r_dstep;   // element strides per query
-};
 
 // K best (distance, index) pairs of a lane, ascending; empty slots are (FLT_MAX, INT_MAX).  push() keeps the K smallest pairs in
 // lexicographic order, which is what "if (d < best1) {...} else if (d < best2) {...}" (bf_knnmatch.cu:353-371) yields when the
@@ -285,248 +259,36 @@ __global__ __launch_bounds__(256) void k_radius_scan(int *cnt, int nq, int nseg,
     n_matches[qi] = run;             // every hit is counted, like the reference's atomicInc (may exceed cols)
 }
 
-// ------------------------------------------------------------------------------------------------ host side
-typedef void (*launch_t)(const Args &, dim3, hipStream_t);
+// ------------------------------------------------------------------------------------------------ launcher
+// The kernel of a plan's passes, instantiated from kBfRows (bf_plan.h) and nowhere else: per row k_knn<D, TT, W | W1, L2 | L1, 2 | 8>
+// and k_radius<D, TT, L2 | L1>; rows whose W1 equals W name one kernel twice: 24 k_knn, 8 k_radius.
+typedef void (*kernel_t)(Args);
 
-template <int D, int TT, int W, int NORM, int K>
-static void launch_knn(const Args &A, dim3 grid, hipStream_t st)
+template <int R = 0>
+static kernel_t kernel_of(const BfPlan &p)
 {
-    hipLaunchKernelGGL((k_knn<D, TT, W, NORM, K>), grid, dim3(64 * W), 0, st, A);
+    constexpr BfRow r = kBfRows[R];
+    constexpr int L2 = MI_NORM_L2, L1 = MI_NORM_L1;
+    if constexpr (R + 1 < kBfRowCount) if (p.row != R) return kernel_of<R + 1>(p);
+    static const kernel_t tab[3][2][2] = {   // [radius, K = 2, K = 8][W, W1][L2, L1]
+        {{k_radius<r.D, r.TT, L2>, k_radius<r.D, r.TT, L1>}, {k_radius<r.D, r.TT, L2>, k_radius<r.D, r.TT, L1>}},
+        {{k_knn<r.D, r.TT, r.W, L2, 2>, k_knn<r.D, r.TT, r.W, L1, 2>}, {k_knn<r.D, r.TT, r.W1, L2, 2>, k_knn<r.D, r.TT, r.W1, L1, 2>}},
+        {{k_knn<r.D, r.TT, r.W, L2, 8>, k_knn<r.D, r.TT, r.W, L1, 8>}, {k_knn<r.D, r.TT, r.W1, L2, 8>, k_knn<r.D, r.TT, r.W1, L1, 8>}}};
+    return tab[p.K == 0 ? 0 : p.K == 2 ? 1 : 2][p.w != r.W][p.norm == L1];
 }
 
-template <int D, int TT, int NORM>
-static void launch_radius(const Args &A, dim3 grid, hipStream_t st)
+void launch(const BfPlan &p, const BfLaunch &l, const Args &A, const bfint::Lists &o, int *n_matches, hipStream_t st)
 {
-    hipLaunchKernelGGL((k_radius<D, TT, NORM>), grid, dim3(64), 0, st, A);
-}
-
-template <int D, int TT, int W>
-static launch_t pick_knn(int norm, int K)
-{
-    if (norm == MI_NORM_L2) return K == 2 ? launch_knn<D, TT, W, MI_NORM_L2, 2> : launch_knn<D, TT, W, MI_NORM_L2, 8>;
-    return K == 2 ? launch_knn<D, TT, W, MI_NORM_L1, 2> : launch_knn<D, TT, W, MI_NORM_L1, 8>;
-}
-
-template <int D, int TT>
-static launch_t pick_radius(int norm)
-{
-    return norm == MI_NORM_L2 ? launch_radius<D, TT, MI_NORM_L2> : launch_radius<D, TT, MI_NORM_L1>;
-}
-
-struct Shape { launch_t fn; int tt, w; };
-
-// matchDispatcher (bf_match.cu:563-570) by descriptor length; long descriptors trade tile height for the query area
-static Shape knn_shape(int d, int norm, int K)
-{
-    // four waves per workgroup measured 2.8-3.5 x faster than one (profiles/r01y: 12 564^2 pairs, D = 64: 0.69 vs 1.95 ms);
-    // MIFLOW_BF_W=1 keeps the single-wave shape reachable (read per call: tests and sweeps switch it inside one process)
-    const char *e = getenv("MIFLOW_BF_W");
-    const int w_small = e && atoi(e) == 1 ? 1 : 4;
-    if (d <= 64) return w_small == 4 ? Shape{pick_knn<64, 32, 4>(norm, K), 32, 4} : Shape{pick_knn<64, 32, 1>(norm, K), 32, 1};
-    if (d <= 128) return w_small == 4 ? Shape{pick_knn<128, 32, 4>(norm, K), 32, 4} : Shape{pick_knn<128, 32, 1>(norm, K), 32, 1};
-    if (d <= 256) return Shape{pick_knn<256, 16, 4>(norm, K), 16, 4};
-    return Shape{pick_knn<512, 8, 2>(norm, K), 8, 2};
-}
-
-static Shape radius_shape(int d, int norm)
-{
-    if (d <= 64) return Shape{pick_radius<64, 32>(norm), 32, 1};
-    if (d <= 128) return Shape{pick_radius<128, 32>(norm), 32, 1};
-    if (d <= 256) return Shape{pick_radius<256, 16>(norm), 16, 1};
-    return Shape{pick_radius<512, 8>(norm), 8, 1};
-}
-
-struct Seg { int nsplit, rows_per_split, seg0, t_base; };
-
-// validates (query, trains[], masks[]) and plans the splits: enough workgroups for 256 CUs, multiples of the LDS tile
-static int plan(const mi_mat *query, const mi_mat *trains, const mi_mat *masks, int n_trains, int tt, std::vector<Seg> &segs, int *nseg)
-{
-    MI_REQUIRE(query && trains && query->data && n_trains > 0, MI_ERR_BAD_ARG, "null argument");
-    MI_REQUIRE(query->type == MI_32FC1, MI_ERR_BAD_TYPE, "descriptors must be CV_32FC1");
-    MI_REQUIRE(query->rows > 0 && query->cols > 0, MI_ERR_BAD_SIZE, "empty query");
-    MI_REQUIRE(query->cols <= 512, MI_ERR_BAD_SIZE, "descriptor length <= 512; longer descriptors are not built");
-    const int qblocks = div_up(query->rows, 64);
-    long long total = 0;
-    int s0 = 0;
-    segs.resize(n_trains);
-    for (int m = 0; m < n_trains; ++m) {
-        const mi_mat &t = trains[m];
-        MI_REQUIRE(t.data && t.type == MI_32FC1, MI_ERR_BAD_TYPE, "descriptors must be CV_32FC1");
-        MI_REQUIRE(t.rows > 0 && t.cols == query->cols, MI_ERR_BAD_SIZE, "query.cols == train.cols, non-empty");
-        if (masks && masks[m].data)
-            MI_REQUIRE(masks[m].type == MI_8UC1 && masks[m].rows == query->rows && masks[m].cols == t.rows, MI_ERR_BAD_SIZE,
-                       "mask must be CV_8UC1, query.rows x train.rows");
-        int nsplit = min(max(1, 2048 / qblocks), div_up(t.rows, tt));
-        const int rps = align_up(div_up(t.rows, nsplit), tt);
-        nsplit = div_up(t.rows, rps);
-        segs[m] = Seg{nsplit, rps, s0, (int)total};
-        s0 += nsplit;
-        total += t.rows;
-        MI_REQUIRE(total < INT_MAX, MI_ERR_BAD_SIZE, "train collection too large");
-    }
-    *nseg = s0;
-    return MI_OK;
-}
-
-static void fill_args(Args &A, const mi_mat *query, const mi_mat &t, const mi_mat *mask, const Seg &s)
-{
-    A.q = (const float *)query->data; A.qstep = query->step;
-    A.t = (const float *)t.data; A.tstep = t.step;
-    A.mask = mask && mask->data ? (const unsigned char *)mask->data : nullptr; A.mstep = A.mask ? mask->step : 0;
-    A.nq = query->rows; A.nt = t.rows; A.d = query->cols;
-    A.rows_per_split = s.rows_per_split; A.t_base = s.t_base; A.seg0 = s.seg0;
-}
-
-struct Out { int *idx; size_t istep; int *img; size_t mstep; float *dist; size_t dstep; };   // element strides per query
-
-static void assign_images(const Out &o, int nq, int ncols, const int *nvalid, const std::vector<Seg> &segs, hipStream_t st)
-{
-    const int blocks = div_up(nq * ncols, 256);
-    for (int m = (int)segs.size() - 1; m >= 0; --m)
-        hipLaunchKernelGGL(k_assign_image, dim3(blocks), dim3(256), 0, st, o.idx, o.istep, o.img, o.mstep, nq, ncols, nvalid, segs[m].t_base, m);
-}
-
-static int run_knn(mi_bfmatcher *h, const mi_mat *query, const mi_mat *trains, const mi_mat *masks, int n_trains, int k, const Out &o,
-                   hipStream_t st)
-{
-    MI_REQUIRE(h, MI_ERR_BAD_ARG, "null handle");
-    MI_REQUIRE(k >= 1, MI_ERR_BAD_ARG, "k >= 1");
-    if (query && query->type != MI_32FC1)          // integer descriptors: the other rows of the reference's (depth, norm) table
-        return bfint::knn(h->norm, query, trains, masks, n_trains, k, o.idx, o.istep, o.img, o.mstep, o.dist, o.dstep, st);
-    MI_REQUIRE(h->norm == MI_NORM_L1 || h->norm == MI_NORM_L2, MI_ERR_BAD_TYPE, "unsupported combination of query.depth() and norm");
-    MI_REQUIRE(n_trains == 1 || o.img, MI_ERR_BAD_ARG, "a collection needs img_idx");
-    const int K = k <= 2 ? 2 : 8;
-    const Shape sh = knn_shape(query ? query->cols : 0, h->norm, K);
-    std::vector<Seg> segs;
-    int nseg = 0;
-    if (int rc = plan(query, trains, masks, n_trains, sh.tt, segs, &nseg)) return rc;
-    const int nq = query->rows;
-    MI_TRY(h->part.ensure(sizeof(float2) * (size_t)nseg * nq * K));
-    const int qblocks = div_up(nq, 64), mblocks = div_up(nq, 256);
-    for (int col0 = 0; col0 < k; col0 += K) {
-        for (int m = 0; m < n_trains; ++m) {
-            Args A = {};
-            fill_args(A, query, trains[m], masks ? &masks[m] : nullptr, segs[m]);
-            A.part = reinterpret_cast<float2 *>(h->part.p);
-            if (col0) { A.lo_idx = o.idx + col0 - 1; A.lo_istep = o.istep; A.lo_dist = o.dist + col0 - 1; A.lo_dstep = o.dstep; }
-            sh.fn(A, dim3(qblocks, segs[m].nsplit), st);
-        }
-        const int ncol = min(K, k - col0);
-        if (K == 2) hipLaunchKernelGGL((k_merge<2>), dim3(mblocks), dim3(256), 0, st, reinterpret_cast<const float2 *>(h->part.p), nq, nseg,
-                                       o.idx, o.istep, o.dist, o.dstep, o.img, o.mstep, col0, ncol);
-        else hipLaunchKernelGGL((k_merge<8>), dim3(mblocks), dim3(256), 0, st, reinterpret_cast<const float2 *>(h->part.p), nq, nseg,
-                                o.idx, o.istep, o.dist, o.dstep, o.img, o.mstep, col0, ncol);
-    }
-    if (o.img) assign_images(o, nq, k, nullptr, segs, st);
-    MI_HIP_TRY(hipGetLastError());
-    return MI_OK;
-}
-
-static bool is_rows(const mi_mat *m, int type, int rows, int cols)
-{
-    return m && m->data && m->type == type && m->rows == rows && m->cols == cols;
+    const dim3 grid(l.gx, l.gy), block(l.block);
+    if (l.op == BF_OP_MERGE)
+        hipLaunchKernelGGL((p.K == 2 ? k_merge<2> : k_merge<8>), grid, block, 0, st, A.part, A.nq, p.nseg, o.idx, (size_t)o.istep, o.dist,
+                           (size_t)o.dstep, o.img, (size_t)o.mstep, l.col0, l.ncol);
+    else if (l.op == BF_OP_ASSIGN_IMAGE)   // radius match: only the entries a row holds (n_matches) are resolved
+        hipLaunchKernelGGL(k_assign_image, grid, block, 0, st, o.idx, (size_t)o.istep, o.img, (size_t)o.mstep, A.nq, p.cols,
+                           p.k ? nullptr : n_matches, p.segs[l.m].t_base, l.m);
+    else if (l.op == BF_OP_RADIUS_SCAN) hipLaunchKernelGGL(k_radius_scan, grid, block, 0, st, A.cnt, A.nq, p.nseg, n_matches);
+    else hipLaunchKernelGGL(kernel_of(p), grid, block, 0, st, A);   // BF_OP_KNN_PASS, BF_OP_RADIUS_COUNT, BF_OP_RADIUS_WRITE
 }
 
 }  // namespace bf
 }  // namespace mi
-
-using namespace mi;
-
-extern "C" {
-
-int mi_bf_create(int norm_type, mi_bfmatcher **out)
-{
-    MI_REQUIRE(out, MI_ERR_BAD_ARG, "null out");
-    *out = nullptr;
-    MI_REQUIRE(norm_type == MI_NORM_L2 || norm_type == MI_NORM_L1 || norm_type == MI_NORM_HAMMING, MI_ERR_BAD_ARG,
-               "norm == NORM_L1 || norm == NORM_L2 || norm == NORM_HAMMING");      // BFMatcher_Impl constructor
-    MI_TRY(require_device());
-    *out = new mi_bfmatcher();
-    (*out)->norm = norm_type;
-    return MI_OK;
-}
-
-void mi_bf_destroy(mi_bfmatcher *h)
-{
-    delete h;
-}
-
-int mi_bf_match(mi_bfmatcher *h, const mi_mat *query, const mi_mat *train, const mi_mat *mask, mi_mat *train_idx, mi_mat *distance, void *stream)
-{
-    MI_REQUIRE(query && train, MI_ERR_BAD_ARG, "null argument");
-    MI_REQUIRE(train_idx && distance && train_idx->data && distance->data, MI_ERR_BAD_ARG, "null argument");
-    MI_REQUIRE(train_idx->type == MI_32SC1 && distance->type == MI_32FC1, MI_ERR_BAD_TYPE, "train_idx CV_32SC1 / distance CV_32FC1");
-    MI_REQUIRE(bf::is_rows(train_idx, MI_32SC1, 1, query->rows) && bf::is_rows(distance, MI_32FC1, 1, query->rows), MI_ERR_BAD_SIZE,
-               "outputs must be 1 x query.rows");
-    const bf::Out o = {(int *)train_idx->data, 1, nullptr, 0, (float *)distance->data, 1};
-    return bf::run_knn(h, query, train, mask, 1, 1, o, (hipStream_t)stream);
-}
-
-int mi_bf_knn_match2(mi_bfmatcher *h, const mi_mat *query, const mi_mat *train, const mi_mat *mask, mi_mat *train_idx, mi_mat *distance,
-                     void *stream)
-{
-    MI_REQUIRE(query && train, MI_ERR_BAD_ARG, "null argument");
-    MI_REQUIRE(train_idx && distance && train_idx->data && distance->data, MI_ERR_BAD_ARG, "null argument");
-    MI_REQUIRE(train_idx->type == MI_32SC2 && distance->type == MI_32FC2, MI_ERR_BAD_TYPE, "k = 2: train_idx CV_32SC2 / distance CV_32FC2");
-    MI_REQUIRE(bf::is_rows(train_idx, MI_32SC2, 1, query->rows) && bf::is_rows(distance, MI_32FC2, 1, query->rows), MI_ERR_BAD_SIZE,
-               "outputs must be 1 x query.rows");
-    const bf::Out o = {(int *)train_idx->data, 2, nullptr, 0, (float *)distance->data, 2};
-    return bf::run_knn(h, query, train, mask, 1, 2, o, (hipStream_t)stream);
-}
-
-int mi_bf_knn_match(mi_bfmatcher *h, const mi_mat *query, const mi_mat *trains, const mi_mat *masks, int n_trains, int k, mi_mat *train_idx,
-                    mi_mat *img_idx, mi_mat *distance, void *stream)
-{
-    MI_REQUIRE(query && trains && train_idx && distance, MI_ERR_BAD_ARG, "null argument");
-    MI_REQUIRE(k >= 1, MI_ERR_BAD_ARG, "k >= 1");
-    MI_REQUIRE(bf::is_rows(train_idx, MI_32SC1, query->rows, k) && bf::is_rows(distance, MI_32FC1, query->rows, k) &&
-                   (!img_idx || bf::is_rows(img_idx, MI_32SC1, query->rows, k)),
-               MI_ERR_BAD_SIZE, "train_idx / img_idx CV_32SC1 and distance CV_32FC1 must be query.rows x k");
-    const bf::Out o = {(int *)train_idx->data, train_idx->step / 4, img_idx ? (int *)img_idx->data : nullptr, img_idx ? img_idx->step / 4 : 0,
-                       (float *)distance->data, distance->step / 4};
-    return bf::run_knn(h, query, trains, masks, n_trains, k, o, (hipStream_t)stream);
-}
-
-int mi_bf_radius_match(mi_bfmatcher *h, const mi_mat *query, const mi_mat *trains, const mi_mat *masks, int n_trains, float max_distance,
-                       mi_mat *train_idx, mi_mat *img_idx, mi_mat *distance, mi_mat *n_matches, void *stream)
-{
-    hipStream_t st = (hipStream_t)stream;
-    MI_REQUIRE(h && query && trains && train_idx && distance && n_matches, MI_ERR_BAD_ARG, "null argument");
-    MI_REQUIRE(n_trains == 1 || img_idx, MI_ERR_BAD_ARG, "a collection needs img_idx");
-    const int cols = train_idx->cols;
-    MI_REQUIRE(cols > 0 && bf::is_rows(train_idx, MI_32SC1, query->rows, cols) && bf::is_rows(distance, MI_32FC1, query->rows, cols) &&
-                   (!img_idx || bf::is_rows(img_idx, MI_32SC1, query->rows, cols)) && bf::is_rows(n_matches, MI_32SC1, 1, query->rows),
-               MI_ERR_BAD_SIZE, "train_idx / img_idx CV_32SC1, distance CV_32FC1: query.rows x cols; n_matches CV_32SC1 1 x query.rows");
-    if (query->type != MI_32FC1)
-        return bfint::radius(h->norm, query, trains, masks, n_trains, max_distance, cols, (int *)train_idx->data, train_idx->step / 4,
-                             img_idx ? (int *)img_idx->data : nullptr, img_idx ? img_idx->step / 4 : 0, (float *)distance->data,
-                             distance->step / 4, (int *)n_matches->data, st);
-    MI_REQUIRE(h->norm == MI_NORM_L1 || h->norm == MI_NORM_L2, MI_ERR_BAD_TYPE, "unsupported combination of query.depth() and norm");
-    const bf::Shape sh = bf::radius_shape(query->cols, h->norm);
-    std::vector<bf::Seg> segs;
-    int nseg = 0;
-    if (int rc = bf::plan(query, trains, masks, n_trains, sh.tt, segs, &nseg)) return rc;
-    const int nq = query->rows;
-    MI_TRY(h->part.ensure(sizeof(int) * (size_t)nseg * nq));
-    const bf::Out o = {(int *)train_idx->data, train_idx->step / 4, img_idx ? (int *)img_idx->data : nullptr, img_idx ? img_idx->step / 4 : 0,
-                       (float *)distance->data, distance->step / 4};
-    const int qblocks = div_up(nq, 64);
-    for (int pass = 0; pass < 2; ++pass) {
-        for (int m = 0; m < n_trains; ++m) {
-            bf::Args A = {};
-            bf::fill_args(A, query, trains[m], masks ? &masks[m] : nullptr, segs[m]);
-            A.cnt = reinterpret_cast<int *>(h->part.p);
-            A.max_dist = max_distance; A.write = pass; A.cols = cols;
-            A.r_idx = o.idx; A.r_istep = o.istep; A.r_img = o.img; A.r_mstep = o.mstep; A.r_dist = o.dist; A.r_dstep = o.dstep;
-            sh.fn(A, dim3(qblocks, segs[m].nsplit), st);
-        }
-        if (pass == 0)
-            hipLaunchKernelGGL(bf::k_radius_scan, dim3(div_up(nq, 256)), dim3(256), 0, st, reinterpret_cast<int *>(h->part.p), nq, nseg,
-                               (int *)n_matches->data);
-    }
-    if (o.img) bf::assign_images(o, nq, cols, (const int *)n_matches->data, segs, st);
-    MI_HIP_TRY(hipGetLastError());
-    return MI_OK;
-}
-
-}  // extern "C"

@@ -369,6 +369,54 @@ def test_mask_pitched_inputs_legacy_entry_points_and_errors(gpu, oracle):
         cuda.createBFMatcher(cuda.BFMatcher.NORM_HAMMING).matchDevice(qc, tt)                   # Hamming on CV_32F: unsupported combination
 
 
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nq", [1, 64, 65])
+@pytest.mark.parametrize("nt_rule", ["tt-1", "tt", "tt+1", "3tt+1"])
+@pytest.mark.parametrize("d,tt", [(17, 32), (100, 32), (200, 16), (304, 8)])
+def test_plan_edges_bit_exact(gpu, oracle, d, tt, nt_rule, nq):
+    """The smallest shapes at which the plan (csrc/bf_plan.h) can go wrong: one descriptor length per row of its shape table, train
+    sets one row short of a tile, a whole tile, one row over and three tiles and a row (more than one split), query counts of one
+    lane, a whole workgroup and one lane over.  k = 1, 2 (K = 2), 8 (one pass of K = 8), 9 (a continuation pass of one column) and 17
+    (two continuation passes), the tail of a list longer than the train set being -1 / -1 / FLT_MAX; radius matches at the median
+    nearest distance and at the median distance of the last list column (hits in every split, rows beyond cols); for 65 queries a
+    two-set collection (tt + 1 and tt - 1 rows, one mask absent and one random) as k = 9 and as two radius matches.  Indices, image indices and the bits of the distances equal the oracle's."""
+    import torch
+    from opencv_contrib_amd import cuda
+    nt = {"tt-1": tt - 1, "tt": tt, "tt+1": tt + 1, "3tt+1": 3 * tt + 1}[nt_rule]
+    rng = np.random.default_rng(d * 1000 + nt * 10 + nq)
+    q, t = _desc(rng, nq, d), _desc(rng, nt, d)
+    T = lambda a: None if a is None else torch.from_numpy(a).to(gpu)
+
+    def same(got, want):
+        for g, w, exact_bits in zip(got, want, (False, False, True, False)):
+            g = g.cpu().numpy()
+            np.testing.assert_array_equal(_bits(g) if exact_bits else g, _bits(w) if exact_bits else w)
+
+    for norm in (NORM_L2, NORM_L1):
+        m = cuda.createBFMatcher(norm)
+        r17 = oracle.bf_knn_match(q, t, 17, norm)                  # a sorted list: its first k columns are the list for k
+        if nt < 17:
+            assert (r17[0][:, nt:] == -1).all() and (r17[1][:, nt:] == -1).all() and (r17[2][:, nt:] == FLT_MAX).all()
+        for k in (1, 2, 8, 9, 17):
+            same(m.knnMatchDevice(T(q), T(t), k=k), [a[:, :k] for a in r17])
+        # at the median nearest distance (rows of no and of one hit), and at the median of the last list column that exists: about half
+        # the rows hold up to 17 hits from every split, so the scan's offsets and rows beyond `cols` are exercised
+        for radius in (float(np.median(r17[2][:, 0])), float(np.median(r17[2][:, min(16, nt - 1)]))):
+            same(m.radiusMatchDevice(T(q), T(t), radius), oracle.bf_radius_match(q, t, radius, max(nt // 100, nq), norm))
+        if nq == 65:
+            trains = [_desc(rng, tt + 1, d), _desc(rng, tt - 1, d)]
+            masks = [None, (rng.random((nq, tt - 1)) < 0.7).astype(np.uint8)]
+            m.add([T(x) for x in trains])
+            r9 = oracle.bf_knn_match(q, trains, 9, norm, masks)
+            same(m.knnMatchDevice(T(q), None, k=9, masks=[T(x) for x in masks]), r9)
+            for radius in (float(np.median(r9[2][:, 0])), float(np.median(r9[2][:, 8]))):
+                same(m.radiusMatchDevice(T(q), None, radius, masks=[T(x) for x in masks]), oracle.bf_radius_match(q, trains, radius, nq, norm, masks))
+
+
 @pytest.mark.gpu
 def test_single_wave_shape_agrees(gpu, oracle, monkeypatch):
     """The one-wave-per-workgroup shape (MIFLOW_BF_W=1, read on every call) against the oracle; every other test runs the
