@@ -88,6 +88,121 @@ def test_emulated_kernels_equal_the_oracle(emul, oracle, dt, norm, hi, d, nq, nt
     np.testing.assert_array_equal(m2, rr[1]); np.testing.assert_array_equal(d2, rr[2])
 
 
+# Edge shapes, run on the CPU through the emulator (below) and on the GPU through the product (tests/test_zzz_bfmatch_int_hip.py):
+# (d, nq, train rows, k).  One element, odd and full descriptor lengths (d = 128: the Shared struct at its full size), query counts of
+# one lane, a whole wave and one or two lanes over, tiles of 31 / 32 / 33 train rows, k larger than the collection (d = 1: one match
+# and fifteen -1 / -1 / FLT_MAX tails).
+EDGE_SHAPES = [(1, 1, (1,), 16), (3, 65, (31, 33, 1), 16), (128, 64, (32, 97), 2), (127, 66, (200,), 7)]
+EDGE_IDS = ["d%d-nq%d-nt%s-k%d" % (d, nq, "_".join(map(str, nts)), k) for d, nq, nts, k in EDGE_SHAPES]
+FLT_MAX = np.float32(np.finfo(np.float32).max)
+
+
+def edge_data(dt, d, nq, nts, mask_first_image=False):
+    """Values from the whole range of the dtype; query row 0 all-min and row 0 of the first train set all-max (the largest element
+    difference in every column).  Masks of density 0.6, the last query's row all zero in image 0, no mask for image 1; no masks at
+    all for a single query.  mask_first_image: image 0 is masked completely for every query.  -> (query, trains, masks or None)"""
+    info = np.iinfo(dt)
+    rng = np.random.default_rng(1000 * d + nq + 7 * len(nts) + int(mask_first_image))
+    draw = lambda n: rng.integers(info.min, info.max, (n, d), dtype=np.int64, endpoint=True).astype(dt)
+    q, trains = draw(nq), [draw(n) for n in nts]
+    q[0] = info.min
+    trains[0][0] = info.max
+    if nq == 1:
+        return q, trains, None
+    masks = [(rng.random((nq, n)) < 0.6).astype(np.uint8) for n in nts]
+    masks[0][-1] = 0
+    if mask_first_image:
+        masks[0][:] = 0
+    if len(nts) > 1:
+        masks[1] = None
+    return q, trains, masks
+
+
+def edge_runs(shape):
+    """The mask_first_image settings a shape runs with"""
+    return (False, True) if shape[:2] == (3, 65) else (False,)
+
+
+def occurring_radius(knn):
+    """A radius that EQUALS a distance of the k-nearest lists `knn` = (idx, img, dist): the (upper) median of the last list column that
+    holds an entry.  The compare of the radius match is a strict <, so entries at exactly this distance must be absent from its result."""
+    idx, _, dist = knn
+    col = max(j for j in range(idx.shape[1]) if (idx[:, j] >= 0).any())
+    v = np.sort(dist[:, col][idx[:, col] >= 0])
+    return float(v[len(v) // 2])
+
+
+def check_radius_is_strict(knn, rr, radius):
+    """rr = the oracle's radius match at `radius` with cols >= the list length: the lists hold a distance equal to the radius, and the
+    radius match stores none of them"""
+    assert (knn[2][knn[0] >= 0] == np.float32(radius)).any()
+    stored = np.arange(rr[0].shape[1])[None] < np.minimum(rr[3], rr[0].shape[1])[:, None]
+    assert (rr[2][stored] < np.float32(radius)).all() and (rr[0][stored] >= 0).all() and (rr[0][~stored] == -1).all()
+
+
+def wrapped_l1(q, trains, masks):
+    """numpy: the int64 L1 sums of every (query, train) pair of the collection, the same mod 2^32 (what an unsigned 32-bit
+    accumulator holds) and the validity of each pair under the masks"""
+    t = np.concatenate(trains).astype(np.int64)
+    true = np.abs(q.astype(np.int64)[:, None] - t[None]).sum(-1)
+    valid = np.concatenate([np.ones((len(q), len(tr)), bool) if masks is None or m is None else m.astype(bool)
+                            for tr, m in zip(trains, masks if masks is not None else [None] * len(trains))], 1)
+    return true, true % (1 << 32), valid
+
+
+def test_oracle_int32_l1_sum_wraps_like_an_unsigned_accumulator(oracle):
+    """int32 L1 at d = 128 over the whole value range: true sums exceed 2^32 and the reference accumulates in `uint`, so the distance
+    is the sum mod 2^32 (values of 2^31 and more included, which a signed accumulator would turn negative) and the lists are ordered
+    by that.  numpy in int64 is the second opinion."""
+    d, nq, nts, k = EDGE_SHAPES[2]
+    q, trains, masks = edge_data("int32", d, nq, nts)
+    true, wrapped, valid = wrapped_l1(q, trains, masks)
+    assert (true[valid] > (1 << 32)).any() and (wrapped[valid] >= (1 << 31)).any()
+    assert true[0, 0] == 128 * ((1 << 32) - 1) and wrapped[0, 0] == (1 << 32) - 128
+    dist = np.where(valid, wrapped.astype(np.float32), np.float32(np.inf))
+    order = np.argsort(dist, axis=1, kind="stable")[:, :k]        # collection order = (image, train index): the tie rule
+    idx, img, got = oracle.bf_knn_match(q, trains, k, NORM_L1, masks)
+    starts = np.cumsum([0] + list(nts))
+    np.testing.assert_array_equal(got, np.take_along_axis(dist, order, 1))
+    np.testing.assert_array_equal(img, np.searchsorted(starts, order, side="right") - 1)
+    np.testing.assert_array_equal(idx, order - starts[img])
+
+
+@pytest.mark.parametrize("dt,norm,hi", CASES)
+@pytest.mark.parametrize("d,nq,nts,k", EDGE_SHAPES, ids=EDGE_IDS)
+def test_emulated_kernels_equal_the_oracle_on_edge_shapes(emul, oracle, dt, norm, hi, d, nq, nts, k):
+    """The edge table through the host build: k-nearest lists, a radius match at a radius that equals an occurring distance (strict
+    <: those entries are absent), and one at radius 0 (no hit, outputs untouched)."""
+    for mask_first in edge_runs((d, nq, nts, k)):
+        q, trains, masks = edge_data(dt, d, nq, nts, mask_first)
+        n = len(nts)
+        tp = (C.c_void_p * n)(*[t.ctypes.data for t in trains])
+        ntc = (C.c_int * n)(*nts)
+        mp = None if masks is None else (C.c_void_p * n)(*[None if m is None else m.ctypes.data for m in masks])
+        r = oracle.bf_knn_match(q, trains, k, norm, masks)
+        if d == 1:
+            assert r[0].tolist() == [[0] + [-1] * 15] and r[1].tolist() == [[0] + [-1] * 15] and (r[2][0, 1:] == FLT_MAX).all()
+        if mask_first:
+            assert (r[1] != 0).all()
+        idx = np.full((nq, k), -7, np.int32); img = np.full((nq, k), -7, np.int32); dist = np.zeros((nq, k), np.float32)
+        assert emul.emul_bfint_knn(q.ctypes.data, nq, tp, ntc, mp, n, d, DEPTH[dt], norm, k, idx.ctypes.data, img.ctypes.data, dist.ctypes.data) == 0
+        np.testing.assert_array_equal(idx, r[0]); np.testing.assert_array_equal(img, r[1]); np.testing.assert_array_equal(dist, r[2])
+        cols = nq
+        radius = occurring_radius(r)
+        for rad in (radius, 0.0):
+            rr = oracle.bf_radius_match(q, trains, rad, cols, norm, masks)
+            if rad:
+                check_radius_is_strict(r, rr, rad)
+            else:
+                assert (rr[3] == 0).all()
+            i2 = np.full((nq, cols), -1, np.int32); m2 = np.full((nq, cols), -1, np.int32); d2 = np.zeros((nq, cols), np.float32)
+            n2 = np.zeros(nq, np.int32)
+            assert emul.emul_bfint_radius(q.ctypes.data, nq, tp, ntc, mp, n, d, DEPTH[dt], norm, rad, cols, i2.ctypes.data, m2.ctypes.data,
+                                          d2.ctypes.data, n2.ctypes.data) == 0
+            np.testing.assert_array_equal(n2, rr[3]); np.testing.assert_array_equal(i2, rr[0])
+            np.testing.assert_array_equal(m2, rr[1]); np.testing.assert_array_equal(d2, rr[2])
+
+
 def test_python_mirror_runs_the_reference_binding_test_on_binary_descriptors(oracle):
     """cudafeatures2d/misc/python/test/test_cudafeatures2d.py:46-54: createBFMatcher(NORM_HAMMING); match, knnMatch(.., 2), radiusMatch(.., 0.1)
     on ORB descriptors (8-bit, 32 bytes; random ones here) must run and return matches -- through the Python mirror with the oracle
