@@ -598,6 +598,61 @@ MI_API int mi_stereobp_iterate(const mi_stereobp_params *p, mi_mat *udlr, const 
 /* Replaces: output_gpu<T>, cuda/stereobp.cu:481-539, + out.setTo(0) and convertTo, stereobp.cpp:342-358; disparity as mi_stereobp_compute's */
 MI_API int mi_stereobp_output(const mi_mat *udlr, const mi_mat *data, int ndisp, mi_mat *disparity, void *stream);
 
+/* ================================================= StereoConstantSpaceBP ===== */
+
+/* cv::cuda::createStereoConstantSpaceBP(ndisp = 128, iters = 8, levels = 4, nr_plane = 4, msg_type = CV_32F), cudastereo.hpp, + the
+ * DEFAULT_* weights of cudastereo/src/stereocsbp.cpp:132-143 (data term 30, data weight 1, disc term 160, single jump 10, min_disp_th 0,
+ * local initial data cost).  msg_type: CV_32F (5) or CV_16S (3); the weights are NOT scaled for 16-bit messages (unlike StereoBP). */
+typedef struct mi_stereocsbp_params {
+    int ndisp, iters, levels, nr_plane;
+    float max_data_term, data_weight, max_disc_term, disc_single_jump;
+    int min_disp_th;
+    int msg_type;
+    int use_local_init_data_cost;
+} mi_stereocsbp_params;
+typedef struct mi_stereocsbp mi_stereocsbp;
+enum { MI_STEREOCSBP_FORM_AUTO = 0, MI_STEREOCSBP_FORM_REG = 1 /* planes <= 64: candidates in registers */, MI_STEREOCSBP_FORM_GEN = 2 /* any */ };
+/* Replaces: StereoCSBPImpl::StereoCSBPImpl, stereocsbp.cpp:137-143 */
+MI_API void mi_stereocsbp_default_params(mi_stereocsbp_params *p);
+/* Replaces: cv::cuda::createStereoConstantSpaceBP, stereocsbp.cpp:337-340 */
+MI_API int mi_stereocsbp_create(const mi_stereocsbp_params *p, mi_stereocsbp **out);
+/* Replaces: the setters / getters of StereoCSBPImpl, stereocsbp.cpp:69-112 (validated at compute, as there) */
+MI_API int mi_stereocsbp_set_params(mi_stereocsbp *h, const mi_stereocsbp_params *p);
+MI_API int mi_stereocsbp_get_params(const mi_stereocsbp *h, mi_stereocsbp_params *p);
+MI_API void mi_stereocsbp_destroy(mi_stereocsbp *h);
+/* Replaces: StereoCSBPImpl::compute(left, right, disparity, stream), stereocsbp.cpp:150-329.  left, right: MI_8UC1 / MI_8UC3 / MI_8UC4
+ * of one size and type, rows may be pitched; disparity: of the image size, MI_16SC1, or MI_8UC1 / MI_32SC1 / MI_32FC1 (saturate_cast of
+ * the 16-bit map, as convertTo); its border is 0.  The reference's asserts (:154-161) come back as errors whose text is the asserted
+ * condition.  levels is clamped to int(log(ndisp) / log(2)) and the clamp is written back to the handle (:171), so get_params returns
+ * it afterwards; ndisp == 1 (0 levels) and an empty coarsest level are rejected: both are undefined in the reference.
+ * Stream-ordered, no host wait. */
+MI_API int mi_stereocsbp_compute(mi_stereocsbp *h, const mi_mat *left, const mi_mat *right, mi_mat *disparity, void *stream);
+/* Device scratch the handle owns (mbuf_ and temp_ of stereocsbp.cpp:127-128): grown by compute, reused, never touched by a rejected call. */
+MI_API int mi_stereocsbp_scratch_bytes(const mi_stereocsbp *h, size_t *bytes);
+/* Replaces: StereoConstantSpaceBP::estimateRecommendedParams, stereocsbp.cpp:342-355 */
+MI_API int mi_stereocsbp_estimate_recommended_params(int width, int height, int *ndisp, int *iters, int *levels, int *nr_plane);
+/* Stage level = the reference's device-layer functions (cuda/stereocsbp.hpp), each the kernels compute() launches, on caller-owned planar
+ * matrices ((planes * level rows) x level cols of the message type; the matrices of one level share one step).  The level is
+ * (rows >> level) x (cols >> level).  p supplies msg_type, ndisp, min_disp_th, the weights and the selection mode.
+ * Replaces: init_data_cost<T>, cuda/stereocsbp.cu:86-350.  temp: ndisp planes, consumed; data_cost_selected, disp_selected: nr_plane planes */
+MI_API int mi_stereocsbp_init_data_cost(const mi_stereocsbp_params *p, const mi_mat *left, const mi_mat *right, int level, int nr_plane,
+                                        mi_mat *temp, mi_mat *data_cost_selected, mi_mat *disp_selected, void *stream);
+/* Replaces: compute_data_cost<T>, cuda/stereocsbp.cu:356-517.  disp_selected_parent: nr_plane2 planes of the next coarser level (half the
+ * level's size; the level's rows and cols must be even); data_cost: nr_plane2 planes of the level */
+MI_API int mi_stereocsbp_compute_data_cost(const mi_stereocsbp_params *p, const mi_mat *left, const mi_mat *right, int level, int nr_plane2,
+                                           const mi_mat *disp_selected_parent, mi_mat *data_cost, void *stream);
+/* Replaces: init_message<T>, cuda/stereocsbp.cu:525-650.  cur_udlrs[5] / new_udlrs[5]: u, d, l, r and disp_selected of the coarser level
+ * (nr_plane2 planes) and of the level (nr_plane planes); data_cost, temp (consumed): nr_plane2 planes of the level */
+MI_API int mi_stereocsbp_init_message(const mi_mat *cur_udlrs, mi_mat *new_udlrs, const mi_mat *data_cost, mi_mat *data_cost_selected,
+                                      mi_mat *temp, int nr_plane, int nr_plane2, void *stream);
+/* Replaces: calc_all_iterations<T>, cuda/stereocsbp.cu:656-744, for t = t0 .. t0 + n_iters - 1, in place; udlr[4]; form:
+ * MI_STEREOCSBP_FORM_*; temp (nr_plane planes) is needed by the general form only and may be NULL otherwise */
+MI_API int mi_stereocsbp_iterate(const mi_stereocsbp_params *p, mi_mat *udlr, const mi_mat *disp_selected, const mi_mat *data_cost_selected,
+                                 mi_mat *temp, int nr_plane, int t0, int n_iters, int form, void *stream);
+/* Replaces: compute_disp<T>, cuda/stereocsbp.cu:752-810, + out.setTo(0) and convertTo, stereocsbp.cpp:303-328 */
+MI_API int mi_stereocsbp_compute_disp(const mi_mat *udlr, const mi_mat *disp_selected, const mi_mat *data_cost_selected, int nr_plane,
+                                      mi_mat *disparity, void *stream);
+
 /* ================================================= superres optical-flow adapters ===== */
 
 /* Replaces: cv::superres::convertToType(GpuMat, CV_8UC1) as used by GpuOpticalFlow::calc, superres/src/optical_flow.cpp:469-470

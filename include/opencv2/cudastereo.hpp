@@ -259,6 +259,76 @@ inline Ptr<cuda::StereoBeliefPropagation> createStereoBeliefPropagation(int ndis
     return makePtr<miflow_detail::StereoBPImpl>(ndisp, iters, levels, msg_type);
 }
 
+/** cudastereo.hpp:217-231 */
+class CV_EXPORTS_W StereoConstantSpaceBP : public cuda::StereoBeliefPropagation {
+public:
+    virtual int getNrPlane() const = 0;                  virtual void setNrPlane(int nr_plane) = 0;
+    virtual bool getUseLocalInitDataCost() const = 0;    virtual void setUseLocalInitDataCost(bool use_local_init_data_cost) = 0;
+    /** stereocsbp.cpp:342-355 */
+    static void estimateRecommendedParams(int width, int height, int &ndisp, int &iters, int &levels, int &nr_plane)
+    {
+        miCheck(mi_stereocsbp_estimate_recommended_params(width, height, &ndisp, &iters, &levels, &nr_plane));
+    }
+};
+
+namespace miflow_detail {
+/** twin of StereoCSBPImpl, cudastereo/src/stereocsbp.cpp:60-334 (no-op setters and constant getters included) */
+class StereoCSBPImpl final : public cuda::StereoConstantSpaceBP {
+public:
+    StereoCSBPImpl(int ndisp, int iters, int levels, int nr_plane, int msg_type)
+    {
+        mi_stereocsbp_default_params(&p_);
+        p_.ndisp = ndisp; p_.iters = iters; p_.levels = levels; p_.nr_plane = nr_plane; p_.msg_type = msg_type;
+        miCheck(mi_stereocsbp_create(&p_, &h_));
+    }
+    ~StereoCSBPImpl() override { mi_stereocsbp_destroy(h_); }
+    StereoCSBPImpl(const StereoCSBPImpl &) = delete;
+    StereoCSBPImpl &operator=(const StereoCSBPImpl &) = delete;
+    void compute(InputArray left, InputArray right, OutputArray disparity) override { compute(left, right, disparity, Stream::Null()); }
+    void compute(InputArray left, InputArray right, OutputArray disparity, Stream &stream) override
+    {
+        disparity.create(left.size(), out_type(disparity));
+        mi_mat l = miMat(left), r = miMat(right), d = miMat(disparity);
+        miCheck(mi_stereocsbp_compute(h_, &l, &r, &d, stream.hipStream()));
+        miCheck(mi_stereocsbp_get_params(h_, &p_));   // levels_ is clamped by compute (stereocsbp.cpp:171)
+    }
+    void compute(InputArray, OutputArray, Stream &) override { CV_Error(Error::StsNotImplemented, "Not implemented"); }   // :331-334
+    int getMinDisparity() const override { return p_.min_disp_th; }  void setMinDisparity(int v) override { p_.min_disp_th = v; push(); }
+    int getNumDisparities() const override { return p_.ndisp; }  void setNumDisparities(int v) override { p_.ndisp = v; push(); }
+    int getBlockSize() const override { return 0; }              void setBlockSize(int) override {}
+    int getSpeckleWindowSize() const override { return 0; }      void setSpeckleWindowSize(int) override {}
+    int getSpeckleRange() const override { return 0; }           void setSpeckleRange(int) override {}
+    int getDisp12MaxDiff() const override { return 0; }          void setDisp12MaxDiff(int) override {}
+    int getNumIters() const override { return p_.iters; }        void setNumIters(int v) override { p_.iters = v; push(); }
+    int getNumLevels() const override { return p_.levels; }      void setNumLevels(int v) override { p_.levels = v; push(); }
+    double getMaxDataTerm() const override { return p_.max_data_term; }       void setMaxDataTerm(double v) override { p_.max_data_term = (float)v; push(); }
+    double getDataWeight() const override { return p_.data_weight; }          void setDataWeight(double v) override { p_.data_weight = (float)v; push(); }
+    double getMaxDiscTerm() const override { return p_.max_disc_term; }       void setMaxDiscTerm(double v) override { p_.max_disc_term = (float)v; push(); }
+    double getDiscSingleJump() const override { return p_.disc_single_jump; } void setDiscSingleJump(double v) override { p_.disc_single_jump = (float)v; push(); }
+    int getMsgType() const override { return p_.msg_type; }      void setMsgType(int v) override { p_.msg_type = v; push(); }
+    int getNrPlane() const override { return p_.nr_plane; }      void setNrPlane(int v) override { p_.nr_plane = v; push(); }
+    bool getUseLocalInitDataCost() const override { return p_.use_local_init_data_cost != 0; }
+    void setUseLocalInitDataCost(bool v) override { p_.use_local_init_data_cost = v ? 1 : 0; push(); }
+private:
+    // stereocsbp.cpp:303: a disparity matrix the caller has given a supported type keeps it (the reference asks fixedType()); else CV_16SC1
+    static int out_type(const GpuMat &d)
+    {
+        const int t = d.type();
+        return !d.empty() && (t == CV_8UC1 || t == CV_32SC1 || t == CV_32FC1) ? t : CV_MAKETYPE(CV_16S, 1);
+    }
+    void push() { miCheck(mi_stereocsbp_set_params(h_, &p_)); }   // values are validated at compute, as in the reference
+    mi_stereocsbp_params p_;
+    mi_stereocsbp *h_ = nullptr;
+};
+}  // namespace miflow_detail
+
+/** cudastereo.hpp:241-242 */
+inline Ptr<cuda::StereoConstantSpaceBP> createStereoConstantSpaceBP(int ndisp = 128, int iters = 8, int levels = 4, int nr_plane = 4,
+                                                                    int msg_type = CV_32F)
+{
+    return makePtr<miflow_detail::StereoCSBPImpl>(ndisp, iters, levels, nr_plane, msg_type);
+}
+
 /** cudastereo.hpp:298-330 */
 class CV_EXPORTS_W DisparityBilateralFilter : public cv::Algorithm {
 public:

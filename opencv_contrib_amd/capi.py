@@ -95,6 +95,15 @@ class StereoBPParams(C.Structure):
 MI_STEREOBP_FORM_AUTO, MI_STEREOBP_FORM_REG, MI_STEREOBP_FORM_GEN = 0, 1, 2
 
 
+class StereoCSBPParams(C.Structure):
+    _fields_ = [("ndisp", C.c_int), ("iters", C.c_int), ("levels", C.c_int), ("nr_plane", C.c_int), ("max_data_term", C.c_float),
+                ("data_weight", C.c_float), ("max_disc_term", C.c_float), ("disc_single_jump", C.c_float), ("min_disp_th", C.c_int),
+                ("msg_type", C.c_int), ("use_local_init_data_cost", C.c_int)]
+
+
+MI_STEREOCSBP_FORM_AUTO, MI_STEREOCSBP_FORM_REG, MI_STEREOCSBP_FORM_GEN = 0, 1, 2
+
+
 class BTVL1Params(C.Structure):
     _fields_ = [("scale", C.c_int), ("iterations", C.c_int), ("tau", C.c_double), ("lambda_", C.c_double), ("alpha", C.c_double),
                 ("btv_kernel_size", C.c_int), ("blur_kernel_size", C.c_int), ("blur_sigma", C.c_double)]
@@ -261,6 +270,19 @@ def lib():
         "mi_stereobp_level_up": (i, [PM, PM, i, vp]),
         "mi_stereobp_iterate": (i, [C.POINTER(StereoBPParams), PM, PM, i, i, i, vp]),
         "mi_stereobp_output": (i, [PM, PM, i, PM, vp]),
+        "mi_stereocsbp_default_params": (None, [C.POINTER(StereoCSBPParams)]),
+        "mi_stereocsbp_create": (i, [C.POINTER(StereoCSBPParams), C.POINTER(vp)]),
+        "mi_stereocsbp_set_params": (i, [vp, C.POINTER(StereoCSBPParams)]),
+        "mi_stereocsbp_get_params": (i, [vp, C.POINTER(StereoCSBPParams)]),
+        "mi_stereocsbp_destroy": (None, [vp]),
+        "mi_stereocsbp_compute": (i, [vp, PM, PM, PM, vp]),
+        "mi_stereocsbp_scratch_bytes": (i, [vp, C.POINTER(C.c_size_t)]),
+        "mi_stereocsbp_estimate_recommended_params": (i, [i, i, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i)]),
+        "mi_stereocsbp_init_data_cost": (i, [C.POINTER(StereoCSBPParams), PM, PM, i, i, PM, PM, PM, vp]),
+        "mi_stereocsbp_compute_data_cost": (i, [C.POINTER(StereoCSBPParams), PM, PM, i, i, PM, PM, vp]),
+        "mi_stereocsbp_init_message": (i, [PM, PM, PM, PM, PM, i, i, vp]),
+        "mi_stereocsbp_iterate": (i, [C.POINTER(StereoCSBPParams), PM, PM, PM, PM, i, i, i, i, vp]),
+        "mi_stereocsbp_compute_disp": (i, [PM, PM, PM, i, PM, vp]),
         "mi_superres_to_gray8": (i, [PM, PM, vp]),
         "mi_split_flow": (i, [PM, PM, PM, vp]),
         "mi_btvl1_default_params": (None, [C.POINTER(BTVL1Params)]),

@@ -989,6 +989,136 @@ def stereobp_output(msgs, data, ndisp, dtype=None):
     return disp
 
 
+class StereoConstantSpaceBP(StereoBeliefPropagation):
+    """cv::cuda::StereoConstantSpaceBP (cudastereo.hpp; cudastereo/src/stereocsbp.cpp:60-355): belief propagation over nr_plane << level
+    candidate disparities per pixel instead of all ndisp, 16-bit or f32 messages, bit-exact to the reference."""
+
+    def __init__(self, ndisp=128, iters=8, levels=4, nr_plane=4, msg_type=CV_32F):
+        self._p = capi.StereoCSBPParams()
+        capi.lib().mi_stereocsbp_default_params(C.byref(self._p))
+        self._p.ndisp, self._p.iters, self._p.levels, self._p.nr_plane, self._p.msg_type = ndisp, iters, levels, nr_plane, msg_type
+        self._h = C.c_void_p()
+        capi.check(capi.lib().mi_stereocsbp_create(C.byref(self._p), C.byref(self._h)))
+
+    def __del__(self):
+        _destroy(self, "mi_stereocsbp_destroy")
+
+    def _set(self, **kw):
+        for k, v in kw.items():
+            setattr(self._p, k, v)
+        capi.check(capi.lib().mi_stereocsbp_set_params(self._h, C.byref(self._p)))
+
+    def getMinDisparity(self): return self._p.min_disp_th
+    def setMinDisparity(self, v): self._set(min_disp_th=v)
+    def getNrPlane(self): return self._p.nr_plane
+    def setNrPlane(self, v): self._set(nr_plane=v)
+    def getUseLocalInitDataCost(self): return bool(self._p.use_local_init_data_cost)
+    def setUseLocalInitDataCost(self, v): self._set(use_local_init_data_cost=int(bool(v)))
+
+    def compute(self, left, right, disparity=None, stream=None):
+        """left, right: uint8 (H, W), (H, W, 3) or (H, W, 4); returns the disparity, int16 (H, W) unless `disparity` (uint8, int16,
+        int32 or float32) is given (stereocsbp.cpp:303).  getNumLevels() returns the clamped level count afterwards (:171)."""
+        import torch
+        if disparity is None:
+            disparity = torch.empty(left.shape[:2], dtype=torch.int16, device=left.device)
+        s = capi.current_stream_ptr() if stream is None else C.c_void_p(stream.cuda_stream)
+        capi.check(capi.lib().mi_stereocsbp_compute(self._h, C.byref(_m(left)), C.byref(_m(right)), C.byref(_m(disparity)), s))
+        capi.check(capi.lib().mi_stereocsbp_get_params(self._h, C.byref(self._p)))
+        return disparity
+
+    def compute_data(self, data, disparity=None, stream=None):
+        """compute(data, disparity, stream), stereocsbp.cpp:331-334."""
+        raise NotImplementedError("Not implemented")
+
+    def scratchBytes(self):
+        """miflow extension: bytes of device scratch the handle holds."""
+        n = C.c_size_t()
+        capi.check(capi.lib().mi_stereocsbp_scratch_bytes(self._h, C.byref(n)))
+        return n.value
+
+    @staticmethod
+    def estimateRecommendedParams(width, height):
+        """-> (ndisp, iters, levels, nr_plane), stereocsbp.cpp:342-355."""
+        nd, it, lv, nr = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        capi.check(capi.lib().mi_stereocsbp_estimate_recommended_params(width, height, C.byref(nd), C.byref(it), C.byref(lv), C.byref(nr)))
+        return nd.value, it.value, lv.value, nr.value
+
+
+def createStereoConstantSpaceBP(ndisp=128, iters=8, levels=4, nr_plane=4, msg_type=CV_32F) -> StereoConstantSpaceBP:
+    """cv::cuda::createStereoConstantSpaceBP (cudastereo.hpp)."""
+    return StereoConstantSpaceBP(ndisp, iters, levels, nr_plane, msg_type)
+
+
+def _csbp_params(msg_type, ndisp=128, min_disp=0, local=True, max_data_term=30.0, data_weight=1.0, max_disc_term=160.0, disc_single_jump=10.0):
+    p = capi.StereoCSBPParams()
+    capi.lib().mi_stereocsbp_default_params(C.byref(p))
+    p.ndisp, p.msg_type, p.min_disp_th, p.use_local_init_data_cost = ndisp, msg_type, min_disp, int(bool(local))
+    p.max_data_term, p.data_weight, p.max_disc_term, p.disc_single_jump = max_data_term, data_weight, max_disc_term, disc_single_jump
+    return p
+
+
+def _csbp_msg_type(t):
+    import torch
+    return CV_32F if t.dtype == torch.float32 else CV_16S
+
+
+def stereocsbp_init_data_cost(left, right, level, nr_plane, ndisp, msg_type=CV_32F, local=True, **kw):
+    """init_data_cost (stereocsbp.cu:86-350) at `level` -> (data_cost_selected, disp_selected), nr_plane planes of the level each."""
+    import torch
+    h, w = left.shape[0] >> level, left.shape[1] >> level
+    mk = lambda n: torch.zeros((n * h, w), dtype=_bp_dtype(msg_type), device=left.device)
+    temp, sel_cost, sel_disp = mk(ndisp), mk(nr_plane), mk(nr_plane)
+    p = _csbp_params(msg_type, ndisp=ndisp, local=local, **kw)
+    capi.check(capi.lib().mi_stereocsbp_init_data_cost(C.byref(p), C.byref(_m(left)), C.byref(_m(right)), level, nr_plane, C.byref(_m(temp)),
+                                                       C.byref(_m(sel_cost)), C.byref(_m(sel_disp)), capi.current_stream_ptr()))
+    return sel_cost, sel_disp
+
+
+def stereocsbp_compute_data_cost(left, right, level, disp_selected_parent, nr_plane2, **kw):
+    """compute_data_cost (stereocsbp.cu:356-517): the costs of the parents' nr_plane2 candidates at the pixels of `level`."""
+    import torch
+    h, w = left.shape[0] >> level, left.shape[1] >> level
+    data_cost = torch.zeros((nr_plane2 * h, w), dtype=disp_selected_parent.dtype, device=left.device)
+    p = _csbp_params(_csbp_msg_type(disp_selected_parent), **kw)
+    capi.check(capi.lib().mi_stereocsbp_compute_data_cost(C.byref(p), C.byref(_m(left)), C.byref(_m(right)), level, nr_plane2,
+                                                          C.byref(_m(disp_selected_parent)), C.byref(_m(data_cost)), capi.current_stream_ptr()))
+    return data_cost
+
+
+def stereocsbp_init_message(cur, data_cost, nr_plane, nr_plane2):
+    """init_message (stereocsbp.cu:525-650): cur = (u, d, l, r, disp_selected) of the coarser level -> (the five of the level,
+    data_cost_selected)."""
+    import torch
+    h, w = data_cost.shape[0] // nr_plane2, data_cost.shape[1]
+    mk = lambda n: torch.zeros((n * h, w), dtype=data_cost.dtype, device=data_cost.device)
+    new = [mk(nr_plane) for _ in range(5)]
+    sel_cost, temp = mk(nr_plane), mk(nr_plane2)
+    capi.check(capi.lib().mi_stereocsbp_init_message(_mats(cur), _mats(new), C.byref(_m(data_cost)), C.byref(_m(sel_cost)), C.byref(_m(temp)),
+                                                     nr_plane, nr_plane2, capi.current_stream_ptr()))
+    return new, sel_cost
+
+
+def stereocsbp_iterate(msgs, disp_selected, data_cost_selected, nr_plane, t0=0, n_iters=1, form=capi.MI_STEREOCSBP_FORM_AUTO, **kw):
+    """calc_all_iterations (stereocsbp.cu:656-744) for t = t0 .. t0 + n_iters - 1 on copies of msgs = (u, d, l, r)."""
+    import torch
+    out = [m.clone() for m in msgs]
+    temp = torch.zeros_like(data_cost_selected)
+    p = _csbp_params(_csbp_msg_type(data_cost_selected), **kw)
+    capi.check(capi.lib().mi_stereocsbp_iterate(C.byref(p), _mats(out), C.byref(_m(disp_selected)), C.byref(_m(data_cost_selected)),
+                                                C.byref(_m(temp)), nr_plane, t0, n_iters, form, capi.current_stream_ptr()))
+    return out
+
+
+def stereocsbp_compute_disp(msgs, disp_selected, data_cost_selected, nr_plane, dtype=None):
+    """compute_disp (stereocsbp.cu:752-810) with the zero border and the conversion of stereocsbp.cpp:303-328."""
+    import torch
+    disp = torch.empty((data_cost_selected.shape[0] // nr_plane, data_cost_selected.shape[1]), dtype=dtype or torch.int16,
+                       device=data_cost_selected.device)
+    capi.check(capi.lib().mi_stereocsbp_compute_disp(_mats(msgs), C.byref(_m(disp_selected)), C.byref(_m(data_cost_selected)), nr_plane,
+                                                     C.byref(_m(disp)), capi.current_stream_ptr()))
+    return disp
+
+
 def stereobm_prefilter_xsobel(img, cap=31):
     import torch
     out = torch.empty_like(img)
