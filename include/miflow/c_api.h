@@ -653,6 +653,47 @@ MI_API int mi_stereocsbp_iterate(const mi_stereocsbp_params *p, mi_mat *udlr, co
 MI_API int mi_stereocsbp_compute_disp(const mi_mat *udlr, const mi_mat *disp_selected, const mi_mat *data_cost_selected, int nr_plane,
                                       mi_mat *disparity, void *stream);
 
+/* ================================================= FAST corner detector ===== */
+
+/* cv::cuda::FastFeatureDetector (cudafeatures2d.hpp:426-442).  type is always TYPE_9_16 (fast.cpp:85-86). */
+typedef struct mi_fast_params {
+    int threshold;            /* 10; >= 0 (deviation: the reference accepts a negative one, which makes flat regions corners) */
+    int nonmax_suppression;   /* 1 */
+    int max_npoints;          /* 5000; >= 1 */
+} mi_fast_params;
+
+typedef struct mi_fast mi_fast;
+
+/* Replaces: the defaults of FastFeatureDetector::create, cudafeatures2d.hpp:434-437 */
+MI_API void mi_fast_default_params(mi_fast_params *p);
+/* Replaces: cv::cuda::FastFeatureDetector::create / FAST_Impl::FAST_Impl, fast.cpp:96-100,211-215.  The parameters are checked before
+ * the device is looked for. */
+MI_API int mi_fast_create(const mi_fast_params *p, mi_fast **out);
+/* Replaces: setThreshold / setNonmaxSuppression / setMaxNumPoints and their getters, fast.cpp:76-83 */
+MI_API int mi_fast_set_params(mi_fast *h, const mi_fast_params *p);
+MI_API int mi_fast_get_params(const mi_fast *h, mi_fast_params *p);
+MI_API void mi_fast_destroy(mi_fast *h);
+/* Device scratch the handle holds (grown on demand, never shrunk); no reference counterpart (BufferPool, fast.cpp:132-139) */
+MI_API int mi_fast_scratch_bytes(const mi_fast *h, size_t *bytes);
+/* Replaces: FAST_Impl::detectAsync, fast.cpp:122-173, with calcKeypoints_gpu and nonmaxSuppression_gpu, cuda/fast.cu:211-372.
+ * img, mask (NULL or data == NULL: none): MI_8UC1 of one size, any base address and step; keypoints: MI_32FC1, 2 rows, at least
+ * max_npoints columns: row 0 receives short2 {x, y} in the 4 bytes of an element, row 1 float(score) with suppression and 0 without;
+ * *n: the number of columns written, in row-major order (y, then x) of the image.  Only the first max_npoints candidates in that order
+ * take part (the reference keeps those whose atomics arrived first); all candidates suppress their neighbours.  rows < 7 or cols < 7:
+ * *n = 0 and nothing is launched; rows or cols above 32767: MI_ERR_BAD_SIZE.  4 launches with suppression, 3 without; waits for
+ * `stream` once, at the end. */
+MI_API int mi_fast_detect(mi_fast *h, const mi_mat *img, const mi_mat *mask, mi_mat *keypoints, int *n, void *stream);
+/* The same over n frames of any sizes: imgs[n], masks[n] (NULL: none; a mask with data == NULL: none for that frame), keypoints[n],
+ * ns[n].  Each frame's launches as above, one wait for all counts.  No reference counterpart. */
+MI_API int mi_fast_detect_batch(mi_fast *h, int n, const mi_mat *imgs, const mi_mat *masks, mi_mat *keypoints, int *ns, void *stream);
+/* Replaces: score.setTo(0) + calcKeypoints<true>'s score plane, fast.cpp:139-143, cuda/fast.cu:211-275 (the stage cv::cuda::ORB runs at
+ * every pyramid level, orb.cpp:739-783).  scores: MI_32SC1 of the image's size: cornerScore where the pixel is a candidate, 0 elsewhere.
+ * Waits for `stream`. */
+MI_API int mi_fast_score(const mi_mat *img, const mi_mat *mask, int threshold, mi_mat *scores, void *stream);
+/* The first n locations of a detect's row 0 as 1 x n MI_32FC2 points, the form mi_sparsepyrlk_calc takes (on the host: FAST_Impl::convert,
+ * fast.cpp:175-208, then the caller's upload). */
+MI_API int mi_fast_locations_to_points(const mi_mat *keypoints, int n, mi_mat *points, void *stream);
+
 /* ================================================= superres optical-flow adapters ===== */
 
 /* Replaces: cv::superres::convertToType(GpuMat, CV_8UC1) as used by GpuOpticalFlow::calc, superres/src/optical_flow.cpp:469-470

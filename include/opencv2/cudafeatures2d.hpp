@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <vector>
 #include "opencv2/core/cuda.hpp"
+#include "opencv2/core/types.hpp"   // KeyPoint, shared with xfeatures2d/cuda.hpp
 
 namespace cv {
 
@@ -312,6 +313,126 @@ private:
 }  // namespace miflow_detail
 
 inline Ptr<DescriptorMatcher> DescriptorMatcher::createBFMatcher(int normType) { return makePtr<miflow_detail::BFMatcherImpl>(normType); }
+
+// ---------------------------------------------------------------- FastFeatureDetector
+}  // namespace cuda
+
+#ifndef MIFLOW_WITH_OPENCV
+/** the constants of the main repository's cv::FastFeatureDetector (opencv2/features2d.hpp) that the factory's default names */
+class FastFeatureDetector {
+public:
+    enum { TYPE_5_8 = 0, TYPE_7_12 = 1, TYPE_9_16 = 2 };
+};
+#endif
+
+namespace cuda {
+
+/** cudafeatures2d.hpp:377-418, of which the detector uses detectAsync and convert.  The reference derives it from cv::Feature2D (main
+ * repository); here it stands on cv::Algorithm. */
+class CV_EXPORTS_W Feature2DAsync : public cv::Algorithm {
+public:
+    virtual ~Feature2DAsync() {}
+    virtual void detect(InputArray image, std::vector<KeyPoint> &keypoints, InputArray mask = GpuMat()) = 0;
+    virtual void detectAsync(InputArray image, OutputArray keypoints, InputArray mask = GpuMat(), Stream &stream = Stream::Null()) = 0;
+    virtual void convert(InputArray gpu_keypoints, std::vector<KeyPoint> &keypoints) = 0;
+};
+
+/** cudafeatures2d.hpp:426-442 over mi_fast_* (include/miflow/c_api.h).  Keypoints come in row-major order of the image (the reference:
+ * in the arrival order of its atomics).  get/setThreshold's getter, get/setNonmaxSuppression and get/setType are FAST_Impl's
+ * (fast.cpp:76-86); the reference's public class declares setThreshold, setMaxNumPoints and getMaxNumPoints only. */
+class CV_EXPORTS_W FastFeatureDetector : public Feature2DAsync {
+public:
+    static const int LOCATION_ROW = 0;
+    static const int RESPONSE_ROW = 1;
+    static const int ROWS_COUNT = 2;
+    static const int FEATURE_SIZE = 7;
+
+    static Ptr<cuda::FastFeatureDetector> create(int threshold = 10, bool nonmaxSuppression = true,
+                                                 int type = cv::FastFeatureDetector::TYPE_9_16, int max_npoints = 5000);
+    virtual void setThreshold(int threshold) = 0;
+    virtual int getThreshold() const = 0;
+    virtual void setNonmaxSuppression(bool f) = 0;
+    virtual bool getNonmaxSuppression() const = 0;
+    virtual void setMaxNumPoints(int max_npoints) = 0;
+    virtual int getMaxNumPoints() const = 0;
+    virtual void setType(int type) = 0;
+    virtual int getType() const = 0;
+    /** shim-only: convert() of a matrix that already is on the host (the reference takes it through InputArray, fast.cpp:188-191):
+     * rows of `step` bytes, npoints columns */
+    virtual void convert(const void *host_keypoints, size_t step, int npoints, std::vector<KeyPoint> &keypoints) = 0;
+    using Feature2DAsync::convert;
+};
+
+namespace miflow_detail {
+/** twin of FAST_Impl, cudafeatures2d/src/fast.cpp:63-209 */
+class FastImpl final : public cuda::FastFeatureDetector {
+public:
+    FastImpl(int threshold, bool nonmaxSuppression, int max_npoints)
+    {
+        p_.threshold = threshold; p_.nonmax_suppression = nonmaxSuppression ? 1 : 0; p_.max_npoints = max_npoints;
+        miCheck(mi_fast_create(&p_, &h_));
+    }
+    ~FastImpl() override { mi_fast_destroy(h_); }
+    FastImpl(const FastImpl &) = delete;
+    FastImpl &operator=(const FastImpl &) = delete;
+    void detect(InputArray image, std::vector<KeyPoint> &keypoints, InputArray mask) override
+    {
+        if (image.empty()) { keypoints.clear(); return; }   // fast.cpp:109-113
+        GpuMat k;
+        detectAsync(image, k, mask, Stream::Null());
+        convert(k, keypoints);
+    }
+    void detectAsync(InputArray image, OutputArray keypoints, InputArray mask, Stream &stream) override
+    {
+        GpuMat buf(ROWS_COUNT, p_.max_npoints, CV_32FC1);   // the pool's buffer of fast.cpp:116
+        mi_mat i = miMat(image), m = miMat(mask), k = miMat(buf);
+        int n = 0;
+        miCheck(mi_fast_detect(h_, &i, mask.empty() ? nullptr : &m, &k, &n, stream.hipStream()));
+        if (n == 0) { keypoints.release(); return; }   // fast.cpp:146-150,158-161
+        keypoints = buf(Rect(0, 0, n, ROWS_COUNT));    // keypoints.cols = count (:164)
+    }
+    void convert(InputArray gpu_keypoints, std::vector<KeyPoint> &keypoints) override
+    {
+        if (gpu_keypoints.empty()) { keypoints.clear(); return; }   // fast.cpp:177-181
+        CV_Assert(gpu_keypoints.rows == ROWS_COUNT);
+        CV_Assert(gpu_keypoints.elemSize() == 4);
+        const int n = gpu_keypoints.cols;
+        std::vector<float> host((size_t)ROWS_COUNT * n);
+        gpu_keypoints.download(host.data(), (size_t)n * 4);
+        convert(host.data(), (size_t)n * 4, n, keypoints);
+    }
+    void convert(const void *host_keypoints, size_t step, int npoints, std::vector<KeyPoint> &keypoints) override
+    {
+        keypoints.resize(npoints);   // fast.cpp:196-207
+        const short *loc = (const short *)((const unsigned char *)host_keypoints + LOCATION_ROW * step);
+        const float *resp = (const float *)((const unsigned char *)host_keypoints + RESPONSE_ROW * step);
+        for (int i = 0; i < npoints; ++i) keypoints[i] = KeyPoint(loc[2 * i], loc[2 * i + 1], (float)FEATURE_SIZE, -1, resp[i]);
+    }
+    void setThreshold(int v) override { set(v, p_.nonmax_suppression, p_.max_npoints); }
+    int getThreshold() const override { return p_.threshold; }
+    void setNonmaxSuppression(bool f) override { set(p_.threshold, f ? 1 : 0, p_.max_npoints); }
+    bool getNonmaxSuppression() const override { return p_.nonmax_suppression != 0; }
+    void setMaxNumPoints(int v) override { set(p_.threshold, p_.nonmax_suppression, v); }
+    int getMaxNumPoints() const override { return p_.max_npoints; }
+    void setType(int type) override { CV_Assert(type == cv::FastFeatureDetector::TYPE_9_16); }   // fast.cpp:85
+    int getType() const override { return cv::FastFeatureDetector::TYPE_9_16; }
+private:
+    void set(int threshold, int nms, int max_npoints)   // a rejected value leaves the object as it was
+    {
+        mi_fast_params q = {threshold, nms, max_npoints};
+        miCheck(mi_fast_set_params(h_, &q));
+        p_ = q;
+    }
+    mi_fast_params p_;
+    mi_fast *h_ = nullptr;
+};
+}  // namespace miflow_detail
+
+inline Ptr<cuda::FastFeatureDetector> FastFeatureDetector::create(int threshold, bool nonmaxSuppression, int type, int max_npoints)
+{
+    CV_Assert(type == cv::FastFeatureDetector::TYPE_9_16);   // fast.cpp:213
+    return makePtr<miflow_detail::FastImpl>(threshold, nonmaxSuppression, max_npoints);
+}
 
 }  // namespace cuda
 }  // namespace cv

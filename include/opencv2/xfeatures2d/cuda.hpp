@@ -1,16 +1,15 @@
 // Drop-in for modules/xfeatures2d/include/opencv2/xfeatures2d/cuda.hpp (cv::cuda::SURF_CUDA) over the miflow C-ABI.
 // cv::KeyPoint / std::vector overloads need main-repo types (core/types.hpp); in the stand-alone shim the
-// host-side keypoints are the plain struct below with the fields the reference fills (surf.cuda.cpp:319-356).
+// host-side keypoints are the plain struct of opencv2/core/types.hpp with the fields the reference fills (surf.cuda.cpp:319-356).
 #ifndef MIFLOW_OPENCV_XFEATURES2D_CUDA_HPP
 #define MIFLOW_OPENCV_XFEATURES2D_CUDA_HPP
 
 #include <vector>
 #include "opencv2/core/cuda.hpp"
+#include "opencv2/core/types.hpp"   // KeyPoint, shared with cudafeatures2d.hpp
 
 namespace cv {
 #ifndef MIFLOW_WITH_OPENCV
-struct Point2f { float x = 0, y = 0; };
-struct KeyPoint { Point2f pt; float size = 0, angle = -1, response = 0; int octave = 0, class_id = -1; };
 #ifndef MIFLOW_HAVE_NORM_TYPES
 #define MIFLOW_HAVE_NORM_TYPES
 enum NormTypes { NORM_INF = 1, NORM_L1 = 2, NORM_L2 = 4, NORM_HAMMING = 6 };   // opencv2/core/base.hpp

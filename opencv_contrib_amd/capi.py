@@ -104,6 +104,10 @@ class StereoCSBPParams(C.Structure):
 MI_STEREOCSBP_FORM_AUTO, MI_STEREOCSBP_FORM_REG, MI_STEREOCSBP_FORM_GEN = 0, 1, 2
 
 
+class FastParams(C.Structure):
+    _fields_ = [("threshold", C.c_int), ("nonmax_suppression", C.c_int), ("max_npoints", C.c_int)]
+
+
 class BTVL1Params(C.Structure):
     _fields_ = [("scale", C.c_int), ("iterations", C.c_int), ("tau", C.c_double), ("lambda_", C.c_double), ("alpha", C.c_double),
                 ("btv_kernel_size", C.c_int), ("blur_kernel_size", C.c_int), ("blur_sigma", C.c_double)]
@@ -283,6 +287,16 @@ def lib():
         "mi_stereocsbp_init_message": (i, [PM, PM, PM, PM, PM, i, i, vp]),
         "mi_stereocsbp_iterate": (i, [C.POINTER(StereoCSBPParams), PM, PM, PM, PM, i, i, i, i, vp]),
         "mi_stereocsbp_compute_disp": (i, [PM, PM, PM, i, PM, vp]),
+        "mi_fast_default_params": (None, [C.POINTER(FastParams)]),
+        "mi_fast_create": (i, [C.POINTER(FastParams), C.POINTER(vp)]),
+        "mi_fast_set_params": (i, [vp, C.POINTER(FastParams)]),
+        "mi_fast_get_params": (i, [vp, C.POINTER(FastParams)]),
+        "mi_fast_destroy": (None, [vp]),
+        "mi_fast_scratch_bytes": (i, [vp, C.POINTER(C.c_size_t)]),
+        "mi_fast_detect": (i, [vp, PM, PM, PM, C.POINTER(i), vp]),
+        "mi_fast_detect_batch": (i, [vp, i, PM, PM, PM, C.POINTER(i), vp]),
+        "mi_fast_score": (i, [PM, PM, i, PM, vp]),
+        "mi_fast_locations_to_points": (i, [PM, i, PM, vp]),
         "mi_superres_to_gray8": (i, [PM, PM, vp]),
         "mi_split_flow": (i, [PM, PM, PM, vp]),
         "mi_btvl1_default_params": (None, [C.POINTER(BTVL1Params)]),

@@ -1521,3 +1521,130 @@ def surf_detTrace(sum_, octave, nOctaveLayers=2):
                                             capi.current_stream_ptr()))
     torch.cuda.synchronize()
     return det, tr
+
+
+# ---------------------------------------------------------------- FastFeatureDetector (cudafeatures2d.hpp:426-442, src/fast.cpp)
+def _u8(t):
+    """a uint8 device tensor as the kernels take it: rows of any pitch, dense within a row (anything else is copied)"""
+    return t if t.dim() != 2 or t.stride(1) == 1 or t.shape[1] <= 1 else t.contiguous()
+
+
+class FastFeatureDetector:
+    """cv::cuda::FastFeatureDetector.  Images and masks are uint8 device tensors; keypoints are the reference's 2 x n CV_32FC1 matrix
+    (row 0: short2 {x, y} in an element's 4 bytes, row 1: the response), here in row-major order of the image."""
+    LOCATION_ROW, RESPONSE_ROW, ROWS_COUNT, FEATURE_SIZE = 0, 1, 2, 7   # cudafeatures2d.hpp:429-432
+    TYPE_5_8, TYPE_7_12, TYPE_9_16 = 0, 1, 2                            # cv::FastFeatureDetector (main repository, features2d.hpp)
+
+    def __init__(self, threshold=10, nonmaxSuppression=True, type=2, max_npoints=5000):
+        self._h = None
+        if type != self.TYPE_9_16:
+            raise MiError(-1, "type == cv::FastFeatureDetector::TYPE_9_16")   # fast.cpp:213
+        self._p = capi.FastParams(int(threshold), int(bool(nonmaxSuppression)), int(max_npoints))
+        h = C.c_void_p()
+        capi.check(capi.lib().mi_fast_create(C.byref(self._p), C.byref(h)))
+        self._h = h
+
+    @staticmethod
+    def create(threshold=10, nonmaxSuppression=True, type=2, max_npoints=5000) -> "FastFeatureDetector":
+        return FastFeatureDetector(threshold, nonmaxSuppression, type, max_npoints)
+
+    def __del__(self):
+        _destroy(self, "mi_fast_destroy")
+
+    def _set(self, **kw):
+        p = capi.FastParams(self._p.threshold, self._p.nonmax_suppression, self._p.max_npoints)
+        for k, v in kw.items():
+            setattr(p, k, int(v))
+        capi.check(capi.lib().mi_fast_set_params(self._h, C.byref(p)))
+        self._p = p
+
+    def setThreshold(self, threshold): self._set(threshold=threshold)
+    def getThreshold(self): return self._p.threshold
+    def setNonmaxSuppression(self, f): self._set(nonmax_suppression=bool(f))
+    def getNonmaxSuppression(self): return bool(self._p.nonmax_suppression)
+    def setMaxNumPoints(self, max_npoints): self._set(max_npoints=max_npoints)
+    def getMaxNumPoints(self): return self._p.max_npoints
+
+    def setType(self, type):
+        if type != self.TYPE_9_16:
+            raise MiError(-1, "type == cv::FastFeatureDetector::TYPE_9_16")   # fast.cpp:85
+
+    def getType(self): return self.TYPE_9_16
+
+    def scratchBytes(self):
+        b = C.c_size_t()
+        capi.check(capi.lib().mi_fast_scratch_bytes(self._h, C.byref(b)))
+        return b.value
+
+    def detectAsync(self, image, mask=None, stream=None):
+        """-> the (2, n) float32 keypoint matrix on the device; (2, 0) where the reference releases it (fast.cpp:146-150,158-161)"""
+        import torch
+        image = _u8(image)
+        kp = torch.empty((self.ROWS_COUNT, self._p.max_npoints), dtype=torch.float32, device=image.device)
+        n = C.c_int()
+        sp = C.c_void_p(stream) if stream is not None else capi.current_stream_ptr()
+        mm = C.byref(capi.mat_from_tensor(_u8(mask))) if mask is not None else None
+        capi.check(capi.lib().mi_fast_detect(self._h, C.byref(capi.mat_from_tensor(image)), mm, C.byref(capi.mat_from_tensor(kp)), C.byref(n), sp))
+        return kp[:, : n.value]
+
+    def detect(self, image, mask=None):
+        """-> the keypoints as convert() gives them"""
+        return self.convert(self.detectAsync(image, mask))
+
+    def detect_batch(self, images, masks=None, stream=None):
+        """detectAsync of every frame through this handle in one call, with one read-back for all counts; frames may differ in size.
+        masks: None, or one entry per frame (a tensor or None).  -> list of (2, n) keypoint matrices."""
+        import torch
+        n = len(images)
+        if masks is not None and len(masks) != n:
+            raise MiError(-3, "masks: one entry (a tensor or None) per frame")
+        images = [_u8(t) for t in images]
+        kps = [torch.empty((self.ROWS_COUNT, self._p.max_npoints), dtype=torch.float32, device=t.device) for t in images]
+        mi = (capi.Mat * n)(*[capi.mat_from_tensor(t) for t in images])
+        mk = (capi.Mat * n)(*[capi.mat_from_tensor(t) for t in kps])
+        mm = None
+        if masks is not None:
+            keep = [_u8(m) if m is not None else None for m in masks]
+            mm = (capi.Mat * n)(*[capi.mat_from_tensor(m) if m is not None else capi.Mat() for m in keep])
+        ns = (C.c_int * n)()
+        sp = C.c_void_p(stream) if stream is not None else capi.current_stream_ptr()
+        capi.check(capi.lib().mi_fast_detect_batch(self._h, n, mi, mm, mk, ns, sp))
+        return [kp[:, : ns[i]] for i, kp in enumerate(kps)]
+
+    @staticmethod
+    def convert(gpu_keypoints):
+        """FAST_Impl::convert (fast.cpp:175-208): a device or host matrix -> [(x, y, size, angle, response)]"""
+        import numpy as np
+        k = gpu_keypoints.detach().cpu().numpy() if hasattr(gpu_keypoints, "detach") else np.asarray(gpu_keypoints)
+        if k.size == 0:
+            return []
+        if k.shape[0] != FastFeatureDetector.ROWS_COUNT or k.itemsize != 4:
+            raise MiError(-1, "h_keypoints.rows == ROWS_COUNT && h_keypoints.elemSize() == 4")
+        k = np.ascontiguousarray(k)
+        loc = k[0].view(np.int16).reshape(-1, 2)
+        resp = k[1].view(np.float32)
+        return [(float(x), float(y), float(FastFeatureDetector.FEATURE_SIZE), -1.0, float(r)) for (x, y), r in zip(loc, resp)]
+
+
+def fast_score(image, mask=None, threshold=10):
+    """The reference's CV_32SC1 score plane (score.setTo(0) + calcKeypoints<true>, fast.cpp:139-143): cornerScore at candidates, 0 elsewhere"""
+    import torch
+    image = _u8(image)
+    scores = torch.empty(image.shape, dtype=torch.int32, device=image.device)
+    if scores.numel() == 0:
+        return scores
+    mm = C.byref(capi.mat_from_tensor(_u8(mask))) if mask is not None else None
+    capi.check(capi.lib().mi_fast_score(C.byref(capi.mat_from_tensor(image)), mm, int(threshold), C.byref(capi.mat_from_tensor(scores)),
+                                        capi.current_stream_ptr()))
+    return scores
+
+
+def fast_locations_to_points(gpu_keypoints):
+    """(2, n) keypoint matrix -> (1, n, 2) float32 points on the device, the form SparsePyrLKOpticalFlow.calc takes"""
+    import torch
+    n = gpu_keypoints.shape[1]
+    pts = torch.empty((1, n, 2), dtype=torch.float32, device=gpu_keypoints.device)
+    if n:
+        capi.check(capi.lib().mi_fast_locations_to_points(C.byref(capi.mat_from_tensor(gpu_keypoints)), n, C.byref(capi.mat_from_tensor(pts)),
+                                                          capi.current_stream_ptr()))
+    return pts
