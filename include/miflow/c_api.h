@@ -694,6 +694,79 @@ MI_API int mi_fast_score(const mi_mat *img, const mi_mat *mask, int threshold, m
  * fast.cpp:175-208, then the caller's upload). */
 MI_API int mi_fast_locations_to_points(const mi_mat *keypoints, int n, mi_mat *points, void *stream);
 
+/* ================================================= ORB ===== */
+
+/* cv::cuda::ORB (cudafeatures2d.hpp:452-505).  DESIGN.md 4.11 has the yardstick and the deviations. */
+typedef struct mi_orb_params {
+    int nfeatures;            /* 500 */
+    float scale_factor;       /* 1.2f; > 1 */
+    int nlevels;              /* 8; 1 .. 32 */
+    int edge_threshold;       /* 31; detection needs edge_threshold >= R (mi_orb_reach): the reference reads out of bounds below it */
+    int first_level;          /* 0 */
+    int wta_k;                /* 2; 2, 3 or 4 */
+    int score_type;           /* 0 = cv::ORB::HARRIS_SCORE, 1 = FAST_SCORE */
+    int patch_size;           /* 31; 2 .. 59 */
+    int fast_threshold;       /* 20 */
+    int blur_for_descriptor;  /* 0 */
+} mi_orb_params;
+
+typedef struct mi_orb mi_orb;
+
+/* Replaces: the defaults of cv::cuda::ORB::create, cudafeatures2d.hpp:463-472 */
+MI_API void mi_orb_default_params(mi_orb_params *p);
+/* Replaces: ORB_Impl::ORB_Impl, orb.cpp:479-571.  pattern0: the pool of 512 test points as a HOST 512 x 2 MI_32SC1 matrix {x, y} -- what
+ * the reference reads from its learned table when patchSize == 31 (an OpenCV binding passes its own) -- or NULL: makeRandomPattern
+ * (orb.cpp:466-477) for every patch size, 31 included.  The parameters are checked before the device is looked for. */
+MI_API int mi_orb_create(const mi_orb_params *p, const mi_mat *pattern0, mi_orb **out);
+/* Replaces: the setters and getters, orb.cpp:361-389.  Deviation: quotas, u_max and the pattern follow the new parameters at once (the
+ * reference computes them in its constructor only). */
+MI_API int mi_orb_set_params(mi_orb *h, const mi_orb_params *p);
+MI_API int mi_orb_get_params(const mi_orb *h, mi_orb_params *p);
+MI_API void mi_orb_destroy(mi_orb *h);
+/* Device scratch the handle holds (grown on demand, never shrunk); no reference counterpart */
+MI_API int mi_orb_scratch_bytes(const mi_orb *h, size_t *bytes);
+/* *source = 0: the generated random pool, 1: the caller's pattern0 */
+MI_API int mi_orb_pattern_source(const mi_orb *h, int *source);
+/* R: how far Harris, the orientation disc and the rotated pattern read from a keypoint with this handle's parameters and pattern */
+MI_API int mi_orb_reach(const mi_orb *h, int *reach);
+/* Replaces: the pattern part of ORB_Impl::ORB_Impl with initializeOrbPattern and makeRandomPattern, orb.cpp:431-477,538-568: the 2 x N
+ * MI_32SC1 matrix the reference uploads (N = 512, 384, 512 for WTA_K 2, 3, 4), on the HOST.  pattern0 as in mi_orb_create. */
+MI_API int mi_orb_make_pattern(int patch_size, int wta_k, const mi_mat *pattern0, mi_mat *out);
+/* Replaces: orb.cpp:506-517 (quota[nlevels]) and :519-534 (u_max[32], *n_u_max = patch_size / 2 + 2).  Host arithmetic only. */
+MI_API int mi_orb_features_per_level(const mi_orb_params *p, int *quota);
+MI_API int mi_orb_u_max(int patch_size, int *u_max, int *n_u_max);
+/* Replaces: ORB_Impl::detectAndCompute / detectAndComputeAsync, orb.cpp:578-866.
+ * use_provided == 0: img, mask (NULL or data == NULL: none): MI_8UC1 on the device, any base address and step; keypoints: MI_32FC1 on
+ * the device, 6 rows (X, Y, RESPONSE, ANGLE, OCTAVE, SIZE), at least min(nfeatures, what the levels can hold) columns; descriptors:
+ * NULL (none wanted) or MI_8UC1, as many rows, 32 columns.  *n = the keypoints found: levels in order, within a level by response
+ * descending and FAST's row-major order among equals (no sort where a level holds no more than its quota).  Waits for `stream` once, at
+ * the end, for the per-level counts.  A level whose inner rectangle is empty: MI_ERR_BAD_SIZE before anything is launched.
+ * use_provided != 0 (orb.cpp:581-635): keypoints is a HOST 6 x *n matrix; its columns are regrouped by octave IN PLACE (stable), which
+ * is the order of the descriptor rows; nlevels becomes the largest octave + 1; locations are cvRound(pt / scale), the caller's angle is
+ * used.  A keypoint nearer than R to its level's border: MI_ERR_BAD_ARG before any launch.  A call that fails, at validation or while
+ * it runs, leaves the matrix and nlevels as they were. */
+MI_API int mi_orb_detect_and_compute(mi_orb *h, const mi_mat *img, const mi_mat *mask, mi_mat *keypoints, mi_mat *descriptors, int *n,
+                                     int use_provided, void *stream);
+/* Stage entries.  Keypoint matrices are the reference's per-level keyPointsPyr_ (orb.cpp:762): MI_32FC1 on the device, row 0 short2
+ * {x, y} in an element's 4 bytes, row 1 the response, row 2 (where used) the angle.  Each waits for `stream`.
+ * Replaces: one level of buildScalePyramids, orb.cpp:672-718: cuda::resize (INTER_LINEAR, the global-memory kernel resize.cu:234-269) of
+ * src into dst_img, whose size decides the factors; dst_mask (NULL: not wanted): src_mask (NULL: all 255) copied (mask_mode 0), resized (1)
+ * or resized and THRESH_TOZERO at 254 (2), then AND the frame of edge_threshold. */
+MI_API int mi_orb_pyramid_level(const mi_mat *src, const mi_mat *src_mask, int mask_mode, int edge_threshold, mi_mat *dst_img, mi_mat *dst_mask,
+                                void *stream);
+/* Replaces: cull, orb.cpp:722-737, with cull_gpu, orb.cu:62-89: the first n_points of (response descending, index ascending) in that
+ * order; count <= n_points: unchanged; n_points == 0: none.  in / out: 2 or 3 rows, rows 0 and 1 are moved. */
+MI_API int mi_orb_cull(const mi_mat *in, int count, int n_points, mi_mat *out, int *count_out, void *stream);
+/* Replaces: HarrisResponses_gpu, orb.cu:94-161 (block size 7, k = 0.04): row 1 of keypoints[:, :n] from row 0 */
+MI_API int mi_orb_harris(const mi_mat *img, mi_mat *keypoints, int n, void *stream);
+/* Replaces: IC_Angle_gpu, orb.cu:173-243, and loadUMax: row 2 of keypoints[:, :n] from row 0; m01, m10 (NULL: not wanted): 1 x n MI_32SC1 */
+MI_API int mi_orb_angle(const mi_mat *img, mi_mat *keypoints, int n, int patch_size, mi_mat *m01, mi_mat *m10, void *stream);
+/* Replaces: blurFilter_->apply, orb.cpp:570,815: createGaussianFilter(CV_8UC1, -1, 7 x 7, sigma 2, BORDER_REFLECT_101) */
+MI_API int mi_orb_blur(const mi_mat *src, mi_mat *dst, void *stream);
+/* Replaces: computeOrbDescriptor_gpu, orb.cu:250-411: rows 0 and 2 of keypoints[:, :n]; pattern: HOST 2 x N MI_32SC1 as
+ * mi_orb_make_pattern gives it; descriptors: MI_8UC1, at least n rows, 32 columns */
+MI_API int mi_orb_descriptors(const mi_mat *img, const mi_mat *keypoints, int n, const mi_mat *pattern, int wta_k, mi_mat *descriptors, void *stream);
+
 /* ================================================= superres optical-flow adapters ===== */
 
 /* Replaces: cv::superres::convertToType(GpuMat, CV_8UC1) as used by GpuOpticalFlow::calc, superres/src/optical_flow.cpp:469-470

@@ -434,6 +434,213 @@ inline Ptr<cuda::FastFeatureDetector> FastFeatureDetector::create(int threshold,
     return makePtr<miflow_detail::FastImpl>(threshold, nonmaxSuppression, max_npoints);
 }
 
+// ---------------------------------------------------------------- ORB
+}  // namespace cuda
+
+#ifndef MIFLOW_WITH_OPENCV
+/** the constants of the main repository's cv::ORB (opencv2/features2d.hpp) that the factory's defaults and descriptorSize() name */
+class ORB {
+public:
+    enum { kBytes = 32, HARRIS_SCORE = 0, FAST_SCORE = 1 };
+};
+#endif
+
+namespace cuda {
+
+/** cudafeatures2d.hpp:452-505 over mi_orb_* (include/miflow/c_api.h).  DESIGN.md 4.11 has what differs from the reference: the pool of
+ * test points is an argument (`pattern0`, 512 points {x, y}; none: makeRandomPattern for every patch size), the culls keep FAST's
+ * row-major order among equal responses, and setters take effect on quotas, u_max and pattern at once. */
+class CV_EXPORTS_W ORB : public Feature2DAsync {
+public:
+    static const int X_ROW = 0;
+    static const int Y_ROW = 1;
+    static const int RESPONSE_ROW = 2;
+    static const int ANGLE_ROW = 3;
+    static const int OCTAVE_ROW = 4;
+    static const int SIZE_ROW = 5;
+    static const int ROWS_COUNT = 6;
+    enum { PATTERN_RANDOM = 0, PATTERN_PROVIDED = 1 };
+
+    static Ptr<cuda::ORB> create(int nfeatures = 500, float scaleFactor = 1.2f, int nlevels = 8, int edgeThreshold = 31, int firstLevel = 0,
+                                 int WTA_K = 2, int scoreType = cv::ORB::HARRIS_SCORE, int patchSize = 31, int fastThreshold = 20,
+                                 bool blurForDescriptor = false);
+    /** shim-only: the same with the caller's pool of 512 test points {x, y} (an OpenCV binding passes the learned table of its cv::ORB) */
+    static Ptr<cuda::ORB> create(const int *pattern0, int nfeatures, float scaleFactor, int nlevels, int edgeThreshold, int firstLevel, int WTA_K,
+                                 int scoreType, int patchSize, int fastThreshold, bool blurForDescriptor);
+    virtual void detectAndCompute(InputArray image, InputArray mask, std::vector<KeyPoint> &keypoints, OutputArray descriptors,
+                                  bool useProvidedKeypoints = false) = 0;
+    virtual void detectAndComputeAsync(InputArray image, InputArray mask, OutputArray keypoints, OutputArray descriptors,
+                                       bool useProvidedKeypoints = false, Stream &stream = Stream::Null()) = 0;
+    virtual int descriptorSize() const = 0;
+    virtual int descriptorType() const = 0;
+    virtual int defaultNorm() const = 0;
+    virtual void setMaxFeatures(int maxFeatures) = 0;
+    virtual int getMaxFeatures() const = 0;
+    virtual void setScaleFactor(double scaleFactor) = 0;
+    virtual double getScaleFactor() const = 0;
+    virtual void setNLevels(int nlevels) = 0;
+    virtual int getNLevels() const = 0;
+    virtual void setEdgeThreshold(int edgeThreshold) = 0;
+    virtual int getEdgeThreshold() const = 0;
+    virtual void setFirstLevel(int firstLevel) = 0;
+    virtual int getFirstLevel() const = 0;
+    virtual void setWTA_K(int wta_k) = 0;
+    virtual int getWTA_K() const = 0;
+    virtual void setScoreType(int scoreType) = 0;
+    virtual int getScoreType() const = 0;
+    virtual void setPatchSize(int patchSize) = 0;
+    virtual int getPatchSize() const = 0;
+    virtual void setFastThreshold(int fastThreshold) = 0;
+    virtual int getFastThreshold() const = 0;
+    virtual void setBlurForDescriptor(bool blurForDescriptor) = 0;
+    virtual bool getBlurForDescriptor() const = 0;
+    /** shim-only: PATTERN_RANDOM or PATTERN_PROVIDED */
+    virtual int getPatternSource() const = 0;
+};
+
+namespace miflow_detail {
+/** twin of ORB_Impl, cudafeatures2d/src/orb.cpp:338-913 */
+class OrbImpl final : public cuda::ORB {
+public:
+    OrbImpl(const int *pattern0, int nfeatures, float scaleFactor, int nlevels, int edgeThreshold, int firstLevel, int WTA_K, int scoreType,
+            int patchSize, int fastThreshold, bool blurForDescriptor)
+    {
+        CV_Assert(patchSize >= 2);                               // orb.cpp:500
+        CV_Assert(WTA_K == 2 || WTA_K == 3 || WTA_K == 4);       // orb.cpp:501
+        p_ = {nfeatures, scaleFactor, nlevels, edgeThreshold, firstLevel, WTA_K, scoreType, patchSize, fastThreshold, blurForDescriptor ? 1 : 0};
+        mi_mat pool = {const_cast<int *>(pattern0), 8, 512, 2, MI_32SC1};
+        miCheck(mi_orb_create(&p_, pattern0 ? &pool : nullptr, &h_));
+    }
+    ~OrbImpl() override { mi_orb_destroy(h_); }
+    OrbImpl(const OrbImpl &) = delete;
+    OrbImpl &operator=(const OrbImpl &) = delete;
+
+    void detect(InputArray image, std::vector<KeyPoint> &keypoints, InputArray mask) override
+    {
+        GpuMat k;
+        run(image, mask, &k, nullptr, Stream::Null());
+        convert(k, keypoints);
+    }
+    void detectAsync(InputArray image, OutputArray keypoints, InputArray mask, Stream &stream) override
+    {
+        GpuMat k;
+        run(image, mask, &k, nullptr, stream);
+        if (k.empty()) keypoints.release(); else keypoints = k;
+    }
+    void detectAndCompute(InputArray image, InputArray mask, std::vector<KeyPoint> &keypoints, OutputArray descriptors,
+                          bool useProvidedKeypoints) override
+    {
+        if (useProvidedKeypoints) { provided(image, keypoints, descriptors); return; }
+        GpuMat k, d;
+        run(image, mask, &k, &d, Stream::Null());
+        if (d.empty()) descriptors.release(); else descriptors = d;
+        convert(k, keypoints);   // orb.cpp:639-641
+    }
+    void detectAndComputeAsync(InputArray image, InputArray mask, OutputArray keypoints, OutputArray descriptors, bool useProvidedKeypoints,
+                               Stream &stream) override
+    {
+        CV_Assert(!useProvidedKeypoints);   // the provided keypoints live in detectAndCompute's vector (orb.cpp:581-635)
+        GpuMat k, d;
+        run(image, mask, &k, &d, stream);
+        if (k.empty()) keypoints.release(); else keypoints = k;
+        if (d.empty()) descriptors.release(); else descriptors = d;
+    }
+    void convert(InputArray gpu_keypoints, std::vector<KeyPoint> &keypoints) override
+    {
+        if (gpu_keypoints.empty()) { keypoints.clear(); return; }   // orb.cpp:870-874
+        CV_Assert(gpu_keypoints.rows == ROWS_COUNT);
+        CV_Assert(gpu_keypoints.type() == CV_32FC1);
+        const int n = gpu_keypoints.cols;
+        std::vector<float> h((size_t)ROWS_COUNT * n);
+        gpu_keypoints.download(h.data(), (size_t)n * 4);
+        keypoints.resize(n);   // orb.cpp:889-912
+        for (int i = 0; i < n; ++i) {
+            KeyPoint kp(h[(size_t)X_ROW * n + i], h[(size_t)Y_ROW * n + i], h[(size_t)SIZE_ROW * n + i], h[(size_t)ANGLE_ROW * n + i],
+                        h[(size_t)RESPONSE_ROW * n + i]);
+            kp.octave = (int)h[(size_t)OCTAVE_ROW * n + i];
+            keypoints[i] = kp;
+        }
+    }
+    int descriptorSize() const override { return cv::ORB::kBytes; }
+    int descriptorType() const override { return CV_8U; }
+    int defaultNorm() const override { return NORM_HAMMING; }
+    void setMaxFeatures(int v) override { mi_orb_params q = p_; q.nfeatures = v; set(q); }
+    int getMaxFeatures() const override { return p_.nfeatures; }
+    void setScaleFactor(double v) override { mi_orb_params q = p_; q.scale_factor = (float)v; set(q); }
+    double getScaleFactor() const override { return p_.scale_factor; }
+    void setNLevels(int v) override { mi_orb_params q = p_; q.nlevels = v; set(q); }
+    int getNLevels() const override { return p_.nlevels; }
+    void setEdgeThreshold(int v) override { mi_orb_params q = p_; q.edge_threshold = v; set(q); }
+    int getEdgeThreshold() const override { return p_.edge_threshold; }
+    void setFirstLevel(int v) override { mi_orb_params q = p_; q.first_level = v; set(q); }
+    int getFirstLevel() const override { return p_.first_level; }
+    void setWTA_K(int v) override { CV_Assert(v == 2 || v == 3 || v == 4); mi_orb_params q = p_; q.wta_k = v; set(q); }   // orb.cpp:376
+    int getWTA_K() const override { return p_.wta_k; }
+    void setScoreType(int v) override { mi_orb_params q = p_; q.score_type = v; set(q); }
+    int getScoreType() const override { return p_.score_type; }
+    void setPatchSize(int v) override { CV_Assert(v >= 2); mi_orb_params q = p_; q.patch_size = v; set(q); }             // orb.cpp:382
+    int getPatchSize() const override { return p_.patch_size; }
+    void setFastThreshold(int v) override { mi_orb_params q = p_; q.fast_threshold = v; set(q); }
+    int getFastThreshold() const override { return p_.fast_threshold; }
+    void setBlurForDescriptor(bool v) override { mi_orb_params q = p_; q.blur_for_descriptor = v ? 1 : 0; set(q); }
+    bool getBlurForDescriptor() const override { return p_.blur_for_descriptor != 0; }
+    int getPatternSource() const override { int s = 0; miCheck(mi_orb_pattern_source(h_, &s)); return s; }
+private:
+    void set(const mi_orb_params &q)   // a rejected value leaves the object as it was
+    {
+        miCheck(mi_orb_set_params(h_, &q));
+        p_ = q;
+    }
+    // detection: *kp (and *desc, if wanted) receive the first n columns / rows, or stay empty
+    void run(InputArray image, InputArray mask, GpuMat *kp, GpuMat *desc, Stream &stream)
+    {
+        const int cap = p_.nfeatures > 0 ? p_.nfeatures : 1;
+        GpuMat kbuf(ROWS_COUNT, cap, CV_32FC1), dbuf;
+        if (desc) dbuf.create(cap, cv::ORB::kBytes, CV_8UC1);
+        mi_mat i = miMat(image), m = miMat(mask), k = miMat(kbuf), d = miMat(dbuf);
+        int n = 0;
+        miCheck(mi_orb_detect_and_compute(h_, &i, mask.empty() ? nullptr : &m, &k, desc ? &d : nullptr, &n, 0, stream.hipStream()));
+        if (n == 0) return;   // orb.cpp:793-797,834-838: released
+        *kp = kbuf(Rect(0, 0, n, ROWS_COUNT));
+        if (desc) *desc = dbuf(Rect(0, 0, cv::ORB::kBytes, n));
+    }
+    void provided(InputArray image, std::vector<KeyPoint> &keypoints, OutputArray descriptors)
+    {
+        int n = (int)keypoints.size();
+        if (n == 0) { descriptors.release(); return; }
+        std::vector<float> h((size_t)ROWS_COUNT * n);
+        for (int i = 0; i < n; ++i) {
+            const KeyPoint &kp = keypoints[i];
+            CV_Assert(kp.octave >= 0);   // orb.cpp:591
+            h[(size_t)X_ROW * n + i] = kp.pt.x; h[(size_t)Y_ROW * n + i] = kp.pt.y; h[(size_t)RESPONSE_ROW * n + i] = kp.response;
+            h[(size_t)ANGLE_ROW * n + i] = kp.angle; h[(size_t)OCTAVE_ROW * n + i] = (float)kp.octave; h[(size_t)SIZE_ROW * n + i] = kp.size;
+        }
+        GpuMat dbuf(n, cv::ORB::kBytes, CV_8UC1);
+        mi_mat i = miMat(image), k = {h.data(), (size_t)n * 4, ROWS_COUNT, n, MI_32FC1}, d = miMat(dbuf);
+        const int rc = mi_orb_detect_and_compute(h_, &i, nullptr, &k, &d, &n, 1, nullptr);
+        mi_orb_get_params(h_, &p_);   // nlevels is overwritten (orb.cpp:587-594)
+        miCheck(rc);
+        descriptors = dbuf;
+    }
+    mi_orb_params p_;
+    mi_orb *h_ = nullptr;
+};
+}  // namespace miflow_detail
+
+inline Ptr<cuda::ORB> ORB::create(int nfeatures, float scaleFactor, int nlevels, int edgeThreshold, int firstLevel, int WTA_K, int scoreType,
+                                  int patchSize, int fastThreshold, bool blurForDescriptor)
+{
+    return makePtr<miflow_detail::OrbImpl>(nullptr, nfeatures, scaleFactor, nlevels, edgeThreshold, firstLevel, WTA_K, scoreType, patchSize,
+                                           fastThreshold, blurForDescriptor);
+}
+
+inline Ptr<cuda::ORB> ORB::create(const int *pattern0, int nfeatures, float scaleFactor, int nlevels, int edgeThreshold, int firstLevel, int WTA_K,
+                                  int scoreType, int patchSize, int fastThreshold, bool blurForDescriptor)
+{
+    return makePtr<miflow_detail::OrbImpl>(pattern0, nfeatures, scaleFactor, nlevels, edgeThreshold, firstLevel, WTA_K, scoreType, patchSize,
+                                           fastThreshold, blurForDescriptor);
+}
+
 }  // namespace cuda
 }  // namespace cv
 #endif

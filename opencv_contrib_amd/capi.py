@@ -108,6 +108,11 @@ class FastParams(C.Structure):
     _fields_ = [("threshold", C.c_int), ("nonmax_suppression", C.c_int), ("max_npoints", C.c_int)]
 
 
+class OrbParams(C.Structure):
+    _fields_ = [("nfeatures", C.c_int), ("scale_factor", C.c_float), ("nlevels", C.c_int), ("edge_threshold", C.c_int), ("first_level", C.c_int),
+                ("wta_k", C.c_int), ("score_type", C.c_int), ("patch_size", C.c_int), ("fast_threshold", C.c_int), ("blur_for_descriptor", C.c_int)]
+
+
 class BTVL1Params(C.Structure):
     _fields_ = [("scale", C.c_int), ("iterations", C.c_int), ("tau", C.c_double), ("lambda_", C.c_double), ("alpha", C.c_double),
                 ("btv_kernel_size", C.c_int), ("blur_kernel_size", C.c_int), ("blur_sigma", C.c_double)]
@@ -297,6 +302,24 @@ def lib():
         "mi_fast_detect_batch": (i, [vp, i, PM, PM, PM, C.POINTER(i), vp]),
         "mi_fast_score": (i, [PM, PM, i, PM, vp]),
         "mi_fast_locations_to_points": (i, [PM, i, PM, vp]),
+        "mi_orb_default_params": (None, [C.POINTER(OrbParams)]),
+        "mi_orb_create": (i, [C.POINTER(OrbParams), PM, C.POINTER(vp)]),
+        "mi_orb_set_params": (i, [vp, C.POINTER(OrbParams)]),
+        "mi_orb_get_params": (i, [vp, C.POINTER(OrbParams)]),
+        "mi_orb_destroy": (None, [vp]),
+        "mi_orb_scratch_bytes": (i, [vp, C.POINTER(C.c_size_t)]),
+        "mi_orb_pattern_source": (i, [vp, C.POINTER(i)]),
+        "mi_orb_reach": (i, [vp, C.POINTER(i)]),
+        "mi_orb_make_pattern": (i, [i, i, PM, PM]),
+        "mi_orb_features_per_level": (i, [C.POINTER(OrbParams), C.POINTER(i)]),
+        "mi_orb_u_max": (i, [i, C.POINTER(i), C.POINTER(i)]),
+        "mi_orb_detect_and_compute": (i, [vp, PM, PM, PM, PM, C.POINTER(i), i, vp]),
+        "mi_orb_pyramid_level": (i, [PM, PM, i, i, PM, PM, vp]),
+        "mi_orb_cull": (i, [PM, i, i, PM, C.POINTER(i), vp]),
+        "mi_orb_harris": (i, [PM, PM, i, vp]),
+        "mi_orb_angle": (i, [PM, PM, i, i, PM, PM, vp]),
+        "mi_orb_blur": (i, [PM, PM, vp]),
+        "mi_orb_descriptors": (i, [PM, PM, i, PM, i, PM, vp]),
         "mi_superres_to_gray8": (i, [PM, PM, vp]),
         "mi_split_flow": (i, [PM, PM, PM, vp]),
         "mi_btvl1_default_params": (None, [C.POINTER(BTVL1Params)]),

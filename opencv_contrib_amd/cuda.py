@@ -1648,3 +1648,261 @@ def fast_locations_to_points(gpu_keypoints):
         capi.check(capi.lib().mi_fast_locations_to_points(C.byref(capi.mat_from_tensor(gpu_keypoints)), n, C.byref(capi.mat_from_tensor(pts)),
                                                           capi.current_stream_ptr()))
     return pts
+
+
+def _host_mat(a):
+    """a C-contiguous 2-D int32 / float32 / uint8 NumPy array as a HOST mi_mat (the array must outlive the call)"""
+    import numpy as np
+    types = {np.dtype(np.uint8): capi.MI_8UC1, np.dtype(np.int32): capi.MI_32SC1, np.dtype(np.float32): capi.MI_32FC1}
+    assert a.ndim == 2 and a.flags.c_contiguous and a.dtype in types
+    return capi.Mat(a.ctypes.data, a.strides[0], a.shape[0], a.shape[1], types[a.dtype])
+
+
+def _orb_pool(pattern0):
+    """pattern0 (None, or 512 points {x, y}) -> (the int32 (512, 2) array to keep alive or None, the argument for the C call)"""
+    import numpy as np
+    if pattern0 is None:
+        return None, None
+    pool = np.ascontiguousarray(np.asarray(pattern0).reshape(-1, 2), dtype=np.int32)
+    return pool, C.byref(_host_mat(pool))
+
+
+class ORB:
+    """cv::cuda::ORB (cudafeatures2d.hpp:452-505).  Images and masks are uint8 device tensors; keypoints are the reference's 6 x n
+    CV_32FC1 matrix (rows X, Y, RESPONSE, ANGLE, OCTAVE, SIZE), descriptors n x 32 uint8.  pattern0: the pool of 512 test points the
+    reference reads from its learned table when patchSize == 31 (an OpenCV binding passes its own), None: makeRandomPattern."""
+    X_ROW, Y_ROW, RESPONSE_ROW, ANGLE_ROW, OCTAVE_ROW, SIZE_ROW, ROWS_COUNT = 0, 1, 2, 3, 4, 5, 6   # cudafeatures2d.hpp:455-461
+    HARRIS_SCORE, FAST_SCORE = 0, 1     # cv::ORB (main repository, features2d.hpp)
+    kBytes = 32
+    NORM_HAMMING = 6                    # cv::NORM_HAMMING (main repository, core/base.hpp)
+    PATTERN_RANDOM, PATTERN_PROVIDED = 0, 1
+
+    def __init__(self, nfeatures=500, scaleFactor=1.2, nlevels=8, edgeThreshold=31, firstLevel=0, WTA_K=2, scoreType=0, patchSize=31,
+                 fastThreshold=20, blurForDescriptor=False, pattern0=None):
+        self._h = None
+        self._p = capi.OrbParams(int(nfeatures), float(scaleFactor), int(nlevels), int(edgeThreshold), int(firstLevel), int(WTA_K), int(scoreType),
+                                 int(patchSize), int(fastThreshold), int(bool(blurForDescriptor)))
+        self._pool, pm = _orb_pool(pattern0)
+        h = C.c_void_p()
+        capi.check(capi.lib().mi_orb_create(C.byref(self._p), pm, C.byref(h)))
+        self._h = h
+
+    @staticmethod
+    def create(nfeatures=500, scaleFactor=1.2, nlevels=8, edgeThreshold=31, firstLevel=0, WTA_K=2, scoreType=0, patchSize=31, fastThreshold=20,
+               blurForDescriptor=False, pattern0=None) -> "ORB":
+        return ORB(nfeatures, scaleFactor, nlevels, edgeThreshold, firstLevel, WTA_K, scoreType, patchSize, fastThreshold, blurForDescriptor, pattern0)
+
+    def __del__(self):
+        _destroy(self, "mi_orb_destroy")
+
+    def _set(self, **kw):
+        p = capi.OrbParams()
+        C.memmove(C.byref(p), C.byref(self._p), C.sizeof(p))
+        for k, v in kw.items():
+            setattr(p, k, v)
+        capi.check(capi.lib().mi_orb_set_params(self._h, C.byref(p)))
+        self._p = p
+
+    def _sync(self):
+        capi.check(capi.lib().mi_orb_get_params(self._h, C.byref(self._p)))
+
+    def setMaxFeatures(self, v): self._set(nfeatures=int(v))
+    def getMaxFeatures(self): return self._p.nfeatures
+    def setScaleFactor(self, v): self._set(scale_factor=float(v))
+    def getScaleFactor(self): return float(self._p.scale_factor)
+    def setNLevels(self, v): self._set(nlevels=int(v))
+    def getNLevels(self): return self._p.nlevels
+    def setEdgeThreshold(self, v): self._set(edge_threshold=int(v))
+    def getEdgeThreshold(self): return self._p.edge_threshold
+    def setFirstLevel(self, v): self._set(first_level=int(v))
+    def getFirstLevel(self): return self._p.first_level
+    def setWTA_K(self, v): self._set(wta_k=int(v))              # orb.cpp:376 asserts 2, 3 or 4: the library does
+    def getWTA_K(self): return self._p.wta_k
+    def setScoreType(self, v): self._set(score_type=int(v))
+    def getScoreType(self): return self._p.score_type
+    def setPatchSize(self, v): self._set(patch_size=int(v))    # orb.cpp:382 asserts >= 2: the library does
+    def getPatchSize(self): return self._p.patch_size
+    def setFastThreshold(self, v): self._set(fast_threshold=int(v))
+    def getFastThreshold(self): return self._p.fast_threshold
+    def setBlurForDescriptor(self, v): self._set(blur_for_descriptor=int(bool(v)))
+    def getBlurForDescriptor(self): return bool(self._p.blur_for_descriptor)
+
+    def descriptorSize(self): return self.kBytes
+    def descriptorType(self): return 0   # CV_8U
+    def defaultNorm(self): return self.NORM_HAMMING
+
+    def getPatternSource(self):
+        """PATTERN_RANDOM (generated by makeRandomPattern) or PATTERN_PROVIDED (the caller's pattern0)"""
+        s = C.c_int()
+        capi.check(capi.lib().mi_orb_pattern_source(self._h, C.byref(s)))
+        return s.value
+
+    def getReach(self):
+        """R: edgeThreshold must be at least this for detection"""
+        r = C.c_int()
+        capi.check(capi.lib().mi_orb_reach(self._h, C.byref(r)))
+        return r.value
+
+    def scratchBytes(self):
+        b = C.c_size_t()
+        capi.check(capi.lib().mi_orb_scratch_bytes(self._h, C.byref(b)))
+        return b.value
+
+    def detectAndComputeAsync(self, image, mask=None, keypoints=None, useProvidedKeypoints=False, stream=None, computeDescriptors=True):
+        """-> (keypoints, descriptors).  Detection: the (6, n) float32 keypoint matrix and the (n, 32) uint8 descriptors (None unless
+        wanted) on the device.  useProvidedKeypoints: `keypoints` is a host (6, n) matrix; it comes back regrouped by octave (stable), the
+        order of the descriptor rows (orb.cpp:595-600), and nlevels becomes the largest octave + 1."""
+        import numpy as np
+        import torch
+        image = _u8(image)
+        sp = C.c_void_p(stream) if stream is not None else capi.current_stream_ptr()
+        n = C.c_int()
+        if useProvidedKeypoints:
+            kp = np.array(keypoints.detach().cpu().numpy() if hasattr(keypoints, "detach") else keypoints, dtype=np.float32, order="C")
+            if kp.ndim != 2 or kp.shape[0] != self.ROWS_COUNT:
+                raise MiError(-3, "h_keypoints.rows == ROWS_COUNT")
+            n.value = kp.shape[1]
+            desc = torch.empty((kp.shape[1], self.kBytes), dtype=torch.uint8, device=image.device)
+            km = _host_mat(kp) if kp.shape[1] else capi.Mat(kp.ctypes.data, 4, 6, 0, capi.MI_32FC1)
+            dm = C.byref(capi.mat_from_tensor(desc)) if kp.shape[1] else None
+            try:
+                capi.check(capi.lib().mi_orb_detect_and_compute(self._h, C.byref(capi.mat_from_tensor(image)), None, C.byref(km), dm, C.byref(n), 1, sp))
+            finally:
+                self._sync()
+            return kp, desc
+        cap = max(self._p.nfeatures, 1)
+        kp = torch.empty((self.ROWS_COUNT, cap), dtype=torch.float32, device=image.device)
+        desc = torch.empty((cap, self.kBytes), dtype=torch.uint8, device=image.device) if computeDescriptors else None
+        mask = _u8(mask) if mask is not None else None   # held in a local: a copy made here must outlive the call
+        mm = C.byref(capi.mat_from_tensor(mask)) if mask is not None else None
+        dm = C.byref(capi.mat_from_tensor(desc)) if desc is not None else None
+        capi.check(capi.lib().mi_orb_detect_and_compute(self._h, C.byref(capi.mat_from_tensor(image)), mm, C.byref(capi.mat_from_tensor(kp)), dm,
+                                                        C.byref(n), 0, sp))
+        return kp[:, : n.value], (desc[: n.value] if desc is not None else None)
+
+    def detectAndCompute(self, image, mask=None, keypoints=None, useProvidedKeypoints=False):
+        """-> (keypoints as convert() gives them, descriptors on the device)"""
+        kp, desc = self.detectAndComputeAsync(image, mask, keypoints, useProvidedKeypoints)
+        return self.convert(kp), desc
+
+    def detectAsync(self, image, mask=None, stream=None):
+        return self.detectAndComputeAsync(image, mask, stream=stream, computeDescriptors=False)[0]
+
+    def detect(self, image, mask=None):
+        return self.convert(self.detectAsync(image, mask))
+
+    @staticmethod
+    def convert(gpu_keypoints):
+        """ORB_Impl::convert (orb.cpp:868-913): a device or host matrix -> [(x, y, size, angle, response, octave)]"""
+        import numpy as np
+        k = gpu_keypoints.detach().cpu().numpy() if hasattr(gpu_keypoints, "detach") else np.asarray(gpu_keypoints)
+        if k.size == 0:
+            return []
+        if k.shape[0] != ORB.ROWS_COUNT or k.dtype != np.float32:
+            raise MiError(-1, "h_keypoints.rows == ROWS_COUNT && h_keypoints.type() == CV_32FC1")
+        return [(float(k[0, i]), float(k[1, i]), float(k[5, i]), float(k[3, i]), float(k[2, i]), int(k[4, i])) for i in range(k.shape[1])]
+
+
+def orb_make_pattern(patchSize=31, WTA_K=2, pattern0=None):
+    """The 2 x N int32 matrix the reference uploads (orb.cpp:538-568), on the host"""
+    import numpy as np
+    out = np.zeros((2, 512 if WTA_K == 2 else 128 * WTA_K), np.int32)
+    pool, pm = _orb_pool(pattern0)
+    capi.check(capi.lib().mi_orb_make_pattern(int(patchSize), int(WTA_K), pm, C.byref(_host_mat(out))))
+    return out
+
+
+def orb_features_per_level(nfeatures=500, scaleFactor=1.2, nlevels=8):
+    """n_features_per_level, orb.cpp:506-517"""
+    p = capi.OrbParams()
+    capi.lib().mi_orb_default_params(C.byref(p))
+    p.nfeatures, p.scale_factor, p.nlevels = int(nfeatures), float(scaleFactor), int(nlevels)
+    q = (C.c_int * 32)()
+    capi.check(capi.lib().mi_orb_features_per_level(C.byref(p), q))
+    return list(q[: p.nlevels])
+
+
+def orb_u_max(patchSize=31):
+    """u_max, orb.cpp:519-534"""
+    u, n = (C.c_int * 32)(), C.c_int()
+    capi.check(capi.lib().mi_orb_u_max(int(patchSize), u, C.byref(n)))
+    return list(u[: n.value])
+
+
+def _mat_or_none(t):
+    return C.byref(capi.mat_from_tensor(t)) if t is not None else None
+
+
+def orb_pyramid_level(src, dsize, src_mask=None, mask_mode=0, edgeThreshold=31, want_mask=True):
+    """One level of buildScalePyramids (orb.cpp:672-718) -> (image, mask) of dsize = (rows, cols)"""
+    import torch
+    src = _u8(src)
+    img = torch.empty(dsize, dtype=torch.uint8, device=src.device)
+    mask = torch.empty(dsize, dtype=torch.uint8, device=src.device) if want_mask else None
+    src_mask = _u8(src_mask) if src_mask is not None else None   # held in a local: a copy made here must outlive the call
+    capi.check(capi.lib().mi_orb_pyramid_level(C.byref(capi.mat_from_tensor(src)), _mat_or_none(src_mask),
+                                               int(mask_mode), int(edgeThreshold), C.byref(capi.mat_from_tensor(img)), _mat_or_none(mask),
+                                               capi.current_stream_ptr()))
+    return img, mask
+
+
+def orb_cull(keypoints, n_points, out=None):
+    """cull (orb.cpp:722-737) of a (2 or 3, count) keypoint matrix -> (2, kept): response descending, index ascending among equals"""
+    import torch
+    count = keypoints.shape[1]
+    kept = count if count <= n_points else n_points
+    if out is None:
+        out = torch.empty((2, max(kept, 1)), dtype=torch.float32, device=keypoints.device)
+    n = C.c_int()
+    if count == 0:
+        return out[:, :0]
+    capi.check(capi.lib().mi_orb_cull(C.byref(capi.mat_from_tensor(keypoints)), count, int(n_points), C.byref(capi.mat_from_tensor(out)), C.byref(n),
+                                      capi.current_stream_ptr()))
+    return out[:, : n.value]
+
+
+def orb_harris(image, keypoints):
+    """HarrisResponses_gpu (orb.cu:94-161): writes row 1 of the (>= 2, n) keypoint matrix from row 0, in place"""
+    if keypoints.shape[1] == 0:
+        return keypoints
+    capi.check(capi.lib().mi_orb_harris(C.byref(capi.mat_from_tensor(_u8(image))), C.byref(capi.mat_from_tensor(keypoints)), keypoints.shape[1],
+                                        capi.current_stream_ptr()))
+    return keypoints
+
+
+def orb_angle(image, keypoints, patchSize=31):
+    """IC_Angle_gpu (orb.cu:173-243): writes row 2 of the (3, n) keypoint matrix from row 0, in place -> (m_01, m_10) int32"""
+    import torch
+    n = keypoints.shape[1]
+    m01 = torch.zeros((1, max(n, 1)), dtype=torch.int32, device=keypoints.device)
+    m10 = torch.zeros_like(m01)
+    if n == 0:
+        return m01[0, :0], m10[0, :0]
+    capi.check(capi.lib().mi_orb_angle(C.byref(capi.mat_from_tensor(_u8(image))), C.byref(capi.mat_from_tensor(keypoints)), n, int(patchSize),
+                                       C.byref(capi.mat_from_tensor(m01)), C.byref(capi.mat_from_tensor(m10)), capi.current_stream_ptr()))
+    return m01[0, :n], m10[0, :n]
+
+
+def orb_blur(image, out=None):
+    """createGaussianFilter(CV_8UC1, -1, 7 x 7, sigma 2, BORDER_REFLECT_101) (orb.cpp:570,815)"""
+    import torch
+    image = _u8(image)
+    if out is None:
+        out = torch.empty(tuple(image.shape), dtype=torch.uint8, device=image.device)
+    capi.check(capi.lib().mi_orb_blur(C.byref(capi.mat_from_tensor(image)), C.byref(capi.mat_from_tensor(out)), capi.current_stream_ptr()))
+    return out
+
+
+def orb_descriptors(image, keypoints, pattern, WTA_K=2, out=None):
+    """computeOrbDescriptor_gpu (orb.cu:250-411) from rows 0 and 2 of the (3, n) keypoint matrix; pattern: host 2 x N int32 -> (n, 32)"""
+    import numpy as np
+    import torch
+    n = keypoints.shape[1]
+    if out is None:
+        out = torch.empty((max(n, 1), ORB.kBytes), dtype=torch.uint8, device=keypoints.device)
+    pat = np.ascontiguousarray(pattern, dtype=np.int32)
+    if n == 0:
+        return out[:0]
+    capi.check(capi.lib().mi_orb_descriptors(C.byref(capi.mat_from_tensor(_u8(image))), C.byref(capi.mat_from_tensor(keypoints)), n,
+                                             C.byref(_host_mat(pat)), int(WTA_K), C.byref(capi.mat_from_tensor(out)), capi.current_stream_ptr()))
+    return out[:n]
