@@ -1,0 +1,563 @@
+"""The header-only C++ classes of include/opencv2/ against the oracles: StereoSGM, DisparityBilateralFilter, DensePyrLKOpticalFlow,
+SparsePyrLKOpticalFlow and DescriptorMatcher (float and integer descriptors).  tests/cpp/classes_gpu.cpp runs one family of cases per
+process through the public classes alone and writes back what they returned; every comparison here is equality of indices and of the
+bits of every float with the oracle computed in the test, never with the Python mirror.
+
+What only a C++ caller reaches: every output the classes create is a GpuMat::create matrix, pitched to 256-byte rows when it has more
+than one row (the Python mirror allocates dense outputs), and once per class the output is a Rect view inside a larger matrix whose
+every other byte is a sentinel: the view is written in place and the frame stays intact."""
+import os
+import struct
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIBDIR = os.path.join(ROOT, "opencv_contrib_amd")
+sys.path.insert(0, ROOT)
+from opencv_contrib_amd import synth  # noqa: E402
+from test_bfmatch import _reference_case, _reference_data  # noqa: E402
+
+NORM_L1, NORM_L2, NORM_HAMMING = 2, 4, 6
+STS_NOT_IMPLEMENTED, STS_ASSERT = -213, -215
+SENTINEL = 0xA5
+_DEPTH = [np.uint8, np.int8, np.uint16, np.int16, np.int32, np.float32, np.float64]      # CV_8U .. CV_64F
+
+
+# ------------------------------------------------------------------ the program and its files
+@pytest.fixture(scope="module")
+def classes_exe(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("classes_gpu") / "classes_gpu")
+    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"),
+                        os.path.join(ROOT, "tests", "cpp", "classes_gpu.cpp"), "-o", exe, "-L" + LIBDIR, "-lmiflow", "-Wl,-rpath," + LIBDIR],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    return exe
+
+
+def _write(path, arrays):
+    """name -> (rows, cols) or (rows, cols, channels) array, as records {name length, type, rows, cols; name; elements}"""
+    with open(path, "wb") as f:
+        for name, a in arrays.items():
+            a = np.ascontiguousarray(a)
+            assert a.ndim in (2, 3)
+            cn = 1 if a.ndim == 2 else a.shape[2]
+            f.write(struct.pack("4i", len(name), _DEPTH.index(a.dtype.type) + (cn - 1) * 8, a.shape[0], a.shape[1]))
+            f.write(name.encode())
+            f.write(a.tobytes())
+
+
+def _read(path):
+    raw, out, o = open(path, "rb").read(), {}, 0
+    while o < len(raw):
+        n, t, r, c = struct.unpack_from("4i", raw, o)
+        name = raw[o + 16:o + 16 + n].decode()
+        cn = (t >> 3) + 1
+        a = np.frombuffer(raw, np.dtype(_DEPTH[t & 7]), r * c * cn, o + 16 + n).reshape((r, c) if cn == 1 else (r, c, cn))
+        assert name not in out, name
+        out[name] = a
+        o += 16 + n + a.nbytes
+    return out
+
+
+def _run(exe, family, arrays, tmp_path):
+    fin, fout = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
+    _write(fin, arrays)
+    r = subprocess.run([exe, family, fin, fout], capture_output=True, text=True, timeout=120)
+    if r.returncode != 0:
+        print(r.stderr)
+    assert r.returncode == 0, (r.returncode, r.stderr)
+    out = _read(fout)
+    assert out
+    return out
+
+
+def _bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view({1: np.uint8, 2: np.uint16, 4: np.uint32}[a.dtype.itemsize])
+
+
+def _same(got, want, what=""):
+    """non-empty, same shape and element type, same bits"""
+    want = np.ascontiguousarray(want)
+    assert got.size > 0 and got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, got.dtype, want.shape, want.dtype)
+    np.testing.assert_array_equal(_bits(got), _bits(want), err_msg=what)
+
+
+def _same_output(out, name, form, want, row_bytes):
+    """form 0: the class created the output (pitched when it has more than one row); form 1: a sentinel-framed view, written in place,
+    no byte outside it changed"""
+    _same(out[name], want, name)
+    if form == 0:
+        step = int(out[name + ".step"][0, 0])
+        assert step == (row_bytes if want.shape[0] == 1 else -(-row_bytes // 256) * 256), (name, step)
+        return
+    assert out[name + ".inplace"].tolist() == [[1]], name
+    big = out[name + ".big"]
+    r, c = want.shape[:2]
+    assert big.shape[:2] == (r + 5, c + 7) and big.dtype == want.dtype
+    _same(big[2:2 + r, 3:3 + c], want, name + " through the larger matrix")
+    frame = big.view(np.uint8).reshape(big.shape[0], -1).copy()
+    es = row_bytes // c
+    frame[2:2 + r, 3 * es:(3 + c) * es] = SENTINEL
+    assert (frame == SENTINEL).all(), name + ": a byte outside the view changed"
+
+
+def test_classes_program_builds_and_fails_loudly_without_gpu(classes_exe, tmp_path):
+    """-Wall -Werror against the drop-in headers alone; where no device is present the program exits with status 3 and says why."""
+    import torch
+    assert os.access(classes_exe, os.X_OK)
+    if not torch.cuda.is_available():
+        r = subprocess.run([classes_exe, "sgm", str(tmp_path / "none.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True, timeout=120)
+        assert r.returncode == 3 and "no CPU fallback" in r.stderr, (r.returncode, r.stderr)
+
+
+def test_file_format_round_trip(tmp_path):
+    rng = np.random.default_rng(0)
+    arrays = {"a": rng.integers(0, 255, (3, 5)).astype(np.uint8), "pts": rng.random((1, 4, 2)).astype(np.float32),
+              "none": np.zeros((1, 0, 2), np.float32), "s": rng.integers(-9, 9, (2, 2)).astype(np.int16), "c3": np.zeros((2, 3, 3), np.uint8)}
+    _write(tmp_path / "f.bin", arrays)
+    back = _read(tmp_path / "f.bin")
+    assert list(back) == list(arrays)
+    for k, a in arrays.items():
+        assert back[k].shape == a.shape and back[k].dtype == a.dtype and back[k].tobytes() == a.tobytes()
+
+
+# ------------------------------------------------------------------ StereoSGM
+@pytest.mark.gpu
+def test_stereo_sgm_equals_the_oracle(gpu, oracle, classes_exe, tmp_path):
+    """13 x 15, the smallest frame tests/test_sgm.py computes on: createStereoSGM(0, 64) with its defaults, then through the setters a
+    non-zero minDisparity, MODE_HH and uniquenessRatio 0; 16-bit frames; outputs the class creates (26-byte rows pitched to 256) and
+    sentinel-framed views.  The setters store any value, like the reference's (stereosgm.cpp:38-72): numDisparities 96 is rejected by
+    compute(), and with 64 back the object computes the oracle's map again."""
+    left, right, _ = synth.stereo_pair(13, 15, seed=13, max_disp=10)
+    frames = {0: (left, right), 1: (left.astype(np.uint16) * 257, right.astype(np.uint16) * 257)}
+    # frame, minDisparity, numDisparities, P1, P2, uniquenessRatio, mode, form, how (1: factory defaults, 2: setters, 0: every argument)
+    cases = [(0, 0, 64, 10, 120, 5, 3, 0, 1), (0, 3, 64, 10, 120, 5, 3, 1, 2), (0, 3, 64, 10, 120, 5, 1, 0, 2), (0, 3, 64, 10, 120, 0, 1, 1, 2),
+             (1, 0, 64, 10, 120, 5, 3, 0, 1), (1, -8, 64, 10, 250, 0, 1, 1, 0), (0, -8, 64, 10, 250, 5, 3, 0, 0)]
+    arrays = {"cases": np.array(cases, np.int32)}
+    for k, (l, r) in frames.items():
+        arrays["l%d" % k], arrays["r%d" % k] = l, r
+    out = _run(classes_exe, "sgm", arrays, tmp_path)
+    refs = []
+    for i, (fr, md, nd, p1, p2, ur, mode, form, _) in enumerate(cases):
+        assert "out%d.exc" % i not in out
+        assert out["out%d.params" % i].tolist() == [[md, nd, p1, p2, ur, mode]]
+        refs.append(oracle.sgm_compute(*frames[fr], oracle.sgm_params(md, nd, p1, p2, ur, mode, 1)))
+        _same_output(out, "out%d" % i, form, refs[-1], 15 * 2)
+    assert any(len(np.unique(r)) > 2 for r in refs) and (refs[0] != refs[1]).any() and (refs[1] != refs[2]).any() and (refs[2] != refs[3]).any()
+    setter_threw, compute_threw, nd = out["reject"][0].tolist()
+    assert setter_threw == 0 and compute_threw != 0 and nd == 64
+    _same(out["again"], refs[-1], "after the rejected value")
+
+
+# ------------------------------------------------------------------ DisparityBilateralFilter
+@pytest.mark.gpu
+def test_disparity_bilateral_filter_equals_the_oracle(gpu, oracle, classes_exe, tmp_path):
+    """12 x 20 (tests/test_dbf.py's smallest refined frame) of its blocks case: a guide of 3 x 3 blocks, two surfaces with a jagged edge
+    and outliers, so that a 3 x 3 window already refines pixels.  CV_8UC1 and CV_16SC1 maps, CV_8UC1 and CV_8UC3 guides, radius 1 and
+    5, one and two iterations, the thresholds from the factory and through the setters; dst empty, a framed view, and the map itself."""
+    from test_dbf import _blocks_case
+    img, disp, _ = _blocks_case(12, 20, 5)
+    disps = [disp, disp.astype(np.int16) * 16]
+    imgs = [img, np.ascontiguousarray(np.stack([img, np.roll(img, 3, 1), np.roll(img, 3, 0)], -1))]
+    cases, i = [], 0
+    for dt in (0, 1):
+        for cn in (0, 1):
+            for radius, iters in ((1, 1), (5, 2)):
+                cases.append((dt, cn, 64 * (16 if dt else 1), radius, iters, i % 2, i % 3))
+                i += 1
+    assert {c[6] for c in cases} == {0, 1, 2} and {c[5] for c in cases} == {0, 1}
+    out = _run(classes_exe, "dbf", {"cases": np.array(cases, np.int32), "disp0": disps[0], "disp1": disps[1], "img0": imgs[0], "img1": imgs[1]},
+               tmp_path)
+    for i, (dt, cn, nd, radius, iters, setters, form) in enumerate(cases):
+        assert "out%d.exc" % i not in out
+        extra = dict(edge_threshold=0.05, max_disc_threshold=0.3, sigma_range=25.0) if setters else {}
+        ref = oracle.dbf_apply(disps[dt], imgs[cn], oracle.dbf_params(ndisp=nd, radius=radius, iters=iters, **extra))
+        assert (ref != disps[dt]).sum() >= 5
+        if form == 2:
+            _same(out["out%d" % i], ref, "in place, case %d" % i)
+            assert out["out%d.inplace" % i].tolist() == [[1]]
+        else:
+            _same_output(out, "out%d" % i, form, ref, 20 * ref.dtype.itemsize)
+
+
+# ------------------------------------------------------------------ DensePyrLKOpticalFlow
+@pytest.mark.gpu
+def test_dense_pyrlk_equals_the_oracle(gpu, oracle, classes_exe, tmp_path):
+    """Windows 13 and 21 (k_dense<13>, k_dense<21>) and 8 (the generic kernel), maxLevel 0 and 2, the odd 67 x 101 frame and 20 x 24.
+    useInitialFlow is stored and, as in the reference's dense path (pyrlk.cpp:238-299), not used: the call with it, into a view that
+    holds the sentinel, returns the oracle's flow."""
+    frames = [synth.flow_pair(67, 101, seed=21, dtype="u8")[:2], synth.flow_pair(20, 24, seed=24, dtype="u8")[:2]]
+    # frame, window width, window height, maxLevel, iters, useInitialFlow, form
+    cases = [(0, 13, 13, 2, 10, 0, 0), (0, 21, 21, 0, 10, 0, 1), (1, 8, 8, 2, 5, 0, 0), (1, 13, 13, 0, 10, 1, 1), (1, 21, 21, 2, 10, 0, 1)]
+    arrays = {"cases": np.array(cases, np.int32)}
+    for k, (a, b) in enumerate(frames):
+        arrays["a%d" % k], arrays["b%d" % k] = a, b
+    out = _run(classes_exe, "dense", arrays, tmp_path)
+    for i, (fr, wx, wy, levels, iters, _, form) in enumerate(cases):
+        assert "out%d.exc" % i not in out
+        ref = oracle.pyrlk_dense(*frames[fr], (wx, wy), levels, iters)
+        assert (ref != 0).any()
+        _same_output(out, "out%d" % i, form, ref, ref.shape[1] * 8)
+
+
+# ------------------------------------------------------------------ SparsePyrLKOpticalFlow
+def _points(n, cols, rows):
+    rng = np.random.default_rng(n)
+    if n == 1:
+        return np.array([[cols / 2 + 0.25, rows / 2 - 0.5]], np.float32)
+    return np.stack([rng.uniform(-2, cols + 2, n), rng.uniform(-2, rows + 2, n)], 1).astype(np.float32)
+
+
+@pytest.mark.gpu
+def test_sparse_pyrlk_equals_the_oracle(gpu, oracle, classes_exe, tmp_path):
+    """One object (window 9 x 9, 10 iterations) over 33 x 65 and 64 x 80 frames, N = 0, 1, 63, 64, 65 points, maxLevel 0 and 3, with
+    err, with the default noArray(), with useInitialFlow and a caller's nextPts.  The 1 x N outputs have one row, so GpuMat::create does
+    not pitch them (step = N elements); the framed views do have the larger matrix's step.  Compared by the rule of
+    tests/test_zzz_sparse_pyrlk_hip.py::_same: status and every next point, err where the track completed."""
+    from test_sparse_pyrlk import edge_frames
+    frames = [edge_frames(33, 65), synth.flow_pair(64, 80, seed=1, dtype="u8")[:2]]
+    pts = {n: _points(n, 65, 33) for n in (0, 1, 63, 64, 65)}
+    init = {n: (p + np.float32(0.75)).astype(np.float32) for n, p in pts.items()}
+    # frame, N, maxLevel, err requested, useInitialFlow (2: nextPts of the wrong size), form
+    cases = [(0, 0, 3, 1, 0, 0), (0, 0, 3, 0, 0, 0), (0, 1, 3, 1, 0, 0), (0, 63, 0, 1, 0, 1), (0, 64, 3, 0, 0, 0), (0, 65, 3, 1, 1, 1),
+             (1, 65, 0, 1, 0, 0), (1, 64, 3, 1, 1, 0), (1, 63, 3, 0, 0, 1), (1, 1, 0, 1, 1, 0), (1, 64, 3, 1, 2, 0), (0, 65, 3, 1, 0, 0)]
+    arrays = {"cases": np.array(cases, np.int32)}
+    for k, (a, b) in enumerate(frames):
+        arrays["a%d" % k], arrays["b%d" % k] = a, b
+    for n in pts:
+        arrays["pts%d" % n], arrays["init%d" % n] = pts[n][None], init[n][None]
+    out = _run(classes_exe, "sparse", arrays, tmp_path)
+
+    def check(name, case):
+        fr, n, level, want_err, use_init, form = case
+        rn, rs, re_ = oracle.pyrlk_sparse(*frames[fr], pts[n], (9, 9), level, 10, init[n] if use_init else None)
+        assert rs.sum() > 0
+        if form:
+            _same_output(out, name + ".status", 1, rs[None], n)
+            _same_output(out, name + ".next", 1, rn[None], n * 8)
+        else:
+            _same(out[name + ".status"], rs[None], name)
+            _same(out[name + ".next"], rn[None], name)
+            assert out[name + ".steps"].tolist() == [[n * 8, n, n * 4]]          # one row: not pitched
+        err = out[name + ".err"]
+        assert err.shape == (1, n) and err.dtype == np.float32
+        np.testing.assert_array_equal(_bits(err[0][rs > 0]), _bits(re_[rs > 0]))
+        if form:
+            assert out[name + ".err.inplace"].tolist() == [[1]]
+            frame = out[name + ".err.big"].view(np.uint8).reshape(6, -1).copy()
+            frame[2, 12:12 + 4 * n] = SENTINEL
+            assert (frame == SENTINEL).all()
+        if not want_err:
+            # the second call took the default noArray(): the caller's matrix keeps the first call's bytes
+            assert out[name + ".errkept"].tolist() == [[1]]
+            _same(out[name + ".err1"], err, name + ": err after the call without it")
+
+    seen_exc = 0
+    for i, case in enumerate(cases):
+        name = "out%d" % i
+        if case[1] == 0:
+            assert out[name + ".released"].tolist() == [[1, 1, case[3]]]       # without err the caller's matrix is not an argument
+        elif case[4] == 2:
+            assert out[name + ".exc"].tolist() == [[STS_ASSERT]]
+            seen_exc += 1
+        else:
+            assert name + ".exc" not in out
+            check(name, case)
+    assert seen_exc == 1
+    assert out["reject"][0, 0] != 0 and out["reject"][0, 1:].tolist() == [9, 9]
+    assert "again.exc" not in out
+    check("again", cases[-1])
+
+
+# ------------------------------------------------------------------ DescriptorMatcher
+def _desc(rng, n, d):
+    x = rng.standard_normal((n, d)).astype(np.float32)
+    return (x / np.linalg.norm(x, axis=1, keepdims=True)).astype(np.float32)
+
+
+def _lists(out, name):
+    """the DMatch lists the program wrote, as lists of (queryIdx, trainIdx, imgIdx, distance bits)"""
+    flat, lens = out[name].astype(np.int64) & 0xffffffff, out[name + ".len"][0]
+    assert flat.shape == (int(lens.sum()), 4)
+    ends = np.cumsum(lens)
+    return [[tuple(int(x) for x in m) for m in flat[e - n:e]] for e, n in zip(ends, lens)]
+
+
+def _u(x):
+    return int(x) & 0xffffffff
+
+
+def _knn_lists(r, k, compact):
+    idx, img, dist = (a[:, :k] for a in r)
+    db = _bits(dist)
+    rows = [[(q, _u(idx[q, j]), _u(img[q, j]), int(db[q, j])) for j in range(k) if idx[q, j] != -1] for q in range(idx.shape[0])]
+    return [row for row in rows if row or not compact]
+
+
+def _radius_lists(r, compact):
+    idx, img, dist, n = r
+    db, rows = _bits(dist), []
+    for q in range(idx.shape[0]):
+        m = min(int(n[q]), idx.shape[1])
+        rows.append([(q, _u(idx[q, j]), _u(img[q, j]), int(db[q, j])) for j in np.argsort(dist[q, :m], kind="stable")])
+    return [row for row in rows if row or not compact]
+
+
+def _i32(a):
+    return np.ascontiguousarray(a).view(np.int32)
+
+
+def _check_set(out, oracle, S, norm, q, t, split, mask, ks, radii, stats):
+    """Every form the program ran on one set against the oracle -> updates stats"""
+    nq, nt = q.shape[0], t.shape[0]
+    trains = [t[:split], t[split:]]
+    m0, m1 = mask[:, :split], mask[:, split:]
+    assert out[S + "coll"].tolist() == [[2, 0, 1, 1]] and out[S + "cleared"].tolist() == [[1]]
+    kmax = max(ks)
+    for tg, mk, c in [(0, 0, 0), (0, 1, 0), (0, 1, 1), (1, 0, 0), (1, 1, 0), (1, 1, 1), (1, 2, 0)]:
+        V = ".%d%d%d" % (tg, mk, c)
+        masks = [None, mask][mk] if tg == 0 else [None, [m0, m1], [None, m1]][mk]
+        rk = oracle.bf_knn_match(q, trains if tg else t, kmax, norm, masks)
+        if tg == 0:
+            assert (rk[1][rk[0] != -1] == 0).all()
+        if c == 0:
+            want = [row[0] for row in _knn_lists(rk, 1, False) if row]
+            for mode in "da":
+                got = out[S + "match." + mode + V]
+                assert got.shape == (len(want), 4) and [tuple(_u(x) for x in m) for m in got] == want, S + "match." + mode + V
+            raw = out[S + "match.raw" + V]
+            assert raw.shape == (3 if tg else 2, nq) and raw.dtype == np.int32                  # brute_force_matcher.cpp:367-372, 429-435
+            _same(raw[0], rk[0][:, 0]); _same(raw[-1], _i32(rk[2][:, 0]))
+            if tg:
+                _same(raw[1], rk[1][:, 0])
+            stats["compared"] += len(want)
+        for k in ks:
+            want = _knn_lists(rk, k, bool(c))
+            for mode in "da":
+                name = S + "knn%d.%s%s" % (k, mode, V)
+                if tg and mode == "a" and k != 2:
+                    assert out[name + ".exc"].tolist() == [[STS_NOT_IMPLEMENTED]]            # :664-667
+                    continue
+                assert name + ".exc" not in out, (name, out.get(name + ".exc"))
+                assert _lists(out, name) == want, name
+                stats["compared"] += sum(len(r) for r in want)
+            stats["lens"][(S, "knn%d" % k, tg, mk, c)] = len(want)
+            if c == 0 and (k == 2 or not tg):
+                raw = out[S + "knn%d.raw%s" % (k, V)]
+                if k == 2:                                                                   # :619-626 and the collection's three rows
+                    assert raw.shape == (3 if tg else 2, nq, 2) and raw.dtype == np.int32
+                    _same(raw[0], rk[0][:, :2]); _same(raw[-1], _i32(rk[2][:, :2]))
+                    if tg:
+                        _same(raw[1], rk[1][:, :2])
+                else:                                                                        # :630-636
+                    assert raw.shape == (2 * nq, k) and raw.dtype == np.int32
+                    _same(raw[:nq], rk[0][:, :k]); _same(raw[nq:], _i32(rk[2][:, :k]))
+        for j, radius in enumerate(radii):
+            cols = nq if tg else max(nt // 100, nq)
+            rr = oracle.bf_radius_match(q, trains if tg else t, float(radius), cols, norm, masks)
+            stats["over"] |= bool((rr[3] > cols).any())
+            stats["short"] |= bool((rr[3] < cols).any())
+            want = _radius_lists(rr, bool(c))
+            for mode in "da":
+                name = S + "rad%d.%s%s" % (j, mode, V)
+                assert name + ".exc" not in out, (name, out.get(name + ".exc"))
+                assert _lists(out, name) == want, name
+                stats["compared"] += sum(len(r) for r in want)
+            stats["lens"][(S, "rad%d" % j, tg, mk, c)] = len(want)
+            if c == 0:
+                raw = out[S + "rad%d.raw%s" % (j, V)]
+                if tg:                                                                       # :969-975
+                    assert raw.shape == (3 * nq + 1, nq) and raw.dtype == np.float32
+                else:                                                                        # :897-904
+                    assert raw.shape == (2 * nq + 1, cols) and raw.dtype == np.int32
+                raw = _i32(raw)
+                valid = np.arange(cols)[None, :] < np.minimum(rr[3], cols)[:, None]
+                np.testing.assert_array_equal(raw[-1, :nq], rr[3])
+                np.testing.assert_array_equal(raw[:nq][valid], rr[0][valid])
+                np.testing.assert_array_equal(raw[-1 - nq:-1][valid], _i32(rr[2])[valid])
+                if tg:
+                    np.testing.assert_array_equal(raw[nq:2 * nq][valid], rr[1][valid])
+                stats["compared"] += int(valid.sum())
+
+
+def _bf_arrays(S, q, t, split, mask, ks, radii):
+    return {S + "q": q, S + "t": t, S + "t0": t[:split], S + "t1": t[split:], S + "mask": mask, S + "m0": mask[:, :split],
+            S + "m1": mask[:, split:], S + "ks": np.array([ks], np.int32), S + "radii": np.array([radii], np.float32)}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("norm", [NORM_L1, NORM_L2])
+def test_float_matcher_equals_the_oracle(gpu, oracle, classes_exe, tmp_path, norm):
+    """d = 17 (TT 32) and 200 (TT 16), one descriptor length per row of kBfRows that stays cheap; 1 and 65 queries against 3 TT + 1
+    train rows, as one matrix and as a collection added as TT + 1 and 2 TT rows; match, knnMatch k = 1, 2, 3, 9 and radiusMatch,
+    directly and as *Async on a stream followed by *Convert, unmasked and masked (query 7 of the 65 is masked completely).  Radii: the
+    median nearest distance, and the median distance of list column nq + 1 (or the last): with 65 columns and 97 train rows some rows
+    overflow and some stay short, a single query overflows its one column."""
+    sets, arrays = [], {"norm": np.array([[norm]], np.int32)}
+    for d, tt in ((17, 32), (200, 16)):
+        for nq in (1, 65):
+            nt = 3 * tt + 1
+            rng = np.random.default_rng(d * 1000 + nq + norm)
+            q, t = _desc(rng, nq, d), _desc(rng, nt, d)
+            t[3] = t[1]
+            mask = (rng.random((nq, nt)) < 0.7).astype(np.uint8)
+            if nq > 7:
+                mask[7] = 0
+            full = oracle.bf_knn_match(q, t, nt, norm)[2]
+            radii = [float(np.median(full[:, 0])), float(np.median(full[:, min(nq + 1, nt - 1)]))]
+            S = "s%d." % len(sets)
+            sets.append((S, q, t, tt + 1, mask, [1, 2, 3, 9], radii))
+            arrays.update(_bf_arrays(*sets[-1]))
+    arrays["nsets"] = np.array([[len(sets)]], np.int32)
+    out = _run(classes_exe, "bf", arrays, tmp_path)
+    stats = {"compared": 0, "over": False, "short": False, "lens": {}}
+    over = short = False
+    for s in sets:
+        stats["over"] = stats["short"] = False
+        _check_set(out, oracle, s[0], norm, *s[1:], stats)
+        if s[1].shape == (65, 17):
+            assert stats["over"] and stats["short"]                       # both in the one set whose rows can do either
+        over, short = over or stats["over"], short or stats["short"]
+        if s[1].shape[0] == 65:
+            # compactResult drops the masked-out query: the lists differ in length
+            for form in ["knn%d" % k for k in s[5]] + ["rad0", "rad1"]:
+                for tg in (0, 1):
+                    assert stats["lens"][(s[0], form, tg, 1, 0)] == 65 and stats["lens"][(s[0], form, tg, 1, 1)] < 65, (form, tg)
+            assert all(stats["lens"][(s[0], "knn%d" % k, tg, 1, 1)] == 64 for k in s[5] for tg in (0, 1))
+    assert stats["compared"] > 10000 and over and short
+
+
+class _FromChild:
+    """The lists the C++ class returned, behind the matcher interface tests/test_bfmatch.py::_reference_case drives."""
+
+    def __init__(self, out, mode, mk, sent):
+        self.out, self.mode, self.mk, self.sent, self.added = out, mode, mk, sent, []
+
+    def add(self, descs):
+        self.added.extend(descs)
+
+    def _variant(self, query, train, mask, masks):
+        q, t, t0, t1, full, m = self.sent
+        assert np.array_equal(query, q)
+        if train is not None:
+            assert np.array_equal(train, t) and (mask is None) == (self.mk == 0) and (mask is None or np.array_equal(mask, full))
+        else:
+            assert len(self.added) == 2 and np.array_equal(self.added[0], t0) and np.array_equal(self.added[1], t1)
+            assert (masks is None) == (self.mk == 0) and (masks is None or all(np.array_equal(x, m) for x in masks))
+        return ".%s.%d%d0" % (self.mode, 0 if train is not None else 1, self.mk)
+
+    def match(self, query, train=None, mask=None, masks=None):
+        v = self._variant(query, train, mask, masks)
+        return [tuple(int(x) for x in m) for m in self.out["s0.match" + v]]
+
+    def knnMatch(self, query, train=None, k=2, mask=None, masks=None):
+        return _lists(self.out, "s0.knn%d" % k + self._variant(query, train, mask, masks))
+
+    def radiusMatch(self, query, train=None, maxDistance=0.0, mask=None, masks=None):
+        return _lists(self.out, "s0.rad%d" % [0.25, 0.75].index(maxDistance) + self._variant(query, train, mask, masks))
+
+
+@pytest.mark.gpu
+def test_float_matcher_passes_the_reference_known_answer_test(gpu, classes_exe, tmp_path):
+    """The generator and every expectation of the reference's BruteForceMatcher test (test_bfmatch.py::_reference_data /
+    _reference_case, restated there from cudafeatures2d/test/test_features2d.cpp:274-751) at dimension 57, NORM_L2, with and without
+    masks, on the lists the C++ class returns, directly and through *Async / *Convert."""
+    QC, CF, seed = 300, 4, 57 * 4 + NORM_L2
+    query, train = _reference_data(57, seed, QC, CF)
+    half = train.shape[0] // 2
+    mk = np.ones((QC, half), np.uint8)
+    mk[:, np.arange(QC // 2) * CF] = 0
+    full = np.ones((QC, train.shape[0]), np.uint8)
+    arrays = {"norm": np.array([[NORM_L2]], np.int32), "nsets": np.array([[1]], np.int32)}
+    arrays.update(_bf_arrays("s0.", query, train, half, full, [2, 3], [1.0 / CF, 3.0 / CF]))
+    arrays["s0.m0"] = arrays["s0.m1"] = mk
+    out = _run(classes_exe, "bf", arrays, tmp_path)
+    sent = (query, train, train[:half], train[half:], full, mk)
+    assert out["s0.match.d.000"].shape == (QC, 4) and out["s0.match.d.110"].shape == (QC, 4)
+    for mode in "da":
+        for use_mask in (False, True):
+            if mode == "a":
+                # over a collection only k = 2 has an *Async form (brute_force_matcher.cpp:664-667): k = 3 is checked directly
+                assert out["s0.knn3.a.1%d0.exc" % use_mask].tolist() == [[STS_NOT_IMPLEMENTED]]
+                out = dict(out, **{"s0.knn3.a.1%d0%s" % (use_mask, x): out["s0.knn3.d.1%d0%s" % (use_mask, x)] for x in ("", ".len")})
+            _reference_case(lambda: _FromChild(out, mode, int(use_mask), sent), 57, use_mask, seed)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dt,norm", [("uint8", NORM_HAMMING), ("int32", NORM_L1)])
+def test_integer_matcher_equals_the_oracle(gpu, oracle, classes_exe, tmp_path, dt, norm):
+    """CV_8UC1 with NORM_HAMMING at ORB's 32 bytes and CV_32SC1 with NORM_L1: match, knnMatch k = 2 and 5, radiusMatch, on a train
+    matrix and on a collection, masked and not; exact integer distances, identical lists.  Hamming on CV_32F, k = 17 and knnMatchAsync
+    over a collection with k = 3 give the cv::Exception."""
+    rng = np.random.default_rng(9 + norm)
+    nq, nt, d = 65, 97, 32
+    lo, hi = (0, 256) if dt == "uint8" else (-1000, 1000)
+    q, t = rng.integers(lo, hi, (nq, d)).astype(dt), rng.integers(lo, hi, (nt, d)).astype(dt)
+    t[3] = t[1]
+    mask = (rng.random((nq, nt)) < 0.7).astype(np.uint8)
+    mask[7] = 0
+    full = oracle.bf_knn_match(q, t, 16, norm)[2]
+    radii = [float(np.median(full[:, 0])), float(np.median(full[:, 15])) + 1]
+    arrays = {"norm": np.array([[norm]], np.int32), "nsets": np.array([[1]], np.int32), "xq": _desc(rng, 4, 32), "xt": _desc(rng, 6, 32)}
+    arrays.update(_bf_arrays("s0.", q, t, 33, mask, [2, 5], radii))
+    out = _run(classes_exe, "bf", arrays, tmp_path)
+    stats = {"compared": 0, "over": False, "short": False, "lens": {}}
+    _check_set(out, oracle, "s0.", norm, q, t, 33, mask, [2, 5], radii, stats)
+    assert stats["compared"] > 5000 and stats["lens"][("s0.", "knn5", 1, 1, 1)] == 64
+    for name in ("x.hamming_f32", "x.k17", "x.coll_async_k3"):
+        assert name not in out and out[name + ".exc"].shape == (1, 1) and out[name + ".exc"][0, 0] < 0, name
+    assert out["x.coll_async_k3.exc"].tolist() == [[STS_NOT_IMPLEMENTED]]
+
+
+# ------------------------------------------------------------------ the float matcher's output strides, at the C-ABI
+@pytest.mark.gpu
+@pytest.mark.parametrize("norm", [NORM_L1, NORM_L2])
+def test_float_matcher_outputs_with_three_different_strides(gpu, oracle, norm):
+    """A C++ caller's packed matrix gives trainIdx, imgIdx and distance one common step, and the Python mirror allocates them dense, so
+    neither tells a kernel that writes one block with another block's step.  Here mi_bf_knn_match and mi_bf_radius_match write into
+    column slices of three sentinel-filled tensors of different widths (k + 5, k + 6 and k + 8 elements): k = 2 (one k_merge pass), 9
+    (a continuation pass at column 8) and 1, over a two-image collection (k_assign_image) with one mask absent; a radius match whose
+    rows overflow and stay short (k_radius).  Results equal the oracle's and every element outside the slices keeps its sentinel."""
+    import ctypes as C
+    import torch
+    from opencv_contrib_amd import capi, cuda
+    _m, mats = capi.mat_from_tensor, cuda.BFMatcher._mats
+    rng = np.random.default_rng(17 + norm)
+    nq, d, tt = 65, 17, 32
+    q, trains = _desc(rng, nq, d), [_desc(rng, tt + 1, d), _desc(rng, 2 * tt, d)]
+    masks = [None, (rng.random((nq, 2 * tt)) < 0.7).astype(np.uint8)]
+    T = lambda a: None if a is None else torch.from_numpy(a).to(gpu)
+    tq, tv, mv = T(q), [T(t) for t in trains], [T(x) for x in masks]
+    m = cuda.createBFMatcher(norm)
+
+    def framed(rows, cols, dtype, left, right, value):
+        w = torch.full((rows, left + cols + right), value, dtype=dtype, device=gpu)
+        return w, w[:, left:left + cols]
+
+    def intact(w, left, cols, value):
+        g = w.cpu().numpy()
+        assert (g[:, :left] == value).all() and (g[:, left + cols:] == value).all()
+
+    for k in (1, 2, 9):
+        r = oracle.bf_knn_match(q, trains, k, norm, masks)
+        (wi, vi), (wm, vm), (wd, vd) = framed(nq, k, torch.int32, 2, 3, -77), framed(nq, k, torch.int32, 1, 5, -77), framed(nq, k, torch.float32, 4, 4, -77.0)
+        assert len({vi.stride(0), vm.stride(0), vd.stride(0)}) == 3
+        capi.check(capi.lib().mi_bf_knn_match(m._h, C.byref(_m(tq)), mats(tv), mats(mv), 2, k, C.byref(_m(vi)), C.byref(_m(vm)), C.byref(_m(vd)),
+                                              capi.current_stream_ptr()))
+        _same(vi.cpu().numpy(), r[0]); _same(vm.cpu().numpy(), r[1]); _same(vd.cpu().numpy(), r[2])
+        intact(wi, 2, k, -77); intact(wm, 1, k, -77); intact(wd, 4, k, -77.0)
+    full = oracle.bf_knn_match(q, trains, 3 * tt + 1, norm, masks)[2]
+    radius, cols = float(np.median(full[:, 12])), 12
+    rr = oracle.bf_radius_match(q, trains, radius, cols, norm, masks)
+    assert (rr[3] > cols).any() and (rr[3] < cols).any()
+    (wi, vi), (wm, vm), (wd, vd) = framed(nq, cols, torch.int32, 3, 2, -1), framed(nq, cols, torch.int32, 5, 1, -1), framed(nq, cols, torch.float32, 1, 7, 0.0)
+    wn, vn = framed(1, nq, torch.int32, 3, 3, -77)
+    assert len({vi.stride(0), vm.stride(0), vd.stride(0)}) == 3
+    capi.check(capi.lib().mi_bf_radius_match(m._h, C.byref(_m(tq)), mats(tv), mats(mv), 2, radius, C.byref(_m(vi)), C.byref(_m(vm)), C.byref(_m(vd)),
+                                             C.byref(_m(vn)), capi.current_stream_ptr()))
+    _same(vn.cpu().numpy()[0], rr[3]); _same(vi.cpu().numpy(), rr[0]); _same(vm.cpu().numpy(), rr[1]); _same(vd.cpu().numpy(), rr[2])
+    intact(wi, 3, cols, -1); intact(wm, 5, cols, -1); intact(wd, 1, cols, 0.0); intact(wn, 3, nq, -77)
