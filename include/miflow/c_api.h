@@ -412,7 +412,8 @@ MI_API void mi_surf_destroy(mi_surf *h);
  * clamp_to_one applies cuda::min(mask, 1.0) first (surf.cuda.cpp:167). */
 MI_API int mi_surf_integral(mi_surf *h, const mi_mat *img, int clamp_to_one, mi_mat *sum, void *stream);
 /* Replaces: icvCalcLayerDetAndTrace_gpu, xfeatures2d/src/cuda/surf.cu:205-222; det/trace: MI_32FC1,
- * ((n_octave_layers+2) * (rows >> octave)) x cols, same step */
+ * ((n_octave_layers+2) * (rows >> octave)) x cols, same step.  An image too small for this octave by the class's own limits
+ * (surf.cuda.cpp:144-151 with nOctaves = octave + 1) is MI_ERR_BAD_SIZE, as it is for detection. */
 MI_API int mi_surf_det_trace(mi_surf *h, const mi_mat *sum, int octave, int n_octave_layers, mi_mat *det, mi_mat *trace, void *stream);
 
 /* ======================================================== sparse PyrLK ===== */

@@ -230,6 +230,7 @@ def lib():
         "mi_surf_integral": (i, [vp, PM, i, PM, vp]),
         "mi_surf_det_trace": (i, [vp, PM, i, i, PM, PM, vp]),
         "miflow_selftest_wave_scan": (i, [C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
+        "miflow_selftest_surf_libm": (i, [vp, vp, i, vp, vp, vp]),
         "mi_densepyrlk_default_params": (None, [C.POINTER(DensePyrLKParams)]),
         "mi_densepyrlk_create": (i, [C.POINTER(DensePyrLKParams), C.POINTER(vp)]),
         "mi_densepyrlk_set_params": (i, [vp, C.POINTER(DensePyrLKParams)]),

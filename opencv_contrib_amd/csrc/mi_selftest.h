@@ -14,6 +14,9 @@ MI_API int miflow_selftest_wave_min(const unsigned *in_host, unsigned *out_host 
 MI_API int miflow_selftest_tmax16(const unsigned *in_host /*[1024]*/, unsigned *out_host /*[64]*/);
 /* out_host[i] = inclusive prefix sum of in_host[0..i] over the 64 lanes (DPP scan of the SURF integral) */
 MI_API int miflow_selftest_wave_scan(const unsigned *in_host, unsigned *out_host /*[64]*/);
+/* the three libm calls of the SURF orientation and descriptor kernels on n <= 2^22 host values: atan2_host[i] = atan2f(a_host[i],
+ * b_host[i]) as k_orientation compiles it, (sin_host[i], cos_host[i]) = sincos_rounded(a_host[i]) (csrc/surf_kernels.hip) */
+MI_API int miflow_selftest_surf_libm(const float *a_host, const float *b_host, int n, float *atan2_host, float *sin_host, float *cos_host);
 /* out_host[0..63] = value received from lane n-1, out_host[64..127] = from lane n+1 when every lane n contributes n+100
  * (DPP wave shifts of the blocked TV-L1 kernels) */
 MI_API int miflow_selftest_lane_shift(int *out_host /*[128]*/);

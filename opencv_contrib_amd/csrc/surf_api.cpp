@@ -376,6 +376,10 @@ int mi_surf_det_trace(mi_surf *h, const mi_mat *sum, int octave, int n_octave_la
     MI_REQUIRE(sum && sum->data && sum->type == MI_32SC1 && sum->step % 4 == 0 && sum->rows > 1 && sum->cols > 1, MI_ERR_BAD_ARG, "bad sum");
     const int rows = sum->rows - 1, cols = sum->cols - 1, lr = rows >> octave;
     MI_REQUIRE(octave >= 0 && octave < 16 && n_octave_layers > 0 && lr > 0, MI_ERR_BAD_ARG, "bad octave / layers");
+    // the class's limits for this octave being its last (surf.cuda.cpp:144-151)
+    const int min_size = calc_size(octave, 0), min_margin = ((calc_size(octave, 2) >> 1) >> octave) + 1;
+    MI_REQUIRE(rows - min_size >= 0 && cols - min_size >= 0 && lr - 2 * min_margin > 0 && (cols >> octave) - 2 * min_margin > 0, MI_ERR_BAD_SIZE,
+               "image too small for this octave");
     MI_REQUIRE(det && trace && det->data && trace->data && det->type == MI_32FC1 && trace->type == MI_32FC1 &&
                det->rows == (n_octave_layers + 2) * lr && trace->rows == det->rows && det->cols == cols && trace->cols == cols &&
                det->step == trace->step && det->step % 4 == 0, MI_ERR_BAD_ARG, "det/trace must be CV_32FC1 ((layers+2)*layer_rows) x cols, same step");
@@ -393,6 +397,24 @@ int miflow_selftest_wave_scan(const unsigned *in_host, unsigned *out_host)
     int rc = surf::dbg_scan(d, d + 64, nullptr);
     if (!rc) { MI_HIP_TRY(hipDeviceSynchronize()); MI_HIP_TRY(hipMemcpy(out_host, d + 64, sizeof(unsigned) * 64, hipMemcpyDeviceToHost)); }
     return rc;
+}
+
+int miflow_selftest_surf_libm(const float *a_host, const float *b_host, int n, float *atan2_host, float *sin_host, float *cos_host)
+{
+    MI_REQUIRE(a_host && b_host && atan2_host && sin_host && cos_host, MI_ERR_BAD_ARG, "null argument");
+    MI_REQUIRE(n > 0 && n <= (1 << 22), MI_ERR_BAD_ARG, "n must be in 1 .. 2^22");
+    float *d = nullptr;
+    DevTmp tmp;
+    const size_t N = (size_t)n;
+    MI_TRY(tmp.alloc(&d, 5 * N));
+    MI_HIP_TRY(hipMemcpy(d, a_host, sizeof(float) * N, hipMemcpyHostToDevice));
+    MI_HIP_TRY(hipMemcpy(d + N, b_host, sizeof(float) * N, hipMemcpyHostToDevice));
+    MI_TRY(surf::dbg_libm(d, d + N, n, d + 2 * N, d + 3 * N, d + 4 * N, nullptr));
+    MI_HIP_TRY(hipDeviceSynchronize());
+    MI_HIP_TRY(hipMemcpy(atan2_host, d + 2 * N, sizeof(float) * N, hipMemcpyDeviceToHost));
+    MI_HIP_TRY(hipMemcpy(sin_host, d + 3 * N, sizeof(float) * N, hipMemcpyDeviceToHost));
+    MI_HIP_TRY(hipMemcpy(cos_host, d + 4 * N, sizeof(float) * N, hipMemcpyDeviceToHost));
+    return MI_OK;
 }
 
 }  // extern "C"

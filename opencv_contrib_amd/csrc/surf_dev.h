@@ -45,6 +45,7 @@ int orientation(const unsigned *sum, int sld, int rows, int cols, float *kp, int
 int descriptors(const unsigned char *img, long long istep, int rows, int cols, const float *kp, int kld, int nfeat, bool extended,
                 float *desc, long long dstep_floats, const float *dw /* [400] */, hipStream_t s, const unsigned *nfeat_dev = nullptr);
 int dbg_scan(const unsigned *in_dev, unsigned *out_dev, hipStream_t s);
+int dbg_libm(const float *a_dev, const float *b_dev, int n, float *atan2_dev, float *sin_dev, float *cos_dev, hipStream_t s);
 
 }  // namespace surf
 }  // namespace mi

@@ -872,6 +872,15 @@ __device__ __noinline__ float2 sincos_rounded(float x)
     const double a = (n & 1) ? C : S, b = (n & 1) ? S : C;
     return make_float2((float)((n & 2) ? -a : a), (float)((n == 1 || n == 2) ? -b : b));
 }
+// test hook (mi_selftest.h): the three libm calls of this file on n values -- atan2f as k_orientation calls it, sincos_rounded
+__global__ __launch_bounds__(256) void k_dbg_libm(const float *a, const float *b, int n, float *at, float *sn, float *cs)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    at[i] = atan2f(a[i], b[i]);
+    const float2 sc = sincos_rounded(a[i]);
+    sn[i] = sc.x; cs[i] = sc.y;
+}
 // window geometry of feature f (surf.cu:733-760)
 __device__ __forceinline__ float desc_window(Win &w, const unsigned char *img, long long istep, int rows, int cols, const float *kp, int kld, int f)
 {
@@ -1721,6 +1730,13 @@ int descriptors(const unsigned char *img, long long istep, int rows, int cols, c
 int dbg_scan(const unsigned *in_dev, unsigned *out_dev, hipStream_t s)
 {
     hipLaunchKernelGGL(k_dbg_scan, dim3(1), dim3(64), 0, s, in_dev, out_dev);
+    MI_HIP_TRY(hipGetLastError());
+    return MI_OK;
+}
+
+int dbg_libm(const float *a_dev, const float *b_dev, int n, float *atan2_dev, float *sin_dev, float *cos_dev, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_dbg_libm, dim3((n + 255) / 256), dim3(256), 0, s, a_dev, b_dev, n, atan2_dev, sin_dev, cos_dev);
     MI_HIP_TRY(hipGetLastError());
     return MI_OK;
 }

@@ -124,6 +124,11 @@ def _bind_surf(L):
     L.orc_surf_descriptor.argtypes = [_u8p, i, i, f, f, f, f, i, _f32p, _f32p]
     L.orc_surf_detect_describe.restype = i
     L.orc_surf_detect_describe.argtypes = [C.POINTER(SURFParams), _u8p, C.c_void_p, i, i, _f32p, i, C.c_void_p, i]
+    L.orc_surf_descriptors_rounded.restype = None
+    L.orc_surf_descriptors_rounded.argtypes = [_u8p, i, i, i, _f32p, _f32p, _f32p, _f32p, i, _f32p, _f32p, i32p, _f32p]
+    L.orc_surf_orientation_candidates_n.restype = None
+    L.orc_surf_orientation_candidates_n.argtypes = [u32p, i, i, i, _f32p, _f32p, _f32p, i32p, _f32p, _f32p, _f32p, C.c_double, _f32p, i32p,
+                                                    i32p, C.c_void_p]
 
 
 def _bind_farneback(L):
@@ -518,6 +523,10 @@ def surf_det_trace(sum_, octave, n_octave_layers=2):
     sum_ = np.ascontiguousarray(sum_, np.uint32)
     rows, cols = sum_.shape[0] - 1, sum_.shape[1] - 1
     lr = rows >> octave
+    # the class's limits for this octave being its last (surf.cuda.cpp:144-151)
+    min_size, min_margin = 9 << octave, (((21 << octave) >> 1) >> octave) + 1
+    if rows < min_size or cols < min_size or lr - 2 * min_margin <= 0 or (cols >> octave) - 2 * min_margin <= 0:
+        raise ValueError("image too small for this octave")
     det = np.empty(((n_octave_layers + 2) * lr, cols), np.float32)
     tr = np.empty_like(det)
     lib().orc_surf_det_trace(sum_, rows, cols, octave, n_octave_layers, det, tr)
@@ -583,14 +592,49 @@ def surf_orientation(img, x, y, size, angle_in):
     return out
 
 
-def surf_descriptors(img, x, y, size, angle, extended):
-    """compute_descriptors (surf.cu:733-912) of provided keypoints -> (n, 64 | 128) float32."""
+SURF_DELTA_DEG = 2.0 ** -13      # see surf_orientation_candidates
+SURF_MAX_UNDECIDED = 3
+
+
+def surf_orientation_candidates(img, x, y, size, delta_deg=SURF_DELTA_DEG, want_yx=True):
+    """compute_orientation with every atan2 in long double, rounded once (orc_surf_orientation_candidates, surf_ref.c): per keypoint the
+    directions an atan2f of bounded error may lead to.  A sample is undecided when its angle in degrees lies closer than delta_deg to a
+    half-integer -- 2^-13 covers an atan2f up to 2 ulp off the correctly rounded value: 2 ulp of a value in [4, 8) are 1.8 * 2^-15
+    degrees, the + 2 pi adds half an ulp = 0.46 * 2^-15, the degree multiply 0.5 * 2^-15, in all 2.8 * 2^-15 < 4 * 2^-15.  The window
+    search runs for both roundings of every undecided sample (at most 3 of them).
+    -> dict: status (n,) as surf_orientation_samples (-1 early return, 0 all samples outside, else the samples inside);
+             undecided (n,); n_candidates (n,): 0 where status == -1 or undecided > 3; candidates (n, 8) float32, [k, 0] the direction
+             with no rounding flipped, NaN beyond n_candidates[k]; yx (n, 113, 2): the (Y, X) handed to each sample's atan2."""
     img = _u8(img)
     rows, cols = img.shape
-    x, y, size, angle = (np.atleast_1d(np.asarray(v, np.float32)) for v in (x, y, size, angle))
+    x, y, size = (np.ascontiguousarray(np.atleast_1d(np.asarray(v, np.float32))) for v in (x, y, size))
+    n = len(x)
+    status = surf_orientation_samples(rows, cols, x, y, size)
+    ax, ay, aw, _ = surf_tables()
+    cand = np.full((n, 8), np.nan, np.float32)
+    ncand, und = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    yx = np.zeros((n, 113, 2), np.float32) if want_yx else None
+    lib().orc_surf_orientation_candidates_n(surf_integral(img), rows, cols, n, x, y, size, status, ax, ay, aw, float(delta_deg), cand.reshape(-1),
+                                            ncand, und, yx.ctypes.data if want_yx else None)
+    return {"status": status, "undecided": und, "n_candidates": ncand, "candidates": cand, "yx": yx}
+
+
+def surf_descriptors(img, x, y, size, angle, extended, rounded=False):
+    """compute_descriptors (surf.cu:733-912) of provided keypoints -> (n, 64 | 128) float32.
+    rounded=True: the sine and cosine of the direction from sinl / cosl rounded once instead of the host's sinf / cosf
+    -> (descriptors, hard (n,) bool, alternatives {k: (1 | 3, dsz)}): a feature is `hard` when a long-double value lies within 2^-16 of
+    a float ulp of a rounding boundary, where a double-precision evaluation may round the other way; its alternatives are the
+    descriptors under the neighbouring roundings."""
+    img = _u8(img)
+    rows, cols = img.shape
+    x, y, size, angle = (np.ascontiguousarray(np.atleast_1d(np.asarray(v, np.float32))) for v in (x, y, size, angle))
     dw = surf_tables()[3]
     out = np.empty((len(x), 128 if extended else 64), np.float32)
     L = lib()
+    if rounded:
+        nalt, alt = np.zeros(len(x), np.int32), np.zeros((len(x), 3, out.shape[1]), np.float32)
+        L.orc_surf_descriptors_rounded(img, rows, cols, len(x), x, y, size, angle, int(bool(extended)), dw, out.reshape(-1), nalt, alt.reshape(-1))
+        return out, nalt > 0, {int(k): alt[k, :nalt[k]].copy() for k in np.flatnonzero(nalt)}
     for k in range(len(x)):
         L.orc_surf_descriptor(img, rows, cols, x[k], y[k], size[k], angle[k], int(bool(extended)), dw, out[k])
     return out

@@ -365,8 +365,17 @@ static float area_filter(const Win *w, float x, float y, float s)
 }
 
 /* surf.cu:733-912: one descriptor (64 or 128 floats), normalised */
-void orc_surf_descriptor(const uint8_t *img, int rows, int cols, float fx, float fy, float fsize, float fdir, int extended,
-                         const float *dw, float *desc)
+static float desc_ddir(float fdir)
+{
+    float ddir = 360.0f - fdir;
+    if (fabsf(ddir - 360.f) < FLT_EPSILON) ddir = 0.f;
+    ddir *= CV_PI_F / 180.0f;
+    return ddir;
+}
+
+/* the descriptor of a window whose direction has the sine `sn` and the cosine `cs` */
+static void descriptor_sc(const uint8_t *img, int rows, int cols, float fx, float fy, float fsize, float sn, float cs, int extended,
+                          const float *dw, float *desc)
 {
     Win w;
     w.img = img; w.rows = rows; w.cols = cols; w.cx = fx; w.cy = fy;
@@ -374,10 +383,7 @@ void orc_surf_descriptor(const uint8_t *img, int rows, int cols, float fx, float
     const int win_size = (int)((PATCH_SZ + 1) * s);
     w.win = win_size;
     w.off = -(win_size - 1.0f) / 2.0f;
-    float ddir = 360.0f - fdir;
-    if (fabsf(ddir - 360.f) < FLT_EPSILON) ddir = 0.f;
-    ddir *= CV_PI_F / 180.0f;
-    w.s = sinf(ddir); w.c = cosf(ddir);
+    w.s = sn; w.c = cs;
     float P[PATCH_SZ + 1][PATCH_SZ + 1];
     for (int yl = 0; yl <= PATCH_SZ; ++yl)
         for (int xl = 0; xl <= PATCH_SZ; ++xl)
@@ -427,6 +433,173 @@ void orc_surf_descriptor(const uint8_t *img, int rows, int cols, float fx, float
         for (int i = 0; i < off; ++i) part[i] = part[i] + part[i + off];
     const float len = sqrtf(part[0]);
     for (int k = 0; k < dsz; ++k) desc[k] = desc[k] / len;
+}
+
+void orc_surf_descriptor(const uint8_t *img, int rows, int cols, float fx, float fy, float fsize, float fdir, int extended,
+                         const float *dw, float *desc)
+{
+    const float ddir = desc_ddir(fdir);
+    descriptor_sc(img, rows, cols, fx, fy, fsize, sinf(ddir), cosf(ddir), extended, dw, desc);
+}
+
+/* ---- libm-exact modes: what the HIP kernels are held to feature by feature (tests/surf_check.py).  The kernels and the restatement
+ * above perform the same binary32 operations in the same order but for three libm calls: atan2f in the orientation (113 samples and
+ * the final direction) and the sine / cosine of the descriptor's direction.  Here these three are evaluated in long double and rounded
+ * once, and where a libm within its stated error may legitimately decide otherwise, every admissible decision is enumerated. */
+
+/* v rounded to float; *other = the float on the other side of v, *hard = 1 when v lies within 2^-16 of a float ulp of the midpoint of
+ * the two (a double-precision evaluation may round either way there) */
+static float round_once(long double v, float *other, int *hard)
+{
+    const float f = (float)v;
+    const float o = nextafterf(f, v >= (long double)f ? INFINITY : -INFINITY);
+    const long double mid = ((long double)f + (long double)o) / 2, ulp = fabsl((long double)o - (long double)f);
+    *other = o;
+    *hard = fabsl(v - mid) < ulp / 65536;
+    return f;
+}
+
+/* compute_descriptors with the sine and cosine of the direction correctly rounded (sinl / cosl rounded once).  desc: dsz floats;
+ * returns the number of alternatives (0 unless a value is `hard`: then 1 or 3 -- the other rounding of the sine, of the cosine, of both)
+ * written to alt[k * dsz]. */
+int orc_surf_descriptor_rounded(const uint8_t *img, int rows, int cols, float fx, float fy, float fsize, float fdir, int extended,
+                                const float *dw, float *desc, float *alt)
+{
+    const float ddir = desc_ddir(fdir);
+    const int dsz = extended ? 128 : 64;
+    float so, co;
+    int sh, ch, n = 0;
+    const float sn = round_once(sinl((long double)ddir), &so, &sh), cs = round_once(cosl((long double)ddir), &co, &ch);
+    descriptor_sc(img, rows, cols, fx, fy, fsize, sn, cs, extended, dw, desc);
+    if (sh) descriptor_sc(img, rows, cols, fx, fy, fsize, so, cs, extended, dw, alt + dsz * n++);
+    if (ch) descriptor_sc(img, rows, cols, fx, fy, fsize, sn, co, extended, dw, alt + dsz * n++);
+    if (sh && ch) descriptor_sc(img, rows, cols, fx, fy, fsize, so, co, extended, dw, alt + dsz * n++);
+    return n;
+}
+
+/* n descriptors at once: desc n x dsz, nalt[n], alt n x 3 x dsz */
+void orc_surf_descriptors_rounded(const uint8_t *img, int rows, int cols, int n, const float *x, const float *y, const float *size,
+                                  const float *dir, int extended, const float *dw, float *desc, int *nalt, float *alt)
+{
+    const int dsz = extended ? 128 : 64;
+#pragma omp parallel for schedule(dynamic, 8)
+    for (int i = 0; i < n; ++i)
+        nalt[i] = orc_surf_descriptor_rounded(img, rows, cols, x[i], y[i], size[i], dir[i], extended, dw, desc + (size_t)i * dsz,
+                                              alt + (size_t)i * 3 * dsz);
+}
+
+/* the kernel's float tail after an atan2 (surf.cu:565-567, 651-657) */
+static inline float to_degrees(float a)
+{
+    if (a < 0) a += 2.0f * CV_PI_F;
+    return a * (180.0f / CV_PI_F);
+}
+
+/* the window search of compute_orientation (surf.cu:577-650) over the rounded sample angles a[128] -> the winning sums */
+static void best_window(const float *sX, const float *sY, const int *a, float *rx, float *ry)
+{
+    float bx[4], by[4], bm[4];
+    for (int ty = 0; ty < 4; ++ty) {
+        float bestx = 0, besty = 0, best_mod = 0;
+        for (int i = 0; i < 18; ++i) {
+            const int dir = (i * 4 + ty) * 5;
+            float vx[32], vy[32];
+            for (int tx = 0; tx < 32; ++tx) {
+                float sumx = 0.f, sumy = 0.f;
+                for (int q = 0; q < 4; ++q) {
+                    const int d = abs(a[tx + 32 * q] - dir);
+                    if (d < 30 || d > 330) {
+                        if (q == 0) { sumx = sX[tx]; sumy = sY[tx]; }
+                        else { sumx += sX[tx + 32 * q]; sumy += sY[tx + 32 * q]; }
+                    }
+                }
+                vx[tx] = sumx; vy[tx] = sumy;
+            }
+            const float sumx = reduce32(vx), sumy = reduce32(vy);
+            const float temp_mod = sumx * sumx + sumy * sumy;
+            if (temp_mod > best_mod) { best_mod = temp_mod; bestx = sumx; besty = sumy; }
+        }
+        bx[ty] = bestx; by[ty] = besty; bm[ty] = best_mod;
+    }
+    int bestIdx = 0;
+    if (bm[1] > bm[bestIdx]) bestIdx = 1;
+    if (bm[2] > bm[bestIdx]) bestIdx = 2;
+    if (bm[3] > bm[bestIdx]) bestIdx = 3;
+    *rx = bx[bestIdx]; *ry = by[bestIdx];
+}
+
+/* compute_orientation as orc_surf_orientation, with every atan2 evaluated in long double and rounded once to float, the rest of the
+ * degree conversion in the kernel's float operations.  A sample is UNDECIDED when its angle in degrees, in long double (the same
+ * conversion, unrounded), lies closer than delta_deg to a half-integer: an atan2f within its error bound may round such an angle to
+ * either integer, and only that integer enters the window search.  The search runs once per combination of the two roundings of the
+ * undecided samples (at most ORC_SURF_MAX_UNDECIDED = 3 of them: 8 runs); cand[0] is the direction with no rounding flipped, the
+ * others the distinct directions any flip leads to.  Returns the number of candidates; 0 and *undecided > 3 when there are too many
+ * undecided samples.  yx (or NULL): the 113 (Y, X) pairs handed to atan2, (0, 0) for a sample outside the image.  The early return
+ * (grad_wav_size beyond the image) is the caller's to test, as for orc_surf_orientation. */
+int orc_surf_orientation_candidates(const uint32_t *sum, int rows, int cols, float fx, float fy, float fsize, const float *aptx,
+                                    const float *apty, const float *aptw, double delta_deg, float cand[8], int *undecided, float *yx)
+{
+    const SumTex t = {sum, rows, cols};
+    const float s = fsize * 1.2f / 9.0f;
+    const int grad_wav_size = 2 * rn(2.0f * s);
+    float sX[128], sY[128];
+    int a0[128], a[128], und[ORI_SAMPLES], other[ORI_SAMPLES], nund = 0;
+    for (int tid = 0; tid < 128; ++tid) {
+        float X = 0.f, Y = 0.f;
+        a0[tid] = 0;
+        if (tid < ORI_SAMPLES) {
+            const float margin = (float)(grad_wav_size - 1) / 2.0f;
+            const int x = rn(fx + aptx[tid] * s - margin), y = rn(fy + apty[tid] * s - margin);
+            if (y >= 0 && y < (rows + 1) - grad_wav_size && x >= 0 && x < (cols + 1) - grad_wav_size) {
+                X = aptw[tid] * haar(&t, c_NX, 2, 4, grad_wav_size, y, x);
+                Y = aptw[tid] * haar(&t, c_NY, 2, 4, grad_wav_size, y, x);
+                const long double al = atan2l((long double)Y, (long double)X);
+                const float af = (float)al;
+                a0[tid] = rn(to_degrees(af));
+                long double deg = al;
+                if (af < 0) deg += (long double)(2.0f * CV_PI_F);
+                deg *= (long double)(180.0f / CV_PI_F);
+                const long double fl = floorl(deg);
+                if (fabsl(deg - (fl + 0.5L)) < (long double)delta_deg) {
+                    if (nund < ORI_SAMPLES) { und[nund] = tid; other[nund] = a0[tid] == (int)fl ? (int)fl + 1 : (int)fl; }
+                    ++nund;
+                }
+            }
+            if (yx) { yx[2 * tid] = Y; yx[2 * tid + 1] = X; }
+        }
+        sX[tid] = X; sY[tid] = Y;
+    }
+    *undecided = nund;
+    if (nund > 3) return 0;
+    int n = 0;
+    for (int combo = 0; combo < (1 << nund); ++combo) {
+        memcpy(a, a0, sizeof(a));
+        for (int k = 0; k < nund; ++k)
+            if (combo >> k & 1) a[und[k]] = other[k];
+        float bx, by;
+        best_window(sX, sY, a, &bx, &by);
+        float kp_dir = to_degrees((float)atan2l((long double)by, (long double)bx));
+        kp_dir = 360.0f - kp_dir;
+        if (fabsf(kp_dir - 360.f) < FLT_EPSILON) kp_dir = 0.f;
+        int seen = 0;
+        for (int k = 0; k < n; ++k) seen |= memcmp(&cand[k], &kp_dir, sizeof(float)) == 0;
+        if (!seen) cand[n++] = kp_dir;
+    }
+    return n;
+}
+
+/* n keypoints at once: cand n x 8, ncand[n], undecided[n], yx NULL or n x 113 x 2; status[k] < 0 (early return) is skipped */
+void orc_surf_orientation_candidates_n(const uint32_t *sum, int rows, int cols, int n, const float *x, const float *y, const float *size,
+                                       const int *status, const float *aptx, const float *apty, const float *aptw, double delta_deg,
+                                       float *cand, int *ncand, int *undecided, float *yx)
+{
+#pragma omp parallel for schedule(dynamic, 8)
+    for (int i = 0; i < n; ++i) {
+        ncand[i] = undecided[i] = 0;
+        if (status[i] < 0) continue;
+        ncand[i] = orc_surf_orientation_candidates(sum, rows, cols, x[i], y[i], size[i], aptx, apty, aptw, delta_deg, cand + 8 * (size_t)i,
+                                                   undecided + i, yx ? yx + (size_t)i * 2 * ORI_SAMPLES : NULL);
+    }
 }
 
 void orc_surf_default_params(orc_surf_params *p)

@@ -29,6 +29,16 @@ float orc_surf_orientation(const uint32_t *sum, int rows, int cols, float fx, fl
                            const float *apty, const float *aptw);
 void orc_surf_descriptor(const uint8_t *img, int rows, int cols, float fx, float fy, float fsize, float fdir, int extended,
                          const float *dw, float *desc);
+/* libm-exact modes (surf_ref.c): atan2 / sine / cosine in long double rounded once, every admissible decision enumerated */
+int orc_surf_descriptor_rounded(const uint8_t *img, int rows, int cols, float fx, float fy, float fsize, float fdir, int extended,
+                                const float *dw, float *desc, float *alt /* 3 x dsz */);
+void orc_surf_descriptors_rounded(const uint8_t *img, int rows, int cols, int n, const float *x, const float *y, const float *size,
+                                  const float *dir, int extended, const float *dw, float *desc, int *nalt, float *alt);
+int orc_surf_orientation_candidates(const uint32_t *sum, int rows, int cols, float fx, float fy, float fsize, const float *aptx,
+                                    const float *apty, const float *aptw, double delta_deg, float cand[8], int *undecided, float *yx);
+void orc_surf_orientation_candidates_n(const uint32_t *sum, int rows, int cols, int n, const float *x, const float *y, const float *size,
+                                       const int *status, const float *aptx, const float *apty, const float *aptw, double delta_deg,
+                                       float *cand, int *ncand, int *undecided, float *yx);
 /* keypoints: 7 rows (X, Y, LAPLACIAN(int), OCTAVE(int), SIZE, ANGLE, HESSIAN) x kp_pitch; returns nFeatures (< 0: error) */
 int orc_surf_detect_describe(const orc_surf_params *P, const uint8_t *img, const uint8_t *mask, int rows, int cols,
                              float *keypoints, int kp_pitch, float *descriptors, int want_desc);

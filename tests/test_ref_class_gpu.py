@@ -22,6 +22,7 @@ from oracle import refcu
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from fb_flow_check import assert_flow_equals  # noqa: E402
+from surf_check import assert_surf_equals  # noqa: E402
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not refcu.available(), reason="oracle/_ref/libref_cu.so not built (needs /root/reference)")]
 
@@ -90,7 +91,10 @@ def test_stereobm_hip_vs_the_reference_cuda_class(gpu, kw):
 
 
 @pytest.mark.parametrize("extended,upright", [(False, False), (True, True)])
-def test_surf_hip_vs_the_reference_cuda_class(gpu, extended, upright):
+def test_surf_hip_vs_the_reference_cuda_class(gpu, oracle, extended, upright):
+    """Detector rows: bit-equal to the reference class's own output.  Angles and descriptors: every feature through
+    tests/surf_check.py (the libm-exact oracle at the HIP angle), and beside it the statistical comparison with the reference class's
+    own libm-mode angles and descriptors, as before."""
     from opencv_contrib_amd import cuda
     img = np.rint(synth.texture(200, 260, 11, 2.0)).astype(np.uint8)
     ref = refcu.cuda_class_surf(img, hessian_threshold=50.0, extended=extended, upright=upright)
@@ -101,13 +105,12 @@ def test_surf_hip_vs_the_reference_cuda_class(gpu, extended, upright):
     ki = kp.view(np.int32)
     order = np.lexsort((kp[4], kp[0], kp[1], ki[3]))       # (octave, y, x, size): the order refcu sorts the reference's features by
     kp, ki, desc = kp[:, order], ki[:, order], desc[order]
-    np.testing.assert_array_equal(ki[2], ref["laplacian"])
-    np.testing.assert_array_equal(ki[3], ref["octave"])
-    np.testing.assert_array_equal(kp[4], ref["size"])
-    for row, name in ((0, "x"), (1, "y"), (6, "hessian")):
-        np.testing.assert_allclose(kp[row], ref[name], rtol=1e-6, atol=1e-4, err_msg=name)
-    # the bounds of tests/test_surf.py::_compare (device atan2f / sincosf differ from glibc's by an ulp, which can move a sample across
-    # a 5-degree window edge or a texel boundary)
+    hip = {"x": kp[0], "y": kp[1], "laplacian": ki[2], "octave": ki[3], "size": kp[4], "angle": kp[5], "hessian": kp[6]}
+    assert_surf_equals(oracle, img, {k: np.ascontiguousarray(v) for k, v in hip.items()}, desc,
+                       {k: np.asarray(ref[k]) for k in ("x", "y", "laplacian", "octave", "size", "hessian")}, extended=extended, upright=upright,
+                       what="reference class")
+    # the reference class's own libm-mode angles and descriptors: glibc's atan2f / sinf / cosf differ from the correctly rounded values by
+    # an ulp at a few arguments, which can move a sample across a 5-degree window edge or a texel boundary -- the earlier statistical bounds
     da = np.abs(kp[5] - ref["angle"]); da = np.minimum(da, 360 - da)
     assert (da <= 1e-2).mean() >= 0.99 or (da > 1e-2).sum() <= 2
     dd = np.abs(desc - ref["descriptors"]).max(1)
