@@ -87,6 +87,11 @@ __global__ __launch_bounds__(256) void k_paths(PathArgs A)
     asm volatile("v_mov_b32 %0, 0" : "=v"(vz));
     // census values of a pixel do not depend on the recurrence: they are fetched ahead of it (the loop is otherwise a chain of
     // dependent load -> min -> store steps with nothing to overlap the load latency inside a wave)
+    // Below minDisparity 0 the reference's two horizontal kernels compare in unsigned (stereosgm.cu:677, :693; oracle/sgm_ref.c orc_sgm_path):
+    // left-to-right never loads the right census; right-to-left, when minDisparity + D - 1 < 0, keeps only what its window held at the
+    // start of the line (jj + D - 1 - k >= W) and takes in zeros after that.  Both flags are wave-uniform.
+    const bool l2r_blind = dy == 0 && dx > 0 && A.min_disp < 0;
+    const bool r2l_zero_fed = dy == 0 && dx < 0 && A.min_disp + D - 1 < 0;
     auto fetch = [&](int ii, int jj, unsigned &l_, unsigned (&r_)[V]) {
         const bool in = ii >= 0 && ii < H && jj >= 0 && jj < W;
         const int ic = min(max(ii, 0), H - 1), jc = min(max(jj, 0), W - 1);
@@ -97,7 +102,8 @@ __global__ __launch_bounds__(256) void k_paths(PathArgs A)
         for (int v = 0; v < V; ++v) {
             const int k = lane * V + v;
             const int jr = jj - k - A.min_disp;
-            const bool ok = in && !(k + A.min_disp > jj) && jr < W;   // (jr >= W: negative minDisparity)
+            const bool ok = in && !(k + A.min_disp > jj) && jr < W &&   // (jr >= W: negative minDisparity)
+                            !l2r_blind && !(r2l_zero_fed && jj + D - 1 - k < W);
             r_[v] = ok ? (unsigned)A.right[(size_t)ic * W + min(max(jr, 0), W - 1)] : 0u;
         }
     };
@@ -135,13 +141,15 @@ __global__ __launch_bounds__(256) void k_paths(PathArgs A)
                 cost = min(cost, left_n - m + A.p1);
                 cost = min(cost, right_n - m + A.p1);
                 cost += __popc(l ^ r);
-                cur[v] = cost & 0xff;   // static_cast<uint8_t>(cost)
+                cur[v] = cost;   // whole: the reference's recurrence runs in 32-bit registers, only its store narrows (oracle/sgm_ref.c orc_sgm_path)
             }
+            unsigned b8[V];   // static_cast<uint8_t>(cost)
+#pragma unroll
+            for (int v = 0; v < V; ++v) b8[v] = (unsigned)cur[v] & 0xffu;
             unsigned char *o = out + pix * D + lane * V;
-            if (V == 1) o[0] = (unsigned char)cur[0];
-            else if (V == 2) *reinterpret_cast<unsigned short *>(o) = (unsigned short)(cur[0] | (cur[V > 1 ? 1 : 0] << 8));
-            else *reinterpret_cast<unsigned *>(o) = (unsigned)cur[0] | ((unsigned)cur[V > 1 ? 1 : 0] << 8) | ((unsigned)cur[V > 2 ? 2 : 0] << 16) |
-                                                     ((unsigned)cur[V > 3 ? 3 : 0] << 24);
+            if (V == 1) o[0] = (unsigned char)b8[0];
+            else if (V == 2) *reinterpret_cast<unsigned short *>(o) = (unsigned short)(b8[0] | (b8[V > 1 ? 1 : 0] << 8));
+            else *reinterpret_cast<unsigned *>(o) = b8[0] | (b8[V > 1 ? 1 : 0] << 8) | (b8[V > 2 ? 2 : 0] << 16) | (b8[V > 3 ? 3 : 0] << 24);
 #pragma unroll
             for (int v = 0; v < V; ++v) prev[v] = cur[v];
             i += dy; j += dx;

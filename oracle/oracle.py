@@ -919,6 +919,35 @@ def sgm_wta(aggregated, width, height, num_disparities, num_paths, uniqueness, s
     return left, right
 
 
+def sgm_median(src, emulate_quirks=True):
+    """the 3 x 3 median of a 16-bit map (the reference's median_filter<uint16_t>); the frame is a copy of the source"""
+    a = np.ascontiguousarray(src).view(np.int16) if np.asarray(src).dtype == np.uint16 else np.ascontiguousarray(src, dtype=np.int16)
+    out = np.empty(a.shape, np.int16)
+    lib().orc_sgm_median(C.c_void_p(a.ctypes.data), C.c_void_p(out.ctypes.data), C.c_int(a.shape[0]), C.c_int(a.shape[1]), C.c_int(int(emulate_quirks)))
+    return out
+
+
+def _map16(a):
+    a = np.ascontiguousarray(a)
+    return (a.view(np.int16) if a.dtype == np.uint16 else a.astype(np.int16)).copy()
+
+
+def sgm_check_consistency(left_disp, right_disp, left_img, subpixel=True, emulate_quirks=True):
+    """the left-right check on its own -> the checked left map (int16, -1 = invalid)"""
+    out, r, img = _map16(left_disp), _map16(right_disp), _img816(left_img)
+    assert out.shape == r.shape == img.shape
+    lib().orc_sgm_check_consistency(C.c_void_p(out.ctypes.data), C.c_void_p(r.ctypes.data), C.c_void_p(img.ctypes.data), C.c_int(img.itemsize),
+                                    C.c_int(out.shape[0]), C.c_int(out.shape[1]), C.c_int(int(subpixel)), C.c_int(int(emulate_quirks)))
+    return out
+
+
+def sgm_correct_range(disp, subpixel, min_disparity):
+    """the range correction on its own"""
+    out = _map16(disp)
+    lib().orc_sgm_correct_range(C.c_void_p(out.ctypes.data), C.c_int(out.shape[0]), C.c_int(out.shape[1]), C.c_int(int(subpixel)), C.c_int(min_disparity))
+    return out
+
+
 def sgm_compute(left, right, params: SGMParams | None = None):
     p = params or sgm_params()
     l, r = _img816(left), _img816(right)

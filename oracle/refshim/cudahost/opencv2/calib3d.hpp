@@ -7,6 +7,7 @@
 namespace cv {
 class StereoMatcher : public Algorithm {
 public:
+    enum { DISP_SHIFT = 4, DISP_SCALE = (1 << DISP_SHIFT) };
     virtual void compute(InputArray left, InputArray right, OutputArray disparity) = 0;
     virtual int getMinDisparity() const = 0;
     virtual void setMinDisparity(int minDisparity) = 0;
@@ -44,6 +45,16 @@ public:
 class StereoSGBM : public StereoMatcher {
 public:
     enum { MODE_SGBM = 0, MODE_HH = 1, MODE_SGBM_3WAY = 2, MODE_HH4 = 3 };
+    virtual int getPreFilterCap() const = 0;
+    virtual void setPreFilterCap(int preFilterCap) = 0;
+    virtual int getUniquenessRatio() const = 0;
+    virtual void setUniquenessRatio(int uniquenessRatio) = 0;
+    virtual int getP1() const = 0;
+    virtual void setP1(int P1) = 0;
+    virtual int getP2() const = 0;
+    virtual void setP2(int P2) = 0;
+    virtual int getMode() const = 0;
+    virtual void setMode(int mode) = 0;
 };
 }
 #endif

@@ -45,9 +45,11 @@
 #define CV_PROP
 #define CV_PROP_RW
 #define CV_OVERRIDE override
+#define CV_FINAL final
 #define CV_Assert(expr) do { if (!(expr)) throw std::runtime_error("CV_Assert failed: " #expr); } while (0)
 #define CV_DbgAssert(expr) CV_Assert(expr)
 #define CV_8U 0
+#define CV_16U 2
 #define CV_16S 3
 #define CV_32S 4
 #define CV_32F 5
@@ -55,6 +57,10 @@
 #define CV_MAKETYPE(depth, cn) ((depth) + (((cn) - 1) << 3))
 #define CV_8UC1 CV_MAKETYPE(CV_8U, 1)
 #define CV_8UC3 CV_MAKETYPE(CV_8U, 3)
+#define CV_16UC1 CV_MAKETYPE(CV_16U, 1)
+#ifndef CV_16SC1
+#define CV_16SC1 CV_MAKETYPE(CV_16S, 1)
+#endif
 #define CV_32SC1 CV_MAKETYPE(CV_32S, 1)
 #define CV_32SC4 CV_MAKETYPE(CV_32S, 4)
 #define CV_32FC1 CV_MAKETYPE(CV_32F, 1)
@@ -110,7 +116,15 @@ public:
     virtual ~Algorithm() {}
     virtual String getDefaultName() const { return "my_object"; }
 };
-inline size_t elem_size_of(int type) { const int d = type & 7, cn = (type >> 3) + 1; return (size_t)cn * (d == CV_8U ? 1 : d == CV_16S ? 2 : d == CV_64F ? 8 : 4); }
+inline size_t elem_size_of(int type) { const int d = type & 7, cn = (type >> 3) + 1; return (size_t)cn * (d == CV_8U ? 1 : d == CV_16S || d == CV_16U ? 2 : d == CV_64F ? 8 : 4); }
+
+// What a build may set to stand nearer to a device allocator: the pitch of GpuMat rows (cudaMallocPitch on current devices gives
+// multiples of 512 bytes; the reference's StereoSGM picks its median kernel by the pitch), and the byte every new GpuMat buffer is
+// filled with (device memory is not cleared: running a class with 0x00 and then with 0xFF shows which output it never writes).
+#ifndef CUDAHOST_PITCH_ALIGN
+#define CUDAHOST_PITCH_ALIGN 256
+#endif
+inline unsigned char &cudahost_alloc_fill() { static unsigned char v = 0; return v; }
 
 namespace cuda { class GpuMat; }
 class Mat {   // a dense host matrix: what diff_sum_host (1 x 1 CV_64F), getGaussianKernel (n x 1 CV_32F) and SURF_CUDA's keypoint /
@@ -252,8 +266,8 @@ public:
     {
         if (data && rows == r && cols == c && type_ == type) return;
         type_ = type; rows = r; cols = c;
-        step = ((size_t)c * elem_size_of(type) + 255) / 256 * 256;   // a pitched allocation, like cudaMallocPitch
-        buf_ = std::make_shared<std::vector<unsigned char> >((size_t)r * step + 64);
+        step = ((size_t)c * elem_size_of(type) + CUDAHOST_PITCH_ALIGN - 1) / CUDAHOST_PITCH_ALIGN * CUDAHOST_PITCH_ALIGN;   // a pitched allocation, like cudaMallocPitch
+        buf_ = std::make_shared<std::vector<unsigned char> >((size_t)r * step + 64, cudahost_alloc_fill());
         data = datastart = buf_->data();
         whole_ = Size(c, r);
     }
@@ -284,6 +298,7 @@ public:
     template <typename T> T *ptr(int y = 0) { return reinterpret_cast<T *>(data + (size_t)y * step); }
     template <typename T> const T *ptr(int y = 0) const { return reinterpret_cast<const T *>(data + (size_t)y * step); }
     GpuMat row(int y) const { return (*this)(Rect(0, y, cols, 1)); }
+    GpuMat colRange(int a, int b) const { return (*this)(Rect(a, 0, b - a, rows)); }
     void release() { *this = GpuMat(); }
     template <typename T> operator PtrStep<T>() const { return PtrStep<T>((T *)data, step); }
     template <typename T> operator PtrStepSz<T>() const { return PtrStepSz<T>(rows, cols, (T *)data, step); }

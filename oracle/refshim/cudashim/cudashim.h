@@ -53,6 +53,10 @@ struct ushort4 { unsigned short x, y, z, w; };
 struct short3 { short x, y, z; };
 struct short4 { short x, y, z, w; };
 struct int3 { int x, y, z; };
+// the vector loads and stores of cudastereo/src/cuda/stereosgm.cu (no CUDA alignment: on the host a struct copy of any address will do)
+struct uchar2 { unsigned char x, y; };
+struct ushort2 { unsigned short x, y; };
+struct uint4 { unsigned x, y, z, w; };
 typedef unsigned int uint;
 typedef unsigned char uchar;
 typedef unsigned short ushort;
@@ -87,7 +91,63 @@ template <typename F> void launch(dim3 grid, dim3 block, F f) { launch(grid, blo
 #define blockIdx (cudashim::bid())
 #define blockDim (cudashim::bdim())
 #define gridDim (cudashim::gdim())
+// __syncthreads() is one yield: enough while every thread of a block passes the same barriers.  A file whose kernels also use the warp
+// collectives below is compiled with -DCUDASHIM_COUNTED_BARRIERS: then it counts the block's live threads, so a warp that waits at a
+// shuffle and a warp that waits here do not release each other.
+#ifdef CUDASHIM_COUNTED_BARRIERS
+static inline void __syncthreads() { oclrt_barrier_members(0, oclrt_group_items(), ~0ull); }
+#else
 static inline void __syncthreads() { oclrt_barrier_plain(); }
+#endif
+
+// Warp collectives (CUDA C++ Programming Guide, "Warp Shuffle Functions"): a warp is 32 consecutive threads of the block in linear order.
+// Each one is a collective over the lanes named in `mask`: deposit, wait for the mask's live lanes, read, wait again (so no lane
+// deposits its next value before every lane has read this one).  width (a power of two <= 32) cuts the warp into segments; a source
+// lane outside the caller's segment gives the caller's own value.  A source lane outside `mask` gives whatever that lane deposited last
+// (CUDA: undefined).  Between two collectives the lanes of a warp run one after the other in lane order.
+namespace cudashim {
+inline unsigned long long (&warp_slots())[32][32] { static unsigned long long s[32][32]; return s; }   // [warp of the block][lane]
+inline unsigned linear_tid() { const Idx t = tid(), d = bdim(); return t.x + d.x * (t.y + d.y * t.z); }
+inline void warp_wait(unsigned mask)
+{
+    const size_t first = linear_tid() / 32 * 32, n = oclrt_group_items();
+    oclrt_barrier_members(first, first + 32 <= n ? 32 : n - first, mask);
+}
+template <typename T> inline T shuffle(unsigned mask, T var, int src_lane, bool in_segment)
+{
+    static_assert(sizeof(T) <= 8, "shuffled values are at most 64 bits");
+    const unsigned t = linear_tid(), warp = t / 32;
+    unsigned long long bits = 0;
+    memcpy(&bits, &var, sizeof(T));
+    warp_slots()[warp][t % 32] = bits;
+    warp_wait(mask);
+    if (in_segment) memcpy(&var, &warp_slots()[warp][src_lane], sizeof(T));
+    warp_wait(mask);
+    return var;
+}
+}  // namespace cudashim
+static inline void __syncwarp(unsigned mask = 0xffffffffu) { cudashim::warp_wait(mask); }
+template <typename T> static inline T __shfl_sync(unsigned mask, T var, int srcLane, int width = 32)
+{
+    const int lane = cudashim::linear_tid() % 32, base = lane / width * width;
+    return cudashim::shuffle(mask, var, base + (int)((unsigned)srcLane % (unsigned)width), true);
+}
+template <typename T> static inline T __shfl_up_sync(unsigned mask, T var, unsigned delta, int width = 32)
+{
+    const int lane = cudashim::linear_tid() % 32, base = lane / width * width, src = lane - (int)delta;
+    return cudashim::shuffle(mask, var, src, delta <= 32 && src >= base);
+}
+template <typename T> static inline T __shfl_down_sync(unsigned mask, T var, unsigned delta, int width = 32)
+{
+    const int lane = cudashim::linear_tid() % 32, base = lane / width * width, src = lane + (int)delta;
+    return cudashim::shuffle(mask, var, src, delta <= 32 && src < base + width);
+}
+template <typename T> static inline T __shfl_xor_sync(unsigned mask, T var, int laneMask, int width = 32)
+{
+    // PTX shfl.bfly: the source is lane ^ laneMask; it is taken unless it lies beyond the END of the caller's segment
+    const int lane = cudashim::linear_tid() % 32, base = lane / width * width, src = lane ^ laneMask;
+    return cudashim::shuffle(mask, var, src, src >= 0 && src < 32 && src < base + width);
+}
 
 // device math used by the kernels in global scope (CUDA puts min / max / abs overloads there)
 static inline int min(int a, int b) { return a < b ? a : b; }

@@ -34,12 +34,17 @@ typedef struct fiber {
     ucontext_t ctx;
     wi_state wi;
     int done;
+    int waiting;                 /* inside oclrt_barrier_members */
+    size_t wfirst, wcount;       /* ... of these fibers of the group */
+    unsigned long long wmask;
 } fiber;
 static ucontext_t g_sched;
 static fiber *g_fibers;
 static char *g_stacks;
 static size_t g_nfibers_cap;
 static fiber *g_cur;
+static size_t g_nitems;   /* fibers of the group being run */
+static size_t g_released; /* counting barriers that have opened in this group */
 static oclrt_body g_body;
 static void *g_args;
 
@@ -60,6 +65,36 @@ void oclrt_barrier(unsigned flags)
     g_wi = g_cur->wi;
 }
 
+/* A barrier that counts: returns once every member has arrived at a barrier over the same set or has finished.  The members are
+ * the fibers first + i, i < count, of the group in linear order (x fastest) with i >= 64 or bit i of mask set.  Unlike barrier(),
+ * which is one yield and so keeps a group in step only while every item passes the same barriers, fibers waiting here stay put
+ * while others pass other barriers: a CUDA warp's lanes at a shuffle while another warp stands at __syncthreads().  Every caller
+ * yields once before it looks, so the members leave in the order the scheduler runs them: ascending linear index. */
+void oclrt_barrier_members(size_t first, size_t count, unsigned long long mask)
+{
+    if (!g_cur) { fprintf(stderr, "oclrt: barrier in a kernel launched without uses_barrier\n"); abort(); }
+    fiber *me = g_cur;
+    if (first + count > g_nitems) { fprintf(stderr, "oclrt: barrier members outside the group\n"); abort(); }
+    me->waiting = 1; me->wfirst = first; me->wcount = count; me->wmask = mask;
+    for (;;) {
+        me->wi = g_wi;
+        swapcontext(&me->ctx, &g_sched);
+        g_wi = me->wi;
+        if (!me->waiting) return;   /* released by a member that looked before */
+        int all = 1;
+        for (size_t i = 0; i < count && all; ++i) {
+            if (i < 64 && !((mask >> i) & 1)) continue;
+            const fiber *f = &g_fibers[first + i];
+            all = f->done || (f->waiting && f->wfirst == first && f->wcount == count && f->wmask == mask);
+        }
+        if (!all) continue;
+        for (size_t i = 0; i < count; ++i)
+            if (i >= 64 || ((mask >> i) & 1)) g_fibers[first + i].waiting = 0;
+        ++g_released;
+        return;
+    }
+}
+
 static void run_group_fibers(size_t nitems, const wi_state *items)
 {
     if (nitems > g_nfibers_cap) {
@@ -76,10 +111,14 @@ static void run_group_fibers(size_t nitems, const wi_state *items)
         f->ctx.uc_link = NULL;
         f->wi = items[i];
         f->done = 0;
+        f->waiting = 0;
         makecontext(&f->ctx, fiber_main, 0);
     }
     size_t live = nitems;
+    int stuck_rounds = 0;
+    g_nitems = nitems;
     while (live) {   /* every live item runs to its next barrier (or its end) once per round */
+        const size_t released = g_released, live_before = live;
         for (size_t i = 0; i < nitems; ++i) {
             fiber *f = &g_fibers[i];
             if (f->done) continue;
@@ -88,6 +127,12 @@ static void run_group_fibers(size_t nitems, const wi_state *items)
             swapcontext(&g_sched, &f->ctx);
             if (f->done) --live;
         }
+        /* a round in which no item finished and no barrier opened, and after which every live item waits: nothing can change any more
+         * (the round after the last arrival opens a barrier, so two such rounds in a row mean the members never all arrive) */
+        int stuck = live > 0 && live == live_before && released == g_released;
+        for (size_t i = 0; i < nitems && stuck; ++i) stuck = g_fibers[i].done || g_fibers[i].waiting;
+        stuck_rounds = stuck ? stuck_rounds + 1 : 0;
+        if (stuck_rounds > 2) { fprintf(stderr, "oclrt: barrier members that never arrive\n"); abort(); }
     }
     g_cur = NULL;
 }
@@ -183,3 +228,4 @@ size_t oclrt_group_id(unsigned d) { return d < 3 ? g_wi.grp[d] : 0; }
 size_t oclrt_local_size(unsigned d) { return d < 3 ? g_wi.lsz[d] : 1; }
 size_t oclrt_num_groups(unsigned d) { return d < 3 ? g_wi.ngrp[d] : 1; }
 void oclrt_barrier_plain(void) { oclrt_barrier(0); }
+size_t oclrt_group_items(void) { return g_nitems; }

@@ -21,6 +21,10 @@ typedef void (*oclrt_body)(void *args);   /* calls the compiled kernel with its 
  * loops, parallel over the slowest dimension when `parallel` is set (kernels without __local only). */
 void oclrt_run(int dim, const size_t *gsz, const size_t *lsz, int uses_barrier, int parallel, oclrt_body body, void *args);
 
+/* Inside a group run with uses_barrier: a counting barrier over some of the group's items (see oclrt.c), and the group's item count */
+void oclrt_barrier_members(size_t first, size_t count, unsigned long long mask);
+size_t oclrt_group_items(void);
+
 /* read-only image2d_t stand-in for read_imagef/read_imageui with an unnormalised, clamp-to-edge,
  * nearest sampler (the only sampler the reference kernels use) */
 typedef struct oclrt_image2d {

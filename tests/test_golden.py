@@ -18,7 +18,8 @@ GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
 
 def _files(prefix):
-    return sorted(glob.glob(os.path.join(GOLD, prefix + "_*.npz")))
+    # (prefix_refclass_* / prefix_refstage_* are recordings of the reference's own code, with another layout: their tests read them)
+    return sorted(p for p in glob.glob(os.path.join(GOLD, prefix + "_*.npz")) if "_refclass_" not in p and "_refstage_" not in p)
 
 
 def T(a, dev):

@@ -1,7 +1,9 @@
 """cv::cuda::StereoSGM.  The stage tests restate the reference's own unit tests (cudastereo/test/test_sgm_funcs.cpp):
-random census / cost volumes through each device stage against the CPU twin the reference ships for it, bit-exact
-(EXPECT_MAT_NEAR(gold, dst, 0)); the oracle's census, path aggregation and left winner-takes-all ARE those twins
-(oracle/sgm_ref.c), so these stages are pinned on the reference's own tests."""
+random census / cost volumes through each device stage against oracle/sgm_ref.c, bit-exact (EXPECT_MAT_NEAR(gold, dst, 0)).  The oracle
+is itself held to the reference's kernels and host class as they run (tests/test_sgm_ref.py, tests/golden/sgm_ref*.npz): its census and
+left winner-takes-all are the CPU twins the reference ships; its path aggregation is that twin wherever the twin is defined and no cost
+passes 255, and the reference's KERNELS beyond (costs carried in 32-bit registers, unsigned comparisons below minDisparity 0).  The tests
+at the end of this file hold the HIP stages and the HIP class to the same recorded reference results directly."""
 import os
 import sys
 
@@ -158,8 +160,9 @@ def shifted_census():
 @pytest.mark.parametrize("dxdy", DIRS)
 @pytest.mark.parametrize("D", [64, 128, 256])
 def test_path_aggregation_cost_cast_wraps(gpu, oracle, shifted_census, dxdy, D):
-    """min(.., P2 = 250) + popcount > 255: static_cast<uint8_t> wraps modulo 256, it does not saturate.  With P2 = 224 (224 + 31 = 255)
-    nothing wraps; the outputs of the two must differ or the case does not reach the cast."""
+    """min(.., P2 = 250) + popcount > 255: static_cast<uint8_t> wraps modulo 256, it does not saturate -- and only the stored byte wraps,
+    the recurrence goes on from the whole cost as the reference's registers do (oracle/sgm_ref.c orc_sgm_path).  With P2 = 224
+    (224 + 31 = 255) nothing wraps; the outputs of the two must differ or the case does not reach the cast."""
     l, r = shifted_census
     ref = oracle.sgm_path(l, r, D, 0, 10, 250, *dxdy)
     assert (ref != oracle.sgm_path(l, r, D, 0, 10, 224, *dxdy)).any()
@@ -170,7 +173,8 @@ def test_path_aggregation_cost_cast_wraps(gpu, oracle, shifted_census, dxdy, D):
 @pytest.mark.parametrize("min_disp", [-1, -5, -70])
 @pytest.mark.parametrize("D", [64, 128])
 def test_path_aggregation_negative_min_disparity(gpu, oracle, min_disp, D):
-    """j - k - minDisparity can pass the right end of the row (cost against census 0 there); at -70 on 70 columns it always does."""
+    """j - k - minDisparity can pass the right end of the row (cost against census 0 there); at -70 on 70 columns it always does.  The
+    reference's left-to-right kernel never loads the right census below minDisparity 0 (oracle/sgm_ref.c orc_sgm_path)."""
     l, r = _census_pair(np.random.default_rng(D - min_disp), (9, 70))
     for dxdy in [(1, 0), (0, -1), (-1, 1)]:
         np.testing.assert_array_equal(_hip_path(gpu, l, r, D, min_disp, 10, 120, dxdy), oracle.sgm_path(l, r, D, min_disp, 10, 120, *dxdy))
@@ -296,3 +300,136 @@ def test_compute_handle_reuse_across_sizes(gpu, oracle):
     for pair in (big, small, big):
         out = sgm.compute(torch.from_numpy(pair[0]).to(gpu), torch.from_numpy(pair[1]).to(gpu)).cpu().numpy()
         np.testing.assert_array_equal(out, ref[id(pair)])
+
+
+# ------------------------------------------------------------------ HIP against what the reference's own code recorded (tests/golden/sgm_ref*.npz)
+# The fixtures are written by tools/make_golden_sgm.py from the reference's kernels and host class; no oracle stands in between.
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import make_golden_sgm as G  # noqa: E402
+import json  # noqa: E402
+
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+_u16 = lambda a: np.ascontiguousarray(a).view(np.uint16)
+
+
+def _fixture(name):
+    return np.load(os.path.join(GOLDEN, f"sgm_{name}.npz"))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dt", ["uint8", "uint16"])
+def test_census_equals_the_reference_fixtures(gpu, dt):
+    """where the reference's kernel writes (a whole 9 x 7 window fits); the border it leaves unwritten is 0 here, as in its CPU twin"""
+    import torch
+    from opencv_contrib_amd import cuda
+    z = _fixture("refstage_census")
+    for h, w in G.CENSUS_SHAPES:
+        key = f"{dt}_{h}x{w}"
+        out = cuda.sgm_census(torch.from_numpy(z[key + "_src"]).to(gpu)).cpu().numpy()
+        undef = z[key + "_undef"]
+        np.testing.assert_array_equal(out[~undef], z[key + "_out"][~undef], err_msg=key)
+        assert (out[undef] == 0).all(), key
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ndisp", sorted(G.PATH_CASES))
+def test_path_aggregation_equals_the_reference_fixtures(gpu, ndisp):
+    """All 8 directions of the reference's KERNELS (not of their CPU twin, which they leave where costs pass 255 and below minDisparity
+    0): tiling edges, lines of 1 - 3 pixels, minDisparity 3 / -1 / -70 / below -(D - 1), P2 = 250."""
+    z = _fixture(f"refstage_paths_D{ndisp}")
+    for case in G.PATH_CASES[ndisp]:
+        name, (h, w), min_disp, p2, whole, rolled = case
+        left, right = G.path_inputs(ndisp, case)
+        np.testing.assert_array_equal(G.sha(np.stack([left, right])), z[name + "_in_sha"])
+        for q, dxdy in enumerate(G.DIRS):
+            vol = _hip_path(gpu, left, right, ndisp, min_disp, G.PATH_P1, p2, dxdy)
+            if whole:
+                np.testing.assert_array_equal(vol, z[f"{name}_d{q}_vol"], err_msg=f"{name} direction {dxdy}")
+            np.testing.assert_array_equal(G.path_checksum(vol, h, w, ndisp), z[f"{name}_d{q}_sum"], err_msg=f"{name} direction {dxdy}: rows that differ")
+            np.testing.assert_array_equal(G.sha(vol), z[f"{name}_d{q}_sha"], err_msg=f"{name} direction {dxdy}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ndisp", sorted(G.WTA_SHAPES))
+def test_winner_takes_all_equals_the_reference_fixtures(gpu, ndisp):
+    """both maps; 4 and 8 paths, sub-pixel on and off, uniqueness 0 / 0.95 / 1, costs from {0, 1} (ties everywhere), 0 .. 31 and 0 .. 255"""
+    import torch
+    from opencv_contrib_amd import cuda
+    z = _fixture("refstage_wta")
+    h, w = G.WTA_SHAPES[ndisp]
+    for values in G.WTA_VALUES:
+        for paths in (4, 8):
+            cost = G.wta_cost(ndisp, values, paths)
+            np.testing.assert_array_equal(G.sha(cost), z[f"D{ndisp}_v{values}_p{paths}_in_sha"])
+            tc = torch.from_numpy(cost.reshape(1, -1)).to(gpu)
+            for ui, uniq in enumerate(G.WTA_UNIQ):
+                for sub in (0, 1):
+                    key = f"D{ndisp}_v{values}_p{paths}_u{ui}_s{sub}"
+                    left, right = cuda.sgm_winner_takes_all(tc, w, h, ndisp, paths, uniq, bool(sub))
+                    np.testing.assert_array_equal(_u16(left.cpu().numpy()), z[key + "_left"], err_msg=key)
+                    np.testing.assert_array_equal(_u16(right.cpu().numpy()), z[key + "_right"], err_msg=key)
+
+
+def _class_fixture(name):
+    """(left, right, parameters, the reference's disparity, the pixels of it that do not hang on memory the reference never writes)"""
+    z = _fixture("refclass_" + name)
+    return z["left"], z["right"], json.loads(str(z["params"])), z["disp"], ~G.depends_on_unwritten(z["maps"][1])
+
+
+def _create(kw):
+    from opencv_contrib_amd import cuda
+    return cuda.createStereoSGM(kw["min_disp"], kw["ndisp"], kw["p1"], kw["p2"], kw["uniq"], kw["mode"])
+
+
+CLASS_NAMES = [c[0] for c in G.CLASS_CASES]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", CLASS_NAMES)
+def test_compute_equals_the_reference_class_fixtures(gpu, name):
+    """createStereoSGM(...).compute against the disparity the reference's own class computed, dense inputs and pitched ROI views"""
+    import torch
+    left, right, kw, disp, defined = _class_fixture(name)
+    assert defined.sum() >= defined.size // 2
+    sgm = _create(kw)
+    out = sgm.compute(torch.from_numpy(left).to(gpu), torch.from_numpy(right).to(gpu)).cpu().numpy()
+    np.testing.assert_array_equal(out[defined], disp[defined], err_msg="dense")
+    h, w = left.shape
+    bigl = torch.full((h + 5, w + 37), 77, dtype=torch.from_numpy(left).dtype, device=gpu)
+    bigr = torch.full_like(bigl, 201)
+    bigl[2:2 + h, 20:20 + w] = torch.from_numpy(left).to(gpu)
+    bigr[2:2 + h, 20:20 + w] = torch.from_numpy(right).to(gpu)
+    outbuf = torch.zeros((h + 3, w + 11), dtype=torch.int16, device=gpu)
+    sgm.compute(bigl[2:2 + h, 20:20 + w], bigr[2:2 + h, 20:20 + w], outbuf[1:1 + h, 4:4 + w])
+    np.testing.assert_array_equal(outbuf[1:1 + h, 4:4 + w].cpu().numpy()[defined], disp[defined], err_msg="pitched ROI views")
+    assert (outbuf[0] == 0).all() and (outbuf[:, :4] == 0).all() and (outbuf[:, 4 + w:] == 0).all() and (outbuf[1 + h:] == 0).all()
+
+
+@pytest.mark.gpu
+def test_compute_one_handle_across_the_reference_class_fixtures(gpu):
+    """one handle, its parameters set anew for each fixture, sizes and disparity counts in mixed order (larger, smaller, larger)"""
+    import torch
+    order = ["32x48_D128_hh", "13x15_m1_u0", "64x160_u16", "17x33_D256", "16x16_m3_u100", "64x160_reuse", "13x15_reuse", "32x48_m1_u0",
+             "32x48_D256_u16", "64x160_D128", "17x33_m3_u0"]
+    assert set(order) <= set(CLASS_NAMES)
+    sgm = _create(dict(min_disp=0, ndisp=64, p1=10, p2=120, uniq=5, mode=3))
+    for name in order:
+        left, right, kw, disp, defined = _class_fixture(name)
+        sgm.setMinDisparity(kw["min_disp"]); sgm.setNumDisparities(kw["ndisp"]); sgm.setP1(kw["p1"]); sgm.setP2(kw["p2"])
+        sgm.setUniquenessRatio(kw["uniq"]); sgm.setMode(kw["mode"])
+        out = sgm.compute(torch.from_numpy(left).to(gpu), torch.from_numpy(right).to(gpu)).cpu().numpy()
+        np.testing.assert_array_equal(out[defined], disp[defined], err_msg=name)
+
+
+@pytest.mark.gpu
+def test_compute_rejects_what_the_reference_class_rejects(gpu):
+    import torch
+    from opencv_contrib_amd import capi, cuda
+    z = _fixture("refclass_rejected")
+    assert [int(z[n + "_threw"]) for n in ("mode", "ndisp96", "size", "accepted")] == [1, 1, 1, 0]
+    left, right = G.class_pair((32, 48), (13, 10), False)
+    tl, tr = torch.from_numpy(left).to(gpu), torch.from_numpy(right).to(gpu)
+    for kw, r in ((dict(mode=0), tr), (dict(numDisparities=96), tr), (dict(), torch.from_numpy(right[:, :40].copy()).to(gpu))):
+        with pytest.raises(capi.MiError):
+            cuda.createStereoSGM(**dict(dict(numDisparities=64), **kw)).compute(tl, r)
+    cuda.createStereoSGM(numDisparities=64).compute(tl, tr)
