@@ -768,6 +768,81 @@ MI_API int mi_orb_blur(const mi_mat *src, mi_mat *dst, void *stream);
  * mi_orb_make_pattern gives it; descriptors: MI_8UC1, at least n rows, 32 columns */
 MI_API int mi_orb_descriptors(const mi_mat *img, const mi_mat *keypoints, int n, const mi_mat *pattern, int wta_k, mi_mat *descriptors, void *stream);
 
+/* ================================================= Corner criteria and goodFeaturesToTrack ===== */
+
+/* cv::cuda::createHarrisCorner / createMinEigenValCorner (cudaimgproc.hpp:562,575).
+ * ksize: 3 only, anything else is MI_ERR_NOT_IMPL before any launch: the taps come from getDerivKernels and Mat *= double, main-repository
+ * code the reference tree does not hold.  For 3 they are [-1 0 1] and [1 2 1] * scale, where every reading of the scaling gives the
+ * same bits (+-1 and 2 are exact); for Scharr, 5 and 7 the readings can differ.  CornersDetector only ever passes 3 (gftt.cpp:97-98). */
+typedef struct mi_corner_params {
+    int type;                 /* MI_8UC1 or MI_32FC1 */
+    int block_size;           /* 1 .. 255 */
+    int ksize;                /* 3 */
+    int border_type;          /* cv::BORDER_REPLICATE 1, BORDER_REFLECT 2, BORDER_REFLECT101 4; anything else: MI_ERR_BAD_ARG (corners.cpp:86) */
+    int harris;               /* 0: MinEigenVal, else Harris */
+    double k;                 /* Harris' free parameter; used as float (corners.cpp:126) */
+} mi_corner_params;
+
+typedef struct mi_corner mi_corner;
+
+/* Replaces: CornerBase::CornerBase with Harris / MinEigenVal, corners.cpp:83-113,125-128,153-156.  Checked before the device is looked for. */
+MI_API int mi_corner_create(const mi_corner_params *p, mi_corner **out);
+MI_API void mi_corner_destroy(mi_corner *h);
+/* Replaces: Harris::compute / MinEigenVal::compute, corners.cpp:115-120,136-176 = two separable Sobel filters (cudafilters
+ * filtering.cpp:458-545, cuda/row_filter.hpp:55-141, cuda/column_filter.hpp:55-141) and cornerHarris_gpu / cornerMinEigenVal_gpu,
+ * cuda/corners.cu:62-269.  src: the handle's type, any base address and step; dst: MI_32FC1 of the same size.  One launch while the tile
+ * fits the LDS (blockSize <= 38), two with Dx / Dy planes in scratch above; the same bits either way.  Stream-ordered, no wait. */
+MI_API int mi_corner_compute(mi_corner *h, const mi_mat *src, mi_mat *dst, void *stream);
+
+/* cv::cuda::createGoodFeaturesToTrackDetector (cudaimgproc.hpp:617-618) */
+typedef struct mi_gftt_params {
+    int type;                 /* MI_8UC1; or MI_32FC1 */
+    int max_corners;          /* 1000; >= 0, 0: all */
+    double quality_level;     /* 0.01; > 0 */
+    double min_distance;      /* 0; >= 0 */
+    int block_size;           /* 3 */
+    int use_harris;           /* 0 */
+    double harris_k;          /* 0.04 */
+} mi_gftt_params;
+
+typedef struct mi_gftt mi_gftt;
+
+/* Replaces: the defaults of createGoodFeaturesToTrackDetector, cudaimgproc.hpp:617-618 */
+MI_API void mi_gftt_default_params(mi_gftt_params *p);
+/* Replaces: GoodFeaturesToTrackDetector::GoodFeaturesToTrackDetector, gftt.cpp:90-100 (ksize 3, BORDER_REFLECT101).  The parameters are
+ * checked (gftt.cpp:94) before the device is looked for. */
+MI_API int mi_gftt_create(const mi_gftt_params *p, mi_gftt **out);
+/* Replaces: setMaxCorners / setMinDistance, gftt.cpp:72-73 (every field may change) */
+MI_API int mi_gftt_set_params(mi_gftt *h, const mi_gftt_params *p);
+MI_API int mi_gftt_get_params(const mi_gftt *h, mi_gftt_params *p);
+MI_API void mi_gftt_destroy(mi_gftt *h);
+/* Device scratch the handle holds (grown on demand, never shrunk); no reference counterpart (eig_, tmpCorners_, gftt.cpp:81-85) */
+MI_API int mi_gftt_scratch_bytes(const mi_gftt *h, size_t *bytes);
+/* Replaces: GoodFeaturesToTrackDetector::detect, gftt.cpp:107-214, with findCorners_gpu and sortCorners_gpu, cuda/gftt.cu:55-136, and
+ * cuda::minMax.  img: the handle's type; mask (NULL or data == NULL: none): MI_8UC1 of the same size; corners: MI_32FC2, 1 row, at least
+ * min(maxCorners > 0 ? maxCorners : capacity, capacity) columns with capacity = max(1000, (int)(area * 0.05)); *n: the columns written,
+ * float2 {x, y}.  *n = 0 leaves corners untouched (the reference releases it).  Where the reference leaves the result open this library
+ * has one rule each: among equal responses the order is (y, x) ascending, and when more than `capacity` corners are found the first
+ * `capacity` in row-major order take part.  rows or cols above 32767: MI_ERR_BAD_SIZE before any launch.  Waits for `stream` once for
+ * the count; with minDistance >= 1 the sorted points come to the host, the grid loop of gftt.cpp:140-207 runs there and the survivors
+ * go back, as in the reference. */
+MI_API int mi_gftt_detect(mi_gftt *h, const mi_mat *img, const mi_mat *mask, mi_mat *corners, int *n, void *stream);
+/* Stage entries.  Each waits for `stream`.
+ * Replaces: what mi_corner_compute does, with the two 3-tap kernels given: deriv ([-1 0 1]) and smooth ([1 2 1] * scale): Dx filters rows
+ * with deriv and columns with smooth, Dy the other way round.  form: 0 the plan's choice, 1 one launch, 2 two launches with planes.
+ * threshold (NULL: not wanted): (float)((double)max(dst) * quality_level), computed on the device (gftt.cpp:119-124). */
+MI_API int mi_gftt_response(const mi_mat *src, const float *deriv, const float *smooth, int block_size, int border_type, int harris, float k,
+                            int form, mi_mat *dst, double quality_level, float *threshold, void *stream);
+/* Replaces: findCorners_gpu, gftt.cu:55-112.  response: MI_32FC1; corners: 1 x max_count MI_32FC2; *count = min(found, max_count), the
+ * first in row-major order. */
+MI_API int mi_gftt_find_corners(const mi_mat *response, float threshold, const mi_mat *mask, mi_mat *corners, int *count, void *stream);
+/* Replaces: sortCorners_gpu, gftt.cu:114-136: corners[:n] by response descending, then (y, x) ascending; -0 and +0 are one response.
+ * A corner outside the plane: MI_ERR_BAD_ARG. */
+MI_API int mi_gftt_sort(const mi_mat *response, const mi_mat *corners, int n, mi_mat *sorted, void *stream);
+/* Replaces: the grid loop of gftt.cpp:140-207 (minDistance >= 1).  HOST pointers, no device needed: points: total float2 {x, y} in
+ * sorted order; out: room for total float2; *n_out: the survivors. */
+MI_API int mi_gftt_min_distance(const float *points, int total, int rows, int cols, double min_distance, int max_corners, float *out, int *n_out);
+
 /* ================================================= superres optical-flow adapters ===== */
 
 /* Replaces: cv::superres::convertToType(GpuMat, CV_8UC1) as used by GpuOpticalFlow::calc, superres/src/optical_flow.cpp:469-470

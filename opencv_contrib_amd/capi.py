@@ -108,6 +108,15 @@ class FastParams(C.Structure):
     _fields_ = [("threshold", C.c_int), ("nonmax_suppression", C.c_int), ("max_npoints", C.c_int)]
 
 
+class CornerParams(C.Structure):
+    _fields_ = [("type", C.c_int), ("block_size", C.c_int), ("ksize", C.c_int), ("border_type", C.c_int), ("harris", C.c_int), ("k", C.c_double)]
+
+
+class GfttParams(C.Structure):
+    _fields_ = [("type", C.c_int), ("max_corners", C.c_int), ("quality_level", C.c_double), ("min_distance", C.c_double),
+                ("block_size", C.c_int), ("use_harris", C.c_int), ("harris_k", C.c_double)]
+
+
 class OrbParams(C.Structure):
     _fields_ = [("nfeatures", C.c_int), ("scale_factor", C.c_float), ("nlevels", C.c_int), ("edge_threshold", C.c_int), ("first_level", C.c_int),
                 ("wta_k", C.c_int), ("score_type", C.c_int), ("patch_size", C.c_int), ("fast_threshold", C.c_int), ("blur_for_descriptor", C.c_int)]
@@ -321,6 +330,20 @@ def lib():
         "mi_orb_angle": (i, [PM, PM, i, i, PM, PM, vp]),
         "mi_orb_blur": (i, [PM, PM, vp]),
         "mi_orb_descriptors": (i, [PM, PM, i, PM, i, PM, vp]),
+        "mi_corner_create": (i, [C.POINTER(CornerParams), C.POINTER(vp)]),
+        "mi_corner_destroy": (None, [vp]),
+        "mi_corner_compute": (i, [vp, PM, PM, vp]),
+        "mi_gftt_default_params": (None, [C.POINTER(GfttParams)]),
+        "mi_gftt_create": (i, [C.POINTER(GfttParams), C.POINTER(vp)]),
+        "mi_gftt_set_params": (i, [vp, C.POINTER(GfttParams)]),
+        "mi_gftt_get_params": (i, [vp, C.POINTER(GfttParams)]),
+        "mi_gftt_destroy": (None, [vp]),
+        "mi_gftt_scratch_bytes": (i, [vp, C.POINTER(C.c_size_t)]),
+        "mi_gftt_detect": (i, [vp, PM, PM, PM, C.POINTER(i), vp]),
+        "mi_gftt_response": (i, [PM, C.POINTER(f), C.POINTER(f), i, i, i, f, i, PM, d, C.POINTER(f), vp]),
+        "mi_gftt_find_corners": (i, [PM, f, PM, PM, C.POINTER(i), vp]),
+        "mi_gftt_sort": (i, [PM, PM, i, PM, vp]),
+        "mi_gftt_min_distance": (i, [C.POINTER(f), i, i, i, d, i, C.POINTER(f), C.POINTER(i)]),
         "mi_superres_to_gray8": (i, [PM, PM, vp]),
         "mi_split_flow": (i, [PM, PM, PM, vp]),
         "mi_btvl1_default_params": (None, [C.POINTER(BTVL1Params)]),

@@ -1650,6 +1650,161 @@ def fast_locations_to_points(gpu_keypoints):
     return pts
 
 
+BORDER_REPLICATE, BORDER_REFLECT, BORDER_REFLECT101 = 1, 2, 4   # cv::BorderTypes (main repository)
+
+
+def _src_type(t):
+    import torch
+    types = {torch.uint8: capi.MI_8UC1, torch.float32: capi.MI_32FC1}
+    if t.dim() != 2 or t.dtype not in types:
+        raise MiError(-2, "a 2-D uint8 or float32 image")
+    return types[t.dtype]
+
+
+class CornernessCriteria:
+    """cv::cuda::CornernessCriteria (cudaimgproc.hpp:538-549): compute(src) -> the float32 response plane on the device.  Made by
+    createHarrisCorner / createMinEigenValCorner; srcType is capi.MI_8UC1 or capi.MI_32FC1 (the OpenCV codes)."""
+
+    def __init__(self, srcType, blockSize, ksize, borderType, harris, k=0.0):
+        self._h = None
+        self._p = capi.CornerParams(int(srcType), int(blockSize), int(ksize), int(borderType), int(bool(harris)), float(k))
+        h = C.c_void_p()
+        capi.check(capi.lib().mi_corner_create(C.byref(self._p), C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        _destroy(self, "mi_corner_destroy")
+
+    def compute(self, src, dst=None, stream=None):
+        import torch
+        src = _u8(src)
+        if _src_type(src) != self._p.type:
+            raise MiError(-2, "src.type() == srcType")   # corners.cpp:117
+        if dst is None:
+            dst = torch.empty(src.shape, dtype=torch.float32, device=src.device)
+        sp = C.c_void_p(stream) if stream is not None else capi.current_stream_ptr()
+        capi.check(capi.lib().mi_corner_compute(self._h, C.byref(capi.mat_from_tensor(src)), C.byref(capi.mat_from_tensor(dst)), sp))
+        return dst
+
+
+def createHarrisCorner(srcType, blockSize, ksize, k, borderType=BORDER_REFLECT101) -> CornernessCriteria:
+    """cv::cuda::createHarrisCorner, cudaimgproc.hpp:562"""
+    return CornernessCriteria(srcType, blockSize, ksize, borderType, True, k)
+
+
+def createMinEigenValCorner(srcType, blockSize, ksize, borderType=BORDER_REFLECT101) -> CornernessCriteria:
+    """cv::cuda::createMinEigenValCorner, cudaimgproc.hpp:575"""
+    return CornernessCriteria(srcType, blockSize, ksize, borderType, False)
+
+
+class CornersDetector:
+    """cv::cuda::CornersDetector (cudaimgproc.hpp:581-597), made by createGoodFeaturesToTrackDetector.  detect(image[, mask]) -> the
+    corners as a (1, N, 2) float32 device tensor {x, y}, strongest first, which SparsePyrLKOpticalFlow.calc takes as prevPts unchanged;
+    (1, 0, 2) where the reference releases the output."""
+
+    def __init__(self, srcType, maxCorners=1000, qualityLevel=0.01, minDistance=0.0, blockSize=3, useHarrisDetector=False, harrisK=0.04):
+        self._h = None
+        self._p = capi.GfttParams(int(srcType), int(maxCorners), float(qualityLevel), float(minDistance), int(blockSize),
+                                  int(bool(useHarrisDetector)), float(harrisK))
+        h = C.c_void_p()
+        capi.check(capi.lib().mi_gftt_create(C.byref(self._p), C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        _destroy(self, "mi_gftt_destroy")
+
+    def _set(self, **kw):
+        p = capi.GfttParams.from_buffer_copy(self._p)
+        for k, v in kw.items():
+            setattr(p, k, v)
+        capi.check(capi.lib().mi_gftt_set_params(self._h, C.byref(p)))
+        self._p = p
+
+    def setMaxCorners(self, maxCorners): self._set(max_corners=int(maxCorners))
+    def setMinDistance(self, minDistance): self._set(min_distance=float(minDistance))
+
+    def scratchBytes(self):
+        b = C.c_size_t()
+        capi.check(capi.lib().mi_gftt_scratch_bytes(self._h, C.byref(b)))
+        return b.value
+
+    def detect(self, image, mask=None, stream=None):
+        import torch
+        image = _u8(image)
+        if _src_type(image) != self._p.type:
+            raise MiError(-2, "image.type() == srcType")
+        rows, cols = image.shape
+        cap = max(1000, int(rows * cols * 0.05))   # gftt.cpp:122
+        need = min(self._p.max_corners, cap) if self._p.max_corners > 0 else cap
+        out = torch.empty((1, need, 2), dtype=torch.float32, device=image.device)
+        n = C.c_int()
+        sp = C.c_void_p(stream) if stream is not None else capi.current_stream_ptr()
+        mm = C.byref(capi.mat_from_tensor(_u8(mask))) if mask is not None else None
+        capi.check(capi.lib().mi_gftt_detect(self._h, C.byref(capi.mat_from_tensor(image)), mm, C.byref(capi.mat_from_tensor(out)), C.byref(n), sp))
+        return out[:, : n.value]
+
+
+def createGoodFeaturesToTrackDetector(srcType, maxCorners=1000, qualityLevel=0.01, minDistance=0.0, blockSize=3, useHarrisDetector=False,
+                                      harrisK=0.04) -> CornersDetector:
+    """cv::cuda::createGoodFeaturesToTrackDetector, cudaimgproc.hpp:617-618"""
+    return CornersDetector(srcType, maxCorners, qualityLevel, minDistance, blockSize, useHarrisDetector, harrisK)
+
+
+def _f3(v):
+    return (C.c_float * 3)(*[float(x) for x in v])
+
+
+def gftt_response(src, deriv, smooth, blockSize, borderType=BORDER_REFLECT101, harris=False, k=0.04, form=0, dst=None, qualityLevel=None):
+    """Stage entry: the response plane from explicit 3-tap kernels; form 0 / 1 / 2: the plan's choice / one launch / two launches.
+    -> the plane, or (plane, threshold) with qualityLevel: (float)((double)max * qualityLevel) as the device computes it"""
+    import torch
+    src = _u8(src)
+    if dst is None:
+        dst = torch.empty(src.shape, dtype=torch.float32, device=src.device)
+    thr = C.c_float()
+    capi.check(capi.lib().mi_gftt_response(C.byref(capi.mat_from_tensor(src)), _f3(deriv), _f3(smooth), int(blockSize), int(borderType),
+                                           int(bool(harris)), float(k), int(form), C.byref(capi.mat_from_tensor(dst)),
+                                           float(qualityLevel or 0.0), C.byref(thr) if qualityLevel is not None else None,
+                                           capi.current_stream_ptr()))
+    return dst if qualityLevel is None else (dst, thr.value)
+
+
+def gftt_find_corners(response, threshold, mask=None, max_count=1000):
+    """Stage entry: findCorners -> (1, n, 2) float32 {x, y}, the first max_count in row-major order"""
+    import torch
+    out = torch.empty((1, int(max_count), 2), dtype=torch.float32, device=response.device)
+    n = C.c_int()
+    mm = C.byref(capi.mat_from_tensor(_u8(mask))) if mask is not None else None
+    capi.check(capi.lib().mi_gftt_find_corners(C.byref(capi.mat_from_tensor(response)), float(threshold), mm, C.byref(capi.mat_from_tensor(out)),
+                                               C.byref(n), capi.current_stream_ptr()))
+    return out[:, : n.value]
+
+
+def gftt_sort(response, corners):
+    """Stage entry: corners (1, n, 2) by response descending, then (y, x) ascending"""
+    import torch
+    corners = corners.reshape(1, -1, 2).contiguous()
+    n = corners.shape[1]
+    out = torch.empty_like(corners)
+    if n:
+        capi.check(capi.lib().mi_gftt_sort(C.byref(capi.mat_from_tensor(response)), C.byref(capi.mat_from_tensor(corners)), n,
+                                           C.byref(capi.mat_from_tensor(out)), capi.current_stream_ptr()))
+    return out
+
+
+def gftt_min_distance(points, rows, cols, minDistance, maxCorners):
+    """Stage entry, host only: the grid loop of gftt.cpp:140-207 on an (n, 2) float32 NumPy array -> the survivors"""
+    import numpy as np
+    p = np.ascontiguousarray(points, np.float32).reshape(-1, 2)
+    out = np.empty_like(p) if len(p) else np.empty((1, 2), np.float32)
+    src = p if len(p) else np.zeros((1, 2), np.float32)
+    n = C.c_int()
+    fp = C.POINTER(C.c_float)
+    capi.check(capi.lib().mi_gftt_min_distance(src.ctypes.data_as(fp), len(p), int(rows), int(cols), float(minDistance), int(maxCorners),
+                                               out.ctypes.data_as(fp), C.byref(n)))
+    return out[: n.value].copy()
+
+
 def _host_mat(a):
     """a C-contiguous 2-D int32 / float32 / uint8 NumPy array as a HOST mi_mat (the array must outlive the call)"""
     import numpy as np
