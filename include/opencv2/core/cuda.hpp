@@ -100,6 +100,28 @@ inline void miCheck(int rc)
     }
 }
 
+namespace miflow_detail {
+// The one owner of a C-ABI handle and of the parameters the library last accepted, held by every *Impl class of the drop-in headers.
+// One rule for a setter: copy the struct, ask the library, commit on acceptance; a rejected value leaves the object as it was.
+// Create / Set may be nullptr where the class has no such entry (no setter; a create with further arguments goes through `create`).
+template <class H, class P, int (*Create)(const P *, H **), int (*Set)(H *, const P *), void (*Destroy)(H *)>
+class ParamHandle {
+public:
+    explicit ParamHandle(const P &p) : p_(p) { miCheck(Create(&p_, &h_)); }
+    template <class F> ParamHandle(const P &p, F create) : p_(p) { miCheck(create(&p_, &h_)); }   // e.g. ORB's pattern matrix
+    ~ParamHandle() { Destroy(h_); }
+    ParamHandle(const ParamHandle &) = delete;
+    ParamHandle &operator=(const ParamHandle &) = delete;
+    H *get() const { return h_; }
+    const P &params() const { return p_; }
+    template <class F> void set(F edit) { P q = p_; edit(q); miCheck(Set(h_, &q)); p_ = q; }
+    template <class G> void refresh(G get) { miCheck(get(h_, &p_)); }   // a call that changes the library's copy (TV-L1 shrinks nscales)
+private:
+    P p_;
+    H *h_ = nullptr;
+};
+}  // namespace miflow_detail
+
 inline int getCudaEnabledDeviceCount() { return mi_device_count(); }
 inline void setDevice(int d) { miCheck(mi_set_device(d)); }
 inline int getDevice() { int d = 0; miCheck(mi_get_device(&d)); return d; }

@@ -91,10 +91,7 @@ inline mi_mat packedRow(GpuMat &m, int row, int nq, int cn, int type)
 
 class BFMatcherImpl final : public DescriptorMatcher {
 public:
-    explicit BFMatcherImpl(int normType) { miCheck(mi_bf_create(normType, &h_)); }
-    ~BFMatcherImpl() override { mi_bf_destroy(h_); }
-    BFMatcherImpl(const BFMatcherImpl &) = delete;
-    BFMatcherImpl &operator=(const BFMatcherImpl &) = delete;
+    explicit BFMatcherImpl(int normType) : h_(normType, [](const int *norm, mi_bfmatcher **h) { return mi_bf_create(*norm, h); }) {}
 
     bool isMaskSupported() const override { return true; }
     void add(const std::vector<GpuMat> &descriptors) override { coll_.insert(coll_.end(), descriptors.begin(), descriptors.end()); }
@@ -123,7 +120,7 @@ public:
         matches.create(2, nq, CV_32SC1);                                   // {trainIdx; distance}, brute_force_matcher.cpp:367-372
         mi_mat q = miMat(query), t = miMat(train), m = miMat(mask);
         mi_mat i = packedRow(matches, 0, nq, 1, CV_32SC1), d = packedRow(matches, 1, nq, 1, CV_32FC1);
-        miCheck(mi_bf_knn_match(h_, &q, &t, mask.empty() ? nullptr : &m, 1, 1, &i, nullptr, &d, stream.hipStream()));
+        miCheck(mi_bf_knn_match(h_.get(), &q, &t, mask.empty() ? nullptr : &m, 1, 1, &i, nullptr, &d, stream.hipStream()));
     }
     void matchAsync(InputArray query, OutputArray matches, const std::vector<GpuMat> &masks, Stream &stream) override
     {
@@ -134,7 +131,7 @@ public:
         collection(masks, ts, ms);
         mi_mat q = miMat(query);
         mi_mat i = packedRow(matches, 0, nq, 1, CV_32SC1), g = packedRow(matches, 1, nq, 1, CV_32SC1), d = packedRow(matches, 2, nq, 1, CV_32FC1);
-        miCheck(mi_bf_knn_match(h_, &q, ts.data(), ms.empty() ? nullptr : ms.data(), (int)ts.size(), 1, &i, &g, &d, stream.hipStream()));
+        miCheck(mi_bf_knn_match(h_.get(), &q, ts.data(), ms.empty() ? nullptr : ms.data(), (int)ts.size(), 1, &i, &g, &d, stream.hipStream()));
     }
     void matchConvert(InputArray gpu_matches, std::vector<DMatch> &matches) override
     {
@@ -176,7 +173,7 @@ public:
         collection(masks, ts, ms);
         mi_mat q = miMat(query);
         mi_mat i = packedRows(g, 0, nq, k, CV_32SC1), im = packedRows(g, nq, nq, k, CV_32SC1), d = packedRows(g, 2 * nq, nq, k, CV_32FC1);
-        miCheck(mi_bf_knn_match(h_, &q, ts.data(), ms.empty() ? nullptr : ms.data(), (int)ts.size(), k, &i, &im, &d, nullptr));
+        miCheck(mi_bf_knn_match(h_.get(), &q, ts.data(), ms.empty() ? nullptr : ms.data(), (int)ts.size(), k, &i, &im, &d, nullptr));
         std::vector<int> h((size_t)3 * nq * k);
         g.download(h.data(), sizeof(int) * k);
         unpackLists(h.data(), h.data() + (size_t)nq * k, reinterpret_cast<const float *>(h.data() + (size_t)2 * nq * k), nq, k, k, nullptr,
@@ -194,7 +191,7 @@ public:
             matches.create(2 * nq, k, CV_32SC1);                           // :630-636 (no allDist buffer is needed here)
             i = packedRows(matches, 0, nq, k, CV_32SC1); d = packedRows(matches, nq, nq, k, CV_32FC1);
         }
-        miCheck(mi_bf_knn_match(h_, &q, &t, mask.empty() ? nullptr : &m, 1, k, &i, nullptr, &d, stream.hipStream()));
+        miCheck(mi_bf_knn_match(h_.get(), &q, &t, mask.empty() ? nullptr : &m, 1, k, &i, nullptr, &d, stream.hipStream()));
     }
     void knnMatchAsync(InputArray query, OutputArray matches, int k, const std::vector<GpuMat> &masks, Stream &stream) override
     {
@@ -206,7 +203,7 @@ public:
         collection(masks, ts, ms);
         mi_mat q = miMat(query);
         mi_mat i = packedRow(matches, 0, nq, 2, CV_32SC1), g = packedRow(matches, 1, nq, 2, CV_32SC1), d = packedRow(matches, 2, nq, 2, CV_32FC1);
-        miCheck(mi_bf_knn_match(h_, &q, ts.data(), ms.empty() ? nullptr : ms.data(), (int)ts.size(), 2, &i, &g, &d, stream.hipStream()));
+        miCheck(mi_bf_knn_match(h_.get(), &q, ts.data(), ms.empty() ? nullptr : ms.data(), (int)ts.size(), 2, &i, &g, &d, stream.hipStream()));
     }
     void knnMatchConvert(InputArray gpu_matches, std::vector<std::vector<DMatch> > &matches, bool compactResult) override
     {
@@ -250,7 +247,7 @@ public:
         mi_mat q = miMat(query), t = miMat(train), m = miMat(mask);
         mi_mat i = packedRows(matches, 0, nq, cols, CV_32SC1), d = packedRows(matches, nq, nq, cols, CV_32FC1);
         mi_mat n = packedRows(matches, 2 * nq, 1, nq, CV_32SC1);
-        miCheck(mi_bf_radius_match(h_, &q, &t, mask.empty() ? nullptr : &m, 1, maxDistance, &i, nullptr, &d, &n, stream.hipStream()));
+        miCheck(mi_bf_radius_match(h_.get(), &q, &t, mask.empty() ? nullptr : &m, 1, maxDistance, &i, nullptr, &d, &n, stream.hipStream()));
     }
     void radiusMatchAsync(InputArray query, OutputArray matches, float maxDistance, const std::vector<GpuMat> &masks, Stream &stream) override
     {
@@ -262,7 +259,7 @@ public:
         mi_mat q = miMat(query);
         mi_mat i = packedRows(matches, 0, nq, nq, CV_32SC1), g = packedRows(matches, nq, nq, nq, CV_32SC1);
         mi_mat d = packedRows(matches, 2 * nq, nq, nq, CV_32FC1), n = packedRows(matches, 3 * nq, 1, nq, CV_32SC1);
-        miCheck(mi_bf_radius_match(h_, &q, ts.data(), ms.empty() ? nullptr : ms.data(), (int)ts.size(), maxDistance, &i, &g, &d, &n,
+        miCheck(mi_bf_radius_match(h_.get(), &q, ts.data(), ms.empty() ? nullptr : ms.data(), (int)ts.size(), maxDistance, &i, &g, &d, &n,
                                    stream.hipStream()));
     }
     void radiusMatchConvert(InputArray gpu_matches, std::vector<std::vector<DMatch> > &matches, bool compactResult) override
@@ -307,7 +304,7 @@ private:
         }
     }
 
-    mi_bfmatcher *h_ = nullptr;
+    ParamHandle<mi_bfmatcher, int, nullptr, nullptr, mi_bf_destroy> h_;   // the norm type is its only parameter, fixed at create
     std::vector<GpuMat> coll_;
 };
 }  // namespace miflow_detail
@@ -367,14 +364,7 @@ namespace miflow_detail {
 /** twin of FAST_Impl, cudafeatures2d/src/fast.cpp:63-209 */
 class FastImpl final : public cuda::FastFeatureDetector {
 public:
-    FastImpl(int threshold, bool nonmaxSuppression, int max_npoints)
-    {
-        p_.threshold = threshold; p_.nonmax_suppression = nonmaxSuppression ? 1 : 0; p_.max_npoints = max_npoints;
-        miCheck(mi_fast_create(&p_, &h_));
-    }
-    ~FastImpl() override { mi_fast_destroy(h_); }
-    FastImpl(const FastImpl &) = delete;
-    FastImpl &operator=(const FastImpl &) = delete;
+    explicit FastImpl(const mi_fast_params &p) : h_(p) {}
     void detect(InputArray image, std::vector<KeyPoint> &keypoints, InputArray mask) override
     {
         if (image.empty()) { keypoints.clear(); return; }   // fast.cpp:109-113
@@ -384,10 +374,10 @@ public:
     }
     void detectAsync(InputArray image, OutputArray keypoints, InputArray mask, Stream &stream) override
     {
-        GpuMat buf(ROWS_COUNT, p_.max_npoints, CV_32FC1);   // the pool's buffer of fast.cpp:116
+        GpuMat buf(ROWS_COUNT, h_.params().max_npoints, CV_32FC1);   // the pool's buffer of fast.cpp:116
         mi_mat i = miMat(image), m = miMat(mask), k = miMat(buf);
         int n = 0;
-        miCheck(mi_fast_detect(h_, &i, mask.empty() ? nullptr : &m, &k, &n, stream.hipStream()));
+        miCheck(mi_fast_detect(h_.get(), &i, mask.empty() ? nullptr : &m, &k, &n, stream.hipStream()));
         if (n == 0) { keypoints.release(); return; }   // fast.cpp:146-150,158-161
         keypoints = buf(Rect(0, 0, n, ROWS_COUNT));    // keypoints.cols = count (:164)
     }
@@ -408,30 +398,24 @@ public:
         const float *resp = (const float *)((const unsigned char *)host_keypoints + RESPONSE_ROW * step);
         for (int i = 0; i < npoints; ++i) keypoints[i] = KeyPoint(loc[2 * i], loc[2 * i + 1], (float)FEATURE_SIZE, -1, resp[i]);
     }
-    void setThreshold(int v) override { set(v, p_.nonmax_suppression, p_.max_npoints); }
-    int getThreshold() const override { return p_.threshold; }
-    void setNonmaxSuppression(bool f) override { set(p_.threshold, f ? 1 : 0, p_.max_npoints); }
-    bool getNonmaxSuppression() const override { return p_.nonmax_suppression != 0; }
-    void setMaxNumPoints(int v) override { set(p_.threshold, p_.nonmax_suppression, v); }
-    int getMaxNumPoints() const override { return p_.max_npoints; }
+    void setThreshold(int v) override { h_.set([=](auto &q) { q.threshold = v; }); }
+    int getThreshold() const override { return h_.params().threshold; }
+    void setNonmaxSuppression(bool f) override { h_.set([=](auto &q) { q.nonmax_suppression = f ? 1 : 0; }); }
+    bool getNonmaxSuppression() const override { return h_.params().nonmax_suppression != 0; }
+    void setMaxNumPoints(int v) override { h_.set([=](auto &q) { q.max_npoints = v; }); }
+    int getMaxNumPoints() const override { return h_.params().max_npoints; }
     void setType(int type) override { CV_Assert(type == cv::FastFeatureDetector::TYPE_9_16); }   // fast.cpp:85
     int getType() const override { return cv::FastFeatureDetector::TYPE_9_16; }
 private:
-    void set(int threshold, int nms, int max_npoints)   // a rejected value leaves the object as it was
-    {
-        mi_fast_params q = {threshold, nms, max_npoints};
-        miCheck(mi_fast_set_params(h_, &q));
-        p_ = q;
-    }
-    mi_fast_params p_;
-    mi_fast *h_ = nullptr;
+    ParamHandle<mi_fast, mi_fast_params, mi_fast_create, mi_fast_set_params, mi_fast_destroy> h_;
 };
 }  // namespace miflow_detail
 
 inline Ptr<cuda::FastFeatureDetector> FastFeatureDetector::create(int threshold, bool nonmaxSuppression, int type, int max_npoints)
 {
     CV_Assert(type == cv::FastFeatureDetector::TYPE_9_16);   // fast.cpp:213
-    return makePtr<miflow_detail::FastImpl>(threshold, nonmaxSuppression, max_npoints);
+    const mi_fast_params p = {threshold, nonmaxSuppression ? 1 : 0, max_npoints};
+    return makePtr<miflow_detail::FastImpl>(p);
 }
 
 // ---------------------------------------------------------------- ORB
@@ -502,18 +486,13 @@ namespace miflow_detail {
 /** twin of ORB_Impl, cudafeatures2d/src/orb.cpp:338-913 */
 class OrbImpl final : public cuda::ORB {
 public:
-    OrbImpl(const int *pattern0, int nfeatures, float scaleFactor, int nlevels, int edgeThreshold, int firstLevel, int WTA_K, int scoreType,
-            int patchSize, int fastThreshold, bool blurForDescriptor)
+    OrbImpl(const int *pattern0, const mi_orb_params &p)
+        : h_(p, [=](const mi_orb_params *q, mi_orb **h) {
+              mi_mat pool = {const_cast<int *>(pattern0), 8, 512, 2, MI_32SC1};
+              return mi_orb_create(q, pattern0 ? &pool : nullptr, h);
+          })
     {
-        CV_Assert(patchSize >= 2);                               // orb.cpp:500
-        CV_Assert(WTA_K == 2 || WTA_K == 3 || WTA_K == 4);       // orb.cpp:501
-        p_ = {nfeatures, scaleFactor, nlevels, edgeThreshold, firstLevel, WTA_K, scoreType, patchSize, fastThreshold, blurForDescriptor ? 1 : 0};
-        mi_mat pool = {const_cast<int *>(pattern0), 8, 512, 2, MI_32SC1};
-        miCheck(mi_orb_create(&p_, pattern0 ? &pool : nullptr, &h_));
     }
-    ~OrbImpl() override { mi_orb_destroy(h_); }
-    OrbImpl(const OrbImpl &) = delete;
-    OrbImpl &operator=(const OrbImpl &) = delete;
 
     void detect(InputArray image, std::vector<KeyPoint> &keypoints, InputArray mask) override
     {
@@ -564,42 +543,37 @@ public:
     int descriptorSize() const override { return cv::ORB::kBytes; }
     int descriptorType() const override { return CV_8U; }
     int defaultNorm() const override { return NORM_HAMMING; }
-    void setMaxFeatures(int v) override { mi_orb_params q = p_; q.nfeatures = v; set(q); }
-    int getMaxFeatures() const override { return p_.nfeatures; }
-    void setScaleFactor(double v) override { mi_orb_params q = p_; q.scale_factor = (float)v; set(q); }
-    double getScaleFactor() const override { return p_.scale_factor; }
-    void setNLevels(int v) override { mi_orb_params q = p_; q.nlevels = v; set(q); }
-    int getNLevels() const override { return p_.nlevels; }
-    void setEdgeThreshold(int v) override { mi_orb_params q = p_; q.edge_threshold = v; set(q); }
-    int getEdgeThreshold() const override { return p_.edge_threshold; }
-    void setFirstLevel(int v) override { mi_orb_params q = p_; q.first_level = v; set(q); }
-    int getFirstLevel() const override { return p_.first_level; }
-    void setWTA_K(int v) override { CV_Assert(v == 2 || v == 3 || v == 4); mi_orb_params q = p_; q.wta_k = v; set(q); }   // orb.cpp:376
-    int getWTA_K() const override { return p_.wta_k; }
-    void setScoreType(int v) override { mi_orb_params q = p_; q.score_type = v; set(q); }
-    int getScoreType() const override { return p_.score_type; }
-    void setPatchSize(int v) override { CV_Assert(v >= 2); mi_orb_params q = p_; q.patch_size = v; set(q); }             // orb.cpp:382
-    int getPatchSize() const override { return p_.patch_size; }
-    void setFastThreshold(int v) override { mi_orb_params q = p_; q.fast_threshold = v; set(q); }
-    int getFastThreshold() const override { return p_.fast_threshold; }
-    void setBlurForDescriptor(bool v) override { mi_orb_params q = p_; q.blur_for_descriptor = v ? 1 : 0; set(q); }
-    bool getBlurForDescriptor() const override { return p_.blur_for_descriptor != 0; }
-    int getPatternSource() const override { int s = 0; miCheck(mi_orb_pattern_source(h_, &s)); return s; }
+    void setMaxFeatures(int v) override { h_.set([=](auto &q) { q.nfeatures = v; }); }
+    int getMaxFeatures() const override { return h_.params().nfeatures; }
+    void setScaleFactor(double v) override { h_.set([=](auto &q) { q.scale_factor = (float)v; }); }
+    double getScaleFactor() const override { return h_.params().scale_factor; }
+    void setNLevels(int v) override { h_.set([=](auto &q) { q.nlevels = v; }); }
+    int getNLevels() const override { return h_.params().nlevels; }
+    void setEdgeThreshold(int v) override { h_.set([=](auto &q) { q.edge_threshold = v; }); }
+    int getEdgeThreshold() const override { return h_.params().edge_threshold; }
+    void setFirstLevel(int v) override { h_.set([=](auto &q) { q.first_level = v; }); }
+    int getFirstLevel() const override { return h_.params().first_level; }
+    void setWTA_K(int v) override { CV_Assert(v == 2 || v == 3 || v == 4); h_.set([=](auto &q) { q.wta_k = v; }); }   // orb.cpp:376
+    int getWTA_K() const override { return h_.params().wta_k; }
+    void setScoreType(int v) override { h_.set([=](auto &q) { q.score_type = v; }); }
+    int getScoreType() const override { return h_.params().score_type; }
+    void setPatchSize(int v) override { CV_Assert(v >= 2); h_.set([=](auto &q) { q.patch_size = v; }); }             // orb.cpp:382
+    int getPatchSize() const override { return h_.params().patch_size; }
+    void setFastThreshold(int v) override { h_.set([=](auto &q) { q.fast_threshold = v; }); }
+    int getFastThreshold() const override { return h_.params().fast_threshold; }
+    void setBlurForDescriptor(bool v) override { h_.set([=](auto &q) { q.blur_for_descriptor = v ? 1 : 0; }); }
+    bool getBlurForDescriptor() const override { return h_.params().blur_for_descriptor != 0; }
+    int getPatternSource() const override { int s = 0; miCheck(mi_orb_pattern_source(h_.get(), &s)); return s; }
 private:
-    void set(const mi_orb_params &q)   // a rejected value leaves the object as it was
-    {
-        miCheck(mi_orb_set_params(h_, &q));
-        p_ = q;
-    }
     // detection: *kp (and *desc, if wanted) receive the first n columns / rows, or stay empty
     void run(InputArray image, InputArray mask, GpuMat *kp, GpuMat *desc, Stream &stream)
     {
-        const int cap = p_.nfeatures > 0 ? p_.nfeatures : 1;
+        const int cap = h_.params().nfeatures > 0 ? h_.params().nfeatures : 1;
         GpuMat kbuf(ROWS_COUNT, cap, CV_32FC1), dbuf;
         if (desc) dbuf.create(cap, cv::ORB::kBytes, CV_8UC1);
         mi_mat i = miMat(image), m = miMat(mask), k = miMat(kbuf), d = miMat(dbuf);
         int n = 0;
-        miCheck(mi_orb_detect_and_compute(h_, &i, mask.empty() ? nullptr : &m, &k, desc ? &d : nullptr, &n, 0, stream.hipStream()));
+        miCheck(mi_orb_detect_and_compute(h_.get(), &i, mask.empty() ? nullptr : &m, &k, desc ? &d : nullptr, &n, 0, stream.hipStream()));
         if (n == 0) return;   // orb.cpp:793-797,834-838: released
         *kp = kbuf(Rect(0, 0, n, ROWS_COUNT));
         if (desc) *desc = dbuf(Rect(0, 0, cv::ORB::kBytes, n));
@@ -617,28 +591,29 @@ private:
         }
         GpuMat dbuf(n, cv::ORB::kBytes, CV_8UC1);
         mi_mat i = miMat(image), k = {h.data(), (size_t)n * 4, ROWS_COUNT, n, MI_32FC1}, d = miMat(dbuf);
-        const int rc = mi_orb_detect_and_compute(h_, &i, nullptr, &k, &d, &n, 1, nullptr);
-        mi_orb_get_params(h_, &p_);   // nlevels is overwritten (orb.cpp:587-594)
+        const int rc = mi_orb_detect_and_compute(h_.get(), &i, nullptr, &k, &d, &n, 1, nullptr);
+        h_.refresh([](const mi_orb *h, mi_orb_params *q) { mi_orb_get_params(h, q); return 0; });   // nlevels is overwritten (orb.cpp:587-594); rc is reported first
         miCheck(rc);
         descriptors = dbuf;
     }
-    mi_orb_params p_;
-    mi_orb *h_ = nullptr;
+    ParamHandle<mi_orb, mi_orb_params, nullptr, mi_orb_set_params, mi_orb_destroy> h_;   // created with the pattern: see the constructor
 };
 }  // namespace miflow_detail
 
 inline Ptr<cuda::ORB> ORB::create(int nfeatures, float scaleFactor, int nlevels, int edgeThreshold, int firstLevel, int WTA_K, int scoreType,
                                   int patchSize, int fastThreshold, bool blurForDescriptor)
 {
-    return makePtr<miflow_detail::OrbImpl>(nullptr, nfeatures, scaleFactor, nlevels, edgeThreshold, firstLevel, WTA_K, scoreType, patchSize,
-                                           fastThreshold, blurForDescriptor);
+    return create(static_cast<const int *>(nullptr), nfeatures, scaleFactor, nlevels, edgeThreshold, firstLevel, WTA_K, scoreType, patchSize,
+                  fastThreshold, blurForDescriptor);
 }
 
 inline Ptr<cuda::ORB> ORB::create(const int *pattern0, int nfeatures, float scaleFactor, int nlevels, int edgeThreshold, int firstLevel, int WTA_K,
                                   int scoreType, int patchSize, int fastThreshold, bool blurForDescriptor)
 {
-    return makePtr<miflow_detail::OrbImpl>(pattern0, nfeatures, scaleFactor, nlevels, edgeThreshold, firstLevel, WTA_K, scoreType, patchSize,
-                                           fastThreshold, blurForDescriptor);
+    CV_Assert(patchSize >= 2);                               // orb.cpp:500
+    CV_Assert(WTA_K == 2 || WTA_K == 3 || WTA_K == 4);       // orb.cpp:501
+    const mi_orb_params p = {nfeatures, scaleFactor, nlevels, edgeThreshold, firstLevel, WTA_K, scoreType, patchSize, fastThreshold, blurForDescriptor ? 1 : 0};
+    return makePtr<miflow_detail::OrbImpl>(pattern0, p);
 }
 
 }  // namespace cuda

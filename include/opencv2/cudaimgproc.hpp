@@ -39,81 +39,67 @@ namespace miflow_detail {
 
 class CornerImpl final : public CornernessCriteria {
 public:
-    CornerImpl(int srcType, int blockSize, int ksize, int borderType, bool harris, double k)
-    {
-        mi_corner_params p;
-        p.type = srcType; p.block_size = blockSize; p.ksize = ksize; p.border_type = borderType; p.harris = harris ? 1 : 0; p.k = k;
-        miCheck(mi_corner_create(&p, &h_));
-    }
-    ~CornerImpl() override { mi_corner_destroy(h_); }
-    CornerImpl(const CornerImpl &) = delete;
-    CornerImpl &operator=(const CornerImpl &) = delete;
+    explicit CornerImpl(const mi_corner_params &p) : h_(p) {}
     void compute(InputArray src, OutputArray dst, Stream &stream) override
     {
         dst.create(src.size(), CV_32FC1);   // corners.cpp:144,172
         mi_mat s = miMat(src), d = miMat(dst);
-        miCheck(mi_corner_compute(h_, &s, &d, stream.hipStream()));
+        miCheck(mi_corner_compute(h_.get(), &s, &d, stream.hipStream()));
     }
 private:
-    mi_corner *h_ = nullptr;
+    ParamHandle<mi_corner, mi_corner_params, mi_corner_create, nullptr, mi_corner_destroy> h_;   // no setter
 };
 
 class GfttImpl final : public CornersDetector {
 public:
-    GfttImpl(int srcType, int maxCorners, double qualityLevel, double minDistance, int blockSize, bool useHarrisDetector, double harrisK)
-    {
-        p_.type = srcType; p_.max_corners = maxCorners; p_.quality_level = qualityLevel; p_.min_distance = minDistance;
-        p_.block_size = blockSize; p_.use_harris = useHarrisDetector ? 1 : 0; p_.harris_k = harrisK;
-        miCheck(mi_gftt_create(&p_, &h_));
-    }
-    ~GfttImpl() override { mi_gftt_destroy(h_); }
-    GfttImpl(const GfttImpl &) = delete;
-    GfttImpl &operator=(const GfttImpl &) = delete;
+    explicit GfttImpl(const mi_gftt_params &p) : h_(p) {}
     void detect(InputArray image, OutputArray corners, InputArray mask, Stream &stream) override
     {
         CV_Assert(mask.empty() || (mask.type() == CV_8UC1 && mask.size() == image.size()));   // gftt.cpp:114
         CV_Assert(!image.empty());
         const int capacity = std::max(1000, static_cast<int>(image.size().area() * 0.05));   // gftt.cpp:122
-        GpuMat out(1, p_.max_corners > 0 ? std::min(p_.max_corners, capacity) : capacity, CV_32FC2);
+        GpuMat out(1, h_.params().max_corners > 0 ? std::min(h_.params().max_corners, capacity) : capacity, CV_32FC2);
         mi_mat i = miMat(image), m = miMat(mask), o = miMat(out);
         int n = 0;
-        miCheck(mi_gftt_detect(h_, &i, mask.empty() ? nullptr : &m, &o, &n, stream.hipStream()));
+        miCheck(mi_gftt_detect(h_.get(), &i, mask.empty() ? nullptr : &m, &o, &n, stream.hipStream()));
         if (n == 0) { corners.release(); return; }   // gftt.cpp:126-130
         corners = out(Rect(0, 0, n, 1));
     }
-    void setMaxCorners(int maxCorners) override { set(maxCorners, p_.min_distance); }
-    void setMinDistance(double minDistance) override { set(p_.max_corners, minDistance); }
+    void setMaxCorners(int maxCorners) override { h_.set([=](auto &q) { q.max_corners = maxCorners; }); }
+    void setMinDistance(double minDistance) override { h_.set([=](auto &q) { q.min_distance = minDistance; }); }
 private:
-    void set(int maxCorners, double minDistance)   // a rejected value leaves the object as it was
-    {
-        mi_gftt_params p = p_;
-        p.max_corners = maxCorners; p.min_distance = minDistance;
-        miCheck(mi_gftt_set_params(h_, &p));
-        p_ = p;
-    }
-    mi_gftt_params p_;
-    mi_gftt *h_ = nullptr;
+    ParamHandle<mi_gftt, mi_gftt_params, mi_gftt_create, mi_gftt_set_params, mi_gftt_destroy> h_;
 };
+
+inline Ptr<CornernessCriteria> makeCorner(int srcType, int blockSize, int ksize, int borderType, bool harris, double k)
+{
+    mi_corner_params p;
+    p.type = srcType; p.block_size = blockSize; p.ksize = ksize; p.border_type = borderType; p.harris = harris ? 1 : 0; p.k = k;
+    return makePtr<CornerImpl>(p);
+}
 
 }  // namespace miflow_detail
 
 /** cudaimgproc.hpp:562 */
 inline Ptr<CornernessCriteria> createHarrisCorner(int srcType, int blockSize, int ksize, double k, int borderType = BORDER_REFLECT101)
 {
-    return makePtr<miflow_detail::CornerImpl>(srcType, blockSize, ksize, borderType, true, k);
+    return miflow_detail::makeCorner(srcType, blockSize, ksize, borderType, true, k);
 }
 
 /** cudaimgproc.hpp:575 */
 inline Ptr<CornernessCriteria> createMinEigenValCorner(int srcType, int blockSize, int ksize, int borderType = BORDER_REFLECT101)
 {
-    return makePtr<miflow_detail::CornerImpl>(srcType, blockSize, ksize, borderType, false, 0.0);
+    return miflow_detail::makeCorner(srcType, blockSize, ksize, borderType, false, 0.0);
 }
 
 /** cudaimgproc.hpp:617-618 */
 inline Ptr<CornersDetector> createGoodFeaturesToTrackDetector(int srcType, int maxCorners = 1000, double qualityLevel = 0.01, double minDistance = 0.0,
                                                               int blockSize = 3, bool useHarrisDetector = false, double harrisK = 0.04)
 {
-    return makePtr<miflow_detail::GfttImpl>(srcType, maxCorners, qualityLevel, minDistance, blockSize, useHarrisDetector, harrisK);
+    mi_gftt_params p;
+    p.type = srcType; p.max_corners = maxCorners; p.quality_level = qualityLevel; p.min_distance = minDistance;
+    p.block_size = blockSize; p.use_harris = useHarrisDetector ? 1 : 0; p.harris_k = harrisK;
+    return makePtr<miflow_detail::GfttImpl>(p);
 }
 
 }  // namespace cuda

@@ -36,70 +36,51 @@ public:
 namespace miflow_detail {
 class TVL1Impl final : public OpticalFlowDual_TVL1 {
 public:
-    explicit TVL1Impl(const mi_tvl1_params &p) : p_(p) { miCheck(mi_tvl1_create(&p_, &h_)); }
-    ~TVL1Impl() override { mi_tvl1_destroy(h_); }
-    TVL1Impl(const TVL1Impl &) = delete;
-    TVL1Impl &operator=(const TVL1Impl &) = delete;
+    explicit TVL1Impl(const mi_tvl1_params &p) : h_(p) {}
     void calc(InputArray I0, InputArray I1, InputOutputArray flow, Stream &stream) override
     {
         // BufferPool/merge of the reference (tvl1flow.cpp:175-182): the flow matrix is (re)allocated by the callee
-        if (!p_.use_initial_flow) flow.create(I0.size(), CV_32FC2);
+        if (!h_.params().use_initial_flow) flow.create(I0.size(), CV_32FC2);
         mi_mat a = miMat(I0), b = miMat(I1), f = miMat(flow);
-        miCheck(mi_tvl1_calc(h_, &a, &b, &f, stream.hipStream()));
+        miCheck(mi_tvl1_calc(h_.get(), &a, &b, &f, stream.hipStream()));
         // the reference shrinks nscales_ for good when a pyramid level falls below 16 px (tvl1flow.cpp:243-247)
-        miCheck(mi_tvl1_get_params(h_, &p_));
+        h_.refresh(mi_tvl1_get_params);
     }
     // Batched-frames mode (miflow extension; reached through cv::cuda::miflow::calcBatch): n independent pairs of one size and
     // type per launch sequence, blockIdx.z = pair.  flows[i] is (re)allocated like calc() does.
     void calcBatch(const std::vector<GpuMat> &I0s, const std::vector<GpuMat> &I1s, std::vector<GpuMat> &flows, Stream &stream)
     {
         CV_Assert(!I0s.empty() && I0s.size() == I1s.size());
-        if (!p_.use_initial_flow) flows.resize(I0s.size());
+        if (!h_.params().use_initial_flow) flows.resize(I0s.size());
         CV_Assert(flows.size() == I0s.size());
         std::vector<mi_mat> a(I0s.size()), b(I0s.size()), f(I0s.size());
         for (size_t i = 0; i < I0s.size(); ++i) {
-            if (!p_.use_initial_flow) flows[i].create(I0s[i].size(), CV_32FC2);
+            if (!h_.params().use_initial_flow) flows[i].create(I0s[i].size(), CV_32FC2);
             a[i] = miMat(I0s[i]); b[i] = miMat(I1s[i]); f[i] = miMat(flows[i]);
         }
-        miCheck(mi_tvl1_calc_batch(h_, (int)a.size(), a.data(), b.data(), f.data(), stream.hipStream()));
-        miCheck(mi_tvl1_get_params(h_, &p_));
+        miCheck(mi_tvl1_calc_batch(h_.get(), (int)a.size(), a.data(), b.data(), f.data(), stream.hipStream()));
+        h_.refresh(mi_tvl1_get_params);
     }
     void setExtra(int semantics, int exact_math, int time_block, int lanes)
     {
-        mi_tvl1_params q = p_;
-        q.semantics = semantics; q.exact_math = exact_math; q.time_block = time_block; q.lanes = lanes;
-        miCheck(mi_tvl1_set_params(h_, &q));
-        p_ = q;
+        h_.set([=](auto &q) { q.semantics = semantics; q.exact_math = exact_math; q.time_block = time_block; q.lanes = lanes; });
     }
-    void setStopSlack(int slack)
-    {
-        mi_tvl1_params q = p_;
-        q.stop_slack = slack;
-        miCheck(mi_tvl1_set_params(h_, &q));
-        p_ = q;
-    }
-    void setHostFeedback(int mode)
-    {
-        mi_tvl1_params q = p_;
-        q.host_feedback = mode;
-        miCheck(mi_tvl1_set_params(h_, &q));
-        p_ = q;
-    }
-    const mi_tvl1_params &params() const { return p_; }
+    void setStopSlack(int slack) { h_.set([=](auto &q) { q.stop_slack = slack; }); }
+    void setHostFeedback(int mode) { h_.set([=](auto &q) { q.host_feedback = mode; }); }
+    const mi_tvl1_params &params() const { return h_.params(); }
     String getDefaultName() const override { return "DenseOpticalFlow.OpticalFlowDual_TVL1"; }   // tvl1flow.cpp:122
 #define MIFLOW_PROP(T, Name, field) \
-    T get##Name() const override { return (T)p_.field; } \
-    void set##Name(T v) override { mi_tvl1_params q = p_; q.field = v; miCheck(mi_tvl1_set_params(h_, &q)); p_ = q; }
+    T get##Name() const override { return (T)h_.params().field; } \
+    void set##Name(T v) override { h_.set([=](auto &q) { q.field = v; }); }
     MIFLOW_PROP(double, Tau, tau) MIFLOW_PROP(double, Lambda, lambda) MIFLOW_PROP(double, Gamma, gamma)
     MIFLOW_PROP(double, Theta, theta) MIFLOW_PROP(int, NumScales, nscales) MIFLOW_PROP(int, NumWarps, warps)
     MIFLOW_PROP(double, Epsilon, epsilon) MIFLOW_PROP(int, NumIterations, iterations) MIFLOW_PROP(double, ScaleStep, scale_step)
 #undef MIFLOW_PROP
-    bool getUseInitialFlow() const override { return p_.use_initial_flow != 0; }
-    void setUseInitialFlow(bool v) override { mi_tvl1_params q = p_; q.use_initial_flow = v; miCheck(mi_tvl1_set_params(h_, &q)); p_ = q; }
-    mi_tvl1 *handle() { return h_; }
+    bool getUseInitialFlow() const override { return h_.params().use_initial_flow != 0; }
+    void setUseInitialFlow(bool v) override { h_.set([=](auto &q) { q.use_initial_flow = v; }); }
+    mi_tvl1 *handle() { return h_.get(); }
 private:
-    mi_tvl1_params p_;
-    mi_tvl1 *h_ = nullptr;
+    ParamHandle<mi_tvl1, mi_tvl1_params, mi_tvl1_create, mi_tvl1_set_params, mi_tvl1_destroy> h_;
 };
 }  // namespace miflow_detail
 
@@ -183,21 +164,18 @@ public:
 namespace miflow_detail {
 class FarnebackImpl final : public FarnebackOpticalFlow {
 public:
-    explicit FarnebackImpl(const mi_farneback_params &p) : p_(p) { miCheck(mi_farneback_create(&p_, &h_)); }
-    ~FarnebackImpl() override { mi_farneback_destroy(h_); }
-    FarnebackImpl(const FarnebackImpl &) = delete;
-    FarnebackImpl &operator=(const FarnebackImpl &) = delete;
+    explicit FarnebackImpl(const mi_farneback_params &p) : h_(p) {}
     void calc(InputArray I0, InputArray I1, InputOutputArray flow, Stream &stream) override
     {
-        if (!(p_.flags & MI_OPTFLOW_USE_INITIAL_FLOW)) flow.create(I0.size(), CV_32FC2);   // farneback.cpp:189-198 (create + merge)
+        if (!(h_.params().flags & MI_OPTFLOW_USE_INITIAL_FLOW)) flow.create(I0.size(), CV_32FC2);   // farneback.cpp:189-198 (create + merge)
         mi_mat a = miMat(I0), b = miMat(I1), f = miMat(flow);
-        miCheck(mi_farneback_calc(h_, &a, &b, &f, stream.hipStream()));
+        miCheck(mi_farneback_calc(h_.get(), &a, &b, &f, stream.hipStream()));
     }
     // Batched-frames mode (miflow extension; reached through cv::cuda::miflow::calcBatch)
     void calcBatch(const std::vector<GpuMat> &I0s, const std::vector<GpuMat> &I1s, std::vector<GpuMat> &flows, Stream &stream)
     {
         CV_Assert(!I0s.empty() && I0s.size() == I1s.size());
-        const bool init = (p_.flags & MI_OPTFLOW_USE_INITIAL_FLOW) != 0;
+        const bool init = (h_.params().flags & MI_OPTFLOW_USE_INITIAL_FLOW) != 0;
         if (!init) flows.resize(I0s.size());
         CV_Assert(flows.size() == I0s.size());
         std::vector<mi_mat> a(I0s.size()), b(I0s.size()), f(I0s.size());
@@ -205,21 +183,20 @@ public:
             if (!init) flows[i].create(I0s[i].size(), CV_32FC2);
             a[i] = miMat(I0s[i]); b[i] = miMat(I1s[i]); f[i] = miMat(flows[i]);
         }
-        miCheck(mi_farneback_calc_batch(h_, (int)a.size(), a.data(), b.data(), f.data(), stream.hipStream()));
+        miCheck(mi_farneback_calc_batch(h_.get(), (int)a.size(), a.data(), b.data(), f.data(), stream.hipStream()));
     }
     String getDefaultName() const override { return "DenseOpticalFlow.FarnebackOpticalFlow"; }   // farneback.cpp:132
 #define MIFLOW_PROP(T, Name, field) \
-    T get##Name() const override { return (T)p_.field; } \
-    void set##Name(T v) override { mi_farneback_params q = p_; q.field = v; miCheck(mi_farneback_set_params(h_, &q)); p_ = q; }
+    T get##Name() const override { return (T)h_.params().field; } \
+    void set##Name(T v) override { h_.set([=](auto &q) { q.field = v; }); }
     MIFLOW_PROP(int, NumLevels, num_levels) MIFLOW_PROP(double, PyrScale, pyr_scale) MIFLOW_PROP(int, WinSize, win_size)
     MIFLOW_PROP(int, NumIters, num_iters) MIFLOW_PROP(int, PolyN, poly_n) MIFLOW_PROP(double, PolySigma, poly_sigma)
     MIFLOW_PROP(int, Flags, flags)
 #undef MIFLOW_PROP
-    bool getFastPyramids() const override { return p_.fast_pyramids != 0; }
-    void setFastPyramids(bool v) override { mi_farneback_params q = p_; q.fast_pyramids = v; miCheck(mi_farneback_set_params(h_, &q)); p_ = q; }
+    bool getFastPyramids() const override { return h_.params().fast_pyramids != 0; }
+    void setFastPyramids(bool v) override { h_.set([=](auto &q) { q.fast_pyramids = v; }); }
 private:
-    mi_farneback_params p_;
-    mi_farneback *h_ = nullptr;
+    ParamHandle<mi_farneback, mi_farneback_params, mi_farneback_create, mi_farneback_set_params, mi_farneback_destroy> h_;
 };
 }  // namespace miflow_detail
 
@@ -257,28 +234,22 @@ public:
 namespace miflow_detail {
 class DensePyrLKImpl final : public DensePyrLKOpticalFlow {
 public:
-    explicit DensePyrLKImpl(const mi_densepyrlk_params &p) : p_(p) { miCheck(mi_densepyrlk_create(&p_, &h_)); }
-    ~DensePyrLKImpl() override { mi_densepyrlk_destroy(h_); }
-    DensePyrLKImpl(const DensePyrLKImpl &) = delete;
-    DensePyrLKImpl &operator=(const DensePyrLKImpl &) = delete;
+    explicit DensePyrLKImpl(const mi_densepyrlk_params &p) : h_(p) {}
     void calc(InputArray prevImg, InputArray nextImg, InputOutputArray flow, Stream &stream) override
     {
         flow.create(prevImg.size(), CV_32FC2);   // cuda::merge into _flow, pyrlk.cpp:390-391
         mi_mat a = miMat(prevImg), b = miMat(nextImg), f = miMat(flow);
-        miCheck(mi_densepyrlk_calc(h_, &a, &b, &f, stream.hipStream()));
+        miCheck(mi_densepyrlk_calc(h_.get(), &a, &b, &f, stream.hipStream()));
     }
     String getDefaultName() const override { return "DenseOpticalFlow.DensePyrLKOpticalFlow"; }   // pyrlk.cpp:394
-    Size getWinSize() const override { return Size(p_.win_width, p_.win_height); }
-    void setWinSize(Size v) override { p_.win_width = v.width; p_.win_height = v.height; push(); }
-    int getMaxLevel() const override { return p_.max_level; }           void setMaxLevel(int v) override { p_.max_level = v; push(); }
-    int getNumIters() const override { return p_.iters; }               void setNumIters(int v) override { p_.iters = v; push(); }
-    bool getUseInitialFlow() const override { return p_.use_initial_flow != 0; }
-    void setUseInitialFlow(bool v) override { p_.use_initial_flow = v; push(); }
+    Size getWinSize() const override { return Size(h_.params().win_width, h_.params().win_height); }
+    void setWinSize(Size v) override { h_.set([=](auto &q) { q.win_width = v.width; q.win_height = v.height; }); }
+    int getMaxLevel() const override { return h_.params().max_level; }           void setMaxLevel(int v) override { h_.set([=](auto &q) { q.max_level = v; }); }
+    int getNumIters() const override { return h_.params().iters; }               void setNumIters(int v) override { h_.set([=](auto &q) { q.iters = v; }); }
+    bool getUseInitialFlow() const override { return h_.params().use_initial_flow != 0; }
+    void setUseInitialFlow(bool v) override { h_.set([=](auto &q) { q.use_initial_flow = v; }); }
 private:
-    void push() { const int rc = mi_densepyrlk_set_params(h_, &p_); if (rc) p_ = ok_; miCheck(rc); ok_ = p_; }   // a rejected value is rolled back
-    mi_densepyrlk_params p_;
-    mi_densepyrlk_params ok_ = p_;   // last parameters the library accepted
-    mi_densepyrlk *h_ = nullptr;
+    ParamHandle<mi_densepyrlk, mi_densepyrlk_params, mi_densepyrlk_create, mi_densepyrlk_set_params, mi_densepyrlk_destroy> h_;
 };
 }  // namespace miflow_detail
 
@@ -312,10 +283,7 @@ public:
 namespace miflow_detail {
 class SparsePyrLKImpl final : public SparsePyrLKOpticalFlow {
 public:
-    explicit SparsePyrLKImpl(const mi_sparsepyrlk_params &p) : p_(p) { miCheck(mi_sparsepyrlk_create(&p_, &h_)); }
-    ~SparsePyrLKImpl() override { mi_sparsepyrlk_destroy(h_); }
-    SparsePyrLKImpl(const SparsePyrLKImpl &) = delete;
-    SparsePyrLKImpl &operator=(const SparsePyrLKImpl &) = delete;
+    explicit SparsePyrLKImpl(const mi_sparsepyrlk_params &p) : h_(p) {}
     void calc(InputArray prevImg, InputArray nextImg, InputArray prevPts, InputOutputArray nextPts, OutputArray status, OutputArray err,
               Stream &stream) override
     {
@@ -325,25 +293,22 @@ public:
             if (wantErr) err.release();
             return;
         }
-        if (p_.use_initial_flow) CV_Assert(nextPts.size() == prevPts.size() && nextPts.type() == prevPts.type());   // :159-160
+        if (h_.params().use_initial_flow) CV_Assert(nextPts.size() == prevPts.size() && nextPts.type() == prevPts.type());   // :159-160
         else nextPts.create(1, prevPts.cols, prevPts.type());
         status.create(1, prevPts.cols, CV_8UC1);
         if (wantErr) err.create(1, prevPts.cols, CV_32FC1);
         mi_mat a = miMat(prevImg), b = miMat(nextImg), pp = miMat(prevPts), np = miMat(nextPts), st = miMat(status), er = miMat(err);
-        miCheck(mi_sparsepyrlk_calc(h_, &a, &b, &pp, &np, &st, wantErr ? &er : nullptr, stream.hipStream()));
+        miCheck(mi_sparsepyrlk_calc(h_.get(), &a, &b, &pp, &np, &st, wantErr ? &er : nullptr, stream.hipStream()));
     }
     String getDefaultName() const override { return "SparseOpticalFlow.SparsePyrLKOpticalFlow"; }   // pyrlk.cpp:351
-    Size getWinSize() const override { return Size(p_.win_width, p_.win_height); }
-    void setWinSize(Size v) override { p_.win_width = v.width; p_.win_height = v.height; push(); }
-    int getMaxLevel() const override { return p_.max_level; }           void setMaxLevel(int v) override { p_.max_level = v; push(); }
-    int getNumIters() const override { return p_.iters; }               void setNumIters(int v) override { p_.iters = v; push(); }
-    bool getUseInitialFlow() const override { return p_.use_initial_flow != 0; }
-    void setUseInitialFlow(bool v) override { p_.use_initial_flow = v; push(); }
+    Size getWinSize() const override { return Size(h_.params().win_width, h_.params().win_height); }
+    void setWinSize(Size v) override { h_.set([=](auto &q) { q.win_width = v.width; q.win_height = v.height; }); }
+    int getMaxLevel() const override { return h_.params().max_level; }           void setMaxLevel(int v) override { h_.set([=](auto &q) { q.max_level = v; }); }
+    int getNumIters() const override { return h_.params().iters; }               void setNumIters(int v) override { h_.set([=](auto &q) { q.iters = v; }); }
+    bool getUseInitialFlow() const override { return h_.params().use_initial_flow != 0; }
+    void setUseInitialFlow(bool v) override { h_.set([=](auto &q) { q.use_initial_flow = v; }); }
 private:
-    void push() { const int rc = mi_sparsepyrlk_set_params(h_, &p_); if (rc) p_ = ok_; miCheck(rc); ok_ = p_; }   // a rejected value is rolled back
-    mi_sparsepyrlk_params p_;
-    mi_sparsepyrlk_params ok_ = p_;   // last parameters the library accepted
-    mi_sparsepyrlk *h_ = nullptr;
+    ParamHandle<mi_sparsepyrlk, mi_sparsepyrlk_params, mi_sparsepyrlk_create, mi_sparsepyrlk_set_params, mi_sparsepyrlk_destroy> h_;
 };
 }  // namespace miflow_detail
 

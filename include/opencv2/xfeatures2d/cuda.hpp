@@ -90,6 +90,7 @@ public:
     static bool holds(const GpuMat &m, int rows, int cols, int type)
     {
         static const int dsz[8] = {1, 1, 2, 2, 4, 4, 8, 2};
+        if (rows <= 0 || cols <= 0) return false;   // step * (rows - 1) below would wrap
         const size_t es = (size_t)dsz[type & 7] * (size_t)CV_MAT_CN(type);
         return m.data && m.data == m.datastart && m.type() == (type & 0xFFF) && m.step >= (size_t)cols * es &&
                (size_t)(m.dataend - m.datastart) >= m.step * (size_t)(rows - 1) + (size_t)cols * es;
@@ -134,10 +135,11 @@ public:
             GpuMat &dst = fits ? descriptors : fresh;
             mi_mat m = miMat(mask), k = miMat(keypoints), d = miMat(dst);
             int n = 0;
-            miCheck(mi_surf_detect_and_compute(h_, &i, mask.empty() ? nullptr : &m, &k, &d, &n, nullptr));
+            const int rc = mi_surf_detect_and_compute(h_, &i, mask.empty() ? nullptr : &m, &k, &d, &n, nullptr);
+            if (fits && (rc != MI_OK || n == 0)) { descriptors.rows = rows0; descriptors.cols = cols0; }   // an error, too, leaves the caller's header as it was
+            miCheck(rc);
             keypoints.cols = n;   // :209
             if (n > 0) { if (!fits) descriptors = fresh; descriptors.rows = n; }
-            else if (fits) { descriptors.rows = rows0; descriptors.cols = cols0; }
             return;
         }
         if (!upright) { mi_mat k = miMat(keypoints); miCheck(mi_surf_compute_orientation(h_, &i, &k, keypoints.cols, nullptr)); }

@@ -13,16 +13,52 @@ from . import capi
 from .capi import MiError
 
 
+class _Handle:
+    """The one owner of a C-ABI handle `_h` and of the parameter struct `_p` the library last accepted, the base of every class here.
+    One rule for a setter: copy the struct, ask the library, commit on acceptance; a rejected value leaves the object as it was."""
 
-def _destroy(obj, fn_name):
-    """Shared __del__ body of the handle wrappers: never raises (interpreter shutdown, failed __init__, library gone)."""
-    try:
-        h = getattr(obj, "_h", None)
-        if h is not None and getattr(h, "value", h):
-            getattr(capi.lib(), fn_name)(h)
-        obj._h = None
-    except Exception:
-        pass
+    def _open(self, prefix, params, *extra):
+        """mi_<prefix>_create(&params, *extra, &h); params None: the create takes no struct (its arguments are all in `extra`)."""
+        self._h = None
+        self._prefix = prefix
+        h = C.c_void_p()
+        head = () if params is None else (C.byref(params),)
+        capi.check(getattr(capi.lib(), f"mi_{prefix}_create")(*head, *extra, C.byref(h)))
+        self._h = h
+        if params is not None:
+            self._p = params
+
+    def _set(self, **kw):
+        q = type(self._p).from_buffer_copy(self._p)
+        for k, v in kw.items():
+            setattr(q, k, v)
+        capi.check(getattr(capi.lib(), f"mi_{self._prefix}_set_params")(self._h, C.byref(q)))
+        C.memmove(C.byref(self._p), C.byref(q), C.sizeof(q))   # _p keeps its identity: callers hold references to it
+
+    def _close(self):
+        """Never raises (interpreter shutdown, failed __init__, library gone); a second call does nothing."""
+        try:
+            h, self._h = getattr(self, "_h", None), None
+            if h:
+                getattr(capi.lib(), f"mi_{self._prefix}_destroy")(h)
+        except Exception:
+            pass
+
+    __del__ = _close
+
+
+def _stream_ptr(stream):
+    return C.c_void_p(stream) if stream is not None else capi.current_stream_ptr()
+
+
+def _m(t):
+    return capi.mat_from_tensor(t)
+
+
+def _mats(tensors):
+    """sequence of tensors (None: an mi_mat with a NULL data pointer) -> ctypes array of mi_mat"""
+    return (capi.Mat * len(tensors))(*[_m(t) if t is not None else capi.Mat() for t in tensors])
+
 
 def release_cached_memory():
     """miflow extension: hand the scratch blocks that destroyed handles left in libmiflow's process-wide cache (up to
@@ -30,7 +66,7 @@ def release_cached_memory():
     capi.check(capi.lib().mi_release_cached_memory())
 
 
-class OpticalFlowDual_TVL1:
+class OpticalFlowDual_TVL1(_Handle):
     """cv::cuda::OpticalFlowDual_TVL1 (cudaoptflow.hpp:305-386).
 
     Extra, non-reference knobs (C-ABI extensions): `semantics` (0 = arithmetic of the CPU class
@@ -40,9 +76,7 @@ class OpticalFlowDual_TVL1:
     """
 
     def __init__(self, params: capi.TVL1Params):
-        self._h = C.c_void_p()
-        capi.check(capi.lib().mi_tvl1_create(C.byref(params), C.byref(self._h)))
-        self._p = params
+        self._open("tvl1", params)
 
     # -- factory with the reference's signature and defaults (cudaoptflow.hpp:375-385)
     @staticmethod
@@ -68,21 +102,8 @@ class OpticalFlowDual_TVL1:
         p.host_feedback = hostFeedback   # 0 automatic (a call of <= 2 pairs reads the converged flags back between launches), -1 never, 1 every single-lane call
         return OpticalFlowDual_TVL1(p)
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and self._h.value:
-                capi.lib().mi_tvl1_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
-
     def getDefaultName(self) -> str:  # cudaoptflow/src/tvl1flow.cpp:122
         return "DenseOpticalFlow.OpticalFlowDual_TVL1"
-
-    def _set(self, **kw):
-        for k, v in kw.items():
-            setattr(self._p, k, v)
-        capi.check(capi.lib().mi_tvl1_set_params(self._h, C.byref(self._p)))
 
     # getters / setters, cudaoptflow/src/tvl1flow.cpp:90-118
     def getTau(self): return self._p.tau
@@ -114,7 +135,7 @@ class OpticalFlowDual_TVL1:
                 raise MiError(-1, "useInitialFlow requires a flow argument")
             flow = torch.empty((I0.shape[0], I0.shape[1], 2), dtype=torch.float32, device=I0.device)
         m0, m1, mf = capi.mat_from_tensor(I0), capi.mat_from_tensor(I1), capi.mat_from_tensor(flow)
-        sp = C.c_void_p(stream) if stream is not None else capi.current_stream_ptr()
+        sp = _stream_ptr(stream)
         capi.check(capi.lib().mi_tvl1_calc(self._h, C.byref(m0), C.byref(m1), C.byref(mf), sp))
         capi.check(capi.lib().mi_tvl1_get_params(self._h, C.byref(self._p)))   # nscales shrinks like the reference's nscales_
         return flow
@@ -126,10 +147,10 @@ class OpticalFlowDual_TVL1:
         n = len(I0s)
         if flows is None:
             flows = torch.empty((n, I0s[0].shape[0], I0s[0].shape[1], 2), dtype=torch.float32, device=I0s[0].device)
-        A0 = (capi.Mat * n)(*[capi.mat_from_tensor(t) for t in I0s])
-        A1 = (capi.Mat * n)(*[capi.mat_from_tensor(t) for t in I1s])
-        AF = (capi.Mat * n)(*[capi.mat_from_tensor(t) for t in flows])
-        sp = C.c_void_p(stream) if stream is not None else capi.current_stream_ptr()
+        A0 = _mats(I0s)
+        A1 = _mats(I1s)
+        AF = _mats(flows)
+        sp = _stream_ptr(stream)
         capi.check(capi.lib().mi_tvl1_calc_batch(self._h, n, A0, A1, AF, sp))
         capi.check(capi.lib().mi_tvl1_get_params(self._h, C.byref(self._p)))
         return flows
@@ -154,7 +175,7 @@ class OpticalFlowDual_TVL1:
         return [[buf[s * nw + w] for w in range(nw)] for s in range(ns.value)]
 
 
-class TVL1MultiDevice:
+class TVL1MultiDevice(_Handle):
     """Batched-frames mode over the GPUs of one node through the C-ABI (mi_tvl1_multi_*): contiguous shards of independent pairs,
     one host thread + handle + stream pair per device, staging from / to the ROOT device (devices[0]) over RCCL point-to-point
     messages (where librccl is present and the worker sits on another GPU) or peer-to-peer copies; no reduction.
@@ -162,18 +183,9 @@ class TVL1MultiDevice:
     The same device id may appear several times (several workers on one GPU)."""
 
     def __init__(self, alg: "OpticalFlowDual_TVL1", devices=None, chunk=16):
-        self._h = C.c_void_p()
         ids = None if devices is None else (C.c_int * len(devices))(*devices)
-        capi.check(capi.lib().mi_tvl1_multi_create(C.byref(alg._p), 0 if devices is None else len(devices), ids, C.byref(self._h)))
+        self._open("tvl1_multi", None, C.byref(alg._p), 0 if devices is None else len(devices), ids)   # alg keeps its parameters: no _p here
         capi.check(capi.lib().mi_tvl1_multi_set_chunk(self._h, chunk))
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and self._h.value:
-                capi.lib().mi_tvl1_multi_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
 
     def deviceCount(self):
         return capi.lib().mi_tvl1_multi_device_count(self._h)
@@ -196,19 +208,15 @@ class TVL1MultiDevice:
         if flows is None:
             flows = torch.empty((n, I0s[0].shape[0], I0s[0].shape[1], 2), dtype=torch.float32, device=I0s[0].device)
         torch.cuda.synchronize()
-        A0 = (capi.Mat * n)(*[capi.mat_from_tensor(t) for t in I0s])
-        A1 = (capi.Mat * n)(*[capi.mat_from_tensor(t) for t in I1s])
-        AF = (capi.Mat * n)(*[capi.mat_from_tensor(t) for t in flows])
+        A0 = _mats(I0s)
+        A1 = _mats(I1s)
+        AF = _mats(flows)
         capi.check(capi.lib().mi_tvl1_multi_calc_batch(self._h, n, A0, A1, AF))
         return flows
 
 
 # ---------------------------------------------------------------------------------------------
 # stage-level functions (the reference's internal device-layer boundary), used by parity tests
-def _m(t):
-    return capi.mat_from_tensor(t)
-
-
 def tvl1_centeredGradient(src):
     import torch
     dx, dy = torch.empty_like(src), torch.empty_like(src)
@@ -305,7 +313,7 @@ def round_half_even(v: float) -> int:
 
 
 # =============================================================================================
-class StereoBM:
+class StereoBM(_Handle):
     """cv::cuda::StereoBM (cudastereo.hpp:72-90; StereoBMImpl cudastereo/src/stereobm.cpp:67-132).
 
     Setters that are no-ops in the reference (minDisparity, speckle*, disp12MaxDiff, smallerBlockSize,
@@ -317,22 +325,7 @@ class StereoBM:
         p = capi.StereoBMParams()
         capi.lib().mi_stereobm_default_params(C.byref(p))
         p.num_disparities, p.block_size, p.emulate_cuda_edge = numDisparities, blockSize, int(bool(emulateCudaEdge))
-        self._h = C.c_void_p()
-        capi.check(capi.lib().mi_stereobm_create(C.byref(p), C.byref(self._h)))
-        self._p = p
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and self._h.value:
-                capi.lib().mi_stereobm_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
-
-    def _set(self, **kw):
-        for k, v in kw.items():
-            setattr(self._p, k, v)
-        capi.check(capi.lib().mi_stereobm_set_params(self._h, C.byref(self._p)))
+        self._open("stereobm", p)
 
     def getMinDisparity(self): return 0
     def setMinDisparity(self, v): pass
@@ -365,7 +358,7 @@ class StereoBM:
         if disparity is None:  # _disparity.create(left.size(), CV_8UC1)  stereobm.cpp:154
             disparity = torch.empty((left.shape[0], left.shape[1]), dtype=torch.uint8, device=left.device)
         ml, mr, md = capi.mat_from_tensor(left), capi.mat_from_tensor(right), capi.mat_from_tensor(disparity)
-        sp = C.c_void_p(stream) if stream is not None else capi.current_stream_ptr()
+        sp = _stream_ptr(stream)
         capi.check(capi.lib().mi_stereobm_compute(self._h, C.byref(ml), C.byref(mr), C.byref(md), sp))
         return disparity
 
@@ -375,10 +368,10 @@ class StereoBM:
         n = len(lefts)
         if disparities is None:
             disparities = torch.empty((n, lefts[0].shape[0], lefts[0].shape[1]), dtype=torch.uint8, device=lefts[0].device)
-        AL = (capi.Mat * n)(*[capi.mat_from_tensor(t) for t in lefts])
-        AR = (capi.Mat * n)(*[capi.mat_from_tensor(t) for t in rights])
-        AD = (capi.Mat * n)(*[capi.mat_from_tensor(t) for t in disparities])
-        sp = C.c_void_p(stream) if stream is not None else capi.current_stream_ptr()
+        AL = _mats(lefts)
+        AR = _mats(rights)
+        AD = _mats(disparities)
+        sp = _stream_ptr(stream)
         capi.check(capi.lib().mi_stereobm_compute_batch(self._h, n, AL, AR, AD, sp))
         return disparities
 
@@ -388,28 +381,19 @@ def createStereoBM(numDisparities=64, blockSize=19, **kw) -> StereoBM:
     return StereoBM(numDisparities, blockSize, **kw)
 
 
-class DensePyrLKOpticalFlow:
+class DensePyrLKOpticalFlow(_Handle):
     """cv::cuda::DensePyrLKOpticalFlow (cudaoptflow.hpp; cudaoptflow/src/pyrlk.cpp:238-299,354-406)."""
 
     def __init__(self, winSize=(13, 13), maxLevel=3, iters=30, useInitialFlow=False):
-        self._p = capi.DensePyrLKParams()
-        capi.lib().mi_densepyrlk_default_params(C.byref(self._p))
-        self._p.win_width, self._p.win_height, self._p.max_level, self._p.iters = winSize[0], winSize[1], maxLevel, iters
-        self._p.use_initial_flow = int(bool(useInitialFlow))
-        self._h = C.c_void_p()
-        capi.check(capi.lib().mi_densepyrlk_create(C.byref(self._p), C.byref(self._h)))
+        p = capi.DensePyrLKParams()
+        capi.lib().mi_densepyrlk_default_params(C.byref(p))
+        p.win_width, p.win_height, p.max_level, p.iters = winSize[0], winSize[1], maxLevel, iters
+        p.use_initial_flow = int(bool(useInitialFlow))
+        self._open("densepyrlk", p)
 
     @classmethod
     def create(cls, winSize=(13, 13), maxLevel=3, iters=30, useInitialFlow=False):
         return cls(winSize, maxLevel, iters, useInitialFlow)
-
-    def __del__(self):
-        _destroy(self, "mi_densepyrlk_destroy")
-
-    def _set(self, **kw):
-        for k, v in kw.items():
-            setattr(self._p, k, v)
-        capi.check(capi.lib().mi_densepyrlk_set_params(self._h, C.byref(self._p)))
 
     def getDefaultName(self): return "DenseOpticalFlow.DensePyrLKOpticalFlow"   # pyrlk.cpp:394
     def getWinSize(self): return (self._p.win_width, self._p.win_height)
@@ -430,29 +414,20 @@ class DensePyrLKOpticalFlow:
         return flow
 
 
-class SparsePyrLKOpticalFlow:
+class SparsePyrLKOpticalFlow(_Handle):
     """cv::cuda::SparsePyrLKOpticalFlow for CV_8UC1 frames (cudaoptflow.hpp:85-104,203-223; cudaoptflow/src/pyrlk.cpp:149-231,308-352).
     calc(prevImg, nextImg, prevPts (1, N, 2) or (N, 2) float32[, nextPts]) -> (nextPts (1, N, 2), status (1, N) uint8, err (1, N))."""
 
     def __init__(self, winSize=(21, 21), maxLevel=3, iters=30, useInitialFlow=False):
-        self._p = capi.SparsePyrLKParams()
-        capi.lib().mi_sparsepyrlk_default_params(C.byref(self._p))
-        self._p.win_width, self._p.win_height, self._p.max_level, self._p.iters = winSize[0], winSize[1], maxLevel, iters
-        self._p.use_initial_flow = int(bool(useInitialFlow))
-        self._h = C.c_void_p()
-        capi.check(capi.lib().mi_sparsepyrlk_create(C.byref(self._p), C.byref(self._h)))
+        p = capi.SparsePyrLKParams()
+        capi.lib().mi_sparsepyrlk_default_params(C.byref(p))
+        p.win_width, p.win_height, p.max_level, p.iters = winSize[0], winSize[1], maxLevel, iters
+        p.use_initial_flow = int(bool(useInitialFlow))
+        self._open("sparsepyrlk", p)
 
     @classmethod
     def create(cls, winSize=(21, 21), maxLevel=3, iters=30, useInitialFlow=False):
         return cls(winSize, maxLevel, iters, useInitialFlow)
-
-    def __del__(self):
-        _destroy(self, "mi_sparsepyrlk_destroy")
-
-    def _set(self, **kw):
-        for k, v in kw.items():
-            setattr(self._p, k, v)
-        capi.check(capi.lib().mi_sparsepyrlk_set_params(self._h, C.byref(self._p)))
 
     def getDefaultName(self): return "SparseOpticalFlow.SparsePyrLKOpticalFlow"   # pyrlk.cpp:350
     def getWinSize(self): return (self._p.win_width, self._p.win_height)
@@ -484,27 +459,18 @@ class SparsePyrLKOpticalFlow:
         return npts, status, err
 
 
-class StereoSGM:
+class StereoSGM(_Handle):
     """cv::cuda::StereoSGM (cudastereo.hpp; cudastereo/src/stereosgm.cpp:20-153): semi-global matching on census costs,
     4 (MODE_HH4) or 8 (MODE_HH) paths, CV_16SC1 output with 4 fractional bits."""
 
     MODE_HH, MODE_HH4 = 1, 3
 
     def __init__(self, minDisparity=0, numDisparities=128, P1=10, P2=120, uniquenessRatio=5, mode=3, emulateCudaQuirks=True):
-        self._p = capi.StereoSGMParams()
-        capi.lib().mi_stereosgm_default_params(C.byref(self._p))
-        self._p.min_disparity, self._p.num_disparities, self._p.P1, self._p.P2 = minDisparity, numDisparities, P1, P2
-        self._p.uniqueness_ratio, self._p.mode, self._p.emulate_cuda_quirks = uniquenessRatio, mode, int(bool(emulateCudaQuirks))
-        self._h = C.c_void_p()
-        capi.check(capi.lib().mi_stereosgm_create(C.byref(self._p), C.byref(self._h)))
-
-    def __del__(self):
-        _destroy(self, "mi_stereosgm_destroy")
-
-    def _set(self, **kw):
-        for k, v in kw.items():
-            setattr(self._p, k, v)
-        capi.check(capi.lib().mi_stereosgm_set_params(self._h, C.byref(self._p)))
+        p = capi.StereoSGMParams()
+        capi.lib().mi_stereosgm_default_params(C.byref(p))
+        p.min_disparity, p.num_disparities, p.P1, p.P2 = minDisparity, numDisparities, P1, P2
+        p.uniqueness_ratio, p.mode, p.emulate_cuda_quirks = uniquenessRatio, mode, int(bool(emulateCudaQuirks))
+        self._open("stereosgm", p)
 
     # stereosgm.cpp:38-72 (the fixed getters of the reference included)
     def getBlockSize(self): return -1
@@ -583,7 +549,12 @@ class DMatch:
         return f"DMatch(queryIdx={self.queryIdx}, trainIdx={self.trainIdx}, imgIdx={self.imgIdx}, distance={self.distance:.6g})"
 
 
-class BFMatcher:
+def _nonempty(tensors):
+    """an empty tensor of a train or mask collection goes to the library like a missing one"""
+    return [t if t is not None and t.numel() else None for t in tensors]
+
+
+class BFMatcher(_Handle):
     """cv::cuda::DescriptorMatcher::createBFMatcher(NORM_L1 | NORM_L2 | NORM_HAMMING): float descriptors (L1 / L2) and integer ones
     (L1 / Hamming: the reference's (depth, norm) table) (cudafeatures2d.hpp;
     cudafeatures2d/src/brute_force_matcher.cpp:143-1070; kernels cuda/bf_match.cu, bf_knnmatch.cu, bf_radius_match.cu).
@@ -595,14 +566,11 @@ class BFMatcher:
     NORM_L1 = 2
     NORM_L2 = 4
     NORM_HAMMING = 6      # integer descriptors (uint8 / uint16 / int32); NORM_L1 also takes uint8 / uint16 / int16 / int32
+    _mats = staticmethod(_mats)   # the module's array builder under the name callers of the C-ABI know (tests reach it as BFMatcher._mats)
 
     def __init__(self, normType=4):
-        self._h = C.c_void_p()
-        capi.check(capi.lib().mi_bf_create(int(normType), C.byref(self._h)))
+        self._open("bf", None, int(normType))   # the norm type is its only parameter, fixed at create
         self._train = []
-
-    def __del__(self):
-        _destroy(self, "mi_bf_destroy")
 
     # ---- train collection (brute_force_matcher.cpp:187-211)
     def isMaskSupported(self): return True
@@ -620,13 +588,6 @@ class BFMatcher:
             raise capi.MiError(-1, "masks.size() == trainDescCollection.size()")          # makeGpuCollection, :156
         return list(self._train), (list(masks) if masks else None), True
 
-    @staticmethod
-    def _mats(tensors):
-        arr = (capi.Mat * len(tensors))()
-        for j, t in enumerate(tensors):
-            arr[j] = _m(t) if t is not None and t.numel() else capi.Mat(None, 0, 0, 0, 0)
-        return arr
-
     # ---- device forms
     def knnMatchDevice(self, queryDescriptors, trainDescriptors=None, k=2, mask=None, masks=None):
         """-> (trainIdx (nq, k) int32, imgIdx (nq, k) int32, distance (nq, k) float32); entries past the candidates -1 / -1 / FLT_MAX."""
@@ -640,7 +601,7 @@ class BFMatcher:
         idx = torch.empty((nq, k), dtype=torch.int32, device=q.device)
         img = torch.empty((nq, k), dtype=torch.int32, device=q.device)
         dist = torch.empty((nq, k), dtype=torch.float32, device=q.device)
-        capi.check(capi.lib().mi_bf_knn_match(self._h, C.byref(_m(q)), self._mats(trains), self._mats(ms) if ms else None, len(trains), int(k),
+        capi.check(capi.lib().mi_bf_knn_match(self._h, C.byref(_m(q)), _mats(_nonempty(trains)), _mats(_nonempty(ms)) if ms else None, len(trains), int(k),
                                               C.byref(_m(idx)), C.byref(_m(img)), C.byref(_m(dist)), capi.current_stream_ptr()))
         return idx, img, dist
 
@@ -665,7 +626,7 @@ class BFMatcher:
         img = torch.full((nq, cols), -1, dtype=torch.int32, device=q.device)
         dist = torch.zeros((nq, cols), dtype=torch.float32, device=q.device)
         n = torch.empty((1, nq), dtype=torch.int32, device=q.device)
-        capi.check(capi.lib().mi_bf_radius_match(self._h, C.byref(_m(q)), self._mats(trains), self._mats(ms) if ms else None, len(trains),
+        capi.check(capi.lib().mi_bf_radius_match(self._h, C.byref(_m(q)), _mats(_nonempty(trains)), _mats(_nonempty(ms)) if ms else None, len(trains),
                                                  float(maxDistance), C.byref(_m(idx)), C.byref(_m(img)), C.byref(_m(dist)), C.byref(_m(n)),
                                                  capi.current_stream_ptr()))
         return idx, img, dist, n[0]
@@ -793,24 +754,15 @@ class DescriptorMatcher:
 NORM_L1, NORM_L2, NORM_HAMMING = 2, 4, 6
 
 
-class DisparityBilateralFilter:
+class DisparityBilateralFilter(_Handle):
     """cv::cuda::DisparityBilateralFilter (cudastereo.hpp:298-330; cudastereo/src/disparity_bilateral_filter.cpp:58-190):
     joint bilateral refinement of a disparity map at its discontinuities, guided by the image."""
 
     def __init__(self, ndisp=64, radius=3, iters=1):
-        self._p = capi.DispBilateralParams()
-        capi.lib().mi_disp_bilateral_default_params(C.byref(self._p))
-        self._p.ndisp, self._p.radius, self._p.iters = ndisp, radius, iters
-        self._h = C.c_void_p()
-        capi.check(capi.lib().mi_disp_bilateral_create(C.byref(self._p), C.byref(self._h)))
-
-    def __del__(self):
-        _destroy(self, "mi_disp_bilateral_destroy")
-
-    def _set(self, **kw):
-        for k, v in kw.items():
-            setattr(self._p, k, v)
-        capi.check(capi.lib().mi_disp_bilateral_set_params(self._h, C.byref(self._p)))
+        p = capi.DispBilateralParams()
+        capi.lib().mi_disp_bilateral_default_params(C.byref(p))
+        p.ndisp, p.radius, p.iters = ndisp, radius, iters
+        self._open("disp_bilateral", p)
 
     def getNumDisparities(self): return self._p.ndisp
     def setNumDisparities(self, v): self._set(ndisp=v)
@@ -848,24 +800,15 @@ def _bp_dtype(msg_type):
     return torch.float32 if msg_type == CV_32F else torch.int16
 
 
-class StereoBeliefPropagation:
+class StereoBeliefPropagation(_Handle):
     """cv::cuda::StereoBeliefPropagation (cudastereo.hpp:128-189; cudastereo/src/stereobp.cpp:78-378): hierarchical belief propagation
     on a checkerboard schedule, 16-bit or f32 messages, bit-exact to the reference."""
 
     def __init__(self, ndisp=64, iters=5, levels=5, msg_type=CV_32F):
-        self._p = capi.StereoBPParams()
-        capi.lib().mi_stereobp_default_params(C.byref(self._p))
-        self._p.ndisp, self._p.iters, self._p.levels, self._p.msg_type = ndisp, iters, levels, msg_type
-        self._h = C.c_void_p()
-        capi.check(capi.lib().mi_stereobp_create(C.byref(self._p), C.byref(self._h)))
-
-    def __del__(self):
-        _destroy(self, "mi_stereobp_destroy")
-
-    def _set(self, **kw):
-        for k, v in kw.items():
-            setattr(self._p, k, v)
-        capi.check(capi.lib().mi_stereobp_set_params(self._h, C.byref(self._p)))
+        p = capi.StereoBPParams()
+        capi.lib().mi_stereobp_default_params(C.byref(p))
+        p.ndisp, p.iters, p.levels, p.msg_type = ndisp, iters, levels, msg_type
+        self._open("stereobp", p)
 
     def getMinDisparity(self): return 0
     def setMinDisparity(self, v): pass
@@ -941,10 +884,6 @@ def _bp_params(ndisp, msg_type, max_data_term=10.0, data_weight=0.07, max_disc_t
     return p
 
 
-def _mats(tensors):
-    return (capi.Mat * len(tensors))(*[_m(t) for t in tensors])
-
-
 def stereobp_comp_data(left, right, ndisp, msg_type=CV_32F, data=None, **weights):
     """comp_data_gpu (stereobp.cu:132-251) -> data (ndisp * H, W); border elements keep what `data` held (zeros if it is made here)."""
     import torch
@@ -994,19 +933,10 @@ class StereoConstantSpaceBP(StereoBeliefPropagation):
     candidate disparities per pixel instead of all ndisp, 16-bit or f32 messages, bit-exact to the reference."""
 
     def __init__(self, ndisp=128, iters=8, levels=4, nr_plane=4, msg_type=CV_32F):
-        self._p = capi.StereoCSBPParams()
-        capi.lib().mi_stereocsbp_default_params(C.byref(self._p))
-        self._p.ndisp, self._p.iters, self._p.levels, self._p.nr_plane, self._p.msg_type = ndisp, iters, levels, nr_plane, msg_type
-        self._h = C.c_void_p()
-        capi.check(capi.lib().mi_stereocsbp_create(C.byref(self._p), C.byref(self._h)))
-
-    def __del__(self):
-        _destroy(self, "mi_stereocsbp_destroy")
-
-    def _set(self, **kw):
-        for k, v in kw.items():
-            setattr(self._p, k, v)
-        capi.check(capi.lib().mi_stereocsbp_set_params(self._h, C.byref(self._p)))
+        p = capi.StereoCSBPParams()
+        capi.lib().mi_stereocsbp_default_params(C.byref(p))
+        p.ndisp, p.iters, p.levels, p.nr_plane, p.msg_type = ndisp, iters, levels, nr_plane, msg_type
+        self._open("stereocsbp", p)
 
     def getMinDisparity(self): return self._p.min_disp_th
     def setMinDisparity(self, v): self._set(min_disp_th=v)
@@ -1155,13 +1085,11 @@ def stereobm_textureness(img, disp, winsz=19, avg_threshold=3.0):
 OPTFLOW_USE_INITIAL_FLOW, OPTFLOW_FARNEBACK_GAUSSIAN = 4, 256   # cv::OPTFLOW_* (main repo video/tracking.hpp)
 
 
-class FarnebackOpticalFlow:
+class FarnebackOpticalFlow(_Handle):
     """cv::cuda::FarnebackOpticalFlow (cudaoptflow.hpp:258-294; impl cudaoptflow/src/farneback.cpp:96-165)."""
 
     def __init__(self, params: capi.FarnebackParams):
-        self._h = C.c_void_p()
-        capi.check(capi.lib().mi_farneback_create(C.byref(params), C.byref(self._h)))
-        self._p = params
+        self._open("farneback", params)
 
     @staticmethod
     def create(numLevels=5, pyrScale=0.5, fastPyramids=False, winSize=13, numIters=10, polyN=5, polySigma=1.1,
@@ -1172,21 +1100,8 @@ class FarnebackOpticalFlow:
         p.num_iters, p.poly_n, p.poly_sigma, p.flags = numIters, polyN, polySigma, flags
         return FarnebackOpticalFlow(p)
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and self._h.value:
-                capi.lib().mi_farneback_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
-
     def getDefaultName(self) -> str:  # farneback.cpp:132
         return "DenseOpticalFlow.FarnebackOpticalFlow"
-
-    def _set(self, **kw):
-        for k, v in kw.items():
-            setattr(self._p, k, v)
-        capi.check(capi.lib().mi_farneback_set_params(self._h, C.byref(self._p)))
 
     # getters / setters, farneback.cpp:106-128
     def getNumLevels(self): return self._p.num_levels
@@ -1214,7 +1129,7 @@ class FarnebackOpticalFlow:
                 raise MiError(-1, "OPTFLOW_USE_INITIAL_FLOW requires a flow argument")
             flow = torch.empty((I0.shape[0], I0.shape[1], 2), dtype=torch.float32, device=I0.device)
         m0, m1, mf = capi.mat_from_tensor(I0), capi.mat_from_tensor(I1), capi.mat_from_tensor(flow)
-        sp = C.c_void_p(stream) if stream is not None else capi.current_stream_ptr()
+        sp = _stream_ptr(stream)
         capi.check(capi.lib().mi_farneback_calc(self._h, C.byref(m0), C.byref(m1), C.byref(mf), sp))
         return flow
 
@@ -1226,10 +1141,10 @@ class FarnebackOpticalFlow:
             if self._p.flags & OPTFLOW_USE_INITIAL_FLOW:
                 raise MiError(-1, "OPTFLOW_USE_INITIAL_FLOW requires the flows argument")
             flows = torch.empty((n, I0s[0].shape[0], I0s[0].shape[1], 2), dtype=torch.float32, device=I0s[0].device)
-        A0 = (capi.Mat * n)(*[capi.mat_from_tensor(t) for t in I0s])
-        A1 = (capi.Mat * n)(*[capi.mat_from_tensor(t) for t in I1s])
-        AF = (capi.Mat * n)(*[capi.mat_from_tensor(t) for t in flows])
-        sp = C.c_void_p(stream) if stream is not None else capi.current_stream_ptr()
+        A0 = _mats(I0s)
+        A1 = _mats(I1s)
+        AF = _mats(flows)
+        sp = _stream_ptr(stream)
         capi.check(capi.lib().mi_farneback_calc_batch(self._h, n, A0, A1, AF, sp))
         return flows
 
@@ -1353,7 +1268,7 @@ def pyrDown(src):
 
 
 # =============================================================================================
-class SURF_CUDA:
+class SURF_CUDA(_Handle):
     """cv::cuda::SURF_CUDA (xfeatures2d/cuda.hpp:86-196).  Keypoints live in a 7 x N CV_32FC1 device matrix
     (rows X, Y, LAPLACIAN, OCTAVE, SIZE, ANGLE, HESSIAN; LAPLACIAN/OCTAVE hold int bit patterns)."""
 
@@ -1365,33 +1280,20 @@ class SURF_CUDA:
         p = capi.SURFParams()
         p.hessian_threshold, p.n_octaves, p.n_octave_layers = _hessianThreshold, _nOctaves, _nOctaveLayers
         p.extended, p.keypoints_ratio, p.upright = int(bool(_extended)), _keypointsRatio, int(bool(_upright))
-        self._h = C.c_void_p()
-        capi.check(capi.lib().mi_surf_create(C.byref(p), C.byref(self._h)))
-        self._p = p
+        self._open("surf", p)
 
     @staticmethod
     def create(_hessianThreshold, _nOctaves=4, _nOctaveLayers=2, _extended=False, _keypointsRatio=0.01, _upright=False):
         """cuda.hpp:117-118 (extended defaults to false here)."""
         return SURF_CUDA(_hessianThreshold, _nOctaves, _nOctaveLayers, _extended, _keypointsRatio, _upright)
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and self._h.value:
-                capi.lib().mi_surf_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
-
-    def _sync(self):
-        capi.check(capi.lib().mi_surf_set_params(self._h, C.byref(self._p)))
-
     # public fields of the reference class
-    hessianThreshold = property(lambda s: s._p.hessian_threshold, lambda s, v: (setattr(s._p, "hessian_threshold", v), s._sync()))
-    nOctaves = property(lambda s: s._p.n_octaves, lambda s, v: (setattr(s._p, "n_octaves", v), s._sync()))
-    nOctaveLayers = property(lambda s: s._p.n_octave_layers, lambda s, v: (setattr(s._p, "n_octave_layers", v), s._sync()))
-    extended = property(lambda s: bool(s._p.extended), lambda s, v: (setattr(s._p, "extended", int(bool(v))), s._sync()))
-    upright = property(lambda s: bool(s._p.upright), lambda s, v: (setattr(s._p, "upright", int(bool(v))), s._sync()))
-    keypointsRatio = property(lambda s: s._p.keypoints_ratio, lambda s, v: (setattr(s._p, "keypoints_ratio", v), s._sync()))
+    hessianThreshold = property(lambda s: s._p.hessian_threshold, lambda s, v: s._set(hessian_threshold=v))
+    nOctaves = property(lambda s: s._p.n_octaves, lambda s, v: s._set(n_octaves=v))
+    nOctaveLayers = property(lambda s: s._p.n_octave_layers, lambda s, v: s._set(n_octave_layers=v))
+    extended = property(lambda s: bool(s._p.extended), lambda s, v: s._set(extended=int(bool(v))))
+    upright = property(lambda s: bool(s._p.upright), lambda s, v: s._set(upright=int(bool(v))))
+    keypointsRatio = property(lambda s: s._p.keypoints_ratio, lambda s, v: s._set(keypoints_ratio=v))
 
     def descriptorSize(self): return 128 if self._p.extended else 64   # surf.cuda.cpp:277-280
     def defaultNorm(self): return 4                                    # NORM_L2, surf.cuda.cpp:282-285
@@ -1404,7 +1306,7 @@ class SURF_CUDA:
         capi.check(capi.lib().mi_surf_max_features(self._h, img.shape[0], img.shape[1], C.byref(mf)))
         kp = torch.empty((7, mf.value), dtype=torch.float32, device=img.device)   # ensureSizeIsEnough(ROWS_COUNT, maxFeatures)
         n = C.c_int()
-        sp = C.c_void_p(stream) if stream is not None else capi.current_stream_ptr()
+        sp = _stream_ptr(stream)
         mm = C.byref(capi.mat_from_tensor(mask)) if mask is not None else None
         mk = capi.mat_from_tensor(kp)
         capi.check(capi.lib().mi_surf_detect(self._h, C.byref(capi.mat_from_tensor(img)), mm, C.byref(mk), C.byref(n), sp))
@@ -1423,20 +1325,20 @@ class SURF_CUDA:
             mf = C.c_int()
             ok = capi.lib().mi_surf_max_features(self._h, im.shape[0], im.shape[1], C.byref(mf)) == 0
             kps.append(torch.empty((7, mf.value), dtype=torch.float32, device=im.device) if ok else None)
-        mi = (capi.Mat * n)(*[capi.mat_from_tensor(t) for t in imgs])
-        mk = (capi.Mat * n)(*[capi.mat_from_tensor(t) if t is not None else capi.Mat() for t in kps])
+        mi = _mats(imgs)
+        mk = _mats(kps)
         mm = None
         if masks is not None:   # a frame without a mask: an mi_mat with a NULL data pointer
-            mm = (capi.Mat * n)(*[capi.mat_from_tensor(m) if m is not None else capi.Mat() for m in masks])
+            mm = _mats(masks)
         nf = (C.c_int * n)()
-        sp = C.c_void_p(stream) if stream is not None else capi.current_stream_ptr()
+        sp = _stream_ptr(stream)
         capi.check(capi.lib().mi_surf_detect_batch(self._h, n, mi, mm, mk, nf, sp))
         return [kp[:, : nf[i]] for i, kp in enumerate(kps)]
 
     def detectWithDescriptors(self, img, mask=None, keypoints=None, useProvidedKeypoints=False, stream=None):
         """operator()(img, mask, keypoints, descriptors, useProvidedKeypoints) (surf.cuda.cpp:380-397)."""
         import torch
-        sp = C.c_void_p(stream) if stream is not None else capi.current_stream_ptr()
+        sp = _stream_ptr(stream)
         if not useProvidedKeypoints:
             # one enqueue for the frame: the descriptor kernels read the feature count on the device (mi_surf_detect_and_compute)
             mf = C.c_int()
@@ -1463,7 +1365,7 @@ class SURF_CUDA:
     def cpuClassOrientation(self, img, keypoints, stream=None):
         """Writes the ANGLE row of `keypoints` (7, n) in place as SURFInvoker does (270 when upright) and sets SIZE to -1 for the
         keypoints the CPU class erases."""
-        sp = C.c_void_p(stream) if stream is not None else capi.current_stream_ptr()
+        sp = _stream_ptr(stream)
         if keypoints.shape[1] == 0:
             return keypoints
         s = surf_integral(img)
@@ -1473,7 +1375,7 @@ class SURF_CUDA:
 
     def cpuClassDescriptors(self, img, keypoints, stream=None):
         import torch
-        sp = C.c_void_p(stream) if stream is not None else capi.current_stream_ptr()
+        sp = _stream_ptr(stream)
         n = keypoints.shape[1]
         desc = torch.empty((n, self.descriptorSize()), dtype=torch.float32, device=img.device)
         if n:
@@ -1529,40 +1431,26 @@ def _u8(t):
     return t if t.dim() != 2 or t.stride(1) == 1 or t.shape[1] <= 1 else t.contiguous()
 
 
-class FastFeatureDetector:
+class FastFeatureDetector(_Handle):
     """cv::cuda::FastFeatureDetector.  Images and masks are uint8 device tensors; keypoints are the reference's 2 x n CV_32FC1 matrix
     (row 0: short2 {x, y} in an element's 4 bytes, row 1: the response), here in row-major order of the image."""
     LOCATION_ROW, RESPONSE_ROW, ROWS_COUNT, FEATURE_SIZE = 0, 1, 2, 7   # cudafeatures2d.hpp:429-432
     TYPE_5_8, TYPE_7_12, TYPE_9_16 = 0, 1, 2                            # cv::FastFeatureDetector (main repository, features2d.hpp)
 
     def __init__(self, threshold=10, nonmaxSuppression=True, type=2, max_npoints=5000):
-        self._h = None
         if type != self.TYPE_9_16:
             raise MiError(-1, "type == cv::FastFeatureDetector::TYPE_9_16")   # fast.cpp:213
-        self._p = capi.FastParams(int(threshold), int(bool(nonmaxSuppression)), int(max_npoints))
-        h = C.c_void_p()
-        capi.check(capi.lib().mi_fast_create(C.byref(self._p), C.byref(h)))
-        self._h = h
+        self._open("fast", capi.FastParams(int(threshold), int(bool(nonmaxSuppression)), int(max_npoints)))
 
     @staticmethod
     def create(threshold=10, nonmaxSuppression=True, type=2, max_npoints=5000) -> "FastFeatureDetector":
         return FastFeatureDetector(threshold, nonmaxSuppression, type, max_npoints)
 
-    def __del__(self):
-        _destroy(self, "mi_fast_destroy")
-
-    def _set(self, **kw):
-        p = capi.FastParams(self._p.threshold, self._p.nonmax_suppression, self._p.max_npoints)
-        for k, v in kw.items():
-            setattr(p, k, int(v))
-        capi.check(capi.lib().mi_fast_set_params(self._h, C.byref(p)))
-        self._p = p
-
-    def setThreshold(self, threshold): self._set(threshold=threshold)
+    def setThreshold(self, threshold): self._set(threshold=int(threshold))
     def getThreshold(self): return self._p.threshold
-    def setNonmaxSuppression(self, f): self._set(nonmax_suppression=bool(f))
+    def setNonmaxSuppression(self, f): self._set(nonmax_suppression=int(bool(f)))
     def getNonmaxSuppression(self): return bool(self._p.nonmax_suppression)
-    def setMaxNumPoints(self, max_npoints): self._set(max_npoints=max_npoints)
+    def setMaxNumPoints(self, max_npoints): self._set(max_npoints=int(max_npoints))
     def getMaxNumPoints(self): return self._p.max_npoints
 
     def setType(self, type):
@@ -1582,7 +1470,7 @@ class FastFeatureDetector:
         image = _u8(image)
         kp = torch.empty((self.ROWS_COUNT, self._p.max_npoints), dtype=torch.float32, device=image.device)
         n = C.c_int()
-        sp = C.c_void_p(stream) if stream is not None else capi.current_stream_ptr()
+        sp = _stream_ptr(stream)
         mm = C.byref(capi.mat_from_tensor(_u8(mask))) if mask is not None else None
         capi.check(capi.lib().mi_fast_detect(self._h, C.byref(capi.mat_from_tensor(image)), mm, C.byref(capi.mat_from_tensor(kp)), C.byref(n), sp))
         return kp[:, : n.value]
@@ -1600,14 +1488,14 @@ class FastFeatureDetector:
             raise MiError(-3, "masks: one entry (a tensor or None) per frame")
         images = [_u8(t) for t in images]
         kps = [torch.empty((self.ROWS_COUNT, self._p.max_npoints), dtype=torch.float32, device=t.device) for t in images]
-        mi = (capi.Mat * n)(*[capi.mat_from_tensor(t) for t in images])
-        mk = (capi.Mat * n)(*[capi.mat_from_tensor(t) for t in kps])
+        mi = _mats(images)
+        mk = _mats(kps)
         mm = None
         if masks is not None:
             keep = [_u8(m) if m is not None else None for m in masks]
-            mm = (capi.Mat * n)(*[capi.mat_from_tensor(m) if m is not None else capi.Mat() for m in keep])
+            mm = _mats(keep)
         ns = (C.c_int * n)()
-        sp = C.c_void_p(stream) if stream is not None else capi.current_stream_ptr()
+        sp = _stream_ptr(stream)
         capi.check(capi.lib().mi_fast_detect_batch(self._h, n, mi, mm, mk, ns, sp))
         return [kp[:, : ns[i]] for i, kp in enumerate(kps)]
 
@@ -1661,19 +1549,12 @@ def _src_type(t):
     return types[t.dtype]
 
 
-class CornernessCriteria:
+class CornernessCriteria(_Handle):
     """cv::cuda::CornernessCriteria (cudaimgproc.hpp:538-549): compute(src) -> the float32 response plane on the device.  Made by
     createHarrisCorner / createMinEigenValCorner; srcType is capi.MI_8UC1 or capi.MI_32FC1 (the OpenCV codes)."""
 
     def __init__(self, srcType, blockSize, ksize, borderType, harris, k=0.0):
-        self._h = None
-        self._p = capi.CornerParams(int(srcType), int(blockSize), int(ksize), int(borderType), int(bool(harris)), float(k))
-        h = C.c_void_p()
-        capi.check(capi.lib().mi_corner_create(C.byref(self._p), C.byref(h)))
-        self._h = h
-
-    def __del__(self):
-        _destroy(self, "mi_corner_destroy")
+        self._open("corner", capi.CornerParams(int(srcType), int(blockSize), int(ksize), int(borderType), int(bool(harris)), float(k)))   # no setter
 
     def compute(self, src, dst=None, stream=None):
         import torch
@@ -1682,7 +1563,7 @@ class CornernessCriteria:
             raise MiError(-2, "src.type() == srcType")   # corners.cpp:117
         if dst is None:
             dst = torch.empty(src.shape, dtype=torch.float32, device=src.device)
-        sp = C.c_void_p(stream) if stream is not None else capi.current_stream_ptr()
+        sp = _stream_ptr(stream)
         capi.check(capi.lib().mi_corner_compute(self._h, C.byref(capi.mat_from_tensor(src)), C.byref(capi.mat_from_tensor(dst)), sp))
         return dst
 
@@ -1697,28 +1578,14 @@ def createMinEigenValCorner(srcType, blockSize, ksize, borderType=BORDER_REFLECT
     return CornernessCriteria(srcType, blockSize, ksize, borderType, False)
 
 
-class CornersDetector:
+class CornersDetector(_Handle):
     """cv::cuda::CornersDetector (cudaimgproc.hpp:581-597), made by createGoodFeaturesToTrackDetector.  detect(image[, mask]) -> the
     corners as a (1, N, 2) float32 device tensor {x, y}, strongest first, which SparsePyrLKOpticalFlow.calc takes as prevPts unchanged;
     (1, 0, 2) where the reference releases the output."""
 
     def __init__(self, srcType, maxCorners=1000, qualityLevel=0.01, minDistance=0.0, blockSize=3, useHarrisDetector=False, harrisK=0.04):
-        self._h = None
-        self._p = capi.GfttParams(int(srcType), int(maxCorners), float(qualityLevel), float(minDistance), int(blockSize),
-                                  int(bool(useHarrisDetector)), float(harrisK))
-        h = C.c_void_p()
-        capi.check(capi.lib().mi_gftt_create(C.byref(self._p), C.byref(h)))
-        self._h = h
-
-    def __del__(self):
-        _destroy(self, "mi_gftt_destroy")
-
-    def _set(self, **kw):
-        p = capi.GfttParams.from_buffer_copy(self._p)
-        for k, v in kw.items():
-            setattr(p, k, v)
-        capi.check(capi.lib().mi_gftt_set_params(self._h, C.byref(p)))
-        self._p = p
+        self._open("gftt", capi.GfttParams(int(srcType), int(maxCorners), float(qualityLevel), float(minDistance), int(blockSize),
+                                           int(bool(useHarrisDetector)), float(harrisK)))
 
     def setMaxCorners(self, maxCorners): self._set(max_corners=int(maxCorners))
     def setMinDistance(self, minDistance): self._set(min_distance=float(minDistance))
@@ -1738,7 +1605,7 @@ class CornersDetector:
         need = min(self._p.max_corners, cap) if self._p.max_corners > 0 else cap
         out = torch.empty((1, need, 2), dtype=torch.float32, device=image.device)
         n = C.c_int()
-        sp = C.c_void_p(stream) if stream is not None else capi.current_stream_ptr()
+        sp = _stream_ptr(stream)
         mm = C.byref(capi.mat_from_tensor(_u8(mask))) if mask is not None else None
         capi.check(capi.lib().mi_gftt_detect(self._h, C.byref(capi.mat_from_tensor(image)), mm, C.byref(capi.mat_from_tensor(out)), C.byref(n), sp))
         return out[:, : n.value]
@@ -1822,7 +1689,7 @@ def _orb_pool(pattern0):
     return pool, C.byref(_host_mat(pool))
 
 
-class ORB:
+class ORB(_Handle):
     """cv::cuda::ORB (cudafeatures2d.hpp:452-505).  Images and masks are uint8 device tensors; keypoints are the reference's 6 x n
     CV_32FC1 matrix (rows X, Y, RESPONSE, ANGLE, OCTAVE, SIZE), descriptors n x 32 uint8.  pattern0: the pool of 512 test points the
     reference reads from its learned table when patchSize == 31 (an OpenCV binding passes its own), None: makeRandomPattern."""
@@ -1834,29 +1701,14 @@ class ORB:
 
     def __init__(self, nfeatures=500, scaleFactor=1.2, nlevels=8, edgeThreshold=31, firstLevel=0, WTA_K=2, scoreType=0, patchSize=31,
                  fastThreshold=20, blurForDescriptor=False, pattern0=None):
-        self._h = None
-        self._p = capi.OrbParams(int(nfeatures), float(scaleFactor), int(nlevels), int(edgeThreshold), int(firstLevel), int(WTA_K), int(scoreType),
-                                 int(patchSize), int(fastThreshold), int(bool(blurForDescriptor)))
         self._pool, pm = _orb_pool(pattern0)
-        h = C.c_void_p()
-        capi.check(capi.lib().mi_orb_create(C.byref(self._p), pm, C.byref(h)))
-        self._h = h
+        self._open("orb", capi.OrbParams(int(nfeatures), float(scaleFactor), int(nlevels), int(edgeThreshold), int(firstLevel), int(WTA_K),
+                                         int(scoreType), int(patchSize), int(fastThreshold), int(bool(blurForDescriptor))), pm)
 
     @staticmethod
     def create(nfeatures=500, scaleFactor=1.2, nlevels=8, edgeThreshold=31, firstLevel=0, WTA_K=2, scoreType=0, patchSize=31, fastThreshold=20,
                blurForDescriptor=False, pattern0=None) -> "ORB":
         return ORB(nfeatures, scaleFactor, nlevels, edgeThreshold, firstLevel, WTA_K, scoreType, patchSize, fastThreshold, blurForDescriptor, pattern0)
-
-    def __del__(self):
-        _destroy(self, "mi_orb_destroy")
-
-    def _set(self, **kw):
-        p = capi.OrbParams()
-        C.memmove(C.byref(p), C.byref(self._p), C.sizeof(p))
-        for k, v in kw.items():
-            setattr(p, k, v)
-        capi.check(capi.lib().mi_orb_set_params(self._h, C.byref(p)))
-        self._p = p
 
     def _sync(self):
         capi.check(capi.lib().mi_orb_get_params(self._h, C.byref(self._p)))
@@ -1910,7 +1762,7 @@ class ORB:
         import numpy as np
         import torch
         image = _u8(image)
-        sp = C.c_void_p(stream) if stream is not None else capi.current_stream_ptr()
+        sp = _stream_ptr(stream)
         n = C.c_int()
         if useProvidedKeypoints:
             kp = np.array(keypoints.detach().cpu().numpy() if hasattr(keypoints, "detach") else keypoints, dtype=np.float32, order="C")

@@ -158,28 +158,19 @@ def _mats(tensors):
     return arr
 
 
-class BTVL1_CUDA:
+class BTVL1_CUDA(cuda._Handle):
     """cv::superres::createSuperResolution_BTVL1_CUDA() (btv_l1_cuda.cpp:209-588): BTVL1_CUDA_Base::process behind the C-ABI
     (mi_btvl1_process), the frame ring of BTVL1_CUDA and SuperResolution::nextFrame (super_resolution.cpp) in Python."""
 
     def __init__(self):
         p = capi.BTVL1Params()
         capi.lib().mi_btvl1_default_params(C.byref(p))
-        self._h = C.c_void_p()
-        capi.check(capi.lib().mi_btvl1_create(C.byref(p), C.byref(self._h)))
+        self._open("btvl1", p)
         self._p = dict(Scale=p.scale, Iterations=p.iterations, Tau=p.tau, Lambda=p.lambda_, Alpha=p.alpha, KernelSize=p.btv_kernel_size,
                        BlurKernelSize=p.blur_kernel_size, BlurSigma=p.blur_sigma, TemporalAreaRadius=4,   # btv_l1_cuda.cpp:461
                        OpticalFlow=createOptFlow_Farneback_CUDA())                                           # btv_l1_cuda.cpp:292
         self._source = createFrameSource_Empty()
         self._first = True
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            try:
-                capi.lib().mi_btvl1_destroy(h)
-            except Exception:
-                pass
 
     # ---- BTVL1_CUDA_Base
     def _push_params(self):
@@ -262,9 +253,8 @@ class BTVL1_CUDA:
         self._frames = self._fwd = self._bwd = self._outputs = None
         self._cur = self._prev = None
         self._p["OpticalFlow"].collectGarbage()
-        capi.lib().mi_btvl1_destroy(self._h)
-        self._h = C.c_void_p()
-        capi.check(capi.lib().mi_btvl1_create(None, C.byref(self._h)))
+        self._close()
+        self._open("btvl1", None, None)   # NULL: the library's defaults; _push_params sends this object's before every process
 
     # ---- BTVL1_CUDA (btv_l1_cuda.cpp:483-582)
     @staticmethod

@@ -1,6 +1,6 @@
 // Caller code against the drop-in headers alone: StereoSGM, DisparityBilateralFilter, DensePyrLKOpticalFlow, SparsePyrLKOpticalFlow and
 // DescriptorMatcher, run through their public C++ classes on a GPU.  tests/test_cpp_classes_gpu.py writes the inputs, runs
-//     classes_gpu <sgm|dbf|dense|sparse|bf> in.bin out.bin
+//     classes_gpu <sgm|dbf|dense|sparse|bf|params> in.bin out.bin
 // and compares what the classes return with the oracle.  Both files are a flat sequence of records
 //     int32 name length, type (CV_MAKETYPE code), rows, cols; the name; rows * cols elements, dense
 // Every output a class creates itself is a GpuMat::create matrix (pitched rows when rows > 1); where a case asks for it the output is
@@ -15,6 +15,7 @@
 #include "opencv2/cudafeatures2d.hpp"
 #include "opencv2/cudaoptflow.hpp"
 #include "opencv2/cudastereo.hpp"
+#include "opencv2/xfeatures2d/cuda.hpp"
 
 using namespace cv;
 using cuda::GpuMat;
@@ -363,9 +364,54 @@ static void bf()
     }
 }
 
+// A value the library's set_params rejects, for the two classes whose set_params validates: the setter throws, the getter still answers
+// the old value, another setter with a valid value succeeds, and the object then computes what a new object with the same final
+// parameters computes.  Then SURF_CUDA's error path: a call the library refuses before any launch leaves the caller's descriptors
+// header as it was.
+static void params()
+{
+    GpuMat a = up("a"), b = up("b"), pts = up("pts");
+    {
+        Ptr<cuda::OpticalFlowDual_TVL1> alg = cuda::OpticalFlowDual_TVL1::create(0.25, 0.15, 0.3, 3, 2, 0.01, 20);
+        int threw = 0;
+        try { alg->setNumScales(0); } catch (const cv::Exception &e) { threw = e.code; }
+        const int kept = alg->getNumScales();
+        alg->setNumWarps(3);
+        puti("tvl1.reject", {threw, kept, alg->getNumScales(), alg->getNumWarps()});
+        GpuMat f0, f1;
+        alg->calc(a, b, f0);
+        cuda::OpticalFlowDual_TVL1::create(0.25, 0.15, 0.3, 3, 3, 0.01, 20)->calc(a, b, f1);
+        put("tvl1.kept", f0); put("tvl1.fresh", f1);
+    }
+    {
+        Ptr<cuda::SparsePyrLKOpticalFlow> alg = cuda::SparsePyrLKOpticalFlow::create(Size(9, 9), 2, 10);
+        int threw = 0;
+        try { alg->setMaxLevel(16); } catch (const cv::Exception &e) { threw = e.code; }
+        const int kept = alg->getMaxLevel();
+        alg->setNumIters(7);
+        puti("sparse.reject", {threw, kept, alg->getMaxLevel(), alg->getNumIters()});
+        GpuMat n0, s0, n1, s1;
+        alg->calc(a, b, pts, n0, s0);
+        cuda::SparsePyrLKOpticalFlow::create(Size(9, 9), 2, 7)->calc(a, b, pts, n1, s1);
+        put("sparse.kept.next", n0); put("sparse.kept.status", s0); put("sparse.fresh.next", n1); put("sparse.fresh.status", s1);
+    }
+    {
+        cuda::SURF_CUDA surf(arr("surf").f()[0], 2, 2, false, arr("surf").f()[1]);
+        GpuMat kp, desc, wrong(a.rows, a.cols, CV_32FC1);
+        wrong.setTo(0);
+        surf(a, GpuMat(), kp, desc);                  // desc: an allocation of maxFeatures rows, cut to the feature count
+        const int rows0 = desc.rows, cols0 = desc.cols;
+        const uchar *data0 = desc.data;
+        const int maxf = (int)((desc.dataend - desc.datastart - (size_t)cols0 * 4) / desc.step) + 1;
+        int threw = 0;
+        try { surf(wrong, GpuMat(), kp, desc); } catch (const cv::Exception &e) { threw = e.code; }   // MI_ERR_BAD_TYPE before any launch
+        puti("surf.reject", {threw, rows0, cols0, maxf, desc.rows, desc.cols, desc.data == data0});
+    }
+}
+
 int main(int argc, char **argv)
 {
-    if (argc != 4) { fprintf(stderr, "usage: classes_gpu <sgm|dbf|dense|sparse|bf> in.bin out.bin\n"); return 2; }
+    if (argc != 4) { fprintf(stderr, "usage: classes_gpu <sgm|dbf|dense|sparse|bf|params> in.bin out.bin\n"); return 2; }
     try {
         if (cuda::getCudaEnabledDeviceCount() < 1) {
             fprintf(stderr, "classes_gpu: no GPU device, and the library has no CPU fallback\n");
@@ -380,6 +426,7 @@ int main(int argc, char **argv)
         else if (family == "dense") dense();
         else if (family == "sparse") sparse();
         else if (family == "bf") bf();
+        else if (family == "params") params();
         else { fprintf(stderr, "classes_gpu: no family %s\n", argv[1]); return 2; }
         return fclose(out) == 0 ? 0 : 4;
     } catch (const cv::Exception &e) {

@@ -561,3 +561,30 @@ def test_float_matcher_outputs_with_three_different_strides(gpu, oracle, norm):
                                              C.byref(_m(vn)), capi.current_stream_ptr()))
     _same(vn.cpu().numpy()[0], rr[3]); _same(vi.cpu().numpy(), rr[0]); _same(vm.cpu().numpy(), rr[1]); _same(vd.cpu().numpy(), rr[2])
     intact(wi, 3, cols, -1); intact(wm, 5, cols, -1); intact(wd, 1, cols, 0.0); intact(wn, 3, nq, -77)
+
+
+# ------------------------------------------------------------------ a rejected parameter leaves the object as it was
+@pytest.mark.gpu
+def test_rejected_parameter_leaves_the_object_as_it_was(gpu, classes_exe, tmp_path):
+    """OpticalFlowDual_TVL1::setNumScales(0) and SparsePyrLKOpticalFlow::setMaxLevel(16), the two values mi_*_set_params itself refuses:
+    the setter throws StsBadArg, the getter answers the old value, a setter with a valid value then succeeds, and a calc on a 64 x 64
+    pair equals, bit for bit, the calc of a new object made with the same final parameters.
+    SURF_CUDA: operator() enlarges the caller's descriptors header to maxFeatures rows before the enqueue; a call the library refuses
+    before any launch must put the header back.  The library is made to refuse with a CV_32FC1 image (MI_ERR_BAD_TYPE from the first
+    check of mi_surf_detect_and_compute): a keypoints matrix of the wrong type never reaches the library, the class re-creates it."""
+    a, b, _ = synth.flow_pair(64, 64, seed=5, dtype="u8")
+    rng = np.random.default_rng(5)
+    pts = np.stack([rng.uniform(4, 60, 33), rng.uniform(4, 60, 33)], 1).astype(np.float32)
+    out = _run(classes_exe, "params", {"a": a, "b": b, "pts": pts[None], "surf": np.array([[100.0, 0.05]], np.float32)}, tmp_path)
+    STS_BAD_ARG = -5
+    assert out["tvl1.reject"].tolist() == [[STS_BAD_ARG, 3, 3, 3]]            # thrown code, nscales after the throw, nscales, warps at the end
+    _same(out["tvl1.kept"], out["tvl1.fresh"], "TV-L1 after a rejected setNumScales")
+    assert out["tvl1.kept"].shape == (64, 64, 2) and np.isfinite(out["tvl1.kept"]).all() and (out["tvl1.kept"] != 0).any()
+    assert out["sparse.reject"].tolist() == [[STS_BAD_ARG, 2, 2, 7]]          # thrown code, maxLevel after the throw, maxLevel, iters at the end
+    _same(out["sparse.kept.next"], out["sparse.fresh.next"], "sparse PyrLK after a rejected setMaxLevel")
+    _same(out["sparse.kept.status"], out["sparse.fresh.status"])
+    assert out["sparse.kept.status"].sum() > 0
+    threw, rows0, cols0, maxf, rows1, cols1, same_data = out["surf.reject"][0].tolist()
+    assert threw == STS_ASSERT and cols0 == 64
+    assert 0 < rows0 < maxf, "the case needs a feature count below maxFeatures, or an enlarged header would look restored"
+    assert (rows1, cols1, same_data) == (rows0, cols0, 1)
