@@ -843,6 +843,71 @@ MI_API int mi_gftt_sort(const mi_mat *response, const mi_mat *corners, int n, mi
  * sorted order; out: room for total float2; *n_out: the survivors. */
 MI_API int mi_gftt_min_distance(const float *points, int total, int rows, int cols, double min_distance, int max_corners, float *out, int *n_out);
 
+/* ================================================= cv::cuda::BroxOpticalFlow ===== */
+
+/* Parameters of cv::cuda::BroxOpticalFlow::create, cudaoptflow.hpp:179-185 (NCVBroxOpticalFlowDescriptor, NCVBroxOpticalFlow.hpp:69-83). */
+typedef struct mi_brox_params {
+    float alpha;             /* 0.197: flow smoothness */
+    float gamma;             /* 50: gradient constancy importance */
+    float scale_factor;      /* 0.8: pyramid scale factor */
+    int inner_iterations;    /* 5: lagged non-linearity iterations */
+    int outer_iterations;    /* 150: the most pyramid levels */
+    int solver_iterations;   /* 10: red-black SOR iterations of one linear system */
+} mi_brox_params;
+
+typedef struct mi_brox mi_brox;
+
+enum { MI_BROX_FORM_AUTO = 0,      /* the plan's selection rule (csrc/brox_plan.h) */
+       MI_BROX_FORM_PLAIN = 1,     /* one launch per half-pass, as the reference */
+       MI_BROX_FORM_BLOCKED = 2 }; /* both colours of up to 2 solver iterations per launch over an LDS tile; the same bits */
+
+/* Replaces: BroxOpticalFlow::create's defaults, cudaoptflow.hpp:179-185 */
+MI_API void mi_brox_default_params(mi_brox_params *p);
+/* Replaces: BroxOpticalFlow::create and BroxOpticalFlowImpl's constructor, cudaoptflow/src/brox.cpp:59-65,191-194.  Validation as NCVBroxOpticalFlow.cu:606-610 (alpha > 0,
+ * gamma >= 0, the three counts > 0) and 0 < scale_factor < 1: MI_ERR_BAD_ARG.  p == NULL: the defaults. */
+MI_API int mi_brox_create(const mi_brox_params *p, mi_brox **out);
+/* Replaces: the six setters of BroxOpticalFlowImpl, brox.cpp:72,75,78,82,86,90, with create's validation (the reference validates at
+ * the next calc, NCVBroxOpticalFlow.cu:606-610).  A rejected set leaves the handle as it was. */
+MI_API int mi_brox_set_params(mi_brox *h, const mi_brox_params *p);
+/* Replaces: the six getters, brox.cpp:71,74,77,81,85,89. */
+MI_API int mi_brox_get_params(const mi_brox *h, mi_brox_params *p);
+/* No counterpart in the reference, whose solver has one form (the loop of NCVBroxOpticalFlow.cu:912-925): the form of the handle's next
+ * calcs (tests and measurements; MI_BROX_FORM_AUTO at creation). */
+MI_API int mi_brox_set_form(mi_brox *h, int form);
+/* Replaces: BroxOpticalFlowImpl::getBufSize, brox.cpp:112-127 (the counting run of NCVBroxOpticalFlow): the bytes the handle holds now. */
+MI_API int mi_brox_scratch_bytes(const mi_brox *h, size_t *bytes);
+/* The plan of a calc without running it (host only, no device needed): the number of pyramid levels (NCVBroxOpticalFlow.cu:698-785), of
+ * launches and, among them, of solver launches, for a frame of rows x cols in the given form.  The errors are calc's: MI_ERR_BAD_ARG for
+ * a rejected parameter, a frame side below 4 or a pyramid level with a side of 1 (scale_factor at or below 1/16: the reference's
+ * derivative filter would read outside such a level); MI_ERR_BAD_SIZE where a level's supersample window would leave the level above. */
+MI_API int mi_brox_plan_info(const mi_brox_params *p, int rows, int cols, int form, int *levels, int *launches, int *sor_launches);
+/* Replaces: BroxOpticalFlowImpl::calc, cudaoptflow/src/brox.cpp:129-188, and NCVBroxOpticalFlow, cudalegacy/src/cuda/NCVBroxOpticalFlow.cu:598-985.
+ * frame0, frame1: MI_32FC1 of one size, each side at least 4 (MI_ERR_BAD_ARG below); flow: MI_32FC2 of that size; what it held is ignored.
+ * A pyramid whose plan fails (see mi_brox_plan_info) is rejected before any launch.
+ * Stream-ordered: no host wait inside.  Texture reads and rsqrtf are defined in DESIGN.md 4.13. */
+MI_API int mi_brox_calc(mi_brox *h, const mi_mat *frame0, const mi_mat *frame1, mi_mat *flow, void *stream);
+/* Replaces: ~BroxOpticalFlowImpl (implicit; its GpuMat buf releases the scratch, brox.cpp:107) */
+MI_API void mi_brox_destroy(mi_brox *h);
+/* Stage entries.  Every matrix is MI_32FC1; each entry waits for `stream`.
+ * Replaces: nppiStResize_32f_C1R with nppStSupersample, cudalegacy/src/cuda/NPP_staging.cu:2073-2149,2260-2266.  dst has its size already;
+ * the factor is scale_factor (NOT the ratio of the sizes). */
+MI_API int mi_brox_resize_down(const mi_mat *src, mi_mat *dst, float scale_factor, void *stream);
+/* Replaces: nppiStResize_32f_C1R with nppStBicubic, NPP_staging.cu:2152-2231,2267-2273, and ScaleVector, NCVBroxOpticalFlow.cu:145-170,952-961:
+ * dst = bicubic(src) * (1 / scale_factor). */
+MI_API int mi_brox_resize_up(const mi_mat *src, mi_mat *dst, float scale_factor, void *stream);
+/* Replaces: the seven nppiStFilterRowBorder_32f_C1R / nppiStFilterColumnBorder_32f_C1R calls of NCVBroxOpticalFlow.cu:842-868 (kernels
+ * NPP_staging.cu:1433-1501).  planes[7]: Ix0, Iy0 (of i0), Ix, Iy, Ixx, Iyy, Ixy (of i1). */
+MI_API int mi_brox_derivatives(const mi_mat *i0, const mi_mat *i1, mi_mat *planes, void *stream);
+/* Replaces: prepare_sor_stage_1_tex and prepare_sor_stage_2, NCVBroxOpticalFlow.cu:340-473.  images[9]: I0, I1, Ix, Ixx, Ix0, Iy, Iyy, Iy0,
+ * Ixy; coeffs[7]: diffusivity_x, diffusivity_y, inv_denominator_u, inv_denominator_v, numerator_dudv, numerator_u, numerator_v after
+ * stage 2. */
+MI_API int mi_brox_prepare(const mi_mat *u, const mi_mat *v, const mi_mat *du, const mi_mat *dv, const mi_mat *images, float alpha, float gamma,
+                           mi_mat *coeffs, void *stream);
+/* Replaces: the solver loop of sor_pass<0> / sor_pass<1>, NCVBroxOpticalFlow.cu:479-554,912-925.  du, dv: read and overwritten with the
+ * result of `solver_iterations` iterations; form: MI_BROX_FORM_PLAIN or MI_BROX_FORM_BLOCKED (AUTO: the plan's rule). */
+MI_API int mi_brox_sor(const mi_mat *u, const mi_mat *v, mi_mat *du, mi_mat *dv, const mi_mat *coeffs, int form, int solver_iterations,
+                       void *stream);
+
 /* ================================================= superres optical-flow adapters ===== */
 
 /* Replaces: cv::superres::convertToType(GpuMat, CV_8UC1) as used by GpuOpticalFlow::calc, superres/src/optical_flow.cpp:469-470

@@ -261,6 +261,67 @@ inline Ptr<DensePyrLKOpticalFlow> DensePyrLKOpticalFlow::create(Size winSize, in
     return makePtr<miflow_detail::DensePyrLKImpl>(p);
 }
 
+/** cudaoptflow.hpp:155-186 class BroxOpticalFlow; implementation twin of BroxOpticalFlowImpl, cudaoptflow/src/brox.cpp:56-188, and of
+ *  NCVBroxOpticalFlow, cudalegacy/src/cuda/NCVBroxOpticalFlow.cu.  CV_32FC1 frames of one size, each side at least 4.  The parameters
+ *  live in the handle as binary32, as NCVBroxOpticalFlowDescriptor holds them (brox.cpp:151-156): a getter returns the float's value. */
+class BroxOpticalFlow : public DenseOpticalFlow {
+public:
+    virtual double getFlowSmoothness() const = 0;                 virtual void setFlowSmoothness(double alpha) = 0;
+    virtual double getGradientConstancyImportance() const = 0;    virtual void setGradientConstancyImportance(double gamma) = 0;
+    virtual double getPyramidScaleFactor() const = 0;             virtual void setPyramidScaleFactor(double scale_factor) = 0;
+    virtual int getInnerIterations() const = 0;                   virtual void setInnerIterations(int inner_iterations) = 0;
+    virtual int getOuterIterations() const = 0;                   virtual void setOuterIterations(int outer_iterations) = 0;
+    virtual int getSolverIterations() const = 0;                  virtual void setSolverIterations(int solver_iterations) = 0;
+    static Ptr<BroxOpticalFlow> create(double alpha = 0.197, double gamma = 50.0, double scale_factor = 0.8, int inner_iterations = 5,
+                                       int outer_iterations = 150, int solver_iterations = 10);
+};
+
+namespace miflow_detail {
+class BroxImpl final : public BroxOpticalFlow {
+public:
+    explicit BroxImpl(const mi_brox_params &p) : h_(p) {}
+    void calc(InputArray I0, InputArray I1, InputOutputArray flow, Stream &stream) override
+    {
+        flow.create(I0.size(), CV_32FC2);   // brox.cpp:183-185
+        mi_mat a = miMat(I0), b = miMat(I1), f = miMat(flow);
+        miCheck(mi_brox_calc(h_.get(), &a, &b, &f, stream.hipStream()));
+    }
+    String getDefaultName() const override { return "DenseOpticalFlow.BroxOpticalFlow"; }   // brox.cpp:67
+    double getFlowSmoothness() const override { return h_.params().alpha; }
+    void setFlowSmoothness(double v) override { h_.set([=](auto &q) { q.alpha = (float)v; }); }
+    double getGradientConstancyImportance() const override { return h_.params().gamma; }
+    void setGradientConstancyImportance(double v) override { h_.set([=](auto &q) { q.gamma = (float)v; }); }
+    double getPyramidScaleFactor() const override { return h_.params().scale_factor; }
+    void setPyramidScaleFactor(double v) override { h_.set([=](auto &q) { q.scale_factor = (float)v; }); }
+    int getInnerIterations() const override { return h_.params().inner_iterations; }
+    void setInnerIterations(int v) override { h_.set([=](auto &q) { q.inner_iterations = v; }); }
+    int getOuterIterations() const override { return h_.params().outer_iterations; }
+    void setOuterIterations(int v) override { h_.set([=](auto &q) { q.outer_iterations = v; }); }
+    int getSolverIterations() const override { return h_.params().solver_iterations; }
+    void setSolverIterations(int v) override { h_.set([=](auto &q) { q.solver_iterations = v; }); }
+    mi_brox *handle() const { return h_.get(); }   // miflow::setSolverForm
+private:
+    ParamHandle<mi_brox, mi_brox_params, mi_brox_create, mi_brox_set_params, mi_brox_destroy> h_;
+};
+}  // namespace miflow_detail
+
+inline Ptr<BroxOpticalFlow> BroxOpticalFlow::create(double alpha, double gamma, double scale_factor, int inner_iterations, int outer_iterations,
+                                                    int solver_iterations)
+{
+    const mi_brox_params p = {(float)alpha, (float)gamma, (float)scale_factor, inner_iterations, outer_iterations, solver_iterations};
+    return makePtr<miflow_detail::BroxImpl>(p);
+}
+
+namespace miflow {
+/** miflow extension: the solver's form, MI_BROX_FORM_AUTO / PLAIN / BLOCKED; the bits do not depend on it */
+inline void setSolverForm(const Ptr<BroxOpticalFlow> &alg, int form)
+{
+    auto *impl = dynamic_cast<miflow_detail::BroxImpl *>(alg.get());
+    CV_Assert(impl);
+    miCheck(mi_brox_set_form(impl->handle(), form));
+}
+}  // namespace miflow
+
 /** cudaoptflow.hpp:85-104 SparseOpticalFlow, :203-223 SparsePyrLKOpticalFlow; implementation twin of SparsePyrLKOpticalFlowImpl,
  *  cudaoptflow/src/pyrlk.cpp:308-352.  CV_8UC1 frames.  `err` defaults to cuda::noArray() (a shared empty GpuMat): not computed. */
 inline GpuMat &noArray() { static thread_local GpuMat none; none.release(); return none; }

@@ -1,9 +1,11 @@
 // cv::superres GPU optical-flow adapters over libmiflow -- the in-tree CALLER of the hot path.
 //
 // Same interface names as the reference (superres/include/opencv2/superres/optical_flow.hpp:56-141): DenseOpticalFlowExt,
-// FarnebackOpticalFlow, DualTVL1OpticalFlow, createOptFlow_Farneback_CUDA(), createOptFlow_DualTVL1_CUDA().  The classes
-// follow superres/src/optical_flow.cpp:436-505 (GpuOpticalFlow), :665-750 (Farneback_CUDA) and :757-845 (DualTVL1_CUDA):
-// convert both frames to CV_8UC1, push the cached parameters into the cv::cuda class, calc, split the flow into two planes.
+// FarnebackOpticalFlow, DualTVL1OpticalFlow, BroxOpticalFlow, createOptFlow_Farneback_CUDA(), createOptFlow_DualTVL1_CUDA(),
+// createOptFlow_Brox_CUDA().  The classes follow superres/src/optical_flow.cpp:436-505 (GpuOpticalFlow), :502-586 (Brox_CUDA),
+// :665-750 (Farneback_CUDA) and :757-845 (DualTVL1_CUDA): convert both frames to the work type, push the cached parameters into the
+// cv::cuda class, calc, split the flow into two planes.  Brox_CUDA's work type is CV_32FC1 and this shim converts to CV_8UC1 only:
+// it takes CV_32FC1 frames and asserts otherwise.
 // Shim difference: frames and flows are cv::cuda::GpuMat (this repository's stand-in core has no cv::Mat / InputArray).
 #ifndef OPENCV_SUPERRES_OPTICAL_FLOW_MIFLOW_HPP
 #define OPENCV_SUPERRES_OPTICAL_FLOW_MIFLOW_HPP
@@ -59,6 +61,22 @@ public:
     virtual void setUseInitialFlow(bool val) = 0;
 };
 
+class CV_EXPORTS BroxOpticalFlow : public virtual DenseOpticalFlowExt {
+public:
+    virtual double getAlpha() const = 0;
+    virtual void setAlpha(double val) = 0;
+    virtual double getGamma() const = 0;
+    virtual void setGamma(double val) = 0;
+    virtual double getScaleFactor() const = 0;
+    virtual void setScaleFactor(double val) = 0;
+    virtual int getInnerIterations() const = 0;
+    virtual void setInnerIterations(int val) = 0;
+    virtual int getOuterIterations() const = 0;
+    virtual void setOuterIterations(int val) = 0;
+    virtual int getSolverIterations() const = 0;
+    virtual void setSolverIterations(int val) = 0;
+};
+
 namespace detail {
 
 // convertToType(frame, CV_8UC1, ...) of input_array_utility.cpp:291-314, one kernel
@@ -77,7 +95,7 @@ public:
     {
         CV_Assert(frame1.type() == frame0.type());   // optical_flow.cpp:466-467
         CV_Assert(frame1.size() == frame0.size());
-        const cuda::GpuMat input0 = toGray8(frame0, buf_[0]), input1 = toGray8(frame1, buf_[1]);
+        const cuda::GpuMat input0 = toWorkType(frame0, buf_[0]), input1 = toWorkType(frame1, buf_[1]);
         impl(input0, input1, flow_);
         if (!flow2) { flow1 = flow_; return; }
         flow1.create(flow_.size(), CV_32FC1);
@@ -93,6 +111,8 @@ public:
 
 protected:
     virtual void impl(const cuda::GpuMat &input0, const cuda::GpuMat &input1, cuda::GpuMat &flow) = 0;
+    // convertToType(frame, work_type_, ...), optical_flow.cpp:467-468: CV_8UC1 unless the adapter says otherwise
+    virtual cuda::GpuMat toWorkType(const cuda::GpuMat &src, cuda::GpuMat &buf) { return toGray8(src, buf); }
 
 private:
     cuda::GpuMat buf_[2], flow_;
@@ -182,8 +202,52 @@ private:
     Ptr<cuda::OpticalFlowDual_TVL1> alg_;
 };
 
+class Brox_CUDA : public GpuOpticalFlow, public BroxOpticalFlow {
+public:
+    Brox_CUDA() : alg_(cuda::BroxOpticalFlow::create(0.197f, 50.0f, 0.8f, 10, 77, 10))   // optical_flow.cpp:542
+    {
+        alpha_ = alg_->getFlowSmoothness(); gamma_ = alg_->getGradientConstancyImportance(); scaleFactor_ = alg_->getPyramidScaleFactor();
+        innerIterations_ = alg_->getInnerIterations(); outerIterations_ = alg_->getOuterIterations(); solverIterations_ = alg_->getSolverIterations();
+    }
+    double getAlpha() const CV_OVERRIDE { return alpha_; }
+    void setAlpha(double val) CV_OVERRIDE { alpha_ = val; }
+    double getGamma() const CV_OVERRIDE { return gamma_; }
+    void setGamma(double val) CV_OVERRIDE { gamma_ = val; }
+    double getScaleFactor() const CV_OVERRIDE { return scaleFactor_; }
+    void setScaleFactor(double val) CV_OVERRIDE { scaleFactor_ = val; }
+    int getInnerIterations() const CV_OVERRIDE { return innerIterations_; }
+    void setInnerIterations(int val) CV_OVERRIDE { innerIterations_ = val; }
+    int getOuterIterations() const CV_OVERRIDE { return outerIterations_; }
+    void setOuterIterations(int val) CV_OVERRIDE { outerIterations_ = val; }
+    int getSolverIterations() const CV_OVERRIDE { return solverIterations_; }
+    void setSolverIterations(int val) CV_OVERRIDE { solverIterations_ = val; }
+    void collectGarbage() CV_OVERRIDE
+    {
+        alg_ = cuda::BroxOpticalFlow::create(alpha_, gamma_, scaleFactor_, innerIterations_, outerIterations_, solverIterations_);   // :576-580
+        GpuOpticalFlow::collectGarbage();
+    }
+
+protected:
+    void impl(const cuda::GpuMat &input0, const cuda::GpuMat &input1, cuda::GpuMat &flow) CV_OVERRIDE
+    {
+        alg_->setFlowSmoothness(alpha_); alg_->setGradientConstancyImportance(gamma_); alg_->setPyramidScaleFactor(scaleFactor_);
+        alg_->setInnerIterations(innerIterations_); alg_->setOuterIterations(outerIterations_); alg_->setSolverIterations(solverIterations_);
+        alg_->calc(input0, input1, flow);
+    }
+    cuda::GpuMat toWorkType(const cuda::GpuMat &src, cuda::GpuMat &) CV_OVERRIDE
+    {
+        CV_Assert(src.type() == CV_32FC1);   // work type CV_32FC1, optical_flow.cpp:540; no conversion to it in this shim
+        return src;
+    }
+
+private:
+    double alpha_, gamma_, scaleFactor_; int innerIterations_, outerIterations_, solverIterations_;
+    Ptr<cuda::BroxOpticalFlow> alg_;
+};
+
 }  // namespace detail
 
+inline Ptr<BroxOpticalFlow> createOptFlow_Brox_CUDA() { return makePtr<detail::Brox_CUDA>(); }
 inline Ptr<FarnebackOpticalFlow> createOptFlow_Farneback_CUDA() { return makePtr<detail::Farneback_CUDA>(); }
 inline Ptr<DualTVL1OpticalFlow> createOptFlow_DualTVL1_CUDA() { return makePtr<detail::DualTVL1_CUDA>(); }
 

@@ -117,6 +117,11 @@ class GfttParams(C.Structure):
                 ("block_size", C.c_int), ("use_harris", C.c_int), ("harris_k", C.c_double)]
 
 
+class BroxParams(C.Structure):
+    _fields_ = [("alpha", C.c_float), ("gamma", C.c_float), ("scale_factor", C.c_float), ("inner_iterations", C.c_int),
+                ("outer_iterations", C.c_int), ("solver_iterations", C.c_int)]
+
+
 class OrbParams(C.Structure):
     _fields_ = [("nfeatures", C.c_int), ("scale_factor", C.c_float), ("nlevels", C.c_int), ("edge_threshold", C.c_int), ("first_level", C.c_int),
                 ("wta_k", C.c_int), ("score_type", C.c_int), ("patch_size", C.c_int), ("fast_threshold", C.c_int), ("blur_for_descriptor", C.c_int)]
@@ -344,6 +349,20 @@ def lib():
         "mi_gftt_find_corners": (i, [PM, f, PM, PM, C.POINTER(i), vp]),
         "mi_gftt_sort": (i, [PM, PM, i, PM, vp]),
         "mi_gftt_min_distance": (i, [C.POINTER(f), i, i, i, d, i, C.POINTER(f), C.POINTER(i)]),
+        "mi_brox_default_params": (None, [C.POINTER(BroxParams)]),
+        "mi_brox_create": (i, [C.POINTER(BroxParams), C.POINTER(vp)]),
+        "mi_brox_set_params": (i, [vp, C.POINTER(BroxParams)]),
+        "mi_brox_get_params": (i, [vp, C.POINTER(BroxParams)]),
+        "mi_brox_set_form": (i, [vp, i]),
+        "mi_brox_scratch_bytes": (i, [vp, C.POINTER(C.c_size_t)]),
+        "mi_brox_plan_info": (i, [C.POINTER(BroxParams), i, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(i)]),
+        "mi_brox_calc": (i, [vp, PM, PM, PM, vp]),
+        "mi_brox_destroy": (None, [vp]),
+        "mi_brox_resize_down": (i, [PM, PM, f, vp]),
+        "mi_brox_resize_up": (i, [PM, PM, f, vp]),
+        "mi_brox_derivatives": (i, [PM, PM, PM, vp]),
+        "mi_brox_prepare": (i, [PM, PM, PM, PM, PM, f, f, PM, vp]),
+        "mi_brox_sor": (i, [PM, PM, PM, PM, PM, i, i, vp]),
         "mi_superres_to_gray8": (i, [PM, PM, vp]),
         "mi_split_flow": (i, [PM, PM, PM, vp]),
         "mi_btvl1_default_params": (None, [C.POINTER(BTVL1Params)]),

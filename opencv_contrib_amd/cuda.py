@@ -175,6 +175,108 @@ class OpticalFlowDual_TVL1(_Handle):
         return [[buf[s * nw + w] for w in range(nw)] for s in range(ns.value)]
 
 
+BROX_FORM_AUTO, BROX_FORM_PLAIN, BROX_FORM_BLOCKED = 0, 1, 2
+
+
+class BroxOpticalFlow(_Handle):
+    """cv::cuda::BroxOpticalFlow (cudaoptflow.hpp:155-186; cudaoptflow/src/brox.cpp, cudalegacy/src/cuda/NCVBroxOpticalFlow.cu).
+    CV_32FC1 frames, each side at least 4; every result is the reference's kernels' bit for bit."""
+
+    def __init__(self, alpha=0.197, gamma=50.0, scale_factor=0.8, inner_iterations=5, outer_iterations=150, solver_iterations=10):
+        self._open("brox", capi.BroxParams(float(alpha), float(gamma), float(scale_factor), int(inner_iterations), int(outer_iterations),
+                                           int(solver_iterations)))
+
+    @staticmethod
+    def create(alpha=0.197, gamma=50.0, scale_factor=0.8, inner_iterations=5, outer_iterations=150, solver_iterations=10):
+        return BroxOpticalFlow(alpha, gamma, scale_factor, inner_iterations, outer_iterations, solver_iterations)
+
+    def getDefaultName(self) -> str:
+        return "DenseOpticalFlow.BroxOpticalFlow"   # cudaoptflow/src/brox.cpp:67
+
+    def getFlowSmoothness(self): return float(self._p.alpha)
+    def setFlowSmoothness(self, v): self._set(alpha=float(v))
+    def getGradientConstancyImportance(self): return float(self._p.gamma)
+    def setGradientConstancyImportance(self, v): self._set(gamma=float(v))
+    def getPyramidScaleFactor(self): return float(self._p.scale_factor)
+    def setPyramidScaleFactor(self, v): self._set(scale_factor=float(v))
+    def getInnerIterations(self): return self._p.inner_iterations
+    def setInnerIterations(self, v): self._set(inner_iterations=int(v))
+    def getOuterIterations(self): return self._p.outer_iterations
+    def setOuterIterations(self, v): self._set(outer_iterations=int(v))
+    def getSolverIterations(self): return self._p.solver_iterations
+    def setSolverIterations(self, v): self._set(solver_iterations=int(v))
+
+    def setSolverForm(self, form):
+        """miflow extension: BROX_FORM_AUTO (the plan's rule), BROX_FORM_PLAIN or BROX_FORM_BLOCKED; the bits do not depend on it"""
+        capi.check(capi.lib().mi_brox_set_form(self._h, int(form)))
+
+    def scratchBytes(self):
+        b = C.c_size_t()
+        capi.check(capi.lib().mi_brox_scratch_bytes(self._h, C.byref(b)))
+        return b.value
+
+    def calc(self, I0, I1, flow=None, stream=None):
+        """DenseOpticalFlow::calc(I0, I1, flow, stream) (cudaoptflow.hpp:80).  Returns flow (H,W,2) f32; what `flow` held is ignored."""
+        import torch
+        if flow is None:
+            flow = torch.empty((I0.shape[0], I0.shape[1], 2), dtype=torch.float32, device=I0.device)
+        capi.check(capi.lib().mi_brox_calc(self._h, C.byref(_m(I0)), C.byref(_m(I1)), C.byref(_m(flow)), _stream_ptr(stream)))
+        return flow
+
+
+def brox_plan_info(rows, cols, form=BROX_FORM_AUTO, **params):
+    """miflow extension, host only: (levels, launches, solver launches) of a calc at rows x cols; raises what calc would"""
+    p = capi.BroxParams()
+    capi.lib().mi_brox_default_params(C.byref(p))
+    for k, v in params.items():
+        setattr(p, k, v)
+    n = [C.c_int() for _ in range(3)]
+    capi.check(capi.lib().mi_brox_plan_info(C.byref(p), int(rows), int(cols), int(form), *[C.byref(x) for x in n]))
+    return tuple(x.value for x in n)
+
+
+def _like(t, rows=None, cols=None):
+    import torch
+    return torch.empty((t.shape[0] if rows is None else rows, t.shape[1] if cols is None else cols), dtype=torch.float32, device=t.device)
+
+
+def brox_resize_down(src, rows, cols, scale_factor, dst=None):
+    """Stage entry: the pyramid's supersample resize to rows x cols with factor scale_factor"""
+    dst = _like(src, rows, cols) if dst is None else dst
+    capi.check(capi.lib().mi_brox_resize_down(C.byref(_m(src)), C.byref(_m(dst)), float(scale_factor), capi.current_stream_ptr()))
+    return dst
+
+
+def brox_resize_up(src, rows, cols, scale_factor, dst=None):
+    """Stage entry: the bicubic prolongation to rows x cols, times 1 / scale_factor"""
+    dst = _like(src, rows, cols) if dst is None else dst
+    capi.check(capi.lib().mi_brox_resize_up(C.byref(_m(src)), C.byref(_m(dst)), float(scale_factor), capi.current_stream_ptr()))
+    return dst
+
+
+def brox_derivatives(i0, i1, planes=None):
+    """Stage entry -> [Ix0, Iy0, Ix, Iy, Ixx, Iyy, Ixy]"""
+    planes = [_like(i0) for _ in range(7)] if planes is None else planes
+    capi.check(capi.lib().mi_brox_derivatives(C.byref(_m(i0)), C.byref(_m(i1)), _mats(planes), capi.current_stream_ptr()))
+    return planes
+
+
+def brox_prepare(u, v, du, dv, images, alpha, gamma, coeffs=None):
+    """Stage entry.  images: [I0, I1, Ix, Ixx, Ix0, Iy, Iyy, Iy0, Ixy] -> [diffusivity_x, diffusivity_y, inv_denominator_u,
+    inv_denominator_v, numerator_dudv, numerator_u, numerator_v] after stage 2"""
+    coeffs = [_like(u) for _ in range(7)] if coeffs is None else coeffs
+    capi.check(capi.lib().mi_brox_prepare(C.byref(_m(u)), C.byref(_m(v)), C.byref(_m(du)), C.byref(_m(dv)), _mats(images), float(alpha),
+                                          float(gamma), _mats(coeffs), capi.current_stream_ptr()))
+    return coeffs
+
+
+def brox_sor(u, v, du, dv, coeffs, solver_iterations, form=BROX_FORM_AUTO):
+    """Stage entry: du, dv are overwritten with the result of solver_iterations red-black SOR iterations -> (du, dv)"""
+    capi.check(capi.lib().mi_brox_sor(C.byref(_m(u)), C.byref(_m(v)), C.byref(_m(du)), C.byref(_m(dv)), _mats(coeffs), int(form),
+                                      int(solver_iterations), capi.current_stream_ptr()))
+    return du, dv
+
+
 class TVL1MultiDevice(_Handle):
     """Batched-frames mode over the GPUs of one node through the C-ABI (mi_tvl1_multi_*): contiguous shards of independent pairs,
     one host thread + handle + stream pair per device, staging from / to the ROOT device (devices[0]) over RCCL point-to-point

@@ -96,6 +96,37 @@ class Farneback_CUDA(_GpuOpticalFlow):
         return a.calc(in0, in1)
 
 
+class Brox_CUDA(_GpuOpticalFlow):
+    """cv::superres::createOptFlow_Brox_CUDA() (optical_flow.cpp:502-586): defaults 0.197, 50, 0.8, 10, 77, 10, parameters pushed into
+    the cuda class at every calc (:561-566).  The work type is CV_32FC1 (:540); frames of another type are rejected here (the
+    conversion this module has goes to CV_8UC1 only)."""
+
+    def __init__(self):
+        self._alg = cuda.BroxOpticalFlow.create(0.197, 50.0, 0.8, 10, 77, 10)
+        a = self._alg
+        self._p = dict(Alpha=a.getFlowSmoothness(), Gamma=a.getGradientConstancyImportance(), ScaleFactor=a.getPyramidScaleFactor(),
+                       InnerIterations=a.getInnerIterations(), OuterIterations=a.getOuterIterations(), SolverIterations=a.getSolverIterations())
+
+    def _create(self):
+        p = self._p   # collectGarbage re-creates with the cached parameters, optical_flow.cpp:576-580
+        return cuda.BroxOpticalFlow.create(p["Alpha"], p["Gamma"], p["ScaleFactor"], p["InnerIterations"], p["OuterIterations"], p["SolverIterations"])
+
+    def calc(self, frame0, frame1, want_flow2: bool = True):
+        import torch
+        if frame0.dtype != frame1.dtype or frame0.shape != frame1.shape:
+            raise capi.MiError(-3, "frame1.type() == frame0.type() && frame1.size() == frame0.size()")   # optical_flow.cpp:466-467
+        if frame0.dtype != torch.float32 or frame0.dim() != 2:
+            raise capi.MiError(-2, "Brox_CUDA takes CV_32FC1 frames")
+        flow = self._impl(frame0, frame1)
+        return splitFlow(flow) if want_flow2 else flow
+
+    def _impl(self, in0, in1):
+        a, p = self._alg, self._p
+        a.setFlowSmoothness(p["Alpha"]); a.setGradientConstancyImportance(p["Gamma"]); a.setPyramidScaleFactor(p["ScaleFactor"])
+        a.setInnerIterations(p["InnerIterations"]); a.setOuterIterations(p["OuterIterations"]); a.setSolverIterations(p["SolverIterations"])
+        return a.calc(in0, in1)
+
+
 def _add_accessors(cls, names):
     for n in names:
         setattr(cls, "get" + n, (lambda n: lambda self: self._p[n])(n))
@@ -103,11 +134,16 @@ def _add_accessors(cls, names):
 
 
 _add_accessors(DualTVL1_CUDA, ["Tau", "Lambda", "Theta", "ScalesNumber", "WarpingsNumber", "Epsilon", "Iterations", "UseInitialFlow"])
+_add_accessors(Brox_CUDA, ["Alpha", "Gamma", "ScaleFactor", "InnerIterations", "OuterIterations", "SolverIterations"])
 _add_accessors(Farneback_CUDA, ["PyrScale", "LevelsNumber", "WindowSize", "Iterations", "PolyN", "PolySigma", "Flags"])
 
 
 def createOptFlow_DualTVL1_CUDA():
     return DualTVL1_CUDA()
+
+
+def createOptFlow_Brox_CUDA():
+    return Brox_CUDA()
 
 
 def createOptFlow_Farneback_CUDA():

@@ -57,6 +57,16 @@ int main()
         lk->calc(d0, d1, flow);
         report("DensePyrLK", flow);
 
+        // Brox takes CV_32FC1 frames in [0, 1] (the reference's sample: convertTo(CV_32F, 1.0 / 255.0)), with the sample's parameters
+        std::vector<float> g0(f0.size()), g1(f1.size());
+        for (size_t i = 0; i < f0.size(); ++i) { g0[i] = f0[i] / 255.0f; g1[i] = f1[i] / 255.0f; }
+        cuda::GpuMat e0(rows, cols, CV_32FC1), e1(rows, cols, CV_32FC1);
+        e0.upload(g0.data(), (size_t)cols * 4);
+        e1.upload(g1.data(), (size_t)cols * 4);
+        Ptr<cuda::BroxOpticalFlow> brox = cuda::BroxOpticalFlow::create(0.197, 50.0, 0.8, 10, 77, 10);
+        brox->calc(e0, e1, flow);
+        report("Brox", flow);
+
         // sparse tracking of a grid of points
         std::vector<float> pts;
         for (int y = 40; y < rows - 40; y += 20) for (int x = 40; x < cols - 40; x += 20) { pts.push_back((float)x); pts.push_back((float)y); }

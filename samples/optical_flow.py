@@ -1,4 +1,4 @@
-"""Python twin of samples/optical_flow.cpp: the four optical-flow classes of the cv2.cuda-style mirror on a synthetic pair.
+"""Python twin of samples/optical_flow.cpp: the five optical-flow classes of the cv2.cuda-style mirror on a synthetic pair.
 Needs an MI355X (there is no CPU fallback):  python samples/optical_flow.py"""
 import os
 import sys
@@ -18,6 +18,10 @@ def main():
                       ("DensePyrLK", cuda.DensePyrLKOpticalFlow.create())):
         flow = alg.calc(t0, t1).cpu().numpy()
         print(f"{name:12s} EPE vs the analytic flow {synth.epe(flow[20:-20, 20:-20], gt[20:-20, 20:-20]):.3f} px")
+    # Brox takes CV_32FC1 frames in [0, 1], as the reference's sample scales them (cudaoptflow/samples/optical_flow.cpp: convertTo(CV_32F, 1 / 255))
+    f0, f1 = t0.to(torch.float32) / 255.0, t1.to(torch.float32) / 255.0
+    flow = cuda.BroxOpticalFlow.create(0.197, 50.0, 0.8, 10, 77, 10).calc(f0, f1).cpu().numpy()
+    print(f"{'Brox':12s} EPE vs the analytic flow {synth.epe(flow[20:-20, 20:-20], gt[20:-20, 20:-20]):.3f} px")
     ys, xs = np.mgrid[40:200:20, 40:280:20]
     pts = np.stack([xs.ravel(), ys.ravel()], 1).astype(np.float32)
     nxt, status, err = cuda.SparsePyrLKOpticalFlow.create().calc(t0, t1, torch.from_numpy(pts).to(dev))
